@@ -20,6 +20,9 @@ Prints ONE JSON line (rank 0).  Besides the contract's keys:
   end_to_end    prepare_ms + ms_per_step + basis_download_ms;
   other_configs BASELINE.json configs 2, 3 and 5 at their full size (one GPU), each with its own time, roofline and CPU
                 baseline (N = 1 only; ``--no-other-configs`` skips them).
+
+``--dump-outputs DIR`` writes what the last timed step returned to its caller (dump_outputs) so that two builds run with
+the same arguments -- the same seeded input tensor -- can be compared output for output.
 """
 import argparse
 import contextlib
@@ -38,6 +41,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0       # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 FP64_MFMA_PEAK_TFLOPS = 78.6  # MI355X FP64 matrix peak (vendor spec; the guide lists no f64 row; tools/probe_mfma_f64: 70 measured)
 PMC_PROFILE = os.path.join("profiles", "r04e_pmc_traffic.json")      # offline rocprofv3 --pmc passes of THIS build
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
 
 
 def _cpu_info():
@@ -60,6 +64,22 @@ def _median3(fn):
         fn()
         ts.append(time.perf_counter() - t0)
     return float(np.median(ts)), ts
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """Writes ``arrays`` (name -> (array, sample axis)) as ``<out_dir>/<name>.npy`` in float64, at most ``limit`` bytes in
+    all: an array larger than its equal share of ``limit`` keeps a fixed, seeded sample of its slices along the sample axis
+    (in index order), and the indices of the kept slices go to ``<name>_sample.npy``."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = limit // len(arrays) - 1024          # (room for the .npy headers)
+    for name, (a, axis) in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.nbytes > share:
+            n = a.shape[axis]
+            keep = np.sort(np.random.default_rng(seed).choice(n, size=share // (a.nbytes // n + 8), replace=False))
+            a = np.take(a, keep, axis=axis)
+            np.save(os.path.join(out_dir, name + "_sample.npy"), keep.astype(np.float64))
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline_c4(F, N, K, budget_s=18.0):
@@ -466,7 +486,12 @@ def main():
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong",
                     help="strong (default): --verts vertices in all, sharded over the ranks (config 4 is one fixed job); "
                          "weak: --verts vertices PER RANK (the tensor grows with the GPUs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (basis, weights, selected vertices, singular values and "
+                         "residual norms) as DIR/<name>.npy, float64, at most 64 MB (the basis as a seeded vertex sample)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # native libraries (RCCL prints a version banner) write to fd 1: keep the real stdout for the ONE JSON line
     sys.stdout.flush()
@@ -569,6 +594,13 @@ def main():
     download_ms = (time.perf_counter() - t0) * 1e3
     basis_bytes = basis.nbytes
     del basis
+    if args.dump_outputs:
+        # comp.comps: one rank reuses the download above, several ranks gather the basis (every rank takes part)
+        outputs = {"comps": (comp.comps, 1), "weigs": (comp.weigs, 0), "selected_vertices": (comp.selected_vertices, 0),
+                   "measures_at_largeDeforVerts": (comp.measures_at_largeDeforVerts, 0)}
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outputs)
+        del outputs
 
     # Steady-state end to end (one GPU): a SECOND animation on the same context -- its buffers exist, the basis streams into
     # the context's pinned host buffer while the second read of X still computes (HipEngine.components_stream), and `comps`

@@ -12,6 +12,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -25,12 +26,14 @@ def _free_port():
 
 
 @pytest.mark.parametrize("world", [2])
-def test_bench_under_the_launcher_two_processes_one_gpu(world):
+def test_bench_under_the_launcher_two_processes_one_gpu(world, tmp_path):
     env = dict(os.environ, ASB_BENCH_ONE_DEVICE="1", ASB_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0",
                MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="2")
+    dump = tmp_path / "outputs"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
-           "--verts", "60000", "--frames", "256", "--comps", "64", "--no-cpu-baseline", "--no-other-configs"]
+           "--verts", "60000", "--frames", "256", "--comps", "64", "--no-cpu-baseline", "--no-other-configs",
+           "--dump-outputs", str(dump)]
     p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     err = p.stderr.decode(errors="replace")
     assert p.returncode == 0, err[-4000:]
@@ -42,5 +45,15 @@ def test_bench_under_the_launcher_two_processes_one_gpu(world):
     assert d["config"]["n_verts"] == 60000 and d["config"]["K"] == 64
     assert "LAUNCH REHEARSAL" in d["config"]["parallelism"]
     assert d["scaling"] == "strong" and d["dtype"] == "f64"
+    # --dump-outputs: rank 0 writes the gathered result of the last timed step; the (64, 60000, 3) basis as a vertex sample
+    out = {f.stem: np.load(f) for f in dump.glob("*.npy")}
+    assert sorted(out) == ["comps", "comps_sample", "measures_at_largeDeforVerts", "selected_vertices", "weigs"]
+    assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in out.values())
+    assert sum(f.stat().st_size for f in dump.glob("*.npy")) <= 64 * 10 ** 6
+    rows = out["comps_sample"]
+    assert out["comps"].shape == (64, rows.size, 3) and 0 < rows.size < 60000
+    assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < 60000
+    assert out["weigs"].shape == (256, 64) and out["measures_at_largeDeforVerts"].shape == (64, 3)
+    assert len(set(out["selected_vertices"].astype(np.int64).tolist())) == 64
     print("2-process launch on one GPU: %.1f ms per step, %d panel-kernel fallbacks" %
           (d["ms_per_step"], d["roofline"]["panel_kernel_fallbacks"]))

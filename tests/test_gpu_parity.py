@@ -103,9 +103,9 @@ def test_post_process_and_bin_vs_reference_golden(name, tmp_path):
     assert np.array_equal(back, comp.comps)
 
 
-def test_local_support_vs_reference_golden():
+def test_local_support_vs_reference_golden(tmp_path):
     g = load_golden("pca_local_small")
-    param = _param(g)
+    param = _param(g, vertPos_output_directory=str(tmp_path))
     snaps, comp = _run(g["verts"], g["tris"], param)
     assert comp.selected_vertices.tolist() == g["idx"].tolist()
     # local support canonicalises the sign through the +-projection test: no alignment
@@ -231,11 +231,11 @@ def test_project_mode_many_panels(kind, N, F, K):
         assert relerr(np.sqrt(outs[mode]["normR2_local"]), ref["measures"][:, 2]) < 1e-6
 
 
-def test_splocs_vs_reference_golden(capsys):
+def test_splocs_vs_reference_golden(capsys, tmp_path):
     """SPLOCS refinement on the GPU against the trace / refined components the unmodified reference
     produced (captured through pass-through wrappers, oracle/gen_golden.py)."""
     g = load_golden("splocs_small")
-    param = _param(g, splocs_max_itrs=int(g["param_splocs_max_itrs"]),
+    param = _param(g, vertPos_output_directory=str(tmp_path), splocs_max_itrs=int(g["param_splocs_max_itrs"]),
                    splocs_admm_num_itrs=int(g["param_splocs_admm_num_itrs"]),
                    splocs_lambda=float(g["param_splocs_lambda"]), splocs_rho=float(g["param_splocs_rho"]))
     snaps, comp = _run(g["verts"], g["tris"], param)
@@ -507,12 +507,12 @@ def _slice_signs(got, ref):
     return out
 
 
-def test_orthogonal_post_process_vs_reference_golden():
+def test_orthogonal_post_process_vs_reference_golden(tmp_path):
     """q_standarize + q_orthogonal + q_massWeight against the reference's post-processed basis.
     Global-support components have an arbitrary sign and `+ mean` is applied before `orth`, so the
     reference's own signs are installed first (comps setter -> device upload)."""
     g = load_golden("pca_global_avg_mass_orth")
-    param = _param(g)
+    param = _param(g, vertPos_output_directory=str(tmp_path))
     assert param.q_orthogonal and param.q_massWeight
     snaps, comp = _run(g["verts"], g["tris"], param, g["mass"])
     comps, _ = align_signs(comp.comps, comp.weigs, g["comps"])
@@ -755,10 +755,10 @@ def test_device_geodesics_vs_superlu():
     e.close()
 
 
-def test_local_support_with_device_geodesics(monkeypatch):
+def test_local_support_with_device_geodesics(monkeypatch, tmp_path):
     monkeypatch.setenv("ASB_GEODESIC", "device")
     g = load_golden("pca_local_small")
-    snaps, comp = _run(g["verts"], g["tris"], _param(g))
+    snaps, comp = _run(g["verts"], g["tris"], _param(g, vertPos_output_directory=str(tmp_path)))
     assert snaps.compute_geodesic_distance._engine is not None
     print("CG iterations", snaps.compute_geodesic_distance.last_iterations, relerr(comp.comps, g["comps"]))
     assert comp.selected_vertices.tolist() == g["idx"].tolist()
