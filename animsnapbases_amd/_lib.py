@@ -67,6 +67,7 @@ PROTOTYPES = {
     "asb_panel_select": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_int, c_dp, c_dp, ctypes.POINTER(c_i64),
                                  ctypes.POINTER(c_int)]),
     "asb_panel_capacity": (c_i64, [ctypes.c_void_p]),
+    "asb_panel_coop_possible": (c_int, [ctypes.c_void_p]),
     "asb_panel_assemble": (c_int, [ctypes.c_void_p, c_dp, c_dp, c_dp, c_int, c_i64]),
     "asb_panel_assemble_packed": (c_int, [ctypes.c_void_p, c_dp, c_dp, c_int, c_i64]),
     "asb_panel_run": (c_int, [ctypes.c_void_p, c_i64, c_int, c_int, c_int, ctypes.POINTER(c_i64)]),
@@ -99,6 +100,7 @@ PROTOTYPES = {
     "asb_panel_set_coop": (c_int, [ctypes.c_void_p, c_int]),
     "asb_deflate_coop_fallbacks": (c_int, [ctypes.c_void_p, ctypes.POINTER(c_i64)]),
     "asb_deflate_guessed_panels": (c_int, [ctypes.c_void_p, ctypes.POINTER(c_i64)]),
+    "asb_deflate_read_stats": (c_int, [ctypes.c_void_p, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     "asb_deflate_sketch_stats": (c_int, [ctypes.c_void_p, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     "asb_project_switch_residual": (c_int, [ctypes.c_void_p, c_i64]),
     "asb_splocs_trace_begin": (c_int, [ctypes.c_void_p, c_i64]),
@@ -160,6 +162,7 @@ PROTOTYPES = {
     "asb_test_sketch_predict": (c_int, [ctypes.c_void_p, c_dp, c_dp, c_dp, c_i64, c_int, c_int, c_dp, ctypes.POINTER(c_i64),
                                         ctypes.POINTER(c_int)]),
     "asb_test_spd_inverse": (c_int, [ctypes.c_void_p, c_dp, c_i64, c_dp]),
+    "asb_test_project_columns": (c_int, [ctypes.c_void_p, c_dp, c_i64, c_i64, c_int, c_dp, c_int, c_dp, c_i64]),
 }
 
 

@@ -71,7 +71,9 @@ def deflate_panels_multirank(eng, comm, n_rows, K):
     same_stream = spec_word is not None and hasattr(eng, "fetch_double") and bool(oes(eng) if callable(oes) else oes)
     read_word = (lambda: eng.fetch_double(spec_word.data_ptr())) if same_stream else (lambda: spec_word.item())
     # lock-step protection of the co-resident panel kernel (see below): only with the real engine, several ranks, kernel on
-    coop_check = bool(spec_word is not None and comm.multi and hasattr(eng, "panel_set_coop") and
+    # (the library says whether the kernel can run at all: not above its frame limit, where every panel takes the two-kernel loop)
+    coop_fits = eng.panel_coop_possible() if hasattr(eng, "panel_coop_possible") else True
+    coop_check = bool(spec_word is not None and comm.multi and hasattr(eng, "panel_set_coop") and coop_fits and
                       os.environ.get("ASB_PANEL_COOP", "1") != "0")
     global_all = n_rows <= cap
     spec_budget = 16 if (hasattr(eng, "panel_run_spec") and os.environ.get("ASB_SPEC_PANELS", "1") != "0") else 0
@@ -83,7 +85,7 @@ def deflate_panels_multirank(eng, comm, n_rows, K):
         guess_ok = bool(tot[2] == 0 and tot[1] > 0 and tot[0] > 0.25 * tot[1])
     guessing = False
     # several sub-panels per read (see the loop): only with the real engine, the co-resident kernel and device-side counts
-    multi_sub = bool(spec_word is not None and hasattr(eng, "panel_sub_run") and hasattr(eng, "panel_set_coop") and
+    multi_sub = bool(spec_word is not None and hasattr(eng, "panel_sub_run") and hasattr(eng, "panel_set_coop") and coop_fits and
                      os.environ.get("ASB_PANEL_COOP", "1") != "0" and os.environ.get("ASB_DOUBLE_PANELS", "1") != "0")
     sub_max = max(1, min(4, int(os.environ.get("ASB_SUB_PANELS", "4"))))
     sub_cur = min(sub_max, max(1, int(os.environ.get("ASB_SUB_FIRST", "4"))))

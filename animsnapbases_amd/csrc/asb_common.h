@@ -109,6 +109,8 @@ struct asb_ctx {
     int coop_test_stall = 0;          // ASB_COOP_TEST_STALL=1 (tests): the first co-resident launch is made to time out
     int64_t n_guess_panels = 0;       // first panels of the last run whose candidates were guessed (asb_project_run)
     int64_t n_coop_fallbacks = 0;     // launches of k_panel_coop whose record exchange timed out (redone by the two-kernel loop)
+    int64_t n_coop_launches = 0;      // launches of the co-resident panel kernel (k_panel_multi) in the last run
+    int64_t max_read_kept = 0;        // most components one read of X (all its sub-panels) committed in the last run
     // super-panels (asb_project.hip): how the next asb_panel_run behaves / what it did
     int run_writeback = 0, run_theta_band = 0, run_coop_used = 0;
     int spec_panels = 1;              // ASB_SPEC_PANELS=0 -> provable steps only

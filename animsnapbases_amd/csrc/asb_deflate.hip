@@ -45,6 +45,7 @@ extern "C" int asb_deflate_begin(asb_ctx* ctx, int64_t K, int mode, int local_su
     ctx->n_panels = ctx->n_refresh = 0;
     ctx->n_spec_steps = ctx->n_spec_kept = 0;
     ctx->n_guess_panels = 0;
+    ctx->n_coop_launches = ctx->max_read_kept = 0;
     ctx->n_sketch_runs = ctx->n_sketch_reads = 0;
     if (ctx->sk_counts) ASB_HIP(ctx, hipMemsetAsync(ctx->sk_counts, 0, 4 * sizeof(unsigned), ctx->stream));
     ctx->sketch_valid = false;
@@ -337,6 +338,13 @@ extern "C" int asb_deflate_energy_passes(asb_ctx* ctx, int64_t* n_passes) {
 extern "C" int asb_deflate_coop_fallbacks(asb_ctx* ctx, int64_t* n) {
     if (!ctx || !n) return ASB_ERR_ARG;
     *n = ctx->n_coop_fallbacks;
+    return ASB_OK;
+}
+
+extern "C" int asb_deflate_read_stats(asb_ctx* ctx, int64_t* coop_launches, int64_t* max_read_kept) {
+    if (!ctx || !coop_launches || !max_read_kept) return ASB_ERR_ARG;
+    *coop_launches = ctx->n_coop_launches;
+    *max_read_kept = ctx->max_read_kept;
     return ASB_OK;
 }
 

@@ -1475,127 +1475,6 @@ __global__ __launch_bounds__(512, 2) void k_project_l2d(
     }
 }
 
-// --------------------------------------------------------------------------------------
-// k_project_l2e (round 4): the 64-column pass WITHOUT any synchronisation between waves.  k_project_l2d shares one staged copy of
-// the weights among the 8 waves of a block and pays for it with a stage protocol (arrival counters; 0.11 of its 1.41 ms) and a
-// cross-wave reduction.  A lane reads back from LDS exactly the 32 bytes per column tile it loaded itself (Wq is in MFMA lane
-// order), so LDS is only a register-free FIFO: here every wave keeps a PRIVATE ring of two chunks (2 x 8 KB; 8 waves = 128 KB) that
-// it fills itself with direct loads, one chunk ahead, next to its own X chunk -- 8x the L2 traffic for the weights (4.8 GB per
-// launch, 13 % of what the L2s deliver), no barrier, no counters, no reduction: a wave owns its rows for all frames.
-// MEASURED (round 4, ASB_WIDE_VARIANT=60; parity green): 1.456 - 1.475 ms per launch against 1.400 - 1.408 for k_project_l2d on the
-// same box -- and 1.372 - 1.388 with the wait for the weights left out (wrong results): the stage protocol is not what k_project_l2d
-// loses; a wave that waits for its own weights chunk by chunk loses more than eight waves sharing a stage.  Kept as a variant.
-// --------------------------------------------------------------------------------------
-template <int NCT, int NTV, int DBG>
-__device__ __forceinline__ void l2e_rows(const double* __restrict__ X, long long rows, int Fp, const double* __restrict__ Wq,
-                                         const double* __restrict__ wn2, const WideArgs& wa, double* __restrict__ comps,
-                                         long long comp_stride, long long group0, unsigned lds_byte0) {
-    static_assert(NTV >= 1 && NTV <= 4, "row groups per wave");
-    typedef double d2v __attribute__((ext_vector_type(2)));
-    const int l = threadIdx.x & 63, i = l & 15, g = l >> 4;
-    const int nchunk = Fp / 16;
-    const long long base = group0 * 16;
-    const double4* xp[NTV];                                     // chunk c: xp[m][4 * c]
-#pragma unroll
-    for (int m = 0; m < NTV; ++m) {
-        long long r = base + 16 * m + i;
-        if (r >= rows) r = rows - 1;
-        xp[m] = reinterpret_cast<const double4*>(X + r * Fp + 4 * g);
-    }
-    d4 acc[NTV][NCT];
-#pragma unroll
-    for (int m = 0; m < NTV; ++m)
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) acc[m][ct] = (d4){0.0, 0.0, 0.0, 0.0};
-    double4 a0[NTV], a1[NTV];
-    // the weights of chunk c into ring slot c & 1 (asm: the compiler counts only the X loads; the hardware retires both kinds in
-    // the order issued, so the compiler's wait for the X chunk issued BEHIND these covers them -- as in k_project_l2d)
-    auto issue_w = [&](int c) {
-#pragma unroll
-        for (int q = 0; q < 2 * NCT; ++q) {
-            const int ct = q >> 1, h = q & 1;
-            const double* src = Wq + (long long)ct * Fp * 16 + (long long)c * 256 + l * 4 + h * 2;
-            const unsigned lds_byte = __builtin_amdgcn_readfirstlane(lds_byte0 + (unsigned)(((c & 1) * 2 * NCT + q) * 128 * 8));
-            unsigned m0_keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                         : "=&s"(m0_keep) : "v"(src), "s"(lds_byte) : "memory");
-        }
-    };
-    auto load_x = [&](int c, double4 (&a)[NTV]) {
-        const int cc = c < nchunk ? c : nchunk - 1;            // (behind the end: the last chunk once more -- the same loads on every path)
-#pragma unroll
-        for (int m = 0; m < NTV; ++m) a[m] = xp[m][4 * cc];
-    };
-    auto compute = [&](int c, double4 (&a)[NTV]) {
-        // this chunk's weights have landed once everything but the X chunk requested last (2 NTV loads) is back
-        if (NTV == 4) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else if (NTV == 3) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        else if (NTV == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) {
-            d2v b0, b1;
-            const unsigned addr = lds_byte0 + (unsigned)((((c & 1) * 2 * NCT + 2 * ct) * 128 + l * 2) * 8);
-            asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:1024\n\ts_waitcnt lgkmcnt(0)" : "=&v"(b0), "=&v"(b1) : "v"(addr));
-#pragma unroll
-            for (int m = 0; m < NTV; ++m) acc[m][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[m].x, b0.x, acc[m][ct], 0, 0, 0);
-#pragma unroll
-            for (int m = 0; m < NTV; ++m) acc[m][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[m].y, b0.y, acc[m][ct], 0, 0, 0);
-#pragma unroll
-            for (int m = 0; m < NTV; ++m) acc[m][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[m].z, b1.x, acc[m][ct], 0, 0, 0);
-#pragma unroll
-            for (int m = 0; m < NTV; ++m) acc[m][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[m].w, b1.y, acc[m][ct], 0, 0, 0);
-            // the next chunk's weights go out BEHIND the wait for this chunk's X (the first MFMAs above): they have this chunk's
-            // remaining 48 MFMAs and the other wave's 64 to arrive, and the next chunk's X wait (issued behind them) covers them
-            if (ct == 0 && c + 1 < nchunk) issue_w(c + 1);
-        }
-    };
-    load_x(0, a0);
-    issue_w(0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // first chunk of the rows: one exposed latency
-    for (int c = 0; c < nchunk; c += 2) {
-        load_x(c + 1, a1);
-        compute(c, a0);
-        load_x(c + 2, a0);
-        if (c + 1 < nchunk) compute(c + 1, a1);
-    }
-    (void)DBG;
-#pragma unroll
-    for (int ct = 0; ct < NCT; ++ct) {
-        if (i < wa.nc[ct]) {
-            const double inv = wn2[16 * ct + i];
-            double* dst = comps + (wa.kb[ct] + i) * comp_stride + base + g;
-#pragma unroll
-            for (int m = 0; m < NTV; ++m)
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if (base + 16 * m + g + 4 * q < rows) dst[16 * m + 4 * q] = acc[m][ct][q] / inv;
-        }
-    }
-}
-template <int NCT, int DBG = 0>
-__global__ __launch_bounds__(512, 2) void k_project_l2e(const double* __restrict__ X, long long rows, int Fp, const double* __restrict__ Wq,
-                                                        const double* __restrict__ wn2, WideArgs wa, double* __restrict__ comps,
-                                                        long long comp_stride) {
-    extern __shared__ double l2e_lds[];
-    const int w = threadIdx.x >> 6;
-    const unsigned lds_byte0 = (unsigned)(w * 2 * 2 * NCT * 128 * 8);        // this wave's ring: 2 chunks x 2 NCT KB
-    const long long ngroups = (rows + 15) / 16;
-    const long long g0 = ngroups * blockIdx.x / gridDim.x, g1 = ngroups * (blockIdx.x + 1) / gridDim.x;
-    // the block's groups in contiguous shares per wave (9 or 10 of 73 - 74 at config 4), each share in turns of at most four
-    const long long n = g1 - g0, w0 = g0 + n * w / 8, w1 = g0 + n * (w + 1) / 8;
-    for (long long gr = w0; gr < w1; gr += 4) {
-        const int ntv = (int)(w1 - gr < 4 ? w1 - gr : 4);
-        switch (ntv) {
-            case 4: l2e_rows<NCT, 4, DBG>(X, rows, Fp, Wq, wn2, wa, comps, comp_stride, gr, lds_byte0); break;
-            case 3: l2e_rows<NCT, 3, DBG>(X, rows, Fp, Wq, wn2, wa, comps, comp_stride, gr, lds_byte0); break;
-            case 2: l2e_rows<NCT, 2, DBG>(X, rows, Fp, Wq, wn2, wa, comps, comp_stride, gr, lds_byte0); break;
-            default: l2e_rows<NCT, 1, DBG>(X, rows, Fp, Wq, wn2, wa, comps, comp_stride, gr, lds_byte0); break;
-        }
-    }
-    (void)l2e_lds;
-}
-
 // scal[(k0+t)*4+3] = sum over blocks of colpart[b][t]  (= |w_t|^2 |c_t|_F^2 on this shard)
 // scal[(k0 + t) * 4 + 3] = sum over the blocks' partial column sums; one wave per column (launch with 1024 threads)
 __global__ __launch_bounds__(1024) void k_colsum(const double* __restrict__ colpart, int nblk, int ncols, long long k0,
@@ -1915,24 +1794,8 @@ static int launch_l2d(asb_ctx* ctx, const WideArgs& wa) {
                        ctx->wn2t3, wa, (ctx->wide_out ? ctx->wide_out : ctx->comps), rows);
     return ASB_OK;
 }
-template <int DBG>
-static int launch_l2e(asb_ctx* ctx, const WideArgs& wa) {
-    const long long rows = 3 * ctx->n_loc, ngroups = (rows + 15) / 16;
-    const size_t lds = (size_t)8 * 2 * 2 * 4 * 128 * sizeof(double);
-    static bool attr_set_dev[64] = {false};
-    bool& attr_set = attr_set_dev[ctx->dev & 63];
-    if (!attr_set) {
-        ASB_HIP(ctx, hipFuncSetAttribute((const void*)k_project_l2e<4, DBG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
-    const long long nb = ngroups < ctx->n_cu ? ngroups : ctx->n_cu;
-    hipLaunchKernelGGL((k_project_l2e<4, DBG>), dim3((unsigned)nb), dim3(512), lds, ctx->stream, ctx->X, rows, (int)ctx->Fp, ctx->Wq3, ctx->wn2t3, wa,
-                       (ctx->wide_out ? ctx->wide_out : ctx->comps), rows);
-    return ASB_OK;
-}
 template <int NCT>
 static int launch_l2w(asb_ctx* ctx, int variant, const WideArgs& wa) {
-    if (variant == 60 && NCT == 4) return launch_l2e<0>(ctx, wa);                // no synchronisation between waves (private weight rings): slower
     if (variant == 45 && NCT == 4) return launch_l2d<4, 3, 0>(ctx, wa);      // balanced partition, barrier per stage (two buffers)
     if (variant == 47 && NCT == 4) return launch_l2d<4, 2, 1>(ctx, wa);      // shorter stages
     if (variant == 52 && NCT == 4) return launch_l2d<4, 3, 1, 3, 11>(ctx, wa);  // + weights of the next column tile read ahead (BPF)
@@ -2091,10 +1954,10 @@ int asb_project_columns(asb_ctx* ctx, const double* Wfk, int64_t ldw, int64_t k0
 }
 
 __global__ void k_build_wq_tiles(const double* __restrict__ Wt3, int Fp, double* __restrict__ Wq3, unsigned* __restrict__ tile_counter);
-// the same product for up to 64 columns in ONE pass over X (the four-tile kernels of the panel reads; SPLOCS' c = W^T X took four
-// 16-column passes): out_rows[(k0 + j) - k0] for j < ncols, ncols <= 64
+// the same product for up to 16 * ASB_MAX_SUB = 128 columns in ONE pass over X (the multi-tile kernels of the panel reads; SPLOCS'
+// c = W^T X, at most 64 columns, took four 16-column passes): out_rows[(k0 + j) - k0] for j < ncols
 int asb_project_columns_wide(asb_ctx* ctx, const double* Wfk, int64_t ldw, int64_t k0, int ncols, double* out_rows, const double* col_scale) {
-    if (ncols < 1 || ncols > 64) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_project_columns_wide: %d columns", ncols);
+    if (ncols < 1 || ncols > 16 * ASB_MAX_SUB) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_project_columns_wide: %d columns", ncols);
     int rc;
     if ((rc = asb_alloc(ctx, &ctx->Wt3, (size_t)ASB_MAX_SUB * ctx->Fp * 16))) return rc;
     if ((rc = asb_alloc(ctx, &ctx->Wq3, (size_t)ASB_MAX_SUB * ctx->Fp * 16))) return rc;
@@ -2113,6 +1976,46 @@ int asb_project_columns_wide(asb_ctx* ctx, const double* Wfk, int64_t ldw, int64
     rc = launch_wide(ctx, ntile, wa);
     ctx->wide_out = nullptr;
     return rc;
+}
+
+// test hook: out (out_cols x 3 n_loc, host, in/out) -- columns j < ncols = X . W[:, k0 + j] / col_scale[k0 + j] with X the uploaded
+// snapshots and W (F x ldw, host, frame-major); col_scale (ldw entries, host) may be NULL.  The whole of `out` goes to the device
+// and comes back, so whatever the kernels write beyond the ncols columns shows.  path 0: asb_project_columns, 16 columns per pass;
+// path 1: asb_project_columns_wide, one pass through launch_wide (ceil(ncols / 16) tiles, ncols <= 128)
+extern "C" int asb_test_project_columns(asb_ctx* ctx, const double* W_host, int64_t ldw, int64_t k0, int ncols, const double* col_scale_host,
+                                        int path, double* out_host, int64_t out_cols) {
+    if (!ctx || !ctx->X || !W_host || !out_host) return ASB_ERR_ARG;
+    if (ncols < 1 || k0 < 0 || k0 + ncols > ldw || out_cols < ncols || (path != 0 && path != 1) || (path == 1 && ncols > 16 * ASB_MAX_SUB))
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_project_columns: ncols=%d k0=%lld ldw=%lld out_cols=%lld path=%d", ncols, (long long)k0,
+                 (long long)ldw, (long long)out_cols, path);
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    const size_t rows = (size_t)3 * ctx->n_loc, nw = (size_t)ctx->F * ldw, no = (size_t)out_cols * rows;
+    double *W = nullptr, *sc = nullptr, *out = nullptr;
+    hipError_t e = hipMalloc((void**)&W, nw * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&out, no * sizeof(double));
+    if (e == hipSuccess && col_scale_host) e = hipMalloc((void**)&sc, (size_t)ldw * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(W, W_host, nw * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(out, out_host, no * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess && sc) e = hipMemcpy(sc, col_scale_host, (size_t)ldw * sizeof(double), hipMemcpyHostToDevice);
+    int rc = ASB_OK;
+    if (e == hipSuccess) {
+        if (path == 1) {
+            rc = asb_project_columns_wide(ctx, W, ldw, k0, ncols, out, sc);
+        } else {
+            for (int j = 0; j < ncols && rc == ASB_OK; j += ASB_PANEL_COLS) {
+                const int nc = ncols - j < ASB_PANEL_COLS ? ncols - j : ASB_PANEL_COLS;
+                rc = asb_project_columns(ctx, W, ldw, k0 + j, nc, out + (size_t)j * rows, sc);
+            }
+        }
+        e = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipMemcpy(out_host, out, no * sizeof(double), hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(W);
+    (void)hipFree(out);
+    if (sc) (void)hipFree(sc);
+    if (rc) return rc;
+    if (e != hipSuccess) ASB_FAIL(ctx, ASB_ERR_HIP, "asb_test_project_columns: %s", hipGetErrorString(e));
+    return ASB_OK;
 }
 
 // start of a run on a tensor whose initial energies are known (E0): scal <- 0, hist <- 0, energy <- E0, range scalars restored --
@@ -3091,6 +2994,7 @@ static int launch_panel_multi(asb_ctx* ctx, int grid, const MultiArgs& ma, bool*
         const hipError_t e = hipLaunchCooperativeKernel((const void*)k_panel_multi<NJ>, dim3(grid), dim3(256), args, 0, ctx->stream);
         if (e == hipSuccess) {
             *launched = true;
+            ctx->n_coop_launches++;
             return ASB_OK;
         }
         (void)hipGetLastError();
@@ -3102,6 +3006,7 @@ static int launch_panel_multi(asb_ctx* ctx, int grid, const MultiArgs& ma, bool*
                        ctx->coop_test_stall, ctx->spec_w_rank);
     ASB_CHECK_LAUNCH(ctx);
     *launched = true;
+    ctx->n_coop_launches++;
     return ASB_OK;
 }
 
@@ -3111,6 +3016,10 @@ static int launch_panel_multi_any(asb_ctx* ctx, int grid, const MultiArgs& ma, b
     if (ctx->Fp <= 1024) return launch_panel_multi<16>(ctx, grid, ma, launched, sub, writeback);
     return launch_panel_multi<32>(ctx, grid, ma, launched, sub, writeback);
 }
+#define ASB_COOP_MAX_FP 2048     // k_panel_multi<32>: a candidate row of 32 x 64 frames in registers (above: the two-kernel loop)
+// every path that needs the co-resident panel kernel (several sub-panels per read, the one-launch read, the guessed first panel)
+// is gated on this: the kernel is switched on and a row of X (Fp frames) fits its registers
+static bool coop_fits(const asb_ctx* ctx) { return ctx->panel_coop && ctx->Fp <= ASB_COOP_MAX_FP; }
 static void print_multi_timeline(asb_ctx* ctx, int nsteps) {
     unsigned long long tl[64 * 6];
     (void)hipMemcpy(tl, ctx->coop_bar + 4, sizeof(tl), hipMemcpyDeviceToHost);
@@ -3132,7 +3041,7 @@ extern "C" int asb_panel_run(asb_ctx* ctx, int64_t k0, int steps, int global_all
     if ((rc = asb_alloc(ctx, &ctx->slab_scratch, (size_t)3 * ctx->Fp))) return rc;
     int cgrid_all = 0;
     size_t n_words = 0;
-    const bool want_coop = ctx->panel_coop && ctx->Fp <= 2048;
+    const bool want_coop = coop_fits(ctx);
     if (want_coop && (rc = coop_buffers(ctx, &cgrid_all, &n_words))) return rc;
     const long long spec_max = want_coop && !global_all ? ctx->run_spec_max : 0;
     hipLaunchKernelGGL(k_panel_arm, dim3(1), dim3(256), 0, ctx->stream, ctx->pstate, ctx->scalar_dev, global_all,
@@ -3350,6 +3259,7 @@ extern "C" int asb_panel_set_coop(asb_ctx* ctx, int on) {
     return old;
 }
 extern "C" int64_t asb_panel_capacity(const asb_ctx* ctx) { return ctx ? ctx->m_cap : 0; }
+extern "C" int asb_panel_coop_possible(const asb_ctx* ctx) { return ctx && coop_fits(ctx) ? 1 : 0; }
 extern "C" int64_t asb_panel_target(const asb_ctx* ctx) { return ctx ? (ctx->m_target_eff ? ctx->m_target_eff : ctx->m_target) : 0; }
 
 // ---- double panels (ASB_DOUBLE_PANELS=1, experimental): TWO sub-panels of up to 16 steps on the same candidate rows (the
@@ -3942,7 +3852,7 @@ static int double_panel(asb_ctx* ctx, long long k, long long k1, int64_t* done_o
     for (int sp = 0; sp < ASB_MAX_SUB; ++sp) kb[sp] = k + (long long)sp * ASB_PANEL_COLS;
     int ntile = 0, spec_ntile = 0, spec_nc[ASB_MAX_SUB] = {0};
     bool chained_runs = false;
-    if (ctx->sub_chain && ctx->panel_coop && ctx->spec_panels && ctx->Fp <= 2048 && nsub_max > 1) {
+    if (ctx->sub_chain && coop_fits(ctx) && ctx->spec_panels && nsub_max > 1) {
         int nt = -1;
         if ((rc = multi_chain_run(ctx, k, k1, nsub_max, &nt, nc, proven, &spec_ntile, spec_nc))) return rc;
         if (nt == 0) return ASB_OK;                      // nothing committed: the caller's refresh / forced path
@@ -4050,6 +3960,7 @@ static int double_panel(asb_ctx* ctx, long long k, long long k1, int64_t* done_o
     if (rejected) ctx->sub_cur = full + 1 < nsub_lim ? full + 1 : nsub_lim;
     else if (ntile == nsub_max) ctx->sub_cur = 2 * nsub_max < nsub_lim ? 2 * nsub_max : nsub_lim;
     if (total > 0) ctx->k_done = k + total;
+    if (total > ctx->max_read_kept) ctx->max_read_kept = total;
     // Structured data: the ranking reshuffled under this read's candidates.  The columns of its rejected steps are a sketch
     // of the residual of EVERY vertex (asb_sketch.hip): a greedy replay in that space names the next read's candidates, and
     // the next read gets all its sub-panels again (its rejected columns are the sketch after it).
@@ -4296,7 +4207,7 @@ extern "C" int asb_panel_read_run(asb_ctx* ctx, int64_t k0, int64_t k1, int nsub
     if (!ctx || !ctx->candR || !ctx->energy || ctx->mode != ASB_DEFLATE_PROJECT || !words_dev || !ntile_out || !nc_out || !proven_out)
         return ASB_ERR_ARG;
     if (k0 < 0 || k1 > ctx->K || k0 >= k1 || nsub_max < 1) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_panel_read_run: bad range");
-    if (!(ctx->panel_coop && ctx->spec_panels && ctx->Fp <= 2048 && ctx->pre_orth && ctx->correct_rows))
+    if (!(coop_fits(ctx) && ctx->spec_panels && ctx->pre_orth && ctx->correct_rows))
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_panel_read_run needs the co-resident panel kernel (and F <= 2048)");
     int rc;
     if ((rc = asb_alloc(ctx, &ctx->Wt3, (size_t)ASB_MAX_SUB * ctx->Fp * 16))) return rc;
@@ -4419,6 +4330,7 @@ extern "C" int asb_panel_read_commit(asb_ctx* ctx, const double* words, int64_t*
         if (keep[ct] < ctx->rd_nc[ct]) rejected = true; else ++full;
     }
     if (total > 0) ctx->k_done = ctx->rd_k0 + total;
+    if (total > ctx->max_read_kept) ctx->max_read_kept = total;
     *total_out = total;
     if (full_out) *full_out = full;
     if (rejected_out) *rejected_out = rejected ? 1 : 0;
@@ -4427,7 +4339,7 @@ extern "C" int asb_panel_read_commit(asb_ctx* ctx, const double* words, int64_t*
 
 // ---- guessed candidates of a first panel (see asb_project_run)
 static bool guess_possible(const asb_ctx* ctx) {
-    return ctx->first_panel_mean && ctx->spec_panels && ctx->panel_coop && ctx->Fp <= 2048 && ctx->EV && ctx->ev_valid && ctx->e0_valid &&
+    return ctx->first_panel_mean && ctx->spec_panels && coop_fits(ctx) && ctx->EV && ctx->ev_valid && ctx->e0_valid &&
            ctx->n_energy_pass == 0 && ctx->m_target >= 256 && ctx->n_loc > ctx->m_cap;
 }
 // thresholds of the scores EV + g (E - EV) into sc[SC_TAUG ..]: about mq[q] / world of this shard's vertices above each.
@@ -4651,7 +4563,7 @@ int asb_project_run(asb_ctx* ctx, int64_t k0, int64_t k1) {
     long long k = k0;
     int stalled = 0;
     const int global_all = ctx->n_loc <= ctx->m_cap;
-    const bool use_double = ctx->double_panels && !global_all && ctx->panel_coop && ctx->Fp <= 2048 && ctx->spec_panels;
+    const bool use_double = ctx->double_panels && !global_all && coop_fits(ctx) && ctx->spec_panels;
     while (k < k1) {
         ctx->sel_e2 = nullptr;
         // rows below k are final (projection mode never rewrites a committed column): their copy to the pinned buffer runs

@@ -23,6 +23,7 @@
 #include <vector>
 
 #define ASB_EPS 2.220446049250313e-16
+#define ASB_TRI_EXTRA 2          // inverse-iteration steps behind the growth criterion (k_tri_invit)
 
 // ======================================================================================================================
 // 1. symmetric tridiagonal eigen-problem
@@ -143,7 +144,10 @@ __global__ void k_tri_shifts(const double* __restrict__ lam_desc, int k, const d
 
 // Inverse iteration for vector v (thread v): Gaussian elimination with row interchanges of T - shift I (EISPACK TINVIT:
 // multipliers rv4, rows of U in rv1 / rv2 / rv3), then back substitution from a constant start vector, at most five
-// refinement steps, stop as soon as the iterate has grown to norm >= 1.  No re-orthogonalisation inside clusters: the
+// refinement steps until the iterate has grown to norm >= 1, then ASB_TRI_EXTRA more (as LAPACK's dstein).  The growth
+// criterion alone only bounds the residual by ~ n^1.5 eps |T| (start vector of 1-norm n eps |T|): 6e-13 at n = 1300, where
+// one more step from the nearly converged vector grows it by ~ 1 / |lambda - shift| and leaves a residual at eps |T| level.
+// No re-orthogonalisation inside clusters: the
 // caller only needs the SPAN of the vectors (Rayleigh-Ritz on the snapshot matrix follows) -- see DESIGN.md.
 // All per-vector arrays are interleaved: element i of vector v at [i * k + v].
 __global__ __launch_bounds__(64) void k_tri_invit(const double* __restrict__ d, const double* __restrict__ e, int n, int k,
@@ -199,7 +203,8 @@ __global__ __launch_bounds__(64) void k_tri_invit(const double* __restrict__ d, 
     }
     for (int i = 0; i < n; ++i) rv6[(size_t)i * k] = uk;
     bool ok = false;
-    for (int its = 0; its < 6 && !ok; ++its) {
+    int extra = 0;
+    for (int its = 0; its < 6 + ASB_TRI_EXTRA; ++its) {
         double bu = 0.0, bv = 0.0, nrm = 0.0;
         for (int i = n - 1; i >= 0; --i) {      // back substitution with U
             const size_t a = (size_t)i * k;
@@ -209,8 +214,13 @@ __global__ __launch_bounds__(64) void k_tri_invit(const double* __restrict__ d, 
             bu = x;
             nrm += fabs(x);
         }
-        if (nrm >= 1.0) { ok = true; break; }
-        if (its == 5) break;
+        if (ok && !(nrm < DBL_MAX)) break;      // (an extra step overflowed: flagged below)
+        if (nrm >= 1.0) {
+            ok = true;
+            if (extra++ == ASB_TRI_EXTRA) break;
+        } else if (ok || its >= 5) {
+            break;
+        }
         if (nrm == 0.0 || !(nrm == nrm)) {      // exactly orthogonal start (or overflow): a unit vector instead
             for (int i = 0; i < n; ++i) rv6[(size_t)i * k] = 0.0;
             rv6[(size_t)(its % n) * k] = eps4;

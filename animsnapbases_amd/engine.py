@@ -297,6 +297,10 @@ class HipEngine(object):
     def panel_capacity(self):
         return int(self.lib.asb_panel_capacity(self.h))
 
+    def panel_coop_possible(self):
+        """Whether the co-resident panel kernel can run on this context (switched on and F <= 2048)."""
+        return bool(self.lib.asb_panel_coop_possible(self.h))
+
     def panel_row_len(self):
         return 3 * ((self.F + 15) // 16 * 16)
 
@@ -400,9 +404,11 @@ class HipEngine(object):
         self._ck(self.lib.asb_deflate_sketch_stats(self.h, ctypes.byref(h), ctypes.byref(i)))
         j = ctypes.c_int64()
         self._ck(self.lib.asb_deflate_switch_stats(self.h, ctypes.byref(j)))
+        l, m = ctypes.c_int64(), ctypes.c_int64()
+        self._ck(self.lib.asb_deflate_read_stats(self.h, ctypes.byref(l), ctypes.byref(m)))
         return dict(panels=a.value, refreshes=b.value, unproven_tried=c.value, unproven_kept=d.value, energy_passes=e.value,
                     coop_fallbacks=f.value, guessed_panels=g.value, sketch_runs=h.value, sketch_reads=i.value,
-                    residual_switch_at=j.value)
+                    residual_switch_at=j.value, coop_launches=l.value, max_read_kept=m.value)
 
     def project_switch_residual(self, k):
         """The run leaves the projection mode at component k and continues in the residual loop (asb.h)."""
@@ -637,6 +643,19 @@ class HipEngine(object):
         sig, sw = np.empty(nv), ctypes.c_int64()
         self._ck(self.lib.asb_test_jacobi_rows(self.h, ptr(A), nv, m, ptr(U), ptr(sig), ctypes.byref(sw)))
         return U, sig, sw.value
+
+    def test_project_columns(self, W, k0, ncols, out, col_scale=None, path=0):
+        """out[:ncols] = X . W[:, k0:k0 + ncols] / col_scale[k0:k0 + ncols] through the 16-column (path 0) or the multi-tile
+        (path 1) projection kernels; W (F, ldw); out (out_cols, 3 n_loc) is updated in place, all of it round-trips."""
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        assert W.ndim == 2 and W.shape[0] == self.F
+        assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape[1] == 3 * self.n_loc
+        if col_scale is not None:
+            col_scale = np.ascontiguousarray(col_scale, dtype=np.float64)
+            assert col_scale.shape == (W.shape[1],)
+        self._ck(self.lib.asb_test_project_columns(self.h, ptr(W), W.shape[1], int(k0), int(ncols), ptr(col_scale), int(path),
+                                                   ptr(out), out.shape[0]))
+        return out
 
     def test_chol_tinv(self, G):
         G = np.ascontiguousarray(G, dtype=np.float64)

@@ -166,6 +166,9 @@ int64_t asb_panel_target(const asb_ctx* ctx);
 int asb_panel_select(asb_ctx* ctx, int64_t k, int64_t forced_gidx, int global_all, double* rows_out_dev,
                      long long* idx_out_dev, int64_t* n_local, int* overflow);
 int64_t asb_panel_capacity(const asb_ctx* ctx);
+/* 1 if the co-resident panel kernel can run on this context (switched on, and F <= 2048 so that a candidate row fits its
+ * registers), else 0.  Several sub-panels per read and asb_panel_read_run need it; a driver asks before taking them. */
+int asb_panel_coop_possible(const asb_ctx* ctx);
 /* replicated candidate buffer from the all-gathered padded pieces:
  * rows_g_dev (world, maxcount, 3, Fp), idx_g_dev (world, maxcount), counts (host, world) */
 int asb_panel_assemble(asb_ctx* ctx, const double* rows_g_dev, const long long* idx_g_dev,
@@ -215,6 +218,9 @@ int asb_deflate_coop_fallbacks(asb_ctx* ctx, int64_t* n);
  * like any others (asb_deflate_spec_stats), so the sequence is still that of posComponents.py:75-77.  *n = 1 if the last
  * run did so.  ASB_FIRST_PANEL_MEAN=0 switches it off. */
 int asb_deflate_guessed_panels(asb_ctx* ctx, int64_t* n);
+/* Of the last run: launches of the co-resident panel kernel (0 when F > 2048: every panel took the two-kernel loop), and
+ * the most components one read of X committed over all its sub-panels (above 64: more than four tiles in one read). */
+int asb_deflate_read_stats(asb_ctx* ctx, int64_t* coop_launches, int64_t* max_read_kept);
 /* Structured data (every component removes a direction all vertices share): the energies at the start of a read no longer
  * say who wins a few steps later, and its pass rejects most of its unproven steps.  The coefficient columns of those rejected
  * steps are a rank-r sketch of every vertex's residual; a greedy replay of posComponents.py:76-96 in that space (asb_sketch.hip:
@@ -544,6 +550,12 @@ int asb_test_sketch_predict(asb_ctx* ctx, const double* cols, const double* wn2,
 /* test hook: inverse of a host symmetric positive definite matrix (n x n) through the device's blocked
  * Gauss-Jordan / f64-MFMA GEMM path that the device geodesics use for their two SPD systems */
 int asb_test_spd_inverse(asb_ctx* ctx, const double* A_host, int64_t n, double* Ainv_host);
+/* test hook: out (out_cols x 3 n_loc, host, in and out) gets, in columns j < ncols, X . W[:, k0 + j] / col_scale[k0 + j] -- X the
+ * uploaded snapshots (row 3 v + d of the shard), W (F x ldw, host, frame-major), col_scale (ldw, host; NULL: 1).  All of `out`
+ * travels to the device and back, so a write beyond the ncols columns shows.  path 0: the 16-column kernel, one pass per 16
+ * columns; path 1: the multi-tile kernels in one pass (ceil(ncols / 16) tiles, ncols <= 128; ASB_WIDE_VARIANT applies). */
+int asb_test_project_columns(asb_ctx* ctx, const double* W_host, int64_t ldw, int64_t k0, int ncols, const double* col_scale_host,
+                             int path, double* out_host, int64_t out_cols);
 
 #ifdef __cplusplus
 }
