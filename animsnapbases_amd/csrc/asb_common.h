@@ -271,6 +271,18 @@ struct asb_ctx {
     long long* deim_pt = nullptr;
     double *eig_lam = nullptr, *eig_v = nullptr;  // asb_sym_eig_topk: eigenvalues (n, descending), leading vectors (n x k)
     int64_t eig_n = 0, eig_k = 0;
+    // reconstruction-error sweeps and the held-out animation (asb_recon.hip)
+    double* rc_part = nullptr;        // per-block partials of asb_recon_sweep + the reduced row
+    int* rc_ks = nullptr;             // sweep points
+    int64_t ho_F = 0, ho_Fp = 0;      // held-out frames, padded to 16
+    int64_t ho_K = 0;                 // components the held-out factor was built for (0: none yet)
+    double* ho_Y = nullptr;           // (3*n_loc, ho_Fp) held-out tensor, transformed like X
+    double* ho_Ct = nullptr;          // (3*n_loc, K) transposed basis for the Gram products
+    double *ho_P = nullptr, *ho_G = nullptr;      // Y C^T (ho_F x K), C C^T (K x K) when the caller passes no buffers
+    double* ho_T = nullptr;           // (K, K) L^-1, rows of dependent components zero
+    double* ho_Q = nullptr;           // (K, 3*n_loc) Q = L^-1 C
+    double* ho_Zt = nullptr;          // (K, ho_Fp) Z^T = L^-1 P^T
+    double* ho_W = nullptr;           // (ho_F, K) least-squares weights on the components
 
     // ---- profiling of the dominant streaming kernel ----
     bool prof = false;

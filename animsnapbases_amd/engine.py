@@ -420,6 +420,43 @@ class HipEngine(object):
         self._ck(self.lib.asb_deflate_download_residual(self.h, ptr(out)))
         return out
 
+    # ------------------------------------------------------------------ reconstruction errors / held-out projection
+    def recon_sweep(self, which, ks):
+        """One read of the training (which 0) or held-out (1) tensor for all sweep points ``ks``: this shard's
+        (S, 3) squared errors per axis, (S,) largest |error| and [sum T_x^2, sum T_y^2, sum T_z^2, max T]."""
+        ks = np.ascontiguousarray(ks, dtype=np.int64)
+        S = ks.shape[0]
+        sums, mx, norms = np.empty((S, 3)), np.empty(S), np.empty(4)
+        self._ck(self.lib.asb_recon_sweep(self.h, int(which), ptr(ks), S, ptr(sums), ptr(mx), ptr(norms)))
+        return sums, mx, norms
+
+    def heldout_upload(self, Y, massL, subtract, pre_scale_factor):
+        """Y: host (F', N_glob, 3); this engine's vertex shard is taken from it and transformed like the training tensor."""
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        F, N, three = Y.shape
+        assert three == 3
+        if massL is not None:
+            massL = np.ascontiguousarray(massL, dtype=np.float64)
+            assert massL.shape == (N,)
+        self._ck(self.lib.asb_heldout_upload(self.h, ptr(Y), F, N, self.v0, self.n_loc, ptr(massL), int(bool(subtract)),
+                                             float(pre_scale_factor)))
+        self.F_heldout = F
+
+    def heldout_gram(self, P_dev_ptr=None, G_dev_ptr=None):
+        self._ck(self.lib.asb_heldout_gram(self.h, ctypes.c_void_p(P_dev_ptr) if P_dev_ptr else None,
+                                           ctypes.c_void_p(G_dev_ptr) if G_dev_ptr else None))
+
+    def heldout_factor(self, P_dev_ptr=None, G_dev_ptr=None):
+        n = ctypes.c_int64()
+        self._ck(self.lib.asb_heldout_factor(self.h, ctypes.c_void_p(P_dev_ptr) if P_dev_ptr else None,
+                                             ctypes.c_void_p(G_dev_ptr) if G_dev_ptr else None, ctypes.byref(n)))
+        return n.value
+
+    def heldout_weights(self):
+        out = np.empty((self.F_heldout, self.K))
+        self._ck(self.lib.asb_heldout_weights(self.h, ptr(out)))
+        return out
+
     # ------------------------------------------------------------------ SPLOCS
     def splocs_begin(self):
         self._ck(self.lib.asb_splocs_begin(self.h))

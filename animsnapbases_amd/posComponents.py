@@ -23,6 +23,7 @@ from .utils import log_time, store_components, testSparsity, test_linear_depende
 
 
 SMALL_TENSOR_BYTES = 256 << 20
+SWEEP_POINTS_PER_READ = 1024      # asb_recon_sweep: sweep points per read of the tensor
 
 
 def n_loc_of(snaps):
@@ -414,18 +415,97 @@ class posComponents:  # Components == bases
 
     @log_time("")
     def test_convergence(self, start, end, step, writer=None):
-        """posComponents.py:191-214."""
-        snapshots = self.pos_snapshots.snapTensor.copy()
-        fro_err, rel_err_x, rel_err_y, rel_err_z, max_err = [], [], [], [], []
-        for k in range(start, end + 1, step):
-            reconstructed = tensordot(self.weigs[:, :k], self.comps[:k, :, :], axes=([1], [0]))
-            fro_err.append(self.frobenius_error(snapshots, reconstructed))
-            rel_err = self.relative_error_per_component(snapshots, reconstructed)
-            rel_err_x.append(rel_err[0])
-            rel_err_y.append(rel_err[1])
-            rel_err_z.append(rel_err[2])
-            max_err.append(self.max_pointwise_error(snapshots, reconstructed))
-        return fro_err, max_err, rel_err_x, rel_err_y, rel_err_z
+        """posComponents.py:191-214 on the device: ``reconstruction_errors(start, end, step, "train")`` (one read of the
+        prepared tensor in HBM; ``snapTensor`` is not downloaded and no (F, N, 3) reconstruction is formed)."""
+        return self.reconstruction_errors(start, end, step, "train")
+
+    # ------------------------------------------------------------------ extras: reconstruction errors, held-out projection
+    def _device_basis(self):
+        """The current basis in HBM (a basis assigned through the ``comps`` setter is uploaded first); returns K."""
+        snaps = self.pos_snapshots
+        eng, comm = snaps._engine, snaps._comm
+        if not self._comps_on_device:
+            if self._comps is None:
+                raise ValueError("no components: run compute_components_store_singvalues first")
+            C = np.asarray(self._comps, dtype=np.float64)
+            if C.ndim != 3 or C.shape[1:] != (snaps.nVerts, 3):
+                raise ValueError("components of shape %s do not match the %d vertices of the snapshots"
+                                 % (C.shape, snaps.nVerts))
+            v0, n_loc = snaps._shards[comm.rank]
+            eng.components_upload(np.ascontiguousarray(C[:, v0:v0 + n_loc, :]))
+            self._comps_on_device = True
+            self._comps_streamed = False
+        return eng.K
+
+    def _heldout_prepare(self, verts):
+        """Uploads a held-out (F', N, 3) animation, transforms it like the training tensor and factorises the Gram
+        products of the current basis (sums over the ranks); returns the number of dependent components dropped."""
+        snaps = self.pos_snapshots
+        eng, comm = snaps._engine, snaps._comm
+        if verts is None:
+            raise ValueError("no test animation (pos_snapshots.test_verts is None)")
+        Y = np.asarray(verts, dtype=np.float64)
+        if Y.ndim != 3 or Y.shape[1:] != (snaps.nVerts, 3) or Y.shape[0] < 1:
+            raise ValueError("held-out animation of shape %s: (F', %d, 3) expected" % (Y.shape, snaps.nVerts))
+        self._device_basis()
+        eng.heldout_upload(Y, snaps.massL, snaps._standarize, snaps.pre_scale_factor)
+        Pbuf = Gbuf = None
+        if comm.multi:
+            Pbuf, Gbuf = comm.new_gram_buffers(Y.shape[0], eng.K, eng.device_exchange)
+        eng.heldout_gram(Pbuf.data_ptr() if Pbuf is not None else None, Gbuf.data_ptr() if Gbuf is not None else None)
+        if comm.multi:                 # partial Gram products: all-reduce (sum) over the ranks
+            comm.allreduce_tensor(Pbuf)
+            comm.allreduce_tensor(Gbuf)
+        return eng.heldout_factor(Pbuf.data_ptr() if Pbuf is not None else None, Gbuf.data_ptr() if Gbuf is not None else None)
+
+    def reconstruction_errors(self, start, end, step, animation="train"):
+        """Extra (not in the reference): the error-against-k sweep of ``test_convergence`` (posComponents.py:192-249) for
+        k in range(start, end + 1, step), as the same five lists ``fro_err, max_err, rel_err_x, rel_err_y, rel_err_z``.
+
+        ``animation``: "train" -- the prepared training tensor with the greedy ``weigs`` and the current ``comps``, the
+        reference's arithmetic; "test" -- ``pos_snapshots.test_verts``; or an (F', N, 3) ndarray.  A held-out animation is
+        transformed like the training tensor (mass weighting, training mean row, training pre_scale_factor) and
+        reconstructed with its least-squares weights on the first k components (the joint fit over all 3N coordinates).
+        k = 0 gives the errors of the tensor itself.  Every rank returns the same lists."""
+        snaps = self.pos_snapshots
+        eng, comm = snaps._engine, snaps._comm
+        if isinstance(animation, str) and animation not in ("train", "test"):
+            raise ValueError("animation must be 'train', 'test' or an (F', N, 3) array, not %r" % animation)
+        K = self._device_basis()
+        if start < 0 or step < 1 or end > K:
+            raise ValueError("range(%d, %d + 1, %d) is not a sweep over the %d components" % (start, end, step, K))
+        train = isinstance(animation, str) and animation == "train"
+        if train:
+            if self.weigs is None or end > self.weigs.shape[1]:
+                raise ValueError("no greedy weights for k = %d: run compute_components_store_singvalues first" % end)
+        else:
+            self._heldout_prepare(snaps.test_verts if isinstance(animation, str) else animation)
+        ks = np.arange(start, end + 1, step, dtype=np.int64)
+        S = ks.shape[0]
+        if S == 0:
+            return [], [], [], [], []
+        sums, mx = np.empty((S, 3)), np.empty(S)
+        norms = None
+        for s0 in range(0, S, SWEEP_POINTS_PER_READ):
+            s1 = min(S, s0 + SWEEP_POINTS_PER_READ)
+            sums[s0:s1], mx[s0:s1], norms = eng.recon_sweep(0 if train else 1, ks[s0:s1])
+        sums = comm.allreduce_sum(sums.reshape(-1)).reshape(S, 3)
+        mx = comm.allreduce_max(mx)
+        n2 = comm.allreduce_sum(norms[:3])
+        tmax = comm.allreduce_max(norms[3:])[0]
+        with errstate(divide='ignore', invalid='ignore'):
+            fro_err = np.sqrt(sums.sum(axis=1))
+            rel = np.sqrt(sums) / np.sqrt(n2)[None, :]
+            max_err = mx / tmax
+        return fro_err.tolist(), max_err.tolist(), rel[:, 0].tolist(), rel[:, 1].tolist(), rel[:, 2].tolist()
+
+    def project_animation(self, verts=None):
+        """Extra (not in the reference): the (F', K) least-squares weights of an (F', N, 3) animation (None: the test
+        animation, ``pos_snapshots.test_verts``) on the current basis, in the standardised, mass-weighted space of the
+        training tensor: W = P G^-1 with P = Y C^T, G = C C^T.  A component that depends on the earlier ones gets weight 0."""
+        snaps = self.pos_snapshots
+        self._heldout_prepare(snaps.test_verts if verts is None else verts)
+        return snaps._engine.heldout_weights()
 
     @staticmethod
     def frobenius_error(f, f_reconstructed):

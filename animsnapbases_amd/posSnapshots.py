@@ -61,12 +61,14 @@ class posSnapshots:
     # ------------------------------------------------------------------ construction helpers
     @classmethod
     def from_arrays(cls, verts, tris, rest_shape="first", masses_file="", standarize=True, massWeight=False,
-                    engine=None, comm=None, mass=None):
-        """In-memory construction (no animation files): ``verts`` (F,N,3), ``tris`` (M,3) or None."""
+                    engine=None, comm=None, mass=None, test_verts=None):
+        """In-memory construction (no animation files): ``verts`` (F,N,3), ``tris`` (M,3) or None; ``test_verts``: the
+        held-out (F',N,3) animation (posSnapshots.py:119-121), or None."""
         self = cls.__new__(cls)
         self._preset_mass = mass
         cls.__init__(self, None, None, rest_shape, masses_file, None, standarize, massWeight,
-                     verts=np.asarray(verts), tris=tris, engine=engine, comm=comm)
+                     verts=np.asarray(verts), tris=tris, engine=engine, comm=comm,
+                     test_verts=None if test_verts is None else np.asarray(test_verts))
         return self
 
     @classmethod
@@ -103,6 +105,7 @@ class posSnapshots:
     @log_time("")
     def do_snapshots_precomputations(self, standarize, massWeight):
         """posSnapshots.py:64-105."""
+        self._standarize = bool(standarize)     # (the held-out animation of posComponents.reconstruction_errors repeats it)
         self.read()
         if self._engine is None:
             dev, stream = 0, None

@@ -499,6 +499,33 @@ int asb_energy_block_argmax(asb_ctx* ctx, int p, int64_t* block_out, double* val
 /* V[gidx, :, :] -> row_out (K, 3); returns 1 (and writes nothing) when another rank owns gidx */
 int asb_deim_row(asb_ctx* ctx, int64_t gidx, double* row_out);
 
+/* ------------------------------------- reconstruction errors / held-out projection ---- */
+/* posComponents.test_convergence, snapbases/posComponents.py:192-249, without forming a reconstruction: ONE read of the
+ * tensor per call.  which 0: the training tensor X with the greedy weights (W of the deflation) and the device-resident
+ * basis, tensordot(weigs[:, :k], comps[:k]) (:196-197); which 1: the held-out tensor of asb_heldout_upload with the
+ * least-squares prefix weights of asb_heldout_factor.  ks: S strictly increasing sweep points 0 <= k_1 < ... <= K
+ * (S <= 1024).  This shard's partial values: sums_out (S x 3) sum_{f,v} (T_d - R_k,d)^2 per axis (:217-237),
+ * max_out (S) max |T - R_k| (:239-249), norms_out (4) sum T_x^2, sum T_y^2, sum T_z^2 and the SIGNED max T (np.max(f)).
+ * Deterministic (fixed-order reductions, no atomics).  Any output pointer may be NULL. */
+int asb_recon_sweep(asb_ctx* ctx, int which, const int64_t* ks, int64_t S, double* sums_out, double* max_out,
+                    double* norms_out);
+/* The test animation of posSnapshots.py:119-121 (test_verts), host (F, N_glob, 3): vertices [v0, v0+n_loc) of this shard
+ * (the training shard), transformed exactly as the training tensor was (:82, :168, :172): times massL[v0+v] when massL !=
+ * NULL, minus the TRAINING mean row when subtract != 0, times the training pre_scale_factor.  F may differ from the
+ * training F. */
+int asb_heldout_upload(asb_ctx* ctx, const double* Y, int64_t F, int64_t N_glob, int64_t v0, int64_t n_loc,
+                       const double* massL, int subtract, double pre_scale_factor);
+/* P = Y C^T (F x K) and G = C C^T (K x K) of this shard for the current basis, into the caller's device buffers (to be
+ * all-reduced over ranks) or into the context when NULL -- the products of asb_splocs_gram. */
+int asb_heldout_gram(asb_ctx* ctx, double* P_dev, double* G_dev);
+/* With the (summed) P, G (NULL: the context's own): G = L L^T on the host, Q = L^-1 C and Z = P L^-T on the device, so
+ * that the projection of Y onto span(c_0 .. c_k-1) is Z[:, :k] Q[:k] for every prefix k.  A pivot <= 3 N eps trace(G)
+ * marks a component dependent on the earlier ones: its row of Q and column of Z are zero (span and errors unchanged).
+ * n_dropped (optional): how many were dropped. */
+int asb_heldout_factor(asb_ctx* ctx, const double* P_dev, const double* G_dev, int64_t* n_dropped);
+/* the least-squares weights of the held-out frames on the components, W = Z L^-1 (host, F x K; 0 for dropped ones) */
+int asb_heldout_weights(asb_ctx* ctx, double* W_out);
+
 /* ------------------------------------------------ SPLOCS refinement ----------- */
 /* posComponents.splocs_glob_optimization, snapbases/posComponents.py:132-189.
  * State after a residual-mode deflation: C = comps, W = weigs, U = 0 (:135-139).  One outer
