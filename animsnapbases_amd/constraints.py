@@ -31,6 +31,9 @@ from .distributed import Comm
 from .engine import HipEngine
 from .utils import log_time, summed_grams, testSparsity, test_linear_dependency, test_linear_dependency_grams
 
+INTERP_SWEEP_POINTS = 64               # asb_interp_sweep: sweep points per read of the tensor
+INTERP_COEF_BYTES = 512 << 20          # ... and at most this much of their coefficients (3 rp F doubles per point) in HBM
+
 
 def read_sparse_matrix(file_name, file_type, key=None):
     """The sparse operator files of the reference (utils/utils.py:289-323): ``.npz`` holding a pickled scipy matrix under
@@ -1100,6 +1103,133 @@ class constraintsComponents:  # Components == bases
             u, piv = lu_factor(VPt[:, :, l].T @ VPt[:, :, l])
             coef[l] = lu_solve((u, piv), VPt[:, :, l].T @ np.ascontiguousarray(frames[:, Pt, l]).T)
         return eng.components_expand(coef)
+
+    # ------------------------------------------------------------------ extras: interpolation-error sweeps
+    def interpolation_errors(self, r_values, case="train"):
+        """Extra (not in the reference): the convergence test of run_geom_tests (generate_figures/nl_reduction_tests.py:117-225)
+        -- for every r of ``r_values`` the ``geom_constructed(r, case)`` reconstruction and its ``frobenius_error``,
+        ``max_pointwise_error`` and ``relative_error_per_component`` (constraintsComponents.py:489-556) -- as five lists
+        ``fro, max, rel_x, rel_y, rel_z``, without forming a reconstruction.  "train": the prepared tensor in HBM (what
+        ``snapTensor`` returns, post-processing included), never downloaded; "test": ``test_snapTensor`` as given (the reference
+        never transforms it), uploaded once.  The rows at the interpolation points are gathered on the device (and exchanged
+        between ranks), the small normal equations are solved on the host by LU as the reference does, and one read of the
+        tensor per chunk of sweep points does the rest (asb_interp_sweep).  Every rank returns the same lists."""
+        from scipy.linalg import lu_factor, lu_solve
+        ns = self.nonlinearSnapshots
+        eng, comm = ns._engine, ns._comm
+        if case not in ("train", "test"):
+            raise ValueError("unknown frames to reconstruct: %r ('train' or 'test')" % (case,))
+        r_values = [int(r) for r in r_values]
+        if not r_values:
+            return [], [], [], [], []
+        K = int(self.numComp)
+        for r in r_values:
+            if r < 1 or r > K:
+                raise ValueError("r = %d is outside 1..%d" % (r, K))
+        ranges = self.geom_alpha_ranges
+        if ranges is None or len(ranges) == 0:
+            raise ValueError("no interpolation points: run deim() or a block interpolation first")
+        ranges = np.asarray(ranges, dtype=np.int64)
+        kind = getattr(self.param, "constProj_bases_interpolation_type", "")
+        p = int(ns.constraintsSize) if kind in ("geom", "deim_block_form") else 1
+        pts = self.geom_Pt if getattr(self.param, "constProj_snapshots_type", "") == "verts_bending" else self.geom_alpha
+        rp = np.array([r * p for r in r_values], dtype=np.int64)
+        npt = np.empty(len(r_values), dtype=np.int64)
+        for s, r in enumerate(r_values):
+            if r > ranges.shape[0]:
+                raise ValueError("r = %d: interpolation points exist for r <= %d only" % (r, ranges.shape[0]))
+            npt[s] = ranges[r - 1]
+            if npt[s] < rp[s]:
+                raise ValueError("r = %d: %d interpolation rows for %d basis vectors: the normal matrix is singular"
+                                 % (r, npt[s], rp[s]))
+        which = 0
+        if case == "test":
+            Y = ns.test_snapTensor
+            if Y is None:
+                raise ValueError("no test frames (test_snapTensor is None)")
+            Y = np.asarray(Y, dtype=np.float64)
+            if Y.ndim != 3 or Y.shape[0] < 1 or Y.shape[1:] != (ns.frames_rows, 3):
+                raise ValueError("test frames of shape %s: (F', %d, 3) expected" % (Y.shape, ns.frames_rows))
+        if not self._comps_on_device:
+            v0, n_loc = ns._shards[comm.rank]
+            eng.components_upload(np.ascontiguousarray(self._comps[:, v0:v0 + n_loc, :]))
+            self._comps_on_device = True
+        if int(rp.max()) > eng.K:
+            raise ValueError("r = %d needs %d basis vectors, the basis has %d" % (r_values[int(np.argmax(rp))], rp.max(), eng.K))
+        Pt = np.asarray(pts[:int(npt.max())], dtype=np.int64)
+        VPt = np.zeros((Pt.shape[0], eng.K, 3))               # V[Pt, :, :] from the ranks that own the rows
+        for i, g in enumerate(Pt):
+            row = eng.deim_row(int(g))
+            if row is not None:
+                VPt[i] = row
+        if case == "test":
+            eng.heldout_upload(Y, None, False, 1.0)
+            which = 1
+        B, _ = eng.rows_gather(which, Pt)                     # f[:, Pt, :] of this shard, (|Pt|, F, 3)
+        if comm.multi:
+            VPt = comm.allreduce_sum(VPt.reshape(-1)).reshape(VPt.shape)
+            B = comm.allreduce_sum(B.reshape(-1)).reshape(B.shape)
+        F = B.shape[1]
+        S = len(r_values)
+        sums, mx, norms = np.empty((S, 3)), np.empty(S), None
+        s0 = 0
+        while s0 < S:
+            s1, cbytes = s0, 0
+            while s1 < S and s1 - s0 < INTERP_SWEEP_POINTS and (s1 == s0 or cbytes + 24 * rp[s1] * F <= INTERP_COEF_BYTES):
+                cbytes += 24 * int(rp[s1]) * F
+                s1 += 1
+            M = []
+            for s in range(s0, s1):
+                n, k = int(npt[s]), int(rp[s])
+                for l in range(3):
+                    A = VPt[:n, :k, l]          # (the slices geom_constructed multiplies: the same A^T A)
+                    M.append(lu_solve(lu_factor(A.T @ A), A.T).reshape(-1))        # (A^T A)^-1 A^T, (k, n)
+            sums[s0:s1], mx[s0:s1], norms = eng.interp_sweep(which, rp[s0:s1], npt[s0:s1], np.concatenate(M), B)
+            s0 = s1
+        sums = comm.allreduce_sum(sums.reshape(-1)).reshape(S, 3)
+        mx = comm.allreduce_max(mx)
+        n2 = comm.allreduce_sum(norms[:3])
+        fmax = comm.allreduce_max(norms[3:])[0]
+        with np.errstate(divide='ignore', invalid='ignore'):
+            fro = np.sqrt(sums.sum(axis=1))
+            rel = np.sqrt(sums) / np.sqrt(n2)[None, :]
+            max_err = mx / fmax
+        return fro.tolist(), max_err.tolist(), rel[:, 0].tolist(), rel[:, 1].tolist(), rel[:, 2].tolist()
+
+    def store_convergence_tests(self, steps=1):
+        """Extra (not in the reference): the three CSV files of run_geom_tests (generate_figures/nl_reduction_tests.py:117-225)
+        from ``interpolation_errors`` -- <name>_<constProj_name>_<interpolation>_<basis>_train_convergence_tests.csv and
+        _test_convergence_tests.csv (r in range(1, K + 1, steps)) and _num_interpol_elemnets.csv (every r in 1..K, the
+        figure script's outer r_values); no plots.  Rank 0 writes."""
+        p = self.param
+        ns = self.nonlinearSnapshots
+        K = int(self.numComp)
+        base = os.path.join(p.constProj_output_directory, p.name + "_" + p.constProj_name + "_" +
+                            p.constProj_bases_interpolation_type + "_" + p.constProj_basis_type)
+        r_values = list(range(1, K + 1, steps))
+        write = ns._comm.rank == 0
+        header = ['numPoints', 'fro_error', 'max_err', 'relative_errors_x', 'relative_errors_y', 'relative_errors_z',
+                  'relative3d']
+
+        def table(case, file):
+            fro, mx, rx, ry, rz = self.interpolation_errors(r_values, case)
+            if not write:
+                return
+            with open(file + '.csv', 'w', encoding='UTF8') as dataFile:
+                writer = csv.writer(dataFile)
+                writer.writerow(header)
+                for i, r in enumerate(r_values):
+                    rel = [np.float64(rx[i]), np.float64(ry[i]), np.float64(rz[i])]
+                    writer.writerow([r, np.float64(fro[i]), np.float64(mx[i]), rel[0], rel[1], rel[2], np.sum(rel) / 3])
+
+        table("train", base + "_train_convergence_tests")
+        if write:
+            with open(base + "_num_interpol_elemnets" + '.csv', 'w', encoding='UTF8') as dataFile2:
+                writer = csv.writer(dataFile2)
+                writer.writerow(['numPoints', 'num_elements'])
+                for r in range(1, K + 1):
+                    writer.writerow([r, self.geom_alpha_ranges[r - 1]])
+        table("test", base + "_test_convergence_tests")
 
     @log_time(constProj_output_directory)
     def store_components_gradually_to_files(self, start, end, step, fileType):

@@ -283,6 +283,14 @@ struct asb_ctx {
     double* ho_Q = nullptr;           // (K, 3*n_loc) Q = L^-1 C
     double* ho_Zt = nullptr;          // (K, ho_Fp) Z^T = L^-1 P^T
     double* ho_W = nullptr;           // (ho_F, K) least-squares weights on the components
+    // interpolation-error sweeps of constraint bases (asb_interp.hip)
+    long long* is_idx = nullptr;      // rows to gather
+    double* is_B = nullptr;           // (npt, F, 3) rows of the tensor at the interpolation points
+    double* is_M = nullptr;           // per sweep point (3, rp, npt): (A^T A)^-1 A^T
+    double* is_C = nullptr;           // per sweep point (3, rp, F): the coefficients
+    double* is_part = nullptr;        // per-block partials + the reduced row
+    long long* is_off = nullptr;      // C offsets per sweep point; M and C offsets per row of C
+    int* is_int = nullptr;            // rp per sweep point; npt and coordinate per row of C
 
     // ---- profiling of the dominant streaming kernel ----
     bool prof = false;

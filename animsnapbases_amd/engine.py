@@ -457,6 +457,31 @@ class HipEngine(object):
         self._ck(self.lib.asb_heldout_weights(self.h, ptr(out)))
         return out
 
+    # ------------------------------------------------------------------ interpolation-error sweeps (constraint bases)
+    def rows_gather(self, which, gidx):
+        """Rows ``gidx`` (global) of the snapshots (which 0) or of the held-out frames (1) as (n, F, 3), and a bool mask of
+        the rows this shard owns (the others are 0)."""
+        gidx = np.ascontiguousarray(gidx, dtype=np.int64)
+        n = gidx.shape[0]
+        F = self.F if which == 0 else self.F_heldout
+        out, owned = np.empty((n, F, 3)), np.empty(n, dtype=np.int32)
+        self._ck(self.lib.asb_rows_gather(self.h, int(which), ptr(gidx), n, ptr(out), ptr(owned)))
+        return out, owned.astype(bool)
+
+    def interp_sweep(self, which, rp, npt, M, B):
+        """One read of the tensor of ``which`` for the sweep points (rp[s], npt[s]); M: the concatenated (3, rp, npt)
+        matrices, B: (nb, F, 3).  This shard's (S, 3) squared errors per axis, (S,) largest |error| and
+        [sum f_x^2, sum f_y^2, sum f_z^2, max f]."""
+        rp = np.ascontiguousarray(rp, dtype=np.int64)
+        npt = np.ascontiguousarray(npt, dtype=np.int64)
+        M = np.ascontiguousarray(M, dtype=np.float64)
+        B = np.ascontiguousarray(B, dtype=np.float64)
+        S = rp.shape[0]
+        sums, mx, norms = np.empty((S, 3)), np.empty(S), np.empty(4)
+        self._ck(self.lib.asb_interp_sweep(self.h, int(which), ptr(rp), ptr(npt), S, ptr(M), ptr(B), B.shape[0], ptr(sums),
+                                           ptr(mx), ptr(norms)))
+        return sums, mx, norms
+
     # ------------------------------------------------------------------ SPLOCS
     def splocs_begin(self):
         self._ck(self.lib.asb_splocs_begin(self.h))

@@ -526,6 +526,23 @@ int asb_heldout_factor(asb_ctx* ctx, const double* P_dev, const double* G_dev, i
 /* the least-squares weights of the held-out frames on the components, W = Z L^-1 (host, F x K; 0 for dropped ones) */
 int asb_heldout_weights(asb_ctx* ctx, double* W_out);
 
+/* ----------------------------- interpolation-error sweeps of constraint bases ---- */
+/* The row analogue of asb_deim_row: frames[:, gidx, :] of this shard, gathered on the device.  which 0: the prepared
+ * snapshots X (nonlinearSnapshots.snapTensor, post-processing included); 1: the held-out frames of asb_heldout_upload
+ * (test_snapTensor, nonlinear_snapshots.py:115-122, uploaded raw: massL NULL, subtract 0, scale 1).  out (host, n x F x 3);
+ * a row another rank owns is 0 there and owned_out[i] = 0 (owned_out optional), so the rows of all ranks sum to frames[:, gidx]. */
+int asb_rows_gather(asb_ctx* ctx, int which, const int64_t* gidx, int64_t n, double* out, int* owned_out);
+/* nl_reduction_tests.run_geom_tests (generate_figures/nl_reduction_tests.py:117-225) for S <= 64 sweep points without forming a
+ * reconstruction: per point s, the geom_constructed reconstruction (constraintsComponents.py:489-521) from rp[s] basis vectors,
+ * V[:, :rp, l] C_{s,l} with C_{s,l} = M_{s,l} B_l[:npt[s]], formed on the device, and its errors against the tensor of `which`
+ * (as in asb_rows_gather).  M (host): per s in order, 3 x rp[s] x npt[s] doubles, M_{s,l} = (A^T A)^-1 A^T, A = V[Pt_s, :rp, l]
+ * (:515-519); B (host, nb x F x 3): the rows at the interpolation points, nb >= npt[s].  This shard's partial values: sums_out
+ * (S x 3) sum (f - rec)^2 per axis (:524-545), max_out (S) max |f - rec| (:547-556), norms_out (4) sum f_x^2, sum f_y^2,
+ * sum f_z^2 and the SIGNED max f (np.max(f)).  One read of the tensor per call; deterministic (fixed-order reductions, no
+ * atomics).  Any output pointer may be NULL. */
+int asb_interp_sweep(asb_ctx* ctx, int which, const int64_t* rp, const int64_t* npt, int64_t S, const double* M, const double* B,
+                     int64_t nb, double* sums_out, double* max_out, double* norms_out);
+
 /* ------------------------------------------------ SPLOCS refinement ----------- */
 /* posComponents.splocs_glob_optimization, snapbases/posComponents.py:132-189.
  * State after a residual-mode deflation: C = comps, W = weigs, U = 0 (:135-139).  One outer
