@@ -51,6 +51,15 @@ PROTOTYPES = {
     "asb_deflate_residual_norm2": (c_int, [ctypes.c_void_p, ctypes.POINTER(c_dbl)]),
     "asb_deim_block_residual_st": (c_int, [ctypes.c_void_p, c_i64, c_int, c_dp, ctypes.POINTER(c_dbl), ctypes.POINTER(c_i64),
                                            ctypes.POINTER(c_dbl)]),
+    "asb_st_upload_shard": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp, c_i64]),
+    "asb_st_halo_pack": (c_int, [ctypes.c_void_p, c_int, c_dp, c_i64, c_dp]),
+    "asb_st_halo_fill": (c_int, [ctypes.c_void_p, c_int, c_dp, c_dp, c_i64]),
+    "asb_st_halo_deflate": (c_int, [ctypes.c_void_p, c_i64]),
+    "asb_st_shard_residual_argmax": (c_int, [ctypes.c_void_p, ctypes.POINTER(c_i64), ctypes.POINTER(c_dbl)]),
+    "asb_deim_block_residual_st_shard": (c_int, [ctypes.c_void_p, c_i64, c_int, c_dp, ctypes.POINTER(c_dbl), ctypes.POINTER(c_i64),
+                                                 ctypes.POINTER(c_dbl)]),
+    "asb_st_shard_stats": (c_int, [ctypes.c_void_p, c_dp]),
+    "asb_st_halo_download": (c_int, [ctypes.c_void_p, c_int, c_dp]),
     "asb_deflate_reserve": (c_int, [ctypes.c_void_p, c_i64]),
     "asb_components_stream": (c_int, [ctypes.c_void_p, c_int]),
     "asb_components_stream_into": (c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i64]),

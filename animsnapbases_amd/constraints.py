@@ -14,9 +14,9 @@ interpolation solves (an O(k^2) bordered-inverse update whose residual is checke
 ``numpy.linalg.lstsq``, the routine the reference calls at constraintsComponents.py:829, is
 the fallback); LAPACK ``eigh`` on the Gram matrix only with ``ASB_POD_EIG=host``.
 
-Other basis types of the reference (``pod`` per-(p,d) torch SVD, ``pca_blocks``,
-``pca_blocks_with_St``, geometric / block DEIM, polyscope views) are out of scope
- and raise ``NotImplementedError``.
+The other basis types and interpolations of the reference (``pod`` per-(p,d) slices, ``pca_blocks``,
+``pca_blocks_with_St``, geometric / block DEIM) run on the device too; on several ranks all but ``pod``
+(which raises ``NotImplementedError`` there).
 """
 import csv
 import os
@@ -67,6 +67,49 @@ def vertex_star(v, faces):
     for f in faces[(faces == v).any(axis=1)]:
         star.update(int(q) for q in f)
     return list(star)
+
+
+def st_shard_plan(St, shards, rank):
+    """S^T with the constraint rows sharded in contiguous ranges ``shards`` [(v0, n), ...], for ``rank`` -- the same on every
+    rank.  A position vertex belongs to the rank holding the smallest column of its S^T row (rank 0 for an empty row); a
+    rank's halo is the sorted set of constraint rows its owned vertices reference on other ranks.  Returns a dict: ``owned``
+    (ascending vertex ids), the owned rows' CSR (``indptr``, ``slots``, ``data``; columns remapped to local slots, < n this
+    shard, n + i halo row i, each row in the global row's column order), ``halo``, ``halo_sizes`` (one per rank), ``send``
+    (the rows of this shard other ranks keep in their halo) and ``slot`` (where each halo row lands in the all-gather of every
+    rank's ``send`` rows, ``stride`` rows per rank)."""
+    St = St.tocsr()
+    St.sort_indices()
+    indptr = np.asarray(St.indptr, dtype=np.int64)
+    indices = np.asarray(St.indices, dtype=np.int64)
+    starts = np.array([v0 for v0, _ in shards], dtype=np.int64)
+    world = len(shards)
+    n_row = np.diff(indptr)
+    first = np.zeros(St.shape[0], dtype=np.int64)
+    has = n_row > 0
+    first[has] = indices[indptr[:-1][has]]
+    owner = np.where(has, np.searchsorted(starts, first, side="right") - 1, 0)
+    col_rank = np.searchsorted(starts, indices, side="right") - 1
+    ent_owner = np.repeat(owner, n_row)
+    foreign = col_rank != ent_owner
+    halos = [np.unique(indices[foreign & (ent_owner == r)]) for r in range(world)]
+    every = np.unique(indices[foreign])
+    send = [every[(every >= v0) & (every < v0 + n)] for v0, n in shards]
+    stride = max(1, max(len(q) for q in send))
+    halo = halos[rank]
+    src = np.searchsorted(starts, halo, side="right") - 1
+    slot = np.empty(halo.shape[0], dtype=np.int64)
+    for q in range(world):
+        m = src == q
+        slot[m] = q * stride + np.searchsorted(send[q], halo[m])
+    owned = np.flatnonzero(owner == rank).astype(np.int64)
+    sub = St[owned]
+    v0, n = shards[rank]
+    cols = np.asarray(sub.indices, dtype=np.int64)
+    mine = (cols >= v0) & (cols < v0 + n)
+    slots = np.where(mine, cols - v0, n + np.searchsorted(halo, cols))
+    return dict(owned=owned, indptr=np.asarray(sub.indptr, dtype=np.int64), slots=slots, data=np.asarray(sub.data, dtype=np.float64),
+                halo=halo, halo_sizes=[int(h.shape[0]) for h in halos], send=send[rank], slot=slot, stride=stride)
+
 
 constProj_output_directory = ""
 
@@ -331,6 +374,7 @@ class constraintsComponents:  # Components == bases
         self.geom_alpha_ranges = None
         self.geom_Pt = None
         self.St = None
+        self.st_halo_rows = None         # several ranks: the halo size (constraint rows kept as copies) of every rank
         self.singular_values = None
 
     @property
@@ -380,13 +424,53 @@ class constraintsComponents:  # Components == bases
         ns = self.nonlinearSnapshots
         if self.St is None:
             raise ValueError("the differential operator S^T is not set (constProj_weightedSt / costProj_St_key, or .St = ...)")
-        if ns._comm.multi:
-            raise NotImplementedError("the S^T variants run on one rank (every constraint row is needed for S^T R)")
         if self.St.shape[1] != ns.frames_rows:
             raise ValueError("S^T has %d columns, the snapshots %d constraint rows" % (self.St.shape[1], ns.frames_rows))
+        if ns._comm.multi:
+            # several ranks: the rows of S^T of the vertices this rank owns, over its shard and a halo of copied rows
+            if getattr(self, "_st_shard_uploaded", None) is not self.St:
+                plan = st_shard_plan(self.St, ns._shards, ns._comm.rank)
+                ns._engine.st_upload_shard(plan["indptr"], plan["slots"], plan["data"], plan["halo"].shape[0])
+                self._st_plan, self._st_shard_uploaded = plan, self.St
+                self.st_halo_rows = list(plan["halo_sizes"])
+            return
         if getattr(self, "_st_uploaded", None) is not self.St:
             ns._engine.st_upload(self.St)
             self._st_uploaded = self.St
+
+    def _st_halo_exchange(self, which):
+        """Fills this rank's halo copies -- which 0: rows of the residual (after deflate_begin), 1: rows of the device basis --
+        by one all-gather of the rows every rank's halo needs from every other."""
+        import torch
+        ns = self.nonlinearSnapshots
+        eng, comm = ns._engine, ns._comm
+        plan = self._st_plan
+        L = eng.xchg_len() - 2 if which == 0 else 3 * eng.K          # row length: 3 Fp / 3 K doubles
+        n = plan["stride"] * L
+        piece = comm.new_buffer(n, eng.device_exchange)
+        eng.st_halo_pack(which, plan["send"], piece.data_ptr())
+        every = comm.new_buffer(comm.world * n, eng.device_exchange)
+        comm.all_gather_into(every, piece)
+        torch.cuda.synchronize()
+        eng.st_halo_fill(which, every.data_ptr(), plan["slot"], comm.world * plan["stride"])
+
+    def _st_vertex_argmax(self, loc, val):
+        """The global first arg-max over the ranks' owned vertices (lowest vertex id among equal maxima)."""
+        vid = int(self._st_plan["owned"][loc]) if loc >= 0 else -1
+        return int(self.nonlinearSnapshots._comm.global_argmax(np.array([vid], dtype=np.int64), np.array([val]))[0])
+
+    def _basis_rows(self, gidx):
+        """V[gidx, :, :] (n, K, 3) on every rank: deim_row on the owner, all-reduced."""
+        ns = self.nonlinearSnapshots
+        eng, comm = ns._engine, ns._comm
+        out = np.zeros((len(gidx), eng.K, 3))
+        for i, g in enumerate(gidx):
+            row = eng.deim_row(int(g))
+            if row is not None:
+                out[i] = row
+        if comm.multi:
+            out = comm.allreduce_sum(out.reshape(-1)).reshape(out.shape)
+        return out
 
     @log_time(constProj_output_directory)
     def compute_components_store_singvalues(self):
@@ -423,7 +507,9 @@ class constraintsComponents:  # Components == bases
         elements around it are listed -- and then the loop ``for idx in range(len(elems))`` deflates the constraint blocks
         0 .. len(elems) - 1 (the loop INDEX, not the listed elements, is what the reference uses as block number, :201-207),
         p rows each, rank-1 SVD of the row's 3 x F slab, global support; CSV row and measures per block, early exit once
-        |R| < tol.  The residual lives on the device (residual mode, forced rows); one rank."""
+        |R| < tol.  The residual lives on the device (residual mode, forced rows).  Several ranks: every rank maps its owned
+        vertices' rows of S^T R from its shard and a halo copy of the rows other ranks hold (deflated with every component like
+        the owner's), the forced rows go through the record exchange of 'pca_blocks', |R|^2 is all-reduced."""
         if self.support == 'local':
             raise ValueError("Local support maps are not yet available for nonlinear-term components")
         ns = self.nonlinearSnapshots
@@ -439,11 +525,22 @@ class constraintsComponents:  # Components == bases
         cap = int(ns.frs) + p * int(ns.num_constained_elements) + p
         room = min(cap, max(4 * p, 64))
         eng.deflate_begin(room, False, _lib.DEFLATE_RESIDUAL)
+        multi = comm.multi
+        rec = recs = None
+        if multi:
+            self._st_halo_exchange(0)
+            rec, recs = comm.new_records(eng.xchg_len(), eng.device_exchange)
+
+        def norm2():
+            return comm.allreduce_sum(eng.residual_norm2())[0] if multi else eng.residual_norm2()
         S_v_idx, S_ele_idns, meas = [], [], []
         n_done = bases_count = 0
-        normR = np.sqrt(max(eng.residual_norm2(), 0.0))
+        normR = np.sqrt(max(norm2(), 0.0))
         while normR > tol:
-            v, _ = eng.st_residual_argmax()
+            if multi:
+                v = self._st_vertex_argmax(*eng.st_shard_residual_argmax())
+            else:
+                v, _ = eng.st_residual_argmax()
             elems = self._elements_around(v)
             print("vert", v, "elements", len(elems))
             S_v_idx.append(v)
@@ -459,13 +556,20 @@ class constraintsComponents:  # Components == bases
                 sigma = []
                 for i in range(p):
                     eng.force_next(idx * p + i)
-                    eng.pick(n_done)
-                    eng.apply(n_done)
+                    if multi:
+                        eng.local_best(n_done, rec.data_ptr())
+                        comm.all_gather_records(rec, recs)
+                        eng.pick(n_done, recs.data_ptr(), comm.world)
+                        eng.apply(n_done)
+                        eng.st_halo_deflate(n_done)
+                    else:
+                        eng.pick(n_done)
+                        eng.apply(n_done)
                     sigma.append(eng.get_pick(n_done)[1])
                     n_done += 1
-                    print(np.sqrt(max(eng.residual_norm2(), 0.0)))
+                    print(np.sqrt(max(norm2(), 0.0)))
                 bases_count += 1
-                normR = np.sqrt(max(eng.residual_norm2(), 0.0))
+                normR = np.sqrt(max(norm2(), 0.0))
                 singList = [bases_count, idx, normR] + sigma
                 meas.append(singList)
                 if self.storeSingVal and writer is not None:
@@ -951,11 +1055,14 @@ class constraintsComponents:  # Components == bases
         call, host; k p x k p), residual + arg-max on the device."""
         ns = self.nonlinearSnapshots
         eng, comm = ns._engine, ns._comm
-        if comm.multi:
-            raise NotImplementedError("block interpolation runs on one rank")
         p = int(ns.constraintsSize)
         K = self.numComp
         Kp = K * p
+        if comm.multi and group > 1:
+            for a, n in ns._shards:
+                if a % group or n % group:
+                    raise ValueError("'geom_block_form_utilizing_differential_operator' with p = %d needs shards of whole "
+                                     "constraints; %d rows over %d ranks do not split that way" % (group, ns.frames_rows, comm.world))
         v0, n_loc = ns._shards[comm.rank]
         if not self._comps_on_device:
             eng.components_upload(np.ascontiguousarray(self._comps[:, v0:v0 + n_loc, :]))
@@ -973,6 +1080,9 @@ class constraintsComponents:  # Components == bases
                 for i in range(3):
                     coef[i] = np.linalg.lstsq(rows[:, :kp, i], rows[:, kp:kp + p, i], rcond=None)[0]      # (:764-765)
             idx, val, amax = eng.deim_block_step(k, p, coef, group)
+            if comm.multi:                                   # (global row / block index: the first maximum over the shards)
+                idx = int(comm.global_argmax(np.array([idx], dtype=np.int64), np.array([val]))[0])
+                amax = float(comm.allreduce_max(amax)[0])
             if k > 0 and amax <= 1e-8:                       # np.allclose(r, 0) (:768 / :677)
                 print("ERROR!: zero residual!!")
                 return False
@@ -982,7 +1092,10 @@ class constraintsComponents:  # Components == bases
             idxs.append(idx)
             e_points.append(alpha)
             print(k, alpha)
-            new = np.stack([eng.deim_row(alpha * p + m) for m in range(p)])
+            if comm.multi:
+                new = self._basis_rows([alpha * p + m for m in range(p)])
+            else:
+                new = np.stack([eng.deim_row(alpha * p + m) for m in range(p)])
             rows = np.concatenate([rows, new], axis=0)
             Pt.extend(alpha * p + m for m in range(p))
             e_range.append(k + 1)
@@ -1024,6 +1137,8 @@ class constraintsComponents:  # Components == bases
             self._comps_on_device = True
         if eng.K != Kp:
             raise ValueError("the basis has %d vectors, %d blocks of %d expected" % (eng.K, K, p))
+        if comm.multi:
+            self._st_halo_exchange(1)                    # the halo's basis rows, once for the final basis
         self._rank_diagnostic(Kp)
         per_vert = int(self.param.geom_ele_per_vert)
         rows = np.zeros((0, Kp, 3))          # rows[m, j, i] = V[Pt[m], j, i]
@@ -1036,7 +1151,12 @@ class constraintsComponents:  # Components == bases
                 coef = np.empty((3, kp, p))
                 for i in range(3):          # (:662-668: more rows than columns possible -- least squares, as the reference)
                     coef[i] = np.linalg.lstsq(rows[:, :kp, i], rows[:, kp:kp + p, i], rcond=None)[0]
-            v_interpolate, val, am = eng.deim_block_step_st(k, p, coef)
+            if comm.multi:
+                loc, val, am = eng.deim_block_step_st_shard(k, p, coef)
+                v_interpolate = self._st_vertex_argmax(loc, val)
+                am = float(comm.allreduce_max(am)[0])
+            else:
+                v_interpolate, val, am = eng.deim_block_step_st(k, p, coef)
             if k > 0 and am <= 1e-8:     # np.allclose(S^T r, 0) (:677): no ENTRY of S^T r above 1e-8 (am = the largest |entry|)
                 print("ERROR!: zero residual!!")
                 return
@@ -1058,7 +1178,10 @@ class constraintsComponents:  # Components == bases
                         print(k, alpha)
                         new_rows.extend(alpha * p + m for m in range(p))
             if new_rows:
-                rows = np.concatenate([rows, np.stack([eng.deim_row(r_) for r_ in new_rows])], axis=0)
+                if comm.multi:
+                    rows = np.concatenate([rows, self._basis_rows(new_rows)], axis=0)
+                else:
+                    rows = np.concatenate([rows, np.stack([eng.deim_row(r_) for r_ in new_rows])], axis=0)
                 Pt.extend(new_rows)
             e_jump.append(jump)
             e_range.append(int(np.sum(e_jump)))
@@ -1072,12 +1195,13 @@ class constraintsComponents:  # Components == bases
     def geom_constructed(self, r, case, interpol="geom"):
         """constraintsComponents.py:489-521: reconstruction of the train / test frames from the r leading basis blocks and
         the interpolation points: per dimension the normal equations of V_r[Pt] (r p x r p, host LU as the reference), the
-        (e p x r p) by (r p x F) product on the device."""
+        (e p x r p) by (r p x F) product on the device.  Several ranks: the rows at the interpolation points are exchanged,
+        every rank expands its own rows and the result is gathered -- every rank returns the whole (F, e p, 3)."""
         from scipy.linalg import lu_factor, lu_solve
         ns = self.nonlinearSnapshots
         eng, comm = ns._engine, ns._comm
         if comm.multi:
-            raise NotImplementedError("geom_constructed runs on one rank")
+            return self._geom_constructed_ranks(r, case)
         kind = getattr(self.param, "constProj_bases_interpolation_type", "")
         p = int(ns.constraintsSize) if kind in ("geom", "deim_block_form") else 1
         if case == "train":
@@ -1103,6 +1227,40 @@ class constraintsComponents:  # Components == bases
             u, piv = lu_factor(VPt[:, :, l].T @ VPt[:, :, l])
             coef[l] = lu_solve((u, piv), VPt[:, :, l].T @ np.ascontiguousarray(frames[:, Pt, l]).T)
         return eng.components_expand(coef)
+
+    def _geom_constructed_ranks(self, r, case):
+        """geom_constructed on several ranks: V[Pt] (deim_row) and f[:, Pt, :] (rows_gather) of the owners all-reduced, the same
+        host LU as one rank, the expansion of this rank's rows on the device, all-gathered."""
+        from scipy.linalg import lu_factor, lu_solve
+        ns = self.nonlinearSnapshots
+        eng, comm = ns._engine, ns._comm
+        kind = getattr(self.param, "constProj_bases_interpolation_type", "")
+        p = int(ns.constraintsSize) if kind in ("geom", "deim_block_form") else 1
+        if case not in ("train", "test"):
+            raise ValueError("unknown frames to reconstruct.")
+        if getattr(self.param, "constProj_snapshots_type", "") == "verts_bending":
+            Pt = self.geom_Pt[:self.geom_alpha_ranges[r - 1]]
+        else:
+            Pt = self.geom_alpha[:self.geom_alpha_ranges[r - 1]]
+        Pt = np.asarray(Pt, dtype=np.int64)
+        rp = r * p
+        if not self._comps_on_device:
+            v0, n_loc = ns._shards[comm.rank]
+            eng.components_upload(np.ascontiguousarray(self._comps[:, v0:v0 + n_loc, :]))
+            self._comps_on_device = True
+        VPt = self._basis_rows(Pt)[:, :rp, :]                                    # (|Pt|, rp, 3)
+        if case == "train":
+            B, _ = eng.rows_gather(0, Pt)                                        # (|Pt|, F, 3), this shard's rows
+            B = comm.allreduce_sum(B.reshape(-1)).reshape(B.shape)
+            fPt = np.moveaxis(B, 0, 1)                                           # f[:, Pt, :]
+        else:
+            fPt = np.asarray(ns.test_snapTensor)[:, Pt, :]
+        F = fPt.shape[0]
+        coef = np.empty((3, rp, F))
+        for l in range(3):
+            u, piv = lu_factor(VPt[:, :, l].T @ VPt[:, :, l])
+            coef[l] = lu_solve((u, piv), VPt[:, :, l].T @ np.ascontiguousarray(fPt[:, :, l]).T)
+        return comm.all_gather_rows(eng.components_expand(coef), ns.frames_rows, axis=1)
 
     # ------------------------------------------------------------------ extras: interpolation-error sweeps
     def interpolation_errors(self, r_values, case="train"):

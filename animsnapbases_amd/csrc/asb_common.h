@@ -101,6 +101,25 @@ struct asb_ctx {
     double* st_energy = nullptr;      // (st_rows) squared row norms of S^T M
     double* st_amax = nullptr;        // (st_rows) largest |entry| per row of S^T M
     double* st_resid = nullptr;       // (n_loc, 3 p) residual block of the position-space interpolation error
+    // several ranks (asb_st_upload_shard, asb_pod.hip): the S^T rows of the position vertices this rank owns, columns remapped
+    // to local slots -- [0, n_loc) this shard, [n_loc, n_loc + st_h) the halo -- and the halo copies of residual / basis rows
+    long long* sh_indptr = nullptr;
+    long long* sh_indices = nullptr;
+    double* sh_data = nullptr;
+    long long sh_rows = 0, sh_nnz = 0, st_h = 0, sh_n_loc = -1;
+    double* sh_energy = nullptr;      // (sh_rows) squared row norms of S^T M over the owned vertices
+    double* sh_amax = nullptr;        // (sh_rows) largest |entry| per owned row
+    double* halo_R = nullptr;         // (st_h, 3 Fp) residual rows, deflated with every component like the owner's
+    double* halo_C = nullptr;         // (halo_K, st_h, 3) basis rows
+    long long halo_K = 0;             // K of the filled halo basis (0: none)
+    int halo_R_ok = 0;                // the halo residual was filled for the current upload
+    double* halo_energy = nullptr;    // k_stream scratch of the halo pass: (st_h) energies, (st_h, 3) coefficients, partials
+    double* halo_ck = nullptr;
+    double* halo_pmax = nullptr;
+    long long* halo_pidx = nullptr;
+    double* halo_psum = nullptr;
+    double* halo_resid = nullptr;     // (st_h, 3 p) residual block of the position-space interpolation error on the halo
+    long long* halo_map = nullptr;    // pack / fill row lists
     unsigned* coop_bar = nullptr;     // k_panel_multi: flags [-, abort, too many candidates, -] + debug timestamps
     double* coop_rec = nullptr;       // (2, grid) records {e, lam, wn2, slot}
     int panel_coop = 1;               // ASB_PANEL_COOP=0 -> the two-kernel inner loop
@@ -310,8 +329,9 @@ void asb_geo_free(asb_ctx* ctx);
 const double* asb_geo_cached_field(asb_ctx* ctx, long long slot, long long* n_out);
 // small dense linear algebra on the device (asb_linalg.hip)
 // out[i*so_i + j*so_j] = sum_r A[r*lda + i*sa] * B[r*ldb + j]   (f64 MFMA; contraction index r slow in A and B)
+// I_split > 0: split the contraction as an I_split-row product would (a row shard then sums in the order of the whole)
 int asb_gemm_tn_s(asb_ctx* ctx, const double* A, long long lda, long long sa, const double* B, long long ldb, long long Rn,
-                  int I, int J, double* out, long long so_i, long long so_j);
+                  int I, int J, double* out, long long so_i, long long so_j, long long I_split = 0);
 static inline int asb_gemm_tn(asb_ctx* ctx, const double* A, long long lda, const double* B, long long ldb, long long Rn,
                               int I, int J, double* out) {
     return asb_gemm_tn_s(ctx, A, lda, 1, B, ldb, Rn, I, J, out, J, 1);

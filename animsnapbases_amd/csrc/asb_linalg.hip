@@ -233,9 +233,11 @@ __global__ __launch_bounds__(256) void k_transpose_small(const double* __restric
 }
 
 int asb_gemm_tn_s(asb_ctx* ctx, const double* A, long long lda, long long sa, const double* B, long long ldb, long long Rn,
-                  int I, int J, double* out, long long so_i, long long so_j) {
+                  int I, int J, double* out, long long so_i, long long so_j, long long I_split) {
+    const long long Is = I_split > 0 ? I_split : I;
+    const long long tiles_s = ((Is + 15) / 16) * ((J + 15) / 16);
     const int tiles = ((I + 15) / 16) * ((J + 15) / 16);
-    int S = (int)(4096 / (tiles > 0 ? tiles : 1));
+    int S = (int)(4096 / (tiles_s > 0 ? tiles_s : 1));
     if (S < 1) S = 1;
     long long maxS = (Rn + 63) / 64;
     if (S > maxS) S = (int)maxS;
@@ -578,7 +580,8 @@ extern "C" int asb_components_expand(asb_ctx* ctx, const double* coef_host, int6
     int rc = ASB_OK;
     if (e == hipSuccess) e = hipMemcpyAsync(dc, coef_host, (size_t)3 * r * Fo * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
     for (int l = 0; l < 3 && e == hipSuccess && rc == ASB_OK; ++l)
-        rc = asb_gemm_tn_s(ctx, ctx->comps + l, 3 * n, 3, dc + (size_t)l * r * Fo, Fo, r, (int)n, (int)Fo, dout + l, 3, 3 * n);
+        rc = asb_gemm_tn_s(ctx, ctx->comps + l, 3 * n, 3, dc + (size_t)l * r * Fo, Fo, r, (int)n, (int)Fo, dout + l, 3, 3 * n,
+                           (long long)ctx->N_glob);
     if (e == hipSuccess && rc == ASB_OK)
         e = hipMemcpyAsync(out_host, dout, (size_t)Fo * 3 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);

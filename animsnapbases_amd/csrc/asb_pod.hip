@@ -972,3 +972,292 @@ extern "C" int asb_deim_block_residual_st(asb_ctx* ctx, int64_t k, int p, const 
     *maxabs_out = am;
     return ASB_OK;
 }
+
+// --------------------------------------------------------------------------------------
+// S^T on several ranks.  Constraint rows are sharded in contiguous ranges; a position vertex belongs to the rank that holds
+// the smallest column of its S^T row (rank 0 for an empty row).  Its row may reference constraint rows of other ranks: the
+// HALO, st_h rows this rank keeps a copy of -- of the residual (deflated with every component by the same k_stream pass as
+// the owner's rows, so the copy stays bit-for-bit equal) and of the final basis.  The owned rows' CSR is remapped to local
+// slots ([0, n_loc): this shard, [n_loc, n_loc + st_h): the halo) in the global row's column order, so every sum of S^T M
+// runs in the order of the one-rank run.  The caller computes ownership, halo and send lists on the host and exchanges the
+// packed rows (asb_st_halo_pack -> all-gather -> asb_st_halo_fill).
+// --------------------------------------------------------------------------------------
+
+// k_st_row_energy with the row of slot c read from A (c < n_a) or from B (c - n_a): the same per-row arithmetic
+__global__ __launch_bounds__(256) void k_st_row_energy2(const long long* __restrict__ indptr, const long long* __restrict__ indices,
+                                                        const double* __restrict__ data, long long n_rows, const double* __restrict__ A,
+                                                        long long n_a, const double* __restrict__ B, long long ldm, long long ncols,
+                                                        double* __restrict__ E, double* __restrict__ Amax) {
+    constexpr int U = 4;
+    const int lane = threadIdx.x & 63;
+    for (long long v = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); v < n_rows; v += (long long)gridDim.x * 4) {
+        const long long a = indptr[v], b = indptr[v + 1];
+        double e = 0.0, am = 0.0;
+        for (long long c0 = 0; c0 < ncols; c0 += 64 * U) {
+            double acc[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) acc[u] = 0.0;
+            for (long long q = a; q < b; ++q) {
+                const double w = data[q];
+                const long long s = indices[q];
+                const double* row = s < n_a ? A + s * ldm : B + (s - n_a) * ldm;
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const long long c = c0 + lane + 64 * u;
+                    if (c < ncols) acc[u] += w * row[c];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                e += acc[u] * acc[u];
+                am = fmax(am, fabs(acc[u]));
+            }
+        }
+        e = wave_sum(e);
+        if (lane == 0) E[v] = e;
+        if (Amax) {
+            am = wave_max(am);
+            if (lane == 0) Amax[v] = am;
+        }
+    }
+}
+
+// pack: out[q][0 .. len) = row rows[q] of the residual (len = 3 Fp) or of the basis (len = 3 K, [j][i] = comps[j][row][i])
+__global__ __launch_bounds__(256) void k_halo_pack(const double* __restrict__ src, int which, const long long* __restrict__ rows,
+                                                   long long n, long long len, long long n_loc, double* __restrict__ out) {
+    const long long total = n * len;
+    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
+        const long long q = t / len, c = t % len, r = rows[q];
+        out[t] = which == 0 ? src[r * len + c] : src[(c / 3) * 3 * n_loc + 3 * r + c % 3];
+    }
+}
+
+// fill: halo slot s <- row slot[s] of the gathered rows (ld doubles apart)
+__global__ __launch_bounds__(256) void k_halo_fill(const double* __restrict__ src, int which, const long long* __restrict__ slot,
+                                                   long long h, long long len, long long ld, double* __restrict__ dst) {
+    const long long total = h * len;
+    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
+        const long long s = t / len, c = t % len;
+        const double x = src[slot[s] * ld + c];
+        if (which == 0) dst[t] = x;
+        else dst[(c / 3) * 3 * h + 3 * s + c % 3] = x;
+    }
+}
+
+static int grid_for(long long n) { return (int)((n + 255) / 256 < 1024 ? ((n + 255) / 256 > 0 ? (n + 255) / 256 : 1) : 1024); }
+
+extern "C" int asb_st_upload_shard(asb_ctx* ctx, int64_t n_own, int64_t nnz, const int64_t* indptr, const int64_t* indices,
+                                   const double* data, int64_t n_halo) {
+    if (!ctx || n_own < 0 || nnz < 0 || n_halo < 0 || (n_own > 0 && !indptr) || (nnz > 0 && (!indices || !data))) return ASB_ERR_ARG;
+    if (!ctx->X) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_st_upload_shard: no snapshots uploaded");
+    if (n_halo > ctx->N_glob - ctx->n_loc) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_st_upload_shard: %lld halo rows, %lld rows on other ranks",
+                                                     (long long)n_halo, (long long)(ctx->N_glob - ctx->n_loc));
+    const int64_t slots = ctx->n_loc + n_halo;
+    for (int64_t q = 0; q < nnz; ++q)
+        if (indices[q] < 0 || indices[q] >= slots) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_st_upload_shard: column slot out of range");
+    if (n_own > 0 && (indptr[0] != 0 || indptr[n_own] != nnz)) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_st_upload_shard: bad row pointers");
+    for (int64_t v = 0; v < n_own; ++v)
+        if (indptr[v + 1] < indptr[v]) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_st_upload_shard: bad row pointers");
+    int rc;
+    if ((rc = asb_alloc(ctx, &ctx->sh_indptr, (size_t)n_own + 1))) return rc;
+    if ((rc = asb_alloc(ctx, &ctx->sh_indices, (size_t)(nnz > 0 ? nnz : 1)))) return rc;
+    if ((rc = asb_alloc(ctx, &ctx->sh_data, (size_t)(nnz > 0 ? nnz : 1)))) return rc;
+    if ((rc = asb_alloc(ctx, &ctx->sh_energy, (size_t)(n_own > 0 ? n_own : 1)))) return rc;
+    if ((rc = asb_alloc(ctx, &ctx->sh_amax, (size_t)(n_own > 0 ? n_own : 1)))) return rc;
+    const long long zero = 0;
+    ASB_HIP(ctx, hipMemcpyAsync(ctx->sh_indptr, n_own > 0 ? (const void*)indptr : (const void*)&zero, (size_t)(n_own + 1) * 8,
+                                hipMemcpyHostToDevice, ctx->stream));
+    if (nnz > 0) {
+        ASB_HIP(ctx, hipMemcpyAsync(ctx->sh_indices, indices, (size_t)nnz * 8, hipMemcpyHostToDevice, ctx->stream));
+        ASB_HIP(ctx, hipMemcpyAsync(ctx->sh_data, data, (size_t)nnz * 8, hipMemcpyHostToDevice, ctx->stream));
+    }
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->sh_rows = n_own;
+    ctx->sh_nnz = nnz;
+    ctx->st_h = n_halo;
+    ctx->sh_n_loc = ctx->n_loc;
+    ctx->halo_K = 0;
+    ctx->halo_R_ok = 0;
+    return ASB_OK;
+}
+
+static int sh_check(asb_ctx* ctx, const char* who) {
+    if (ctx->sh_n_loc != ctx->n_loc || !ctx->sh_indptr)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "%s: no S^T shard uploaded for this shard (asb_st_upload_shard)", who);
+    return ASB_OK;
+}
+
+// which 0: rows of the residual (3 Fp doubles each); 1: rows of the basis (3 K doubles each)
+static long long halo_len(const asb_ctx* ctx, int which) { return which == 0 ? 3 * (long long)ctx->Fp : 3 * (long long)ctx->K; }
+
+extern "C" int asb_st_halo_pack(asb_ctx* ctx, int which, const int64_t* gidx, int64_t n, double* out_dev) {
+    if (!ctx || (which != 0 && which != 1) || n < 0 || (n > 0 && (!gidx || !out_dev))) return ASB_ERR_ARG;
+    const double* src = which == 0 ? ctx->R : ctx->comps;
+    if (!src || (which == 0 && ctx->mode != ASB_DEFLATE_RESIDUAL))
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_st_halo_pack: no %s on the device", which == 0 ? "residual-mode residual" : "basis");
+    if (n == 0) return ASB_OK;
+    std::vector<long long> loc((size_t)n);
+    for (int64_t q = 0; q < n; ++q) {
+        if (gidx[q] < ctx->v0 || gidx[q] >= ctx->v0 + ctx->n_loc)
+            ASB_FAIL(ctx, ASB_ERR_ARG, "asb_st_halo_pack: row %lld is not on this shard", (long long)gidx[q]);
+        loc[q] = gidx[q] - ctx->v0;
+    }
+    int rc;
+    if ((rc = asb_alloc(ctx, &ctx->halo_map, (size_t)n))) return rc;
+    ASB_HIP(ctx, hipMemcpyAsync(ctx->halo_map, loc.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    const long long len = halo_len(ctx, which);
+    hipLaunchKernelGGL(k_halo_pack, dim3(grid_for(n * len)), dim3(256), 0, ctx->stream, src, which, ctx->halo_map, (long long)n, len,
+                       (long long)ctx->n_loc, out_dev);
+    ASB_CHECK_LAUNCH(ctx);
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));        // (the exchange may run on another stream)
+    return ASB_OK;
+}
+
+extern "C" int asb_st_halo_fill(asb_ctx* ctx, int which, const double* src_dev, const int64_t* slot, int64_t n_src) {
+    if (!ctx || (which != 0 && which != 1) || n_src < 0) return ASB_ERR_ARG;
+    int rc;
+    if ((rc = sh_check(ctx, "asb_st_halo_fill"))) return rc;
+    const long long h = ctx->st_h, len = halo_len(ctx, which);
+    if (h > 0 && (!src_dev || !slot)) return ASB_ERR_ARG;
+    for (long long s = 0; s < h; ++s)
+        if (slot[s] < 0 || slot[s] >= n_src) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_st_halo_fill: source slot out of range");
+    if (which == 0) {
+        if (!ctx->R || ctx->mode != ASB_DEFLATE_RESIDUAL) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_st_halo_fill: needs the residual mode");
+        if ((rc = asb_alloc(ctx, &ctx->halo_R, (size_t)(h > 0 ? h : 1) * len))) return rc;
+        if ((rc = asb_alloc(ctx, &ctx->halo_energy, (size_t)(h > 0 ? h : 1)))) return rc;
+        if ((rc = asb_alloc(ctx, &ctx->halo_ck, (size_t)(h > 0 ? h : 1) * 3))) return rc;
+        const size_t nb = (size_t)(ctx->nblk_cap > 0 ? ctx->nblk_cap : 1);
+        if ((rc = asb_alloc(ctx, &ctx->halo_pmax, nb))) return rc;
+        if ((rc = asb_alloc(ctx, &ctx->halo_pidx, nb))) return rc;
+        if ((rc = asb_alloc(ctx, &ctx->halo_psum, nb))) return rc;
+        ctx->halo_R_ok = 1;
+    } else {
+        if (!ctx->comps) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_st_halo_fill: no basis on the device");
+        if ((rc = asb_alloc(ctx, &ctx->halo_C, (size_t)(h > 0 ? h : 1) * len))) return rc;
+        ctx->halo_K = ctx->K;
+    }
+    if (h == 0) return ASB_OK;
+    if ((rc = asb_alloc(ctx, &ctx->halo_map, (size_t)h))) return rc;
+    static_assert(sizeof(long long) == sizeof(int64_t), "index width");
+    ASB_HIP(ctx, hipMemcpyAsync(ctx->halo_map, slot, (size_t)h * 8, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_halo_fill, dim3(grid_for(h * len)), dim3(256), 0, ctx->stream, src_dev, which, ctx->halo_map, h, len, len,
+                       which == 0 ? ctx->halo_R : ctx->halo_C);
+    ASB_CHECK_LAUNCH(ctx);
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ASB_OK;
+}
+
+// the halo half of asb_deflate_apply(k): the same k_stream instantiation (it depends on Fp only) with the same w_k and |w_k|^2,
+// row energies and coefficients to scratch
+extern "C" int asb_st_halo_deflate(asb_ctx* ctx, int64_t k) {
+    if (!ctx || !ctx->R || !ctx->W || !ctx->scal) return ASB_ERR_ARG;
+    int rc;
+    if ((rc = sh_check(ctx, "asb_st_halo_deflate"))) return rc;
+    if (k < 0 || k >= ctx->K) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_st_halo_deflate: k = %lld out of range", (long long)k);
+    if (ctx->st_h == 0) return ASB_OK;
+    if (!ctx->halo_R_ok) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_st_halo_deflate: the halo residual was not filled (asb_st_halo_fill)");
+    StreamCfg c;
+    if (!pick_cfg(ctx->Fp, c)) ASB_FAIL(ctx, ASB_ERR_LIMIT, "F = %lld too large (max 32768)", (long long)ctx->F);
+    const int grid = stream_grid(ctx, c, ctx->st_h);
+    StreamArgs a{ctx->halo_R, ctx->W + k * ctx->Fp, ctx->scal + k * 4, nullptr, ctx->halo_ck, ctx->halo_energy, ctx->halo_pmax,
+                 ctx->halo_pidx, ctx->halo_psum, (long long)ctx->st_h, nullptr};
+    launch_stream(ctx, c, true, grid, a);
+    ASB_CHECK_LAUNCH(ctx);
+    return ASB_OK;
+}
+
+// first arg-max of E[0 .. n) as a LOCAL index (-1, -1.0 when n == 0)
+static int local_argmax(asb_ctx* ctx, const double* E, long long n, int64_t* idx_out, double* val_out) {
+    if (n == 0) {
+        *idx_out = -1;
+        if (val_out) *val_out = -1.0;
+        return ASB_OK;
+    }
+    return st_argmax(ctx, E, n, idx_out, val_out);
+}
+
+static int sh_row_energies(asb_ctx* ctx, const double* A, const double* B, long long ldm, long long ncols, double* amax) {
+    if (ctx->sh_rows == 0) return ASB_OK;
+    const long long want = (ctx->sh_rows + 3) / 4;
+    const int grid = (int)(want < 8LL * ctx->n_cu ? want : 8LL * ctx->n_cu);
+    hipLaunchKernelGGL(k_st_row_energy2, dim3(grid), dim3(256), 0, ctx->stream, ctx->sh_indptr, ctx->sh_indices, ctx->sh_data,
+                       (long long)ctx->sh_rows, A, (long long)ctx->n_loc, B, ldm, ncols, ctx->sh_energy, amax);
+    ASB_CHECK_LAUNCH(ctx);
+    return ASB_OK;
+}
+
+extern "C" int asb_st_shard_residual_argmax(asb_ctx* ctx, int64_t* v_loc_out, double* val_out) {
+    if (!ctx || !ctx->R || !v_loc_out) return ASB_ERR_ARG;
+    if (ctx->mode != ASB_DEFLATE_RESIDUAL) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_st_shard_residual_argmax needs the residual mode");
+    int rc;
+    if ((rc = sh_check(ctx, "asb_st_shard_residual_argmax"))) return rc;
+    if (ctx->st_h > 0 && !ctx->halo_R_ok) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_st_shard_residual_argmax: the halo residual was not filled");
+    if ((rc = sh_row_energies(ctx, ctx->R, ctx->halo_R, 3 * ctx->Fp, 3 * ctx->Fp, nullptr))) return rc;
+    return local_argmax(ctx, ctx->sh_energy, ctx->sh_rows, v_loc_out, val_out);
+}
+
+extern "C" int asb_deim_block_residual_st_shard(asb_ctx* ctx, int64_t k, int p, const double* coef, double* maxabs_out,
+                                                int64_t* v_loc_out, double* val_out) {
+    if (!ctx || !ctx->comps || k < 0 || p < 1 || (k + 1) * p > ctx->K || !maxabs_out || !v_loc_out) return ASB_ERR_ARG;
+    if (k > 0 && !coef) return ASB_ERR_ARG;
+    int rc;
+    if ((rc = sh_check(ctx, "asb_deim_block_residual_st_shard"))) return rc;
+    if (ctx->st_h > 0 && (!ctx->halo_C || ctx->halo_K != ctx->K))
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_deim_block_residual_st_shard: the halo basis was not filled for this basis (asb_st_halo_fill 1)");
+    const int kp = (int)(k * p);
+    const long long h = ctx->st_h;
+    if ((rc = asb_alloc(ctx, &ctx->pod_coef, (size_t)3 * ctx->K * p + 8))) return rc;
+    if ((rc = asb_alloc(ctx, &ctx->st_resid, (size_t)ctx->n_loc * 3 * p))) return rc;
+    if ((rc = asb_alloc(ctx, &ctx->halo_resid, (size_t)(h > 0 ? h : 1) * 3 * p))) return rc;
+    if (k > 0) ASB_HIP(ctx, hipMemcpyAsync(ctx->pod_coef, coef, (size_t)3 * kp * p * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    long long want = (ctx->n_loc + 255) / 256;
+    int grid = (int)(want < 1024 ? want : 1024);
+    hipLaunchKernelGGL(k_deim_block_residual_out, dim3(grid), dim3(256), 0, ctx->stream, ctx->comps, (long long)ctx->n_loc, kp, p,
+                       ctx->pod_coef, ctx->st_resid, ctx->pmax);
+    if (h > 0) {
+        // the halo rows through the very same kernel: halo_C has the basis layout (K, h, 3)
+        want = (h + 255) / 256;
+        grid = (int)(want < 1024 ? want : 1024);
+        hipLaunchKernelGGL(k_deim_block_residual_out, dim3(grid), dim3(256), 0, ctx->stream, ctx->halo_C, h, kp, p, ctx->pod_coef,
+                           ctx->halo_resid, ctx->pmax);
+    }
+    ASB_CHECK_LAUNCH(ctx);
+    if ((rc = sh_row_energies(ctx, ctx->st_resid, ctx->halo_resid, 3 * p, 3 * p, ctx->sh_amax))) return rc;
+    int64_t am_row = 0;
+    double am = 0.0;
+    if ((rc = local_argmax(ctx, ctx->sh_amax, ctx->sh_rows, &am_row, &am))) return rc;
+    if ((rc = local_argmax(ctx, ctx->sh_energy, ctx->sh_rows, v_loc_out, val_out))) return rc;
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *maxabs_out = am > 0.0 ? am : 0.0;
+    return ASB_OK;
+}
+
+// stats: [0] halo rows, [1] owned position vertices, [2] S^T entries of those, [3] halo basis rows' K (0: not filled)
+extern "C" int asb_st_shard_stats(asb_ctx* ctx, int64_t* out4) {
+    if (!ctx || !out4) return ASB_ERR_ARG;
+    const bool ok = ctx->sh_n_loc == ctx->n_loc && ctx->sh_indptr;
+    out4[0] = ok ? ctx->st_h : 0;
+    out4[1] = ok ? ctx->sh_rows : 0;
+    out4[2] = ok ? ctx->sh_nnz : 0;
+    out4[3] = ok && ctx->halo_C ? ctx->halo_K : 0;
+    return ASB_OK;
+}
+
+// the halo copies to the host: which 0 (h, 3, F) residual rows, 1 (K, h, 3) basis rows
+extern "C" int asb_st_halo_download(asb_ctx* ctx, int which, double* out) {
+    if (!ctx || !out || (which != 0 && which != 1)) return ASB_ERR_ARG;
+    int rc;
+    if ((rc = sh_check(ctx, "asb_st_halo_download"))) return rc;
+    const long long h = ctx->st_h;
+    if (h == 0) return ASB_OK;
+    if (which == 0) {
+        if (!ctx->halo_R_ok) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_st_halo_download: the halo residual was not filled");
+        ASB_HIP(ctx, hipMemcpy2DAsync(out, (size_t)ctx->F * sizeof(double), ctx->halo_R, (size_t)ctx->Fp * sizeof(double),
+                                      (size_t)ctx->F * sizeof(double), (size_t)h * 3, hipMemcpyDeviceToHost, ctx->stream));
+    } else {
+        if (!ctx->halo_C) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_st_halo_download: the halo basis was not filled");
+        ASB_HIP(ctx, hipMemcpyAsync(out, ctx->halo_C, (size_t)ctx->halo_K * 3 * h * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ASB_OK;
+}

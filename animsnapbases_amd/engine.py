@@ -788,6 +788,55 @@ class HipEngine(object):
                                                      ctypes.byref(val)))
         return v.value, val.value, am.value
 
+    # ---- S^T with the constraint rows sharded over several ranks (asb.h: asb_st_upload_shard ...)
+    def st_upload_shard(self, indptr, slots, data, n_halo):
+        """CSR of the position vertices this rank owns, columns as local slots (< n_loc: this shard, then the halo)."""
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        slots = np.ascontiguousarray(slots, dtype=np.int64)
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        self._ck(self.lib.asb_st_upload_shard(self.h, int(indptr.shape[0] - 1), int(data.shape[0]), ptr(indptr), ptr(slots),
+                                              ptr(data), int(n_halo)))
+
+    def st_halo_pack(self, which, gidx, out_dev_ptr):
+        gidx = np.ascontiguousarray(gidx, dtype=np.int64)
+        self._ck(self.lib.asb_st_halo_pack(self.h, int(which), ptr(gidx), int(gidx.shape[0]), ctypes.c_void_p(out_dev_ptr)))
+
+    def st_halo_fill(self, which, src_dev_ptr, slot, n_src):
+        slot = np.ascontiguousarray(slot, dtype=np.int64)
+        self._ck(self.lib.asb_st_halo_fill(self.h, int(which), ctypes.c_void_p(src_dev_ptr), ptr(slot), int(n_src)))
+
+    def st_halo_deflate(self, k):
+        self._ck(self.lib.asb_st_halo_deflate(self.h, int(k)))
+
+    def st_shard_residual_argmax(self):
+        """(index into the owned vertices or -1, energy)"""
+        v, val = ctypes.c_int64(), ctypes.c_double()
+        self._ck(self.lib.asb_st_shard_residual_argmax(self.h, ctypes.byref(v), ctypes.byref(val)))
+        return v.value, val.value
+
+    def deim_block_step_st_shard(self, k, p, coef):
+        """deim_block_step_st over the owned vertices: (index into them or -1, its energy, largest |r| of their rows)."""
+        if coef is not None:
+            coef = np.ascontiguousarray(coef, dtype=np.float64)
+            assert coef.shape == (3, k * p, p)
+        am, v, val = ctypes.c_double(), ctypes.c_int64(), ctypes.c_double()
+        self._ck(self.lib.asb_deim_block_residual_st_shard(self.h, int(k), int(p), ptr(coef), ctypes.byref(am), ctypes.byref(v),
+                                                           ctypes.byref(val)))
+        return v.value, val.value, am.value
+
+    def st_shard_stats(self):
+        """dict(halo, owned, nnz, basis_K)"""
+        out = np.zeros(4, dtype=np.int64)
+        self._ck(self.lib.asb_st_shard_stats(self.h, ptr(out)))
+        return dict(halo=int(out[0]), owned=int(out[1]), nnz=int(out[2]), basis_K=int(out[3]))
+
+    def st_halo_download(self, which):
+        """The halo copies: which 0 (h, 3, F) residual rows, 1 (K, h, 3) basis rows."""
+        st = self.st_shard_stats()
+        out = np.empty((st["halo"], 3, self.F)) if which == 0 else np.empty((st["basis_K"], st["halo"], 3))
+        self._ck(self.lib.asb_st_halo_download(self.h, int(which), ptr(out)))
+        return out
+
     def deim_row(self, gidx):
         row = np.empty((self.K, 3))
         rc = self.lib.asb_deim_row(self.h, int(gidx), ptr(row))

@@ -333,7 +333,8 @@ int asb_components_expand(asb_ctx* ctx, const double* coef_host, int64_t r, int6
 /* the device-resident basis (K, n_loc, 3) to the host */
 int asb_components_download(asb_ctx* ctx, double* comps_out);
 /* ---- the weighted differential operator S^T of the constraint path (constraintsComponents.py:70-74: a scipy sparse matrix
- * read from an .npz; rows = position-space vertices, columns = the e p constraint rows).  One rank holds all constraint rows. */
+ * read from an .npz; rows = position-space vertices, columns = the e p constraint rows).  asb_st_upload and the two calls
+ * below need all constraint rows on this rank; several ranks use the asb_st_*shard* calls further down. */
 int asb_st_upload(asb_ctx* ctx, int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t* indptr_host,
                   const int64_t* indices_host, const double* data_host);
 /* 'pca_blocks_with_St' (constraintsComponents.py:180): v = argmax_rows sum((S^T R_flat)^2) on the CURRENT residual of the
@@ -348,6 +349,32 @@ int asb_deflate_reserve(asb_ctx* ctx, int64_t K_new);
  * asb_deim_block_residual, mapped to position space by S^T ((|V|) x (3 p)); first arg-max of its squared row norms */
 int asb_deim_block_residual_st(asb_ctx* ctx, int64_t k, int p, const double* coef_host, double* maxabs_out, int64_t* v_out,
                                double* val_out);
+/* ---- S^T with the constraint rows sharded over several ranks.  A position vertex belongs to the rank holding the smallest
+ * column of its S^T row (rank 0 for an empty row); the HALO are the h constraint rows its owned vertices reference on other
+ * ranks, kept here as copies.  The caller computes ownership and halo on the host and uploads the owned rows' CSR with the
+ * columns remapped to local slots: [0, n_loc) rows of this shard, [n_loc, n_loc + h) halo slots (sorted halo rows), each
+ * row in the global row's column order (every sum then runs in the one-rank order).  Valid until the next upload. */
+int asb_st_upload_shard(asb_ctx* ctx, int64_t n_own, int64_t nnz, const int64_t* indptr_host, const int64_t* slots_host,
+                        const double* data_host, int64_t n_halo);
+/* The exchange that fills the halo, which 0: rows of the residual-mode residual (after asb_deflate_begin; 3 Fp doubles per
+ * row), which 1: rows of the device basis (3 K doubles per row, [j][i]).  pack: the rows gidx (global, on this shard) into
+ * out_dev (device, n x row length); fill: halo slot s <- row slot_host[s] < n_src of src_dev (device, the rows of every rank
+ * gathered, n_src x row length).  Synchronises the context's stream. */
+int asb_st_halo_pack(asb_ctx* ctx, int which, const int64_t* gidx_host, int64_t n, double* out_dev);
+int asb_st_halo_fill(asb_ctx* ctx, int which, const double* src_dev, const int64_t* slot_host, int64_t n_src);
+/* after asb_deflate_apply(k): the same deflation of the halo residual (same k_stream pass, same w_k), so every halo row
+ * stays equal to its owner's row bit for bit; its energies do not count towards |R|^2 */
+int asb_st_halo_deflate(asb_ctx* ctx, int64_t k);
+/* asb_st_residual_argmax over the OWNED vertices: first arg-max as an index into them (-1 when there are none) */
+int asb_st_shard_residual_argmax(asb_ctx* ctx, int64_t* v_loc_out, double* val_out);
+/* asb_deim_block_residual_st over the owned vertices (halo basis rows: asb_st_halo_fill 1 for the current basis); the
+ * caller max-reduces *maxabs_out and takes the global arg-max */
+int asb_deim_block_residual_st_shard(asb_ctx* ctx, int64_t k, int p, const double* coef_host, double* maxabs_out,
+                                     int64_t* v_loc_out, double* val_out);
+/* out4 = [halo rows h, owned vertices, their S^T entries, K of the halo basis (0: none)] */
+int asb_st_shard_stats(asb_ctx* ctx, int64_t* out4);
+/* the halo copies to the host: which 0 (h, 3, F) residual rows, 1 (K, h, 3) basis rows */
+int asb_st_halo_download(asb_ctx* ctx, int which, double* out_host);
 /* The basis into PINNED host memory, overlapped with the run that produces it (posComponents.py:119 leaves `comps` in host
  * memory: `self.comps = array(C)`).  asb_components_stream(ctx, 1) before asb_deflate_begin: the context keeps a pinned
  * (K, n_loc, 3) buffer and a copy stream; every component row is copied as soon as it is final (projection mode: after each
