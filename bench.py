@@ -2,6 +2,7 @@
 """bench.py -- throughput of the snapshot-reduction hot path on MI355X.
 
     python bench.py --gpus 1 --steps 20 --warmup 5        (the defaults)
+    python bench.py --full                                (+ CPU baselines, end-to-end cycles, other configs)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -15,11 +16,14 @@ selected vertices) is copied back inside the timed region; the (K, N, 3) basis s
 
 Prints ONE JSON line (rank 0).  Besides the contract's keys:
   roofline      dominant kernel (HIP events around every launch of it on the engine's stream) AND the step-level
-                figure: (reads of X per step) x 24 N F bytes / ms_per_step against 8 TB/s;
-  cpu_baseline  the NumPy oracle (a port of the reference's CPU path) on a bounded sample, median of 3;
-  end_to_end    prepare_ms + ms_per_step + basis_download_ms;
+                figure: (reads of X per step) x 24 N F bytes / ms_per_step against 8 TB/s.
+A plain run stops there: set-up, warm-up, the timed steps, the dump, the line.  ``--full`` adds what takes runs of its own:
+  cpu_baseline  the NumPy oracle (a port of the reference's CPU path) on a bounded sample, median of 3 (N = 1 only;
+                ``--no-cpu-baseline`` skips it);
+  end_to_end    prepare_ms + ms_per_step + basis_download_ms, and two further cycles on the warm context (N = 1 only);
   other_configs BASELINE.json configs 2, 3 and 5 at their full size (one GPU), each with its own time, roofline and CPU
-                baseline (N = 1 only; ``--no-other-configs`` skips them).
+                baseline, and config 4's shape on other tensors (N = 1 at the headline's shape only; ``--no-other-configs``
+                skips them, ``--legs`` picks some).
 
 ``--dump-outputs DIR`` writes what the last timed step returned to its caller (dump_outputs) so that two builds run with
 the same arguments -- the same seeded input tensor -- can be compared output for output.
@@ -479,10 +483,12 @@ def main():
     ap.add_argument("--frames", type=int, default=2000)
     ap.add_argument("--comps", type=int, default=128)
     ap.add_argument("--seed", type=int, default=1234, help="seed of the synthetic tensor of the timed steps (rank r uses seed + r)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true")
-    ap.add_argument("--legs", default="", help="comma-separated subset of the other_configs legs to run (default: all)")
-    ap.add_argument("--cpu-budget", type=float, default=18.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: CPU baselines, end-to-end cycles, other configs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: no other_configs")
+    ap.add_argument("--legs", default="", help="with --full: comma-separated subset of the other_configs legs to run (default: all)")
+    ap.add_argument("--cpu-budget", type=float, default=18.0, help="with --full: seconds of the config-4 CPU baseline's sample")
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong",
                     help="strong (default): --verts vertices in all, sharded over the ranks (config 4 is one fixed job); "
                          "weak: --verts vertices PER RANK (the tensor grows with the GPUs)")
@@ -588,14 +594,15 @@ def main():
     if fallbacks and rank == 0:
         print("[bench] WARNING: the panel kernel's exchange timed out %d time(s) over the ranks: those panels were redone by the "
               "two-kernel loop and the timed steps include it (is something else running on these GPUs?)" % fallbacks, file=sys.stderr)
-    # the (K, N, 3) basis back in host memory, as the reference leaves it (rank 0's share; pageable destination)
-    t0 = time.perf_counter()
-    basis = comp.comps if world == 1 else eng.results(want_comps=True, want_weigs=False)["comps"]
-    download_ms = (time.perf_counter() - t0) * 1e3
-    basis_bytes = basis.nbytes
-    del basis
+    if args.full:
+        # the (K, N, 3) basis back in host memory, as the reference leaves it (rank 0's share; pageable destination)
+        t0 = time.perf_counter()
+        basis = comp.comps if world == 1 else eng.results(want_comps=True, want_weigs=False)["comps"]
+        download_ms = (time.perf_counter() - t0) * 1e3
+        basis_bytes = basis.nbytes
+        del basis
     if args.dump_outputs:
-        # comp.comps: one rank reuses the download above, several ranks gather the basis (every rank takes part)
+        # comp.comps: one rank downloads the basis (or reuses the download above), several ranks gather it (every rank takes part)
         outputs = {"comps": (comp.comps, 1), "weigs": (comp.weigs, 0), "selected_vertices": (comp.selected_vertices, 0),
                    "measures_at_largeDeforVerts": (comp.measures_at_largeDeforVerts, 0)}
         if rank == 0:
@@ -607,7 +614,7 @@ def main():
     # is a plain ndarray over that buffer.  Timed as ONE region, input tensor in HBM to basis in host memory, no
     # synchronisation in between; the first cycle warms the path up (pinned pages, allocations), the second is reported.
     steady = None
-    if world == 1 and not forced:
+    if args.full and world == 1 and not forced:
         eng.components_stream(True)
         for cyc in range(2):
             gen.manual_seed(4321 + cyc)
@@ -715,23 +722,24 @@ def main():
                          # SURVEY.md 8(d) priced a step at 24 N F (1 + K) bytes (one read of X per component); the panel
                          # algorithm commits up to 16 components per read, so that figure is not a roofline for it
                          survey_step_bytes=24.0 * N * F * (1 + K)),
+        }
+        if args.full:
             # steady state (what a second animation on a warm context costs) first; `cold` = the first cycle of the process
             # (allocation of the 4.8 GB shard inside prepare, the basis into freshly allocated pageable memory)
-            "end_to_end": dict(steady or {}, basis_bytes=basis_bytes,
-                               note="input already in HBM (F,N,3) -> basis (K,N,3) as an ndarray in (pinned) host memory, one timed "
-                                    "region without intermediate synchronisation, second cycle on a warm context: prepare = "
-                                    "vertex-major layout change + rest shape + standardisation (the calls' host time: the kernels "
-                                    "overlap with what follows), step = extract_k_components with the basis streamed to the host "
-                                    "behind each read of X, basis_wait = what is left of the copy afterwards",
-                               cold={"prepare_ms": prepare_ms, "step_ms": ms_step, "basis_download_ms": download_ms,
-                                     "total_ms": prepare_ms + ms_step + download_ms,
-                                     "snapshots_per_s": F / ((prepare_ms + ms_step + download_ms) * 1e-3),
-                                     "note": "first cycle of the process: prepare includes the allocation of the shard, the "
-                                             "download goes into pageable memory"}),
-        }
-        if not args.no_cpu_baseline and world == 1:      # reported at N = 1 only (the other ranks would wait for it)
+            out["end_to_end"] = dict(steady or {}, basis_bytes=basis_bytes,
+                                     note="input already in HBM (F,N,3) -> basis (K,N,3) as an ndarray in (pinned) host memory, one "
+                                          "timed region without intermediate synchronisation, second cycle on a warm context: prepare "
+                                          "= vertex-major layout change + rest shape + standardisation (the calls' host time: the "
+                                          "kernels overlap with what follows), step = extract_k_components with the basis streamed to "
+                                          "the host behind each read of X, basis_wait = what is left of the copy afterwards",
+                                     cold={"prepare_ms": prepare_ms, "step_ms": ms_step, "basis_download_ms": download_ms,
+                                           "total_ms": prepare_ms + ms_step + download_ms,
+                                           "snapshots_per_s": F / ((prepare_ms + ms_step + download_ms) * 1e-3),
+                                           "note": "first cycle of the process: prepare includes the allocation of the shard, the "
+                                                   "download goes into pageable memory"})
+        if args.full and not args.no_cpu_baseline and world == 1:      # reported at N = 1 only (the other ranks would wait for it)
             out["cpu_baseline"] = cpu_baseline_c4(F, N, K, args.cpu_budget)
-    if world == 1 and not args.no_other_configs and (N, F, K) == (100000, 2000, 128):
+    if args.full and world == 1 and not args.no_other_configs and (N, F, K) == (100000, 2000, 128):
         del comp, snaps, eng
         torch.cuda.empty_cache()
         cpu = not args.no_cpu_baseline

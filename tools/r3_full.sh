@@ -1,5 +1,5 @@
 #!/bin/bash
-# round 3 full session: GPU tests, default bench, kernel statistics (config 4 and config 5), PMC traffic passes
+# round 3 full session: GPU tests, full bench (--full), kernel statistics (config 4 and config 5), PMC traffic passes
 tag=${1:-r3full}
 out=gpurun_out/$tag
 mkdir -p $out
@@ -8,7 +8,7 @@ ok() { [ "$1" -ne 124 ] && [ "$1" -ne 137 ]; }
 timeout -k 10 1000 python -m pytest tests -q -m gpu -x > $out/tests.log 2>&1; rc=$?
 tail -n 6 $out/tests.log
 ok $rc || { echo "tests timed out: stopping"; exit 1; }
-timeout -k 10 700 python bench.py > $out/bench.json 2> $out/bench.err; rc=$?
+timeout -k 10 700 python bench.py --full > $out/bench.json 2> $out/bench.err; rc=$?
 echo "bench rc=$rc"; python -c "import json; d=json.loads(open('$out/bench.json').read()); print(d['ms_per_step'], d['roofline']['frac'], d['end_to_end']['total_ms'], {k:(v.get('ms'),v.get('prepare_ms')) for k,v in d['other_configs'].items()})"
 ok $rc || exit 1
 B="--no-cpu-baseline --no-other-configs"

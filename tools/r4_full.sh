@@ -1,5 +1,5 @@
 #!/bin/bash
-# round 4 full session: GPU tests, default bench (all legs + CPU baselines), kernel statistics (config 4, forced collectives, config 3,
+# round 4 full session: GPU tests, full bench (--full: all legs + CPU baselines), kernel statistics (config 4, forced collectives, config 3,
 # config 5), PMC traffic passes, MFMA-busy pass.   usage: tools/r4_full.sh TAG [skip_tests]
 tag=${1:-r4full}
 out=gpurun_out/$tag
@@ -11,7 +11,7 @@ if [ -z "$2" ]; then
   tail -n 6 $out/tests.log
   ok $rc || { echo "tests timed out: stopping"; exit 1; }
 fi
-timeout -k 10 1000 python bench.py > $out/bench.json 2> $out/bench.err; rc=$?
+timeout -k 10 1000 python bench.py --full > $out/bench.json 2> $out/bench.err; rc=$?
 echo "bench rc=$rc"; python - <<PY
 import json
 d=json.loads(open('$out/bench.json').read())

@@ -9,7 +9,7 @@ if [ -n "$sel" ]; then
   tail -n 25 $out/tests.log; ok $rc || { echo "tests timed out: stopping"; exit 1; }
 fi
 if [ -n "$legs" ]; then
-  timeout -k 10 900 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --legs "$legs" > $out/bench.json 2> $out/bench.err; rc=$?
+  timeout -k 10 900 python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --legs "$legs" > $out/bench.json 2> $out/bench.err; rc=$?
   echo "bench rc=$rc"; python - <<PY
 import json
 d=json.loads(open('$out/bench.json').read())
