@@ -179,6 +179,12 @@ PROTOTYPES = {
                                         ctypes.POINTER(c_int)]),
     "asb_test_spd_inverse": (c_int, [ctypes.c_void_p, c_dp, c_i64, c_dp]),
     "asb_test_project_columns": (c_int, [ctypes.c_void_p, c_dp, c_i64, c_i64, c_int, c_dp, c_int, c_dp, c_i64]),
+    "asb_test_gemm_nn": (c_int, [ctypes.c_void_p, c_dp, c_i64, c_dp, c_i64, c_dp, c_i64, c_i64, c_i64, c_i64, c_dbl, c_dbl, c_int,
+                                 c_i64]),
+    "asb_test_gemm_tn": (c_int, [ctypes.c_void_p, c_int, c_dp, c_i64, c_i64, c_dp, c_i64, c_i64, c_i64, c_i64, c_dp, c_i64, c_i64,
+                                 c_i64, c_i64]),
+    "asb_test_transpose": (c_int, [ctypes.c_void_p, c_dp, c_i64, c_i64, c_dp, c_i64]),
+    "asb_test_sym_eig": (c_int, [ctypes.c_void_p, c_dp, c_i64, c_dp, c_dp, ctypes.POINTER(c_int)]),
 }
 
 

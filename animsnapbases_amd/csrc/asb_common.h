@@ -374,6 +374,10 @@ int asb_deflate_apply_dev(asb_ctx* ctx, int64_t k, const double* s_dev);      //
 // G = X^T X (n x n, both triangles) for a tall row-major X: LDS-tiled f64 MFMA kernel (asb_linalg.hip)
 int asb_syrk_tn(asb_ctx* ctx, const double* X, long long ld, long long R, int n, double* out);
 int asb_gemm_tn_big(asb_ctx* ctx, const double* X, long long ldx, const double* Y, long long ldy, long long R, int I, int J, double* out);
+// test hooks (asb_linalg.hip): a device copy of n host doubles (nullptr: NaN) with `slack` NaN behind it; the result's copy back
+// after the stream drains, freeing f0 .. f2 whatever happened (rc: the status so far, passed through)
+int asb_test_stage(asb_ctx* ctx, const double* h, size_t n, size_t slack, double** d);
+int asb_test_finish(asb_ctx* ctx, int rc, double* out_dev, double* out_host, size_t out_len, double* f0, double* f1, double* f2);
 
 #define ASB_CHECK_LAUNCH(ctx) ASB_HIP(ctx, hipGetLastError())
 

@@ -579,3 +579,22 @@ extern "C" int asb_test_spd_inverse(asb_ctx* ctx, const double* A_host, int64_t 
         for (int64_t j = 0; j < n; ++j) Ainv_host[i * n + j] = pad[(size_t)i * np + j];
     return ASB_OK;
 }
+
+// test hook: asb_gemm_nn as the device paths call it (split-K and cinit chosen by its own rules) on host arrays.  A (M x lda) and
+// B (Kc x ldb) whole, with NaN behind them; all of C (c_len doubles: the ldc padding and whatever tail the caller adds) travels
+// to the device and back, so a write outside the M x N result shows.
+extern "C" int asb_test_gemm_nn(asb_ctx* ctx, const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc,
+                                int64_t M, int64_t N, int64_t Kc, double alpha, double beta, int tri, int64_t c_len) {
+    if (!ctx || !A || !B || !C) return ASB_ERR_ARG;
+    if (M < 1 || N < 1 || Kc < 1 || M > 1 << 30 || N > 1 << 30 || Kc > 1 << 30 || lda < Kc || ldb < N || ldc < N ||
+        (M - 1) * ldc + N > c_len)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_gemm_nn: M = %lld, N = %lld, Kc = %lld, lda = %lld, ldb = %lld, ldc = %lld, c_len = %lld",
+                 (long long)M, (long long)N, (long long)Kc, (long long)lda, (long long)ldb, (long long)ldc, (long long)c_len);
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    double *da = nullptr, *db = nullptr, *dc = nullptr;
+    int rc = asb_test_stage(ctx, A, (size_t)M * lda, 256, &da);
+    if (!rc) rc = asb_test_stage(ctx, B, (size_t)Kc * ldb, 256, &db);
+    if (!rc) rc = asb_test_stage(ctx, C, (size_t)c_len, 0, &dc);
+    if (!rc) rc = asb_gemm_nn(ctx, da, lda, db, ldb, dc, ldc, (int)M, (int)N, (int)Kc, alpha, beta, tri);
+    return asb_test_finish(ctx, rc, dc, C, (size_t)c_len, da, db, dc);
+}

@@ -161,8 +161,12 @@ __global__ __launch_bounds__(256) void k_syrk_finish(const double* __restrict__ 
     }
 }
 
-// G (n x n) = X^T X, X = R rows of stride ld (columns >= n up to ld must be readable: the zero padding of the rows)
+// G (n x n) = X^T X, X = R rows of stride ld (columns >= n up to ld must be readable: the zero padding of the rows).
+// The stages load double2, so ld must be even and X 16-byte aligned: with an odd ld the last column pair of a row reads one
+// element past it and every other row's loads are misaligned.
 int asb_syrk_tn(asb_ctx* ctx, const double* X, long long ld, long long R, int n, double* out) {
+    if ((ld & 1) || ((uintptr_t)X & 15) || ld < n || n < 1 || R < 0)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_syrk_tn: ld = %lld, n = %d, R = %lld (even ld >= n, 16-byte-aligned rows)", ld, n, R);
     const int nb = (n + SY_BM - 1) / SY_BM;
     const int tiles = nb * (nb + 1) / 2;
     // enough blocks for >= 8 rounds of the chip's 512 resident blocks, slabs of at least 512 rows
@@ -195,6 +199,9 @@ __global__ __launch_bounds__(256) void k_sum_parts(const double* __restrict__ pa
 }
 // Out (I x J, row-major) = X^T Y for tall X (R x I, stride ldx) and Y (R x J, stride ldy); even strides, 16-byte aligned rows
 int asb_gemm_tn_big(asb_ctx* ctx, const double* X, long long ldx, const double* Y, long long ldy, long long R, int I, int J, double* out) {
+    if (((ldx | ldy) & 1) || (((uintptr_t)X | (uintptr_t)Y) & 15) || ldx < I || ldy < J || I < 1 || J < 1 || R < 0)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_gemm_tn_big: ldx = %lld, ldy = %lld, I = %d, J = %d, R = %lld (even strides, 16-byte-aligned rows)",
+                 ldx, ldy, I, J, R);
     const int nbi = (I + SY_BM - 1) / SY_BM, nbj = (J + SY_BM - 1) / SY_BM, tiles = nbi * nbj;
     int S = (8 * 512 + tiles - 1) / tiles;
     const long long maxS = (R + 511) / 512;
@@ -442,10 +449,11 @@ extern "C" int asb_orth_gram(asb_ctx* ctx, double* G_dev) {
     if ((rc = asb_transpose(ctx, ctx->comps, K, 3 * n, ctx->oct))) return rc;          // (3n x K): row 3v+l
     double* G = G_dev ? G_dev : ctx->og;
     // K >= 64 (the constraint bases: K = 288 at config 5): the 128 x 128-tile Gram kernel of the POD on the rows l, l + 3, ... --
-    // 0.15 ms per slice against 1.7 ms for the one-wave-per-16 x 16-tile kernel, whose tile count explodes with K^2
+    // 0.15 ms per slice against 1.7 ms for the one-wave-per-16 x 16-tile kernel, whose tile count explodes with K^2.  Even K only:
+    // slice l starts at l K and its rows are 3 K apart, which the kernel's double2 stages need to be even
     static const int big = getenv("ASB_ORTH_SYRK") ? atoi(getenv("ASB_ORTH_SYRK")) : 1;
     for (int l = 0; l < 3; ++l) {
-        if (big && K >= 64) rc = asb_syrk_tn(ctx, ctx->oct + l * K, 3 * K, n, (int)K, G + (size_t)l * K * K);
+        if (big && K >= 64 && !(K & 1)) rc = asb_syrk_tn(ctx, ctx->oct + l * K, 3 * K, n, (int)K, G + (size_t)l * K * K);
         else rc = asb_gemm_tn(ctx, ctx->oct + l * K, 3 * K, ctx->oct + l * K, 3 * K, n, (int)K, (int)K, G + (size_t)l * K * K);
         if (rc) return rc;
     }
@@ -707,4 +715,90 @@ extern "C" int asb_components_pinned(asb_ctx* ctx, double** out) {
     ASB_HIP(ctx, hipStreamSynchronize(ctx->dl_stream));
     *out = ctx->dl_host;
     return ASB_OK;
+}
+
+// ---- test hooks on host arrays (tests/test_gpu_dense_blocks.py) ----------------------------------------------------------
+// A device copy of a host array of n doubles with `slack` NaN behind it (h == nullptr: n NaN too), so that a read past an
+// operand shows in the result; the buffers are the hook's own, not the production callers' padded ones.
+int asb_test_stage(asb_ctx* ctx, const double* h, size_t n, size_t slack, double** d) {
+    *d = nullptr;
+    ASB_HIP(ctx, hipMalloc((void**)d, (n + slack) * sizeof(double)));
+    hipError_t e = hipMemsetAsync(*d, 0xff, (n + slack) * sizeof(double), ctx->stream);       // all bits set: a NaN
+    if (e == hipSuccess && h && n) e = hipMemcpyAsync(*d, h, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(*d);
+        *d = nullptr;
+        ASB_FAIL(ctx, ASB_ERR_HIP, "asb_test_stage: %s", hipGetErrorString(e));
+    }
+    return ASB_OK;
+}
+// out_len doubles device -> host after the stream has drained; frees the listed buffers whatever happened
+int asb_test_finish(asb_ctx* ctx, int rc, double* out_dev, double* out_host, size_t out_len, double* f0, double* f1, double* f2) {
+    hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (rc == ASB_OK && e == hipSuccess && out_host) e = hipMemcpy(out_host, out_dev, out_len * sizeof(double), hipMemcpyDeviceToHost);
+    (void)hipFree(f0);
+    (void)hipFree(f1);
+    (void)hipFree(f2);
+    if (rc) return rc;
+    if (e != hipSuccess) ASB_FAIL(ctx, ASB_ERR_HIP, "asb test hook: %s", hipGetErrorString(e));
+    return ASB_OK;
+}
+
+// X (R x ldx) and Y (R x ldy) whole; out (out_len) in and out.  form 0: asb_gemm_tn_s (out[i so_i + j so_j] = sum_r X[r ldx + i sx]
+// Y[r ldy + j], I_split as given); 1: asb_gemm_tn_big (out I x J contiguous); 2: asb_syrk_tn on X (J = I, Y unused).
+extern "C" int asb_test_gemm_tn(asb_ctx* ctx, int form, const double* X, int64_t ldx, int64_t sx, const double* Y, int64_t ldy,
+                                int64_t R, int64_t I, int64_t J, double* out, int64_t so_i, int64_t so_j, int64_t out_len,
+                                int64_t I_split) {
+    if (!ctx || !X || !out || (form != 2 && !Y)) return ASB_ERR_ARG;
+    const long long last = form == 0 ? (I - 1) * so_i + (J - 1) * so_j : I * J - 1;
+    if (form < 0 || form > 2 || R < 1 || I < 1 || J < 1 || I > 1 << 30 || J > 1 << 30 || (form == 2 && J != I) || last < 0 ||
+        last >= out_len || (form == 0 && (sx < 1 || so_i < 1 || so_j < 1 || (I - 1) * sx >= ldx || J > ldy)))
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_gemm_tn: form %d, R = %lld, I = %lld, J = %lld, ldx = %lld, ldy = %lld, out_len = %lld",
+                 form, (long long)R, (long long)I, (long long)J, (long long)ldx, (long long)ldy, (long long)out_len);
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    double *dx = nullptr, *dy = nullptr, *dout = nullptr;
+    int rc = asb_test_stage(ctx, X, (size_t)R * ldx, 256, &dx);
+    if (!rc && form != 2) rc = asb_test_stage(ctx, Y, (size_t)R * ldy, 256, &dy);
+    if (!rc) rc = asb_test_stage(ctx, out, (size_t)out_len, 0, &dout);
+    if (!rc) {
+        if (form == 0) rc = asb_gemm_tn_s(ctx, dx, ldx, sx, dy, ldy, R, (int)I, (int)J, dout, so_i, so_j, I_split);
+        else if (form == 1) rc = asb_gemm_tn_big(ctx, dx, ldx, dy, ldy, R, (int)I, (int)J, dout);
+        else rc = asb_syrk_tn(ctx, dx, ldx, R, (int)I, dout);
+    }
+    return asb_test_finish(ctx, rc, dout, out, (size_t)out_len, dx, dy, dout);
+}
+
+// in (rows x cols) -> out[c rows + r]; the whole of out (out_len >= rows cols) round-trips
+extern "C" int asb_test_transpose(asb_ctx* ctx, const double* in, int64_t rows, int64_t cols, double* out, int64_t out_len) {
+    if (!ctx || !in || !out) return ASB_ERR_ARG;
+    if (rows < 1 || cols < 1 || rows * cols > out_len || (rows + 31) / 32 > 65535)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_transpose: %lld x %lld, out_len = %lld", (long long)rows, (long long)cols, (long long)out_len);
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    double *din = nullptr, *dout = nullptr;
+    int rc = asb_test_stage(ctx, in, (size_t)rows * cols, 256, &din);
+    if (!rc) rc = asb_test_stage(ctx, out, (size_t)out_len, 0, &dout);
+    if (!rc) rc = asb_transpose(ctx, din, rows, cols, dout);
+    return asb_test_finish(ctx, rc, dout, out, (size_t)out_len, din, dout, nullptr);
+}
+
+// the one-block Jacobi solver (n <= 128) on a host matrix: lam (n) descending, V (n x n) eigenvectors as columns;
+// *status = the solver's status word (2: no convergence within its sweeps)
+extern "C" int asb_test_sym_eig(asb_ctx* ctx, const double* A, int64_t n, double* lam, double* V, int* status) {
+    if (!ctx || !A || !lam || !V || !status) return ASB_ERR_ARG;
+    if (n < 1 || n > 128) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_sym_eig: n = %lld (the one-block solver takes 1 .. 128)", (long long)n);
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    double *da = nullptr, *dv = nullptr;
+    int rc = asb_test_stage(ctx, A, (size_t)n * n, 256, &da);
+    if (!rc) rc = asb_test_stage(ctx, nullptr, (size_t)n * n + n, 0, &dv);         // V, then lam
+    if (!rc) rc = asb_sym_eig(ctx, da, (int)n, dv + (size_t)n * n, dv);
+    int st[4] = {0, 0, 0, 0};
+    if (!rc && hipMemcpyAsync(st, ctx->la_status, sizeof(st), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = ASB_ERR_HIP;
+    std::vector<double> h((size_t)n * n + n);
+    rc = asb_test_finish(ctx, rc, dv, h.data(), h.size(), da, dv, nullptr);
+    if (rc) return rc;
+    std::copy(h.begin(), h.begin() + n * n, V);
+    std::copy(h.begin() + n * n, h.end(), lam);
+    *status = st[0];
+    return rc;
 }

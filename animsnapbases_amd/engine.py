@@ -719,6 +719,49 @@ class HipEngine(object):
                                                    ptr(out), out.shape[0]))
         return out
 
+    # the dense f64 building blocks on host arrays (tests/test_gpu_dense_blocks.py); outputs are updated in place, all of them
+    def test_gemm_nn(self, A, B, C, ldc, M, N, Kc, alpha=1.0, beta=0.0, tri=0):
+        """C (1-D, rows of stride ldc) = beta C + alpha A[:M, :Kc] B[:Kc, :N] through asb_gemm_nn; A, B 2-D contiguous (their
+        widths are the strides); all of C round-trips."""
+        for a in (A, B, C):
+            assert a.dtype == np.float64 and a.flags.c_contiguous
+        assert A.ndim == 2 and B.ndim == 2 and C.ndim == 1
+        self._ck(self.lib.asb_test_gemm_nn(self.h, ptr(A), A.shape[1], ptr(B), B.shape[1], ptr(C), int(ldc), int(M), int(N), int(Kc),
+                                           float(alpha), float(beta), int(tri), C.size))
+        return C
+
+    def test_gemm_tn(self, form, X, R, I, J, out, Y=None, sx=1, so_i=None, so_j=1, I_split=0):
+        """form 0: out.flat[i so_i + j so_j] = sum_r X[r, i sx] Y[r, j] (so_i defaults to J); 1: out[:I*J] = X[:, :I]^T Y[:, :J];
+        2: out[:I*I] = X[:, :I]^T X[:, :I].  X (R, ldx), Y (R, ldy) 2-D contiguous; out 1-D, all of it round-trips."""
+        assert X.dtype == np.float64 and X.flags.c_contiguous and X.shape[0] == R
+        assert out.dtype == np.float64 and out.flags.c_contiguous and out.ndim == 1
+        if Y is not None:
+            assert Y.dtype == np.float64 and Y.flags.c_contiguous and Y.shape[0] == R
+        self._ck(self.lib.asb_test_gemm_tn(self.h, int(form), ptr(X), X.shape[1], int(sx), ptr(Y), Y.shape[1] if Y is not None else 0,
+                                           int(R), int(I), int(J), ptr(out), int(J if so_i is None else so_i), int(so_j), out.size,
+                                           int(I_split)))
+        return out
+
+    def test_transpose(self, A, out):
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        assert out.dtype == np.float64 and out.flags.c_contiguous
+        self._ck(self.lib.asb_test_transpose(self.h, ptr(A), A.shape[0], A.shape[1], ptr(out), out.size))
+        return out
+
+    def test_sym_eig(self, A):
+        """(lam descending, V with eigenvectors as columns, status word) of the one-block Jacobi solver (n <= 128)."""
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        n = A.shape[0]
+        lam, V, st = np.empty(n), np.empty((n, n)), ctypes.c_int()
+        self._ck(self.lib.asb_test_sym_eig(self.h, ptr(A), n, ptr(lam), ptr(V), ctypes.byref(st)))
+        return lam, V, st.value
+
+    def test_spd_inverse(self, A):
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        out = np.empty_like(A)
+        self._ck(self.lib.asb_test_spd_inverse(self.h, ptr(A), A.shape[0], ptr(out)))
+        return out
+
     def test_chol_tinv(self, G):
         G = np.ascontiguousarray(G, dtype=np.float64)
         Tt = np.empty_like(G)

@@ -627,6 +627,22 @@ int asb_test_spd_inverse(asb_ctx* ctx, const double* A_host, int64_t n, double* 
  * columns; path 1: the multi-tile kernels in one pass (ceil(ncols / 16) tiles, ncols <= 128; ASB_WIDE_VARIANT applies). */
 int asb_test_project_columns(asb_ctx* ctx, const double* W_host, int64_t ldw, int64_t k0, int ncols, const double* col_scale_host,
                              int path, double* out_host, int64_t out_cols);
+/* test hooks of the dense f64 building blocks on host arrays.  Operands travel whole (with NaN behind them), outputs round-trip
+ * whole, so a write outside the result shows; arguments are refused as the wrapped function refuses them.
+ * asb_test_gemm_nn: C (c_len doubles, ld ldc) = beta C + alpha A B through asb_gemm_nn (split-K, the triangular form `tri` and the
+ * C -= A B form chosen by its own rules); A (M x lda), B (Kc x ldb).
+ * asb_test_gemm_tn: X (R x ldx), Y (R x ldy), out (out_len doubles).  form 0: out[i so_i + j so_j] = sum_r X[r ldx + i sx] Y[r ldy + j]
+ * (the one-wave-per-tile kernel, contraction split as for an I_split-row product when I_split > 0); form 1: out (I x J) = X^T Y on
+ * the 128 x 128-tile kernel; form 2: out (I x I) = X^T X on its symmetric form (J = I, Y unused).
+ * asb_test_transpose: out[c rows + r] = in[r cols + c] (out_len >= rows cols).
+ * asb_test_sym_eig: the one-block Jacobi solver (n <= 128): lam descending, V (n x n) eigenvectors as columns, *status = its
+ * status word (2: no convergence). */
+int asb_test_gemm_nn(asb_ctx* ctx, const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc, int64_t M,
+                     int64_t N, int64_t Kc, double alpha, double beta, int tri, int64_t c_len);
+int asb_test_gemm_tn(asb_ctx* ctx, int form, const double* X, int64_t ldx, int64_t sx, const double* Y, int64_t ldy, int64_t R,
+                     int64_t I, int64_t J, double* out, int64_t so_i, int64_t so_j, int64_t out_len, int64_t I_split);
+int asb_test_transpose(asb_ctx* ctx, const double* in, int64_t rows, int64_t cols, double* out, int64_t out_len);
+int asb_test_sym_eig(asb_ctx* ctx, const double* A, int64_t n, double* lam, double* V, int* status);
 
 #ifdef __cplusplus
 }
