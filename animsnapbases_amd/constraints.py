@@ -15,8 +15,8 @@ interpolation solves (an O(k^2) bordered-inverse update whose residual is checke
 the fallback); LAPACK ``eigh`` on the Gram matrix only with ``ASB_POD_EIG=host``.
 
 The other basis types and interpolations of the reference (``pod`` per-(p,d) slices, ``pca_blocks``,
-``pca_blocks_with_St``, geometric / block DEIM) run on the device too; on several ranks all but ``pod``
-(which raises ``NotImplementedError`` there).
+``pca_blocks_with_St``, geometric / block DEIM) run on the device too, on one rank or several; ``pod`` on
+several ranks splits its 3p eigen-problems over the ranks (shards of whole constraints).
 """
 import csv
 import os
@@ -376,6 +376,7 @@ class constraintsComponents:  # Components == bases
         self.St = None
         self.st_halo_rows = None         # several ranks: the halo size (constraint rows kept as copies) of every rank
         self.singular_values = None
+        self._phased_pod_slices = False  # tests: drive the multi-rank protocol of 'pod' on one rank
 
     @property
     def comps(self):
@@ -658,17 +659,48 @@ class constraintsComponents:  # Components == bases
         """constraintsComponents.py:274-294 ('pod'): a batched SVD over the (p, d) slices of the snapshots, each an e x F
         matrix; component k carries the k-th left singular vector of every slice.  The reference runs torch's float32 SVD
         on the CPU; here every slice goes through Gram matrix -> device eigen-solver -> U = M V S^-1 in float64 (nothing is
-        written to the CSV by the reference either)."""
+        written to the CSV by the reference either).  Several ranks: see ``_pod_slices_phased``."""
         ns = self.nonlinearSnapshots
         eng, comm = ns._engine, ns._comm
-        if comm.multi:
-            raise NotImplementedError("constProj_basis_type 'pod' runs on one rank")
         p = int(ns.constraintsSize)
         e = ns.frames_rows // p
         K = min(int(self.param.deim_desired_num_components), min(e, ns.frs))
-        eng.pod_slices(p, K)
+        if comm.multi or self._phased_pod_slices:
+            self._pod_slices_phased(p, K)
+        else:
+            eng.pod_slices(p, K)
         self._comps, self._comps_on_device = None, True
         self.numComp = K
+
+    def _pod_slices_phased(self, p, K):
+        """'pod' with the rows sharded over W ranks in whole constraints.  Rounds of W slices: every rank adds its partial
+        Gram matrices of the round's slices to one exchange buffer (all-reduced), rank r solves slice s0 + r of the round --
+        the W eigen-problems of a round run at the same time -- and writes V S^-1 and its refusal flag into its slot of a
+        zeroed (3p, F, K) + 3p buffer; one all-reduce of that buffer hands every slice to every rank (sums with zeros: the
+        owner's bits), and each rank forms its own basis rows.  Exchange memory: min(W, 3p) F^2 + 3p (F K + 1) doubles."""
+        ns = self.nonlinearSnapshots
+        eng, comm = ns._engine, ns._comm
+        for v0, n_loc in ns._shards:
+            if v0 % p or n_loc % p:
+                raise ValueError("'pod' with p = %d needs shards of whole constraints; %d rows over %d ranks do not split "
+                                 "that way" % (p, ns.frames_rows, comm.world))
+        F, S, W = int(ns.frs), 3 * p, comm.world
+        VS = comm.new_buffer(S * F * K + S, eng.device_exchange)
+        G = comm.new_buffer(min(W, S) * F * F, eng.device_exchange)
+        if eng.device_exchange:
+            import torch
+            torch.cuda.synchronize()          # (the zeroed buffers are there before an engine on a stream of its own writes)
+        for s0 in range(0, S, W):
+            n = min(W, S - s0)
+            Gr = G[:n * F * F]
+            eng.pod_slice_grams(p, s0, n, Gr.data_ptr())
+            comm.allreduce_tensor(Gr)
+            if comm.rank < n:
+                s = s0 + comm.rank
+                eng.pod_slice_eig(K, Gr[comm.rank * F * F:].data_ptr(), VS[s * F * K:].data_ptr(), VS[S * F * K + s:].data_ptr())
+        comm.allreduce_tensor(VS)
+        eng.pod_slices_basis(p, K, VS.data_ptr())
+        eng.sync()                            # (the basis GEMMs have read VS before it is released)
 
     @log_time(constProj_output_directory)
     def compute_pod_for_vectorized_nonlinear_snapshots_tensor(self, writer=None):

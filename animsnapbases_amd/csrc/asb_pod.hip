@@ -298,6 +298,90 @@ extern "C" int asb_pod_slices(asb_ctx* ctx, int p, int64_t K) {
     return ASB_OK;
 }
 
+// ---- the per-slice POD in phases (several ranks: rows sharded in whole constraints).  Slice s = 3 p_i + d has the rows
+// 3 (e_i p + p_i) + d; with v0 % p == 0 they are this shard's local rows 3 p e_l + s as well.  The caller all-reduces the
+// partial Gram matrices, lets the owner of each slice solve it (asb_pod_slice_eig into a zeroed exchange buffer), all-reduces
+// that buffer and forms the shard's basis rows from every slice's V S^-1 (asb_pod_slices_basis).  The same GEMM, eigen-solver
+// and scaling calls as asb_pod_slices: on one rank the phases give its basis bit for bit.
+static int pod_whole_constraints(asb_ctx* ctx, int p, const char* who) {
+    if (ctx->v0 % p || ctx->n_loc % p)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "%s: rows [%lld, %lld) are not whole constraints of %d", who, (long long)ctx->v0,
+                 (long long)(ctx->v0 + ctx->n_loc), p);
+    return ASB_OK;
+}
+
+// partial Gram matrices (F x F each) of slices s0 .. s0 + ns - 1 over this shard's constraints into G_dev (ns x F x F)
+extern "C" int asb_pod_slice_grams(asb_ctx* ctx, int p, int s0, int ns, double* G_dev) {
+    if (!ctx || !ctx->X || !G_dev || p < 1 || s0 < 0 || ns < 1 || s0 + ns > 3 * p) return ASB_ERR_ARG;
+    int rc;
+    if ((rc = pod_whole_constraints(ctx, p, "asb_pod_slice_grams"))) return rc;
+    const int64_t F = ctx->F, e_loc = ctx->n_loc / p;
+    const long long stride = 3LL * p * ctx->Fp;
+    for (int s = s0; s < s0 + ns; ++s) {
+        const double* Xs = ctx->X + (long long)s * ctx->Fp;
+        if ((rc = asb_gemm_tn_s(ctx, Xs, stride, 1, Xs, stride, e_loc, (int)F, (int)F, G_dev + (size_t)(s - s0) * F * F, F, 1))) return rc;
+    }
+    return ASB_OK;
+}
+
+// the scaled vectors (F x K) and the refusal flag (status[1] of k_scale_cols_inv_sqrt, as 0.0 / 1.0) into an exchange slot
+__global__ __launch_bounds__(256) void k_pod_slot(const double* __restrict__ V, long long n, const int* __restrict__ status,
+                                                  double* __restrict__ out, double* __restrict__ out_status) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) out[i] = V[i];
+    if (blockIdx.x == 0 && threadIdx.x == 0) out_status[0] = status[1] ? 1.0 : 0.0;
+}
+
+// one slice's eigen-problem: G_dev (F x F, the all-reduced Gram matrix; overwritten) -> V S^-1 (F x K, row-major) into VS_dev
+// and the refusal flag (fewer than K singular values above 1e-7 of the largest) into status_dev[0]
+extern "C" int asb_pod_slice_eig(asb_ctx* ctx, int64_t K, double* G_dev, double* VS_dev, double* status_dev) {
+    if (!ctx || !G_dev || !VS_dev || !status_dev || K < 1) return ASB_ERR_ARG;
+    const int64_t F = ctx->F;
+    if (F < 3) ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_pod_slice_eig needs F >= 3");
+    if (K > F) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pod_slice_eig: K = %lld exceeds F = %lld", (long long)K, (long long)F);
+    int rc;
+    if ((rc = asb_alloc(ctx, &ctx->la_status, (size_t)4))) return rc;
+    std::vector<double> lam((size_t)F);
+    int64_t bad = 0;
+    if ((rc = asb_sym_eig_topk(ctx, G_dev, F, K, lam.data(), nullptr, &bad))) return rc;
+    ASB_HIP(ctx, hipMemsetAsync(ctx->la_status, 0, 4 * sizeof(int), ctx->stream));
+    hipLaunchKernelGGL(k_scale_cols_inv_sqrt, dim3(64), dim3(256), 0, ctx->stream, ctx->eig_v, (int)F, (int)K, ctx->eig_lam, 1e-7,
+                       ctx->la_status);
+    const long long n = (long long)F * K;
+    const long long want = (n + 255) / 256;
+    hipLaunchKernelGGL(k_pod_slot, dim3((unsigned)(want < 1024 ? want : 1024)), dim3(256), 0, ctx->stream, ctx->eig_v, n, ctx->la_status,
+                       VS_dev, status_dev);
+    ASB_CHECK_LAUNCH(ctx);
+    return ASB_OK;
+}
+
+// the shard's basis rows from all 3p slices: VS_all_dev = (3p, F, K) scaled vectors followed by 3p refusal flags (the
+// all-reduced exchange buffer).  A set flag fails with asb_pod_slices' error for the lowest such slice, before any work.
+extern "C" int asb_pod_slices_basis(asb_ctx* ctx, int p, int64_t K, const double* VS_all_dev) {
+    if (!ctx || !ctx->X || !VS_all_dev || p < 1 || K < 1) return ASB_ERR_ARG;
+    int rc;
+    if ((rc = pod_whole_constraints(ctx, p, "asb_pod_slices_basis"))) return rc;
+    const int64_t F = ctx->F, n3 = 3 * ctx->n_loc, e_loc = ctx->n_loc / p, e = ctx->N_glob / p;
+    if (K > F || K > e)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pod_slices_basis: K = %lld exceeds min(e, F) = %lld", (long long)K, (long long)(e < F ? e : F));
+    const int S = 3 * p;
+    std::vector<double> st((size_t)S);
+    ASB_HIP(ctx, hipMemcpyAsync(st.data(), VS_all_dev + (size_t)S * F * K, (size_t)S * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int s = 0; s < S; ++s)
+        if (st[s] != 0.0)
+            ASB_FAIL(ctx, ASB_ERR_NUMERIC, "pod: slice %d has fewer than %lld singular values above 1e-7 of its largest", s, (long long)K);
+    if ((rc = asb_alloc(ctx, &ctx->comps, (size_t)K * n3))) return rc;
+    if ((rc = asb_alloc(ctx, &ctx->s_dev, (size_t)ctx->n_loc))) return rc;
+    ctx->K = K;
+    const long long stride = 3LL * p * ctx->Fp;
+    for (int s = 0; s < S; ++s) {
+        const double* Xs = ctx->X + (long long)s * ctx->Fp;
+        if ((rc = asb_gemm_tn_s(ctx, Xs, 1, stride, VS_all_dev + (size_t)s * F * K, K, F, (int)e_loc, (int)K, ctx->comps + s, 3LL * p, n3)))
+            return rc;
+    }
+    return ASB_OK;
+}
+
 // Rayleigh-Ritz rotation: the (all-reduced) K x F matrix B = Q^T A (B_dev, or the one asb_pod_project left in the context;
 // overwritten) -> its singular values S_host (K, descending) and left vectors U_B by one-sided Jacobi on its rows, then
 // basis <- Q U_B.  The device counterpart of the small SVD the reference gets from gesdd on A itself (:307).

@@ -670,6 +670,20 @@ class HipEngine(object):
         self._ck(self.lib.asb_pod_slices(self.h, int(p), int(K)))
         self.K = int(K)
 
+    def pod_slice_grams(self, p, s0, ns, G_dev_ptr):
+        """Partial Gram matrices of slices s0 .. s0 + ns - 1 over this shard into the device buffer (ns x F x F)."""
+        self._ck(self.lib.asb_pod_slice_grams(self.h, int(p), int(s0), int(ns), ctypes.c_void_p(G_dev_ptr)))
+
+    def pod_slice_eig(self, K, G_dev_ptr, VS_dev_ptr, status_dev_ptr):
+        """One slice's eigen-solve: V S^-1 (F x K) and the refusal flag into device exchange slots."""
+        self._ck(self.lib.asb_pod_slice_eig(self.h, int(K), ctypes.c_void_p(G_dev_ptr), ctypes.c_void_p(VS_dev_ptr),
+                                            ctypes.c_void_p(status_dev_ptr)))
+
+    def pod_slices_basis(self, p, K, VS_all_dev_ptr):
+        """This shard's basis rows from every slice's V S^-1 (the all-reduced exchange buffer)."""
+        self._ck(self.lib.asb_pod_slices_basis(self.h, int(p), int(K), ctypes.c_void_p(VS_all_dev_ptr)))
+        self.K = int(K)
+
     def pod_rotate(self, B_dev_ptr=None):
         S = np.empty(self.K)
         self._ck(self.lib.asb_pod_rotate(self.h, ctypes.c_void_p(B_dev_ptr) if B_dev_ptr else None, ptr(S)))

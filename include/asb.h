@@ -497,6 +497,16 @@ int asb_pod_deflate_end(asb_ctx* ctx, int64_t last);
  * slice of the snapshots -- e x F matrices -- by Gram matrix + device eigen-solver; the K leading left vectors of every
  * slice become the device-resident basis (K, e p, 3).  The reference does this in float32 with torch on the CPU. */
 int asb_pod_slices(asb_ctx* ctx, int p, int64_t K);
+/* The same per-slice POD in phases, for rows sharded over ranks in whole constraints (v0 and n_loc multiples of p); slice
+ * s = 3 p_i + d.  asb_pod_slice_grams: this shard's partial Gram matrices (F x F each) of slices s0 .. s0 + ns - 1 into G_dev
+ * (ns x F x F; the caller all-reduces them).  asb_pod_slice_eig: the owner's eigen-solve of one all-reduced Gram matrix
+ * (G_dev, overwritten) -> V S^-1 (F x K row-major) into VS_dev and the refusal flag (1.0: fewer than K singular values above
+ * 1e-7 of the largest, else 0.0) into status_dev[0].  asb_pod_slices_basis: the shard's basis rows (K, n_loc, 3) from
+ * VS_all_dev = the all-reduced (3p, F, K) vectors followed by the 3p flags; a set flag fails as asb_pod_slices does.  On one
+ * rank the three phases give asb_pod_slices' basis bit for bit. */
+int asb_pod_slice_grams(asb_ctx* ctx, int p, int s0, int ns, double* G_dev);
+int asb_pod_slice_eig(asb_ctx* ctx, int64_t K, double* G_dev, double* VS_dev, double* status_dev);
+int asb_pod_slices_basis(asb_ctx* ctx, int p, int64_t K, const double* VS_all_dev);
 /* asb_qr_apply with ONE Cholesky factor of the sum of the three Gram matrices for all three slices: the basis becomes
  * orthonormal as (3 n)-vectors (the Q of the Rayleigh-Ritz step).  Any K. */
 int asb_qr_apply_joint(asb_ctx* ctx, const double* G_dev);
