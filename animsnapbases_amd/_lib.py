@@ -178,6 +178,13 @@ PROTOTYPES = {
                                      ctypes.POINTER(c_dbl)]),
     "asb_splocs_results": (c_int, [ctypes.c_void_p, c_dp, c_dp]),
     "asb_test_eig3": (None, [c_dp, c_dp]),
+    "asb_test_eig3_fast": (None, [c_dp, c_dp]),
+    "asb_test_pick_cfg": (None, [c_i64, c_dp]),
+    "asb_test_eig3_dev": (c_int, [ctypes.c_void_p, c_int, c_dp, c_i64, c_dp, c_i64]),
+    "asb_test_deflate_step": (c_int, [ctypes.c_void_p, c_i64, c_dp, c_dbl, c_dp]),
+    "asb_test_deflate_state": (c_int, [ctypes.c_void_p, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "asb_test_local_best": (c_int, [ctypes.c_void_p, c_i64, c_dp]),
+    "asb_test_pick_records": (c_int, [ctypes.c_void_p, c_i64, c_dp, c_i64]),
     "asb_test_sketch_predict": (c_int, [ctypes.c_void_p, c_dp, c_dp, c_dp, c_i64, c_int, c_int, c_dp, ctypes.POINTER(c_i64),
                                         ctypes.POINTER(c_int)]),
     "asb_test_spd_inverse": (c_int, [ctypes.c_void_p, c_dp, c_i64, c_dp]),

@@ -7,6 +7,16 @@
 extern "C" void asb_test_eig3(const double* a6, double* out4) {
     eig3_top(a6[0], a6[1], a6[2], a6[3], a6[4], a6[5], out4[0], out4[1], out4[2], out4[3]);
 }
+// the same for the root-and-cross-product solver of the panel kernel and the sketch replay
+extern "C" void asb_test_eig3_fast(const double* a6, double* out4) {
+    eig3_top_fast(a6[0], a6[1], a6[2], a6[3], a6[4], a6[5], out4[0], out4[1], out4[2], out4[3]);
+}
+// the stream configuration of a padded row length: out5 = (ok, T, E2, block, vpb)
+extern "C" void asb_test_pick_cfg(int64_t Fp, int* out5) {
+    StreamCfg c{0, 0, 0, 0};
+    out5[0] = pick_cfg(Fp, c) ? 1 : 0;
+    out5[1] = c.T; out5[2] = c.E2; out5[3] = c.block; out5[4] = c.vpb;
+}
 
 // --------------------------------------------------------------------------------------
 // host side
@@ -372,4 +382,88 @@ extern "C" int asb_deflate_spec_stats(asb_ctx* ctx, int64_t* tried, int64_t* kep
     if (tried) *tried = ctx->n_spec_steps;
     if (kept) *kept = ctx->n_spec_kept;
     return ASB_OK;
+}
+
+// --------------------------------------------------------------------------------------
+// test hooks of the greedy step (tests/test_gpu_deflate_step.py)
+// --------------------------------------------------------------------------------------
+// both 3 x 3 solvers on the device, one thread per matrix: a6 (n x 6) -> out4 (n x 4)
+static __global__ __launch_bounds__(64) void k_test_eig3(const double* __restrict__ a6, long long n, int fast, double* __restrict__ out4) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double* a = a6 + i * 6;
+    double lam, u0, u1, u2;
+    if (fast) eig3_top_fast(a[0], a[1], a[2], a[3], a[4], a[5], lam, u0, u1, u2);
+    else eig3_top(a[0], a[1], a[2], a[3], a[4], a[5], lam, u0, u1, u2);
+    out4[i * 4 + 0] = lam; out4[i * 4 + 1] = u0; out4[i * 4 + 2] = u1; out4[i * 4 + 3] = u2;
+}
+extern "C" int asb_test_eig3_dev(asb_ctx* ctx, int fast, const double* a6, int64_t n, double* out4, int64_t out_len) {
+    if (!ctx || !a6 || !out4) return ASB_ERR_ARG;
+    if (n < 1 || n > (1 << 24) || out_len < 4 * n) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_eig3_dev: n = %lld, out_len = %lld", (long long)n, (long long)out_len);
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    double *da = nullptr, *dout = nullptr;
+    int rc = asb_test_stage(ctx, a6, (size_t)n * 6, 64, &da);
+    if (!rc) rc = asb_test_stage(ctx, out4, (size_t)out_len, 0, &dout);
+    if (!rc) {
+        hipLaunchKernelGGL(k_test_eig3, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, da, (long long)n, fast, dout);
+        if (hipGetLastError() != hipSuccess) rc = ASB_ERR_HIP;
+    }
+    return asb_test_finish(ctx, rc, dout, out4, (size_t)out_len, da, dout, nullptr);
+}
+
+// component k from the caller: w (F doubles; the padding of the row is zeroed here), |w|^2 as given, then the UPDATE pass of
+// asb_deflate_apply itself (s: n_loc support factors or NULL)
+extern "C" int asb_test_deflate_step(asb_ctx* ctx, int64_t k, const double* w, double wn2, const double* s) {
+    if (!ctx || !ctx->R || !ctx->W || !w) return ASB_ERR_ARG;
+    if (ctx->mode != ASB_DEFLATE_RESIDUAL) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_deflate_step needs the residual mode");
+    if (k < 0 || k >= ctx->K) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_deflate_step: k = %lld out of range", (long long)k);
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    std::vector<double> row((size_t)ctx->Fp, 0.0);
+    std::copy(w, w + ctx->F, row.begin());
+    ASB_HIP(ctx, hipMemcpyAsync(ctx->W + k * ctx->Fp, row.data(), row.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    ASB_HIP(ctx, hipMemcpyAsync(ctx->scal + k * 4 + 1, &wn2, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));          // row and wn2 are temporaries of this call
+    return asb_deflate_apply(ctx, k, s);
+}
+
+// state of the residual mode as it stands, every pointer optional: energy (n_loc), the partial records of the last streaming pass
+// pmax / pidx / psum (nblk each; room for nblk_cap), counts = (nblk, nblk_cap), scal ((K + 1) x 4), W (K x Fp, padding included),
+// R (3 n_loc x Fp, padding included)
+extern "C" int asb_test_deflate_state(asb_ctx* ctx, double* energy, double* pmax, int64_t* pidx, double* psum, int64_t* counts,
+                                      double* scal, double* W, double* R) {
+    if (!ctx || !ctx->R || !ctx->energy || !ctx->scal || !ctx->W) return ASB_ERR_ARG;
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    const size_t nb = (size_t)ctx->nblk, d = sizeof(double);
+    if (energy) ASB_HIP(ctx, hipMemcpyAsync(energy, ctx->energy, (size_t)ctx->n_loc * d, hipMemcpyDeviceToHost, ctx->stream));
+    if (pmax) ASB_HIP(ctx, hipMemcpyAsync(pmax, ctx->pmax, nb * d, hipMemcpyDeviceToHost, ctx->stream));
+    if (pidx) ASB_HIP(ctx, hipMemcpyAsync(pidx, ctx->pidx, nb * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    if (psum) ASB_HIP(ctx, hipMemcpyAsync(psum, ctx->psum, nb * d, hipMemcpyDeviceToHost, ctx->stream));
+    if (scal) ASB_HIP(ctx, hipMemcpyAsync(scal, ctx->scal, (size_t)(ctx->K + 1) * 4 * d, hipMemcpyDeviceToHost, ctx->stream));
+    if (W) ASB_HIP(ctx, hipMemcpyAsync(W, ctx->W, (size_t)ctx->K * ctx->Fp * d, hipMemcpyDeviceToHost, ctx->stream));
+    if (R) ASB_HIP(ctx, hipMemcpyAsync(R, ctx->R, (size_t)ctx->n_loc * 3 * ctx->Fp * d, hipMemcpyDeviceToHost, ctx->stream));
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (counts) { counts[0] = ctx->nblk; counts[1] = ctx->nblk_cap; }
+    return ASB_OK;
+}
+
+// the exchange record of asb_deflate_local_best(k) on the host (asb_deflate_xchg_len doubles)
+extern "C" int asb_test_local_best(asb_ctx* ctx, int64_t k, double* rec) {
+    if (!ctx || !ctx->R || !ctx->xrec || !rec) return ASB_ERR_ARG;
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    int rc = asb_deflate_local_best(ctx, k, nullptr);
+    if (rc) return rc;
+    ASB_HIP(ctx, hipMemcpyAsync(rec, ctx->xrec, (size_t)(2 + 3 * ctx->Fp) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ASB_OK;
+}
+
+// asb_deflate_pick(k) over n_rec exchange records given on the host
+extern "C" int asb_test_pick_records(asb_ctx* ctx, int64_t k, const double* recs, int64_t n_rec) {
+    if (!ctx || !ctx->R || !recs) return ASB_ERR_ARG;
+    if (n_rec < 1 || n_rec > 16) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_pick_records: %lld records", (long long)n_rec);
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    double* d = nullptr;
+    int rc = asb_test_stage(ctx, recs, (size_t)n_rec * (2 + 3 * ctx->Fp), 64, &d);
+    if (!rc) rc = asb_deflate_pick(ctx, k, d, n_rec);
+    return asb_test_finish(ctx, rc, nullptr, nullptr, 0, d, nullptr, nullptr);
 }

@@ -10,6 +10,7 @@
 #include "asb_common.h"
 
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 
 
@@ -498,22 +499,20 @@ static void launch_stream_te(asb_ctx* ctx, bool update, int grid, const StreamAr
                            a.s, a.ck, a.energy, a.pmax, a.pidx, a.psum, a.n, F2, a.panel);
 }
 
-template <int E2>
-static void launch_stream_e(asb_ctx* ctx, int T, bool update, int grid, const StreamArgs& a) {
-    switch (T) {
-        case 64: launch_stream_te<64, E2>(ctx, update, grid, a); break;
-        case 128: launch_stream_te<128, E2>(ctx, update, grid, a); break;
-        case 256: launch_stream_te<256, E2>(ctx, update, grid, a); break;
-        case 512: launch_stream_te<512, E2>(ctx, update, grid, a); break;
-        default: launch_stream_te<1024, E2>(ctx, update, grid, a); break;
-    }
-}
-
+// pick_cfg returns seven (T, E2) pairs: (64 .. 1024, 4), (1024, 8), (1024, 16) (tests/test_deflate_step_cpu.py holds it to that);
+// anything else is a bug of the caller and ends the process rather than run a kernel of the wrong width
 static inline void launch_stream(asb_ctx* ctx, const StreamCfg& c, bool update, int grid, const StreamArgs& a) {
-    switch (c.E2) {
-        case 4: launch_stream_e<4>(ctx, c.T, update, grid, a); break;
-        case 8: launch_stream_e<8>(ctx, c.T, update, grid, a); break;
-        default: launch_stream_e<16>(ctx, c.T, update, grid, a); break;
+    const int T = c.T, E2 = c.E2;
+    if (T == 64 && E2 == 4) launch_stream_te<64, 4>(ctx, update, grid, a);
+    else if (T == 128 && E2 == 4) launch_stream_te<128, 4>(ctx, update, grid, a);
+    else if (T == 256 && E2 == 4) launch_stream_te<256, 4>(ctx, update, grid, a);
+    else if (T == 512 && E2 == 4) launch_stream_te<512, 4>(ctx, update, grid, a);
+    else if (T == 1024 && E2 == 4) launch_stream_te<1024, 4>(ctx, update, grid, a);
+    else if (T == 1024 && E2 == 8) launch_stream_te<1024, 8>(ctx, update, grid, a);
+    else if (T == 1024 && E2 == 16) launch_stream_te<1024, 16>(ctx, update, grid, a);
+    else {
+        fprintf(stderr, "launch_stream: no k_stream<%d, %d> (pick_cfg returns seven pairs)\n", T, E2);
+        abort();
     }
 }
 

@@ -782,6 +782,50 @@ class HipEngine(object):
         self._ck(self.lib.asb_test_chol_tinv(self.h, ptr(G), G.shape[0], ptr(Tt)))
         return Tt
 
+    # the greedy step of the residual mode, one piece at a time (tests/test_gpu_deflate_step.py)
+    def test_eig3_dev(self, A6, fast, slack=8):
+        """(n, 4) rows (lambda, u) of eig3_top (fast=False) / eig3_top_fast (True) run on the device on A6 (n, 6); `slack` doubles
+        behind the result round-trip too and are asserted untouched."""
+        A6 = np.ascontiguousarray(A6, dtype=np.float64)
+        n = A6.shape[0]
+        out = np.full(4 * n + slack, -7.25)
+        self._ck(self.lib.asb_test_eig3_dev(self.h, int(bool(fast)), ptr(A6), n, ptr(out), out.size))
+        assert (out[4 * n:] == -7.25).all(), "asb_test_eig3_dev wrote behind its result"
+        return out[:4 * n].reshape(n, 4)
+
+    def test_deflate_step(self, k, w, wn2, s_loc=None):
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        assert w.shape == (self.F,)
+        if s_loc is not None:
+            s_loc = np.ascontiguousarray(s_loc, dtype=np.float64)
+            assert s_loc.shape == (self.n_loc,)
+        self._ck(self.lib.asb_test_deflate_step(self.h, int(k), ptr(w), float(wn2), ptr(s_loc)))
+
+    def test_deflate_state(self, want_R=False, want_W=False):
+        """dict: energy (n_loc), pmax / pidx / psum (nblk), nblk, nblk_cap, scal (K + 1, 4; column 2 holds index bits) and, on
+        request, W (K, Fp) and R (n_loc, 3, Fp) with their padding."""
+        cnt = np.zeros(2, dtype=np.int64)
+        self._ck(self.lib.asb_test_deflate_state(self.h, None, None, None, None, ptr(cnt), None, None, None))
+        nblk, cap = int(cnt[0]), int(cnt[1])
+        Fp = (self.F + 15) // 16 * 16
+        energy, scal = np.empty(self.n_loc), np.empty((self.K + 1, 4))
+        pmax, psum, pidx = np.empty(nblk), np.empty(nblk), np.empty(nblk, dtype=np.int64)
+        W = np.empty((self.K, Fp)) if want_W else None
+        R = np.empty((self.n_loc, 3, Fp)) if want_R else None
+        self._ck(self.lib.asb_test_deflate_state(self.h, ptr(energy), ptr(pmax), ptr(pidx), ptr(psum), None, ptr(scal), ptr(W),
+                                                 ptr(R)))
+        return dict(energy=energy, pmax=pmax, pidx=pidx, psum=psum, nblk=nblk, nblk_cap=cap, scal=scal, W=W, R=R)
+
+    def test_local_best(self, k):
+        rec = np.empty(self.xchg_len())
+        self._ck(self.lib.asb_test_local_best(self.h, int(k), ptr(rec)))
+        return rec
+
+    def test_pick_records(self, k, recs):
+        recs = np.ascontiguousarray(recs, dtype=np.float64)
+        assert recs.ndim == 2 and recs.shape[1] == self.xchg_len()
+        self._ck(self.lib.asb_test_pick_records(self.h, int(k), ptr(recs), recs.shape[0]))
+
     def snapshots_affine(self, inv_scale, add_mean, rowscale_loc=None):
         if rowscale_loc is not None:
             rowscale_loc = np.ascontiguousarray(rowscale_loc, dtype=np.float64)

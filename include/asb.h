@@ -623,6 +623,26 @@ int asb_test_l2w_probe(asb_ctx* ctx, int nct, int mode, int reps, double* ms_out
 /* The 3x3 symmetric eigen-solver used by asb_deflate_pick, run on the HOST (unit test
  * without a GPU).  a6 = (a00,a01,a02,a11,a12,a22); out4 = (lambda_max, u0, u1, u2). */
 void asb_test_eig3(const double* a6, double* out4);
+/* test hooks of the greedy step (csrc/asb_kernels.h; tests/test_deflate_step_cpu.py, tests/test_gpu_deflate_step.py).
+ * asb_test_eig3_fast: as asb_test_eig3 for the root-and-cross-product solver of the panel kernel and the sketch replay (host).
+ * asb_test_pick_cfg: the stream configuration of a padded row length Fp on the host: out5 = (ok, T, E2, block, vpb).
+ * asb_test_eig3_dev: either solver (fast = 0 / 1) on the device, one thread per matrix: a6 (n x 6) -> out4 (n x 4); all of out4
+ * (out_len >= 4 n doubles) round-trips, so a write behind the result shows.
+ * asb_test_deflate_step: residual mode; installs w (F doubles, the row's padding zeroed) and |w|^2 = wn2 as component k and runs
+ * asb_deflate_apply(k, s) on them.
+ * asb_test_deflate_state: what the context holds, every pointer optional: energy (n_loc), the partial records of the last streaming
+ * pass pmax / pidx / psum (counts[0] of them; room for counts[1] = the grid cap), scal ((K + 1) x 4: sigma, |w|^2, index bits, local
+ * |R|^2), W (K x Fp) and R (3 n_loc x Fp) with their padding.
+ * asb_test_local_best: asb_deflate_local_best(k) into the context's record, copied to rec (asb_deflate_xchg_len doubles).
+ * asb_test_pick_records: asb_deflate_pick(k) over n_rec (<= 16) records given on the host. */
+void asb_test_eig3_fast(const double* a6, double* out4);
+void asb_test_pick_cfg(int64_t Fp, int* out5);
+int asb_test_eig3_dev(asb_ctx* ctx, int fast, const double* a6, int64_t n, double* out4, int64_t out_len);
+int asb_test_deflate_step(asb_ctx* ctx, int64_t k, const double* w, double wn2, const double* s);
+int asb_test_deflate_state(asb_ctx* ctx, double* energy, double* pmax, int64_t* pidx, double* psum, int64_t* counts, double* scal,
+                           double* W, double* R);
+int asb_test_local_best(asb_ctx* ctx, int64_t k, double* rec);
+int asb_test_pick_records(asb_ctx* ctx, int64_t k, const double* recs, int64_t n_rec);
 /* tests: the sketch replay on host arrays -- cols (r x 3 n: column i, entry 3 v + d, the coefficient of vertex v's row d on the
  * unit direction i divided by sqrt(wn2[i])), wn2 (r), exact energies E (n) -> scores (n; max over the steps of energy / winner's
  * energy), the replay's winners pred (steps; -1 behind its end), *status = 1 (0: the exchange timed out, scores = energies) */
