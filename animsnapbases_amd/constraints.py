@@ -12,7 +12,7 @@ The F x F symmetric eigen-problem, the K x K Cholesky factors and the small SVD 
 step run on the device too (csrc/asb_eig.hip, csrc/asb_smalldense.hip).  Host work: DEIM's k x k
 interpolation solves (an O(k^2) bordered-inverse update whose residual is checked every step;
 ``numpy.linalg.lstsq``, the routine the reference calls at constraintsComponents.py:829, is
-the fallback); LAPACK ``eigh`` on the Gram matrix only with ``ASB_POD_EIG=host``.
+the fallback); LAPACK ``eigh`` on the Gram matrix only with the attribute ``pod_eig = "host"``.
 
 The other basis types and interpolations of the reference (``pod`` per-(p,d) slices, ``pca_blocks``,
 ``pca_blocks_with_St``, geometric / block DEIM) run on the device too, on one rank or several; ``pod`` on
@@ -713,9 +713,8 @@ class constraintsComponents:  # Components == bases
         eng, comm = ns._engine, ns._comm
         F = ns.frs
         K = min(int(self.param.deim_desired_num_components), F)
-        on_dev = os.environ.get("ASB_POD_EIG", getattr(self, "pod_eig", "device")) == "device"
-        levels_ok = hasattr(eng, "pod_deflate_begin") and not (F & 1) and not any((3 * n) & 1 for _, n in ns._shards) \
-            and os.environ.get("ASB_POD_LEVELS", "1") != "0"
+        on_dev = getattr(self, "pod_eig", "device") == "device"
+        levels_ok = hasattr(eng, "pod_deflate_begin") and not (F & 1) and not any((3 * n) & 1 for _, n in ns._shards)
         S_kept = []                     # singular values of the vectors kept by finished levels
         remaining, level = K, 0
         self.pod_power_steps = 0
@@ -787,7 +786,7 @@ class constraintsComponents:  # Components == bases
             if n_bad:
                 print("[asb] POD: %d of %d inverse iterations missed the growth criterion" % (n_bad, Kv))
             dev_vectors, V = True, None
-        else:       # ASB_POD_EIG=host (explicit) or F < 3: LAPACK on the F x F Gram matrix
+        else:       # pod_eig = "host" (explicit) or F < 3: LAPACK on the F x F Gram matrix
             G = Gbuf.cpu().numpy().reshape(F, F) if Gbuf is not None else eng.pod_gram()
             G = 0.5 * (G + G.T)
             lam, V = np.linalg.eigh(G)                       # ascending

@@ -4,6 +4,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <map>
 #include <string>
 #include <utility>
@@ -133,7 +134,6 @@ struct asb_ctx {
     // super-panels (asb_project.hip): how the next asb_panel_run behaves / what it did
     int run_writeback = 0, run_theta_band = 0, run_coop_used = 0;
     int spec_panels = 1;              // ASB_SPEC_PANELS=0 -> provable steps only
-    int gather_cpt = 2;               // ASB_GATHER_CPT=1 -> one candidate per block in k_gather<256,4>
     int run_spec_max = 0;             // unproven steps the next asb_panel_run may take (0 outside asb_project_run)
     int spec_budget = 16;             // adapted to how many unproven steps survived in the last panels
     long long run_proven = 0;         // provable head of the last asb_panel_run
@@ -141,15 +141,7 @@ struct asb_ctx {
     unsigned char* host_pin = nullptr;      // pinned (coherent, device-mapped) host memory for the small read-backs
     unsigned char* host_pin_dev = nullptr;  // its device address: tiny kernels publish state there, the host polls (asb_pin_alloc)
     unsigned long long pin_seq = 0;         // sequence number of the last publication
-    int host_poll = 1;                      // ASB_HOST_POLL=0: read-backs by copy + stream synchronisation
     long long n_spec_steps = 0, n_spec_kept = 0;      // statistics (asb_deflate_stats)
-    int super_panels = 0;             // ASB_SUPER_PANELS=1
-    long long band_target = 12288, band_cap = 16384;
-    long long* band_idx = nullptr;
-    long long *btmp = nullptr, *bcnt = nullptr;
-    double *band_E = nullptr, *bpmax = nullptr, *bpsum = nullptr;
-    long long* bpidx = nullptr;
-    PanelState* bstate = nullptr;
     double *Wt3 = nullptr, *wn2t3 = nullptr, *Wq3 = nullptr, *gram3 = nullptr;
     int64_t forced_row = -1;      // asb_deflate_force_next: global row the next pick must take
     double* bam_val = nullptr;    // asb_deflate_block_argmax partials
@@ -184,8 +176,6 @@ struct asb_ctx {
     double* ypart = nullptr;     // partial 16x16 tiles between sweeps of k_project_lds
     unsigned int* tile_counter = nullptr;
     double* Wq = nullptr;        // (Fp/16, 4, 16, 4) panel in MFMA lane order (k_project_l2)
-    int l2_variant = 4;          // ASB_L2_VARIANT: 4 = k_project_l2s<4,2,2,1> (two waves per 64-row tile); 0..2 = k_project_l2 (one wave per tile: 32 rows x 4 chunks, 48 x 2, 64 x 2); 5 = four waves per tile
-    int project_kernel = 3;      // 1: k_project_mfma (Wt in registers), 2: k_project_lds (Wt in LDS), 3: k_project_l2 (Wt from L2)
     long long* ctmp = nullptr;   // compaction scratch
     long long* ccnt = nullptr;
     int* hist = nullptr;
@@ -195,13 +185,10 @@ struct asb_ctx {
     double* e_class = nullptr;             // energies at the start of a double panel: who was a candidate (both tiles' checks)
     double* e_tmp = nullptr;               // energies as if a tile stood in full (k_correct_rows<true> -> k_apply_tmp)
     double* wide_out = nullptr;            // asb_project_columns_wide: where the multi-tile pass writes (default: comps)
-    double* e_tmp4 = nullptr;              // k_check_tiles: tentative energies per tile (4 x n_loc)
+    double* e_tmp4 = nullptr;              // k_check_tiles_w: tentative energies per tile (4 x n_loc)
     double* chk_rec = nullptr;             // its per-tile block records: pmax | psum | colpart (4 x nblk_cap x (1 + 1 + 16))
     long long* chk_idx = nullptr;
     long long* tile_res = nullptr;         // per tile: columns kept (-1: not reached); [ASB_MAX_SUB]: the chain flag
-    int spec_w_rank = 24;                  // ASB_SPEC_W_RANK: blocks ranked below it publish their w ahead of the exchange (0: none)
-    int spec_pass = 1;                     // ASB_SPEC_PASS=0: the read's pass is enqueued only once the host knows the sub-panels' counts
-    int coop_launch = 0;                   // ASB_COOP_LAUNCH=1: hipLaunchCooperativeKernel for the panel kernel (-1: tried, refused)
     int sub_chain = 1;                     // the sub-panels of a read enqueued without host reads in between (ASB_SUB_CHAIN=0: one by one)
     int tile_chain = 1;                    // tiles of a read finished without host reads in between (ASB_TILE_CHAIN=0: one read per tile)
     int pre_orth = 1;                      // multi-sub-panel reads project on pre-orthogonalised weights (ASB_PRE_ORTH=0: correct after)
@@ -380,6 +367,12 @@ int asb_test_stage(asb_ctx* ctx, const double* h, size_t n, size_t slack, double
 int asb_test_finish(asb_ctx* ctx, int rc, double* out_dev, double* out_host, size_t out_len, double* f0, double* f1, double* f2);
 
 #define ASB_CHECK_LAUNCH(ctx) ASB_HIP(ctx, hipGetLastError())
+
+// ASB_DEBUG_PANELS: the panel loop's trace on stderr (changes no result); read once per process
+static inline bool asb_debug_panels() {
+    static const bool on = getenv("ASB_DEBUG_PANELS") != nullptr;
+    return on;
+}
 
 // 1 KiB of pinned host memory shared by the small per-panel / per-sweep read-backs:
 //   [0, 256) PanelState, [256, 272) panel-kernel flags, [384, 392) counters, [448, 456) publication sequence number

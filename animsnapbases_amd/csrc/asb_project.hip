@@ -69,10 +69,9 @@ __device__ __forceinline__ bool in_guess(double e, double ev, const double* __re
 // one or two of them -- and costs a read or two where it is not (global modes: rank 50 + noise 13.1 -> 14.9 ms, a slowly decaying
 // spectrum 17.8 -> 21.0 ms with it, 50 bumps 34.2 -> 16.9 ms).  The squared coefficient of variation of the per-vertex energies
 // outside the constant direction, a by-product of the standardisation sweep, separates the two by orders of magnitude (0.02 - 0.07
-// for global modes, 0 for noise, 3.6 for the bumps): the family is on above ASB_DIVERSE_CV2 (0.5).
+// for global modes, 0 for noise, 3.6 for the bumps): the family is on above 0.5.
 static inline bool diverse_on(const asb_ctx* ctx) {
-    static const double thr = getenv("ASB_DIVERSE_CV2") ? atof(getenv("ASB_DIVERSE_CV2")) : 0.5;
-    return ctx->diverse && (!ctx->ev_valid || ctx->ev_cv2 > thr);
+    return ctx->diverse && (!ctx->ev_valid || ctx->ev_cv2 > 0.5);
 }
 #define ASB_DIV_Q (ASB_NG + 1)              // its slot among the thresholds of a multi-score selection
 #define ASB_NQ (ASB_NG + 2)
@@ -954,8 +953,8 @@ __global__ __launch_bounds__(256) void k_build_wq(const double* __restrict__ Wt,
 // drains for that long at the end of every launch with fewer and fewer loads in flight; S waves per tile cut that tail
 // S times while the bytes in flight per CU stay the same.  The quad also reads S * G * 128 B contiguous bytes of a row at
 // a time instead of G * 128.
-template <int NT, int G, int S, int NQ, int OCC = 1>
-__global__ __launch_bounds__(64 * S * NQ, OCC) void k_project_l2s(
+template <int NT, int G, int S, int NQ>
+__global__ __launch_bounds__(64 * S * NQ, 1) void k_project_l2s(
     const double* __restrict__ X, long long rows, int Fp, const double* __restrict__ Wq, const double* __restrict__ wn2,
     int ncols, double* __restrict__ comps, long long comp_stride, unsigned int* __restrict__ counter) {
     // NQ tiles in flight per block (NQ * S waves): NQ = 1 keeps the barriers inside the group of waves that shares a tile
@@ -1067,7 +1066,7 @@ struct WideArgs { long long kb[ASB_MAX_SUB]; int nc[ASB_MAX_SUB]; };
 // while the current group's 4 * NT * NCT * G MFMAs issue.  k_project_wide gives a whole 64-row tile to one wave -- 125 chunks
 // x 32 MFMAs x 64 cycles with two waves per SIMD = 210 us per tile, 2.3 tiles per wave on config 4: a third of the launch
 // is the queue draining -- and fetches its L2 operand right in front of the MFMAs that need it.
-template <int NT, int G, int S, int NCT, int OCC = 1, int PD = 1, int MODE = 0>      // MODE != 0: timing probes (asb_test_l2w_probe)
+template <int NT, int G, int S, int NCT, int OCC = 1>
 __global__ __launch_bounds__(64 * S, OCC) void k_project_l2w(
     const double* __restrict__ X, long long rows, int Fp, const double* __restrict__ Wq, const double* __restrict__ wn2,
     WideArgs wa, double* __restrict__ comps, long long comp_stride, unsigned int* __restrict__ counter) {
@@ -1095,7 +1094,7 @@ __global__ __launch_bounds__(64 * S, OCC) void k_project_l2w(
         const double4* xp[NT];                                  // chunk c: xp[m][4 * c]
 #pragma unroll
         for (int m = 0; m < NT; ++m) {
-            long long r = (long long)(MODE == 1 ? t % 4 : t) * TR + 16 * m + i;      // probe 1: four cache-resident tiles
+            long long r = (long long)t * TR + 16 * m + i;
             if (r >= rows) r = rows - 1;
             xp[m] = reinterpret_cast<const double4*>(X + r * Fp + 4 * g);
         }
@@ -1113,11 +1112,7 @@ __global__ __launch_bounds__(64 * S, OCC) void k_project_l2w(
     }
 #define ASB_L2W_MFMA(GRP)                                                                              \
     _Pragma("unroll") for (int q = 0; q < G; ++q)                                                     \
-        if (MODE == 2) {          /* probe 2: the loads alone */                                       \
-            _Pragma("unroll") for (int ct = 0; ct < NCT; ++ct)                                        \
-                _Pragma("unroll") for (int m = 0; m < NT; ++m)                                        \
-                    acc[m][ct][0] += (a[m][q].x + a[m][q].y) * b[ct][q].x + (a[m][q].z + a[m][q].w) * b[ct][q].w; \
-        } else if ((GRP) * G + q < nchunk) {                                                           \
+        if ((GRP) * G + q < nchunk) {                                                                  \
             _Pragma("unroll") for (int ct = 0; ct < NCT; ++ct) {                                      \
                 _Pragma("unroll") for (int m = 0; m < NT; ++m)                                        \
                     acc[m][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[m][q].x, b[ct][q].x, acc[m][ct], 0, 0, 0); \
@@ -1129,50 +1124,25 @@ __global__ __launch_bounds__(64 * S, OCC) void k_project_l2w(
                     acc[m][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[m][q].w, b[ct][q].w, acc[m][ct], 0, 0, 0); \
             }                                                                                          \
         }
-        if (PD == 2) {
-            // the HBM operand two groups ahead, the L2 operand one: 2 * NT * G * 2 KB in flight per wave
-            double4 a2[NT][G];
-            if (gi * G < nchunk) {
-                ASB_L2W_LOAD_B(b, gi)
-                ASB_L2W_LOAD_A(a, gi)
-                if ((gi + S) * G < nchunk) { ASB_L2W_LOAD_A(an, gi + S) }
+        if (gi * G < nchunk) {
+            ASB_L2W_LOAD_B(b, gi)
+            ASB_L2W_LOAD_A(a, gi)
+        }
+        while (gi * G < nchunk) {
+            const int gn = gi + S;
+            if (gn * G < nchunk) {
+                ASB_L2W_LOAD_B(bn, gn)
+                ASB_L2W_LOAD_A(an, gn)
             }
-            while (gi * G < nchunk) {
-                // B first: loads retire in order, and this group's MFMAs wait for the B issued one iteration ago -- anything
-                // issued in front of it (an A two groups ahead) would have to have landed as well
-                if ((gi + S) * G < nchunk) { ASB_L2W_LOAD_B(bn, gi + S) }
-                if ((gi + 2 * S) * G < nchunk) { ASB_L2W_LOAD_A(a2, gi + 2 * S) }
-                ASB_L2W_MFMA(gi)
+            ASB_L2W_MFMA(gi)
 #pragma unroll
-                for (int q = 0; q < G; ++q) {
+            for (int q = 0; q < G; ++q) {
 #pragma unroll
-                    for (int ct = 0; ct < NCT; ++ct) b[ct][q] = bn[ct][q];
+                for (int ct = 0; ct < NCT; ++ct) b[ct][q] = bn[ct][q];
 #pragma unroll
-                    for (int m = 0; m < NT; ++m) { a[m][q] = an[m][q]; an[m][q] = a2[m][q]; }
-                }
-                gi += S;
+                for (int m = 0; m < NT; ++m) a[m][q] = an[m][q];
             }
-        } else {
-            if (gi * G < nchunk) {
-                ASB_L2W_LOAD_B(b, gi)
-                ASB_L2W_LOAD_A(a, gi)
-            }
-            while (gi * G < nchunk) {
-                const int gn = gi + S;
-                if (gn * G < nchunk) {
-                    ASB_L2W_LOAD_B(bn, gn)
-                    ASB_L2W_LOAD_A(an, gn)
-                }
-                ASB_L2W_MFMA(gi)
-#pragma unroll
-                for (int q = 0; q < G; ++q) {
-#pragma unroll
-                    for (int ct = 0; ct < NCT; ++ct) b[ct][q] = bn[ct][q];
-#pragma unroll
-                    for (int m = 0; m < NT; ++m) a[m][q] = an[m][q];
-                }
-                gi = gn;
-            }
+            gi = gn;
         }
 #undef ASB_L2W_LOAD_A
 #undef ASB_L2W_LOAD_B
@@ -1229,19 +1199,17 @@ __global__ __launch_bounds__(64 * S, OCC) void k_project_l2w(
 // Everything else as in k_project_l2c: 8 waves = (row tile rt) x (frame half sub), X chunks in two register sets used
 // alternately, direct loads / LDS reads by hand so that the compiler counts one kind of pending load.
 // --------------------------------------------------------------------------------------
-template <int NCT, int P, int NTV, int SYNC, int NSB, int MODE, int XDP>
+template <int NCT, int P, int NTV, int SYNC, int NSB, bool BPF>
 __device__ __forceinline__ void l2d_tile(const double* __restrict__ X, long long rows, int Fp, const double* __restrict__ Wq,
                                          const double* __restrict__ wn2, const WideArgs& wa, double* __restrict__ comps,
                                          long long comp_stride, long long group0, double* lds, unsigned cnt_byte) {
     constexpr int RT = 4, NTM = 4, NI = 4 * P * NCT, PER = NI / (2 * RT), NS = NSB;
-    // XDP = XD + 10 BPF.  BPF (round 4): the weights of column tile ct + 1 are read from LDS while tile ct's 16 MFMAs issue (a second
-    // pair of operand registers), instead of read-and-wait in front of every tile: one exposed LDS latency per chunk instead of NCT
-    constexpr int XD = XDP % 10;
-    constexpr bool BPF = XDP >= 10;
+    // BPF (round 4): the weights of column tile ct + 1 are read from LDS while tile ct's 16 MFMAs issue (a second pair of
+    // operand registers), instead of read-and-wait in front of every tile: one exposed LDS latency per chunk instead of NCT
     // SYNC: 0 = block barrier per stage (two buffers); 1 = arrival counters over all 8 waves; 5 = arrival counters PER FRAME-HALF
-    // GROUP of four waves (each group stages the chunks only it reads: a slow wave holds up three others, not seven);
-    // 2 / 3 = debugging forms (barrier with three buffers / counters and barrier)
-    constexpr bool CNT = (SYNC & 1) != 0, BAR = SYNC == 0 || SYNC == 2 || SYNC == 3, GRP = SYNC == 5;
+    // GROUP of four waves (each group stages the chunks only it reads: a slow wave holds up three others, not seven)
+    static_assert(SYNC == 0 || SYNC == 1 || SYNC == 5, "stage synchronisation");
+    constexpr bool CNT = SYNC != 0, BAR = SYNC == 0, GRP = SYNC == 5;
     constexpr int DIST = CNT ? (NS - 1) / 2 : 1;                // the direct loads run DIST stages ahead of the MFMAs
     // a wave inside stage s knows only that every wave has ARRIVED for s, which a wave does while it computes stage s - DIST: the
     // buffer the loads of stage s + DIST overwrite must belong to stage s - DIST - 1 or older (round 3 measured "four buffers,
@@ -1297,11 +1265,7 @@ __device__ __forceinline__ void l2d_tile(const double* __restrict__ X, long long
     for (int m = 0; m < NTA; ++m)
 #pragma unroll
         for (int ct = 0; ct < NCT; ++ct) acc[m][ct] = (d4){0.0, 0.0, 0.0, 0.0};
-    // XD = 2: a THIRD register set, the X chunk of pair j + 2 is requested while pair j computes (twice the tolerance for
-    // a slow HBM access; 32 more registers)
-    static_assert(XD == 1 || XD == 2, "prefetch distance");
-    static_assert(!CNT || XD < P, "the arrival for the next stage must fall inside the stage");
-    double4 a0[NTA], a1[NTA], a2[XD == 2 ? NTA : 1];
+    double4 a0[NTA], a1[NTA];
 #pragma unroll
     for (int d = 0; d < DIST; ++d)
         if (d < nstage) issue_stage(d);
@@ -1309,11 +1273,6 @@ __device__ __forceinline__ void l2d_tile(const double* __restrict__ X, long long
         const int c = sub < nchunk ? sub : nchunk - 1;
 #pragma unroll
         for (int m = 0; m < NTA; ++m) a0[m] = xp[m][4 * c];
-        if (XD == 2) {
-            const int c1 = 2 + sub < nchunk ? 2 + sub : nchunk - 1;
-#pragma unroll
-            for (int m = 0; m < NTA; ++m) a1[m] = xp[m][4 * c1];
-        }
     }
     __builtin_amdgcn_s_waitcnt(0);                              // first stage(s) and first X chunk of the tile: one exposed latency
     if (CNT) {
@@ -1324,30 +1283,25 @@ __device__ __forceinline__ void l2d_tile(const double* __restrict__ X, long long
     auto pair_step = [&](int j, double4 (&cur)[NTA], double4 (&nxt)[NTA]) {
         const int s = j / P;
         if (j == s * P) {
-            if (CNT && MODE != 5) enter(s);
-            if (BAR && MODE != 5) __syncthreads();
+            if (CNT) enter(s);
+            if (BAR) __syncthreads();
         }
-        if (NTV > 0 && (MODE == 3 || MODE == 4)) {                    // probes: no X traffic inside the loop
-#pragma unroll
-            for (int m = 0; m < NTA; ++m) nxt[m] = cur[m];
-        } else if (NTV > 0) {
+        if (NTV > 0) {
             // the next pair's X chunk flies while this pair's MFMAs issue -- unconditionally (behind the last pair: the last
             // chunk once more): the same number of loads on every path keeps the compiler's waits counted ones
-            const int cn = 2 * (j + XD) + sub < nchunk ? 2 * (j + XD) + sub : nchunk - 1;
+            const int cn = 2 * (j + 1) + sub < nchunk ? 2 * (j + 1) + sub : nchunk - 1;
 #pragma unroll
             for (int m = 0; m < NTA; ++m) nxt[m] = xp[m][4 * cn];
         }
-        // pair XD of a stage: the loads of stage s + DIST (issued in the first pair, older than the XD chunks requested since)
-        // have landed once everything but the newest XD * 2 NTV loads is back -- the chunk this pair computes from among them
-        if (CNT && j == s * P + XD && s + DIST < nstage) {
-            if (MODE == 3 || MODE == 4) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else if (XD * NTV == 8) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-            else if (XD * NTV == 6) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-            else if (XD * NTV == 4) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else if (XD * NTV == 3) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-            else if (XD * NTV == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            else if (XD * NTV == 1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // second pair of a stage: the loads of stage s + DIST (issued in the first pair, older than the chunk requested since)
+        // have landed once everything but the newest 2 NTV loads is back -- the chunk this pair computes from among them
+        if (CNT && j == s * P + 1 && s + DIST < nstage) {
+            static_assert(NTV >= 0 && NTV <= 4, "the counted wait is written out for up to four row groups per wave");
+            if (NTV == 4) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+            else if (NTV == 3) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+            else if (NTV == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+            else if (NTV == 1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // NTV = 0: a wave without rows requests no X
             arrive(s + DIST);
         }
         bool issued = false;
@@ -1369,7 +1323,7 @@ __device__ __forceinline__ void l2d_tile(const double* __restrict__ X, long long
                 // the next stage's direct loads go out BEHIND the wait for the current X chunk (the first MFMAs above)
                 if (ct == 0 && j == s * P && s + DIST < nstage) { issue_stage(s + DIST); issued = true; }
             };
-            if (BPF && MODE != 4) {
+            if (BPF) {
                 // tile ct's operands are requested one tile earlier: request ct + 1's, then wait for everything but those (LDS
                 // reads return in order; the in/out operands keep the tile's MFMAs behind the wait) -- two operand pairs, A and B
                 typedef double d2v __attribute__((ext_vector_type(2)));      // (a native vector: in/out asm operands of a struct type are not supported)
@@ -1392,32 +1346,18 @@ __device__ __forceinline__ void l2d_tile(const double* __restrict__ X, long long
 #pragma unroll
                 for (int ct = 0; ct < NCT; ++ct) {
                     double2 b0, b1;
-                    if (MODE == 4) {                            // probe: no LDS reads either
-                        b0 = make_double2(cur[0].x, cur[0].y);
-                        b1 = make_double2(cur[0].z, cur[0].w);
-                    } else {
-                        const unsigned lds_addr = b_addr(ct);
-                        asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:1024\n\ts_waitcnt lgkmcnt(0)"
-                                     : "=&v"(b0), "=&v"(b1) : "v"(lds_addr));
-                    }
+                    const unsigned lds_addr = b_addr(ct);
+                    asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:1024\n\ts_waitcnt lgkmcnt(0)"
+                                 : "=&v"(b0), "=&v"(b1) : "v"(lds_addr));
                     mfma16(ct, b0, b1);
                 }
             }
         }
         if (!issued && j == s * P && s + DIST < nstage) issue_stage(s + DIST);
     };
-    if (XD == 1) {
-        for (int j = 0; j < npair; j += 2) {
-            pair_step(j, a0, a1);
-            if (j + 1 < npair) pair_step(j + 1, a1, a0);
-        }
-    } else {
-        auto& b2 = reinterpret_cast<double4 (&)[NTA]>(a2);
-        for (int j = 0; j < npair; j += 3) {
-            pair_step(j, a0, b2);
-            if (j + 1 < npair) pair_step(j + 1, a1, a0);
-            if (j + 2 < npair) pair_step(j + 2, b2, a1);
-        }
+    for (int j = 0; j < npair; j += 2) {
+        pair_step(j, a0, a1);
+        if (j + 1 < npair) pair_step(j + 1, a1, a0);
     }
     // the two frame halves of a row tile meet through LDS, one column tile at a time (fixed order: half 0 + half 1)
 #pragma unroll
@@ -1442,7 +1382,7 @@ __device__ __forceinline__ void l2d_tile(const double* __restrict__ X, long long
     }
 }
 
-template <int NCT, int P, int SYNC = 1, int NSB = (SYNC ? 3 : 2), int MODE = 0, int XD = 1>      // MODE: timing probes (asb_test_l2w_probe)
+template <int NCT, int P, int SYNC = 1, int NSB = (SYNC ? 3 : 2), bool BPF = false>
 __global__ __launch_bounds__(512, 2) void k_project_l2d(
     const double* __restrict__ X, long long rows, int Fp, const double* __restrict__ Wq, const double* __restrict__ wn2,
     WideArgs wa, double* __restrict__ comps, long long comp_stride) {
@@ -1466,11 +1406,11 @@ __global__ __launch_bounds__(512, 2) void k_project_l2d(
         if (tid < 2 * NS) cnt[tid] = 0u;
         __syncthreads();
         switch (ntv) {
-            case 4: l2d_tile<NCT, P, 4, SYNC, NSB, MODE, XD>(X, rows, Fp, Wq, wn2, wa, comps, comp_stride, start, l2d_lds, CNT_BYTE); break;
-            case 3: l2d_tile<NCT, P, 3, SYNC, NSB, MODE, XD>(X, rows, Fp, Wq, wn2, wa, comps, comp_stride, start, l2d_lds, CNT_BYTE); break;
-            case 2: l2d_tile<NCT, P, 2, SYNC, NSB, MODE, XD>(X, rows, Fp, Wq, wn2, wa, comps, comp_stride, start, l2d_lds, CNT_BYTE); break;
-            case 1: l2d_tile<NCT, P, 1, SYNC, NSB, MODE, XD>(X, rows, Fp, Wq, wn2, wa, comps, comp_stride, start, l2d_lds, CNT_BYTE); break;
-            default: l2d_tile<NCT, P, 0, SYNC, NSB, MODE, XD>(X, rows, Fp, Wq, wn2, wa, comps, comp_stride, start, l2d_lds, CNT_BYTE); break;
+            case 4: l2d_tile<NCT, P, 4, SYNC, NSB, BPF>(X, rows, Fp, Wq, wn2, wa, comps, comp_stride, start, l2d_lds, CNT_BYTE); break;
+            case 3: l2d_tile<NCT, P, 3, SYNC, NSB, BPF>(X, rows, Fp, Wq, wn2, wa, comps, comp_stride, start, l2d_lds, CNT_BYTE); break;
+            case 2: l2d_tile<NCT, P, 2, SYNC, NSB, BPF>(X, rows, Fp, Wq, wn2, wa, comps, comp_stride, start, l2d_lds, CNT_BYTE); break;
+            case 1: l2d_tile<NCT, P, 1, SYNC, NSB, BPF>(X, rows, Fp, Wq, wn2, wa, comps, comp_stride, start, l2d_lds, CNT_BYTE); break;
+            default: l2d_tile<NCT, P, 0, SYNC, NSB, BPF>(X, rows, Fp, Wq, wn2, wa, comps, comp_stride, start, l2d_lds, CNT_BYTE); break;
         }
     }
 }
@@ -1500,7 +1440,7 @@ static void launch_gather_te(asb_ctx* ctx, int grid, const long long* idx_map, l
                              int k0, double* dst, double* e_out, double* pm, long long* pi, double* ps) {
     constexpr int BLOCK = (T >= 256 ? T : 256);
     if constexpr (T == 256 && E2 == 4) {
-        if (dst != nullptr && k0 >= 8 && ctx->gather_cpt == 2) {      // candidate rows late in a run: the L2 reads of W dominate
+        if (dst != nullptr && k0 >= 8) {      // candidate rows late in a run: the L2 reads of W dominate
             // (same grid: the blocks without items still write their neutral partial records, which the caller counts)
             hipLaunchKernelGGL((k_gather<T, E2, 2>), dim3(grid), dim3(BLOCK), 0, ctx->stream, ctx->X, idx_map,
                                (long long)ctx->v0, n_items, panel, ctx->comps, (long long)(3 * ctx->n_loc), ctx->W, k0,
@@ -1541,7 +1481,20 @@ static void launch_project(asb_ctx* ctx, int ncols, double* out);
 // Round 2: instead of copy + hipStreamSynchronize (an interrupt-driven wait of 15-25 us, twice per panel), a one-wave kernel
 // writes the state straight into coherent pinned host memory, its sequence number last (system-scope fence in between), and
 // the host polls that word: the wait ends a microsecond or two after the producing kernels do.  Falls back to the
-// synchronising copy if the word does not arrive (or with ASB_HOST_POLL=0).
+// synchronising copy if the word does not arrive, or where the pinned slot could not be mapped (host_pin_dev == nullptr).
+// pin_wait: the host's side -- spins until the sequence word holds `seq` (acquire); false after `limit_s` seconds (a kernel
+// fault: the caller's stream synchronisation reports it)
+static bool pin_wait(const volatile void* seq_word, unsigned long long seq, double limit_s) {
+    const volatile unsigned long long* word = static_cast<const volatile unsigned long long*>(seq_word);
+    const auto t0 = std::chrono::steady_clock::now();
+    bool arrived = false;
+    for (unsigned spins = 0;; ++spins) {
+        if (*word == seq) { arrived = true; break; }
+        if ((spins & 1023) == 1023 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > limit_s) break;
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return arrived;
+}
 __global__ __launch_bounds__(64) void k_publish_state(const PanelState* __restrict__ st, const unsigned* __restrict__ flags,
                                                       unsigned char* __restrict__ pin, unsigned long long seq) {
     const int l = threadIdx.x;
@@ -1560,26 +1513,12 @@ static int read_panel_state_from(asb_ctx* ctx, const PanelState* st, PanelState*
     int rc = asb_pin_alloc(ctx);
     if (rc) return rc;
     static_assert(sizeof(PanelState) % 8 == 0 && sizeof(PanelState) <= 256, "PanelState must fit its pinned slot");
-    if (ctx->host_poll && ctx->host_pin_dev) {
+    if (ctx->host_pin_dev) {
         const unsigned long long seq = ++ctx->pin_seq;
         hipLaunchKernelGGL(k_publish_state, dim3(1), dim3(64), 0, ctx->stream, st, flags ? ctx->coop_bar : (const unsigned*)nullptr,
                            ctx->host_pin_dev, seq);
         ASB_CHECK_LAUNCH(ctx);
-        volatile unsigned long long* word = reinterpret_cast<volatile unsigned long long*>(ctx->host_pin + 448);
-        const auto t0 = std::chrono::steady_clock::now();
-        bool arrived = false;
-        for (unsigned spins = 0;; ++spins) {
-            if (*word == seq) { arrived = true; break; }
-            if ((spins & 1023) == 1023 &&
-                std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 2.0) break;      // (a kernel fault: the sync below reports it)
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        if (arrived) {
-            memcpy(h, ctx->host_pin, sizeof(PanelState));
-            if (flags) memcpy(flags, ctx->host_pin + 256, 4 * sizeof(unsigned));
-            return ASB_OK;
-        }
-        ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (!pin_wait(ctx->host_pin + 448, seq, 2.0)) ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
         memcpy(h, ctx->host_pin, sizeof(PanelState));
         if (flags) memcpy(flags, ctx->host_pin + 256, 4 * sizeof(unsigned));
         return ASB_OK;
@@ -1606,19 +1545,11 @@ static int fetch_words(asb_ctx* ctx, const void* dev, int n, void* host) {
     int rc = asb_pin_alloc(ctx);
     if (rc) return rc;
     if (n < 1 || n > 16) ASB_FAIL(ctx, ASB_ERR_ARG, "fetch_words: %d words", n);
-    if (ctx->host_poll && ctx->host_pin_dev) {
+    if (ctx->host_pin_dev) {
         const unsigned long long seq = ++ctx->pin_seq;
         hipLaunchKernelGGL(k_publish_words, dim3(1), dim3(64), 0, ctx->stream, (const unsigned long long*)dev, n, ctx->host_pin_dev, seq);
         ASB_CHECK_LAUNCH(ctx);
-        volatile unsigned long long* word = reinterpret_cast<volatile unsigned long long*>(ctx->host_pin + 648);
-        const auto t0 = std::chrono::steady_clock::now();
-        bool arrived = false;
-        for (unsigned spins = 0;; ++spins) {
-            if (*word == seq) { arrived = true; break; }
-            if ((spins & 1023) == 1023 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 2.0) break;
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        if (!arrived) ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (!pin_wait(ctx->host_pin + 648, seq, 2.0)) ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
         memcpy(host, ctx->host_pin + 512, (size_t)n * 8);
         return ASB_OK;
     }
@@ -1647,7 +1578,7 @@ static int fetch_multi_begin(asb_ctx* ctx, unsigned long long* seq) {
     int rc = asb_pin_alloc(ctx);
     if (rc) return rc;
     *seq = 0;
-    if (ctx->host_poll && ctx->host_pin_dev) {
+    if (ctx->host_pin_dev) {
         *seq = ++ctx->pin_seq;
         hipLaunchKernelGGL(k_publish_multi, dim3(1), dim3(64), 0, ctx->stream, ctx->pstate2, ctx->coop_bar, ctx->host_pin_dev, *seq);
         ASB_CHECK_LAUNCH(ctx);
@@ -1656,15 +1587,7 @@ static int fetch_multi_begin(asb_ctx* ctx, unsigned long long* seq) {
 }
 static int fetch_multi_end(asb_ctx* ctx, unsigned long long seq, unsigned long long* out9) {
     if (seq) {
-        volatile unsigned long long* word = reinterpret_cast<volatile unsigned long long*>(ctx->host_pin + 648);
-        const auto t0 = std::chrono::steady_clock::now();
-        bool arrived = false;
-        for (unsigned spins = 0;; ++spins) {
-            if (*word == seq) { arrived = true; break; }
-            if ((spins & 1023) == 1023 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 4.0) break;
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        if (!arrived) ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (!pin_wait(ctx->host_pin + 648, seq, 4.0)) ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
         memcpy(out9, ctx->host_pin + 512, 9 * 8);
         return ASB_OK;
     }
@@ -1760,37 +1683,38 @@ static int project_pass(asb_ctx* ctx, long long k0, int ncols, int proven = ASB_
 // the multi-tile projection kernel (bracketed by the profiling events); tiles built by wide_build_tile.
 // Up to 3 tiles: compiled for two waves per SIMD (<= 256 registers: 8 waves x 8 KB of X in flight per CU); from 4 tiles on
 // the accumulators alone take 128+ registers: one wave per SIMD, the MFMA time per chunk (1024 cycles per tile) hides the
-// load latency instead.  Variants measured on config 4 (tools/wide_variants.sh): deeper prefetch (PD = 2), four waves per
+// load latency instead.  Variants measured on config 4 (round 2): deeper prefetch, four waves per
 // tile, 32- and 48-row tiles, two chunks per group -- all slower than this one for 2 tiles.
-template <int NT, int G, int S, int NCT, int OCC, int PD>
+template <int NT, int G, int S, int NCT, int OCC>
 static int launch_l2w_cfg(asb_ctx* ctx, const WideArgs& wa, int blocks_per_cu) {
     const long long rows = 3 * ctx->n_loc, ntiles = (rows + 16 * NT - 1) / (16 * NT);
     const size_t lds = ((size_t)(S - 1) * NT * NCT * 4 * 64 + 2) * sizeof(double);
     static bool attr_set_dev[64] = {false};              // per device: a second GPU in the same process needs its own
     bool& attr_set = attr_set_dev[ctx->dev & 63];
     if (!attr_set) {
-        ASB_HIP(ctx, hipFuncSetAttribute((const void*)k_project_l2w<NT, G, S, NCT, OCC, PD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        ASB_HIP(ctx, hipFuncSetAttribute((const void*)k_project_l2w<NT, G, S, NCT, OCC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_set = true;
     }
     const long long cap = (long long)blocks_per_cu * ctx->n_cu;
-    hipLaunchKernelGGL((k_project_l2w<NT, G, S, NCT, OCC, PD>), dim3((unsigned)(ntiles < cap ? ntiles : cap)), dim3(64 * S), lds, ctx->stream,
+    hipLaunchKernelGGL((k_project_l2w<NT, G, S, NCT, OCC>), dim3((unsigned)(ntiles < cap ? ntiles : cap)), dim3(64 * S), lds, ctx->stream,
                        ctx->X, rows, (int)ctx->Fp, ctx->Wq3, ctx->wn2t3, wa, (ctx->wide_out ? ctx->wide_out : ctx->comps), rows, ctx->tile_counter);
     return ASB_OK;
 }
-template <int NCT, int P, int SYNC, int NSB = (SYNC ? 3 : 2), int XD = 1>
+template <int NCT, int P, int SYNC, bool BPF = false>
 static int launch_l2d(asb_ctx* ctx, const WideArgs& wa) {
     const long long rows = 3 * ctx->n_loc, ngroups = (rows + 15) / 16;
+    constexpr int NSB = SYNC ? 3 : 2;
     const size_t stage = (size_t)NSB * 4 * P * NCT * 128, redd = (size_t)4 * 4 * 4 * 64;
     const size_t lds = ((stage > redd ? stage : redd) + 4) * sizeof(double);
     static bool attr_set_dev[64] = {false};
     bool& attr_set = attr_set_dev[ctx->dev & 63];
     if (!attr_set) {
-        ASB_HIP(ctx, hipFuncSetAttribute((const void*)k_project_l2d<NCT, P, SYNC, NSB, 0, XD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        ASB_HIP(ctx, hipFuncSetAttribute((const void*)k_project_l2d<NCT, P, SYNC, NSB, BPF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_set = true;
     }
     // one block per CU, each with its own contiguous share of the 16-row groups (no work queue)
     const long long nb = ngroups < ctx->n_cu ? ngroups : ctx->n_cu;
-    hipLaunchKernelGGL((k_project_l2d<NCT, P, SYNC, NSB, 0, XD>), dim3((unsigned)nb), dim3(512), lds, ctx->stream, ctx->X, rows, (int)ctx->Fp, ctx->Wq3,
+    hipLaunchKernelGGL((k_project_l2d<NCT, P, SYNC, NSB, BPF>), dim3((unsigned)nb), dim3(512), lds, ctx->stream, ctx->X, rows, (int)ctx->Fp, ctx->Wq3,
                        ctx->wn2t3, wa, (ctx->wide_out ? ctx->wide_out : ctx->comps), rows);
     return ASB_OK;
 }
@@ -1798,15 +1722,15 @@ template <int NCT>
 static int launch_l2w(asb_ctx* ctx, int variant, const WideArgs& wa) {
     if (variant == 45 && NCT == 4) return launch_l2d<4, 3, 0>(ctx, wa);      // balanced partition, barrier per stage (two buffers)
     if (variant == 47 && NCT == 4) return launch_l2d<4, 2, 1>(ctx, wa);      // shorter stages
-    if (variant == 52 && NCT == 4) return launch_l2d<4, 3, 1, 3, 11>(ctx, wa);  // + weights of the next column tile read ahead (BPF)
-    if (variant == 51 && NCT == 4) return launch_l2d<4, 3, 5, 3>(ctx, wa);   // arrival counters per frame-half group of four waves (no gain: 1.43)
+    if (variant == 52 && NCT == 4) return launch_l2d<4, 3, 1, true>(ctx, wa);   // + weights of the next column tile read ahead (BPF)
+    if (variant == 51 && NCT == 4) return launch_l2d<4, 3, 5>(ctx, wa);      // arrival counters per frame-half group of four waves (no gain: 1.43)
     // (round 2's variants -- one wave per tile, 32- / 48- / 96- / 128-row tiles, deeper prefetch, weights shared through LDS with a
     // barrier per chunk pair (k_project_l2b) or per stage from a tile queue (k_project_l2c) -- were measured and removed; their
     // numbers are in DESIGN.md section 5 and profiles/r02*)
     // default: up to 3 sub-panels every wave fetches its own weights from L2 (two waves per SIMD); 4 sub-panels only fit two waves
     // per SIMD with the weights staged in LDS
     if (NCT == 4) return launch_l2d<4, 3, 1>(ctx, wa);
-    return launch_l2w_cfg<4, 1, 2, NCT, (NCT <= 3 ? 2 : 1), 1>(ctx, wa, NCT <= 3 ? 4 : 2);
+    return launch_l2w_cfg<4, 1, 2, NCT, (NCT <= 3 ? 2 : 1)>(ctx, wa, NCT <= 3 ? 4 : 2);
 }
 static int launch_wide(asb_ctx* ctx, int ntile, const WideArgs& wa) {
     const long long rows = 3 * ctx->n_loc;
@@ -1835,101 +1759,18 @@ static int launch_wide(asb_ctx* ctx, int ntile, const WideArgs& wa) {
     return ASB_OK;
 }
 
-// timing probe of the multi-tile kernel on the context's tensor (results are garbage): mode 0 = the kernel as it runs,
-// 1 = X operand from four cache-resident tiles (MFMA + L2 operand alone), 2 = no MFMAs (the loads alone)
-template <int NCT, int MODE>
-static int l2w_probe_launch(asb_ctx* ctx, const WideArgs& wa) {
-    constexpr int OCC = NCT <= 3 ? 2 : 1;
-    const long long rows = 3 * ctx->n_loc, ntiles = (rows + 63) / 64;
-    const size_t lds = ((size_t)4 * NCT * 4 * 64 + 2) * sizeof(double);
-    ASB_HIP(ctx, hipFuncSetAttribute((const void*)k_project_l2w<4, 1, 2, NCT, OCC, 1, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const long long cap = (long long)(NCT <= 3 ? 4 : 2) * ctx->n_cu;
-    hipLaunchKernelGGL((k_project_l2w<4, 1, 2, NCT, OCC, 1, MODE>), dim3((unsigned)(ntiles < cap ? ntiles : cap)), dim3(128), lds, ctx->stream,
-                       ctx->X, rows, (int)ctx->Fp, ctx->Wq3, ctx->wn2t3, wa, ctx->comps, rows, ctx->tile_counter);
-    return ASB_OK;
-}
-extern "C" int asb_test_l2w_probe(asb_ctx* ctx, int nct, int mode, int reps, double* ms_out) {
-    if (!ctx || !ctx->X || !ctx->comps || !ms_out || reps < 1 || ctx->K < 16 * nct) return ASB_ERR_ARG;
-    int rc;
-    if ((rc = asb_alloc(ctx, &ctx->Wt3, (size_t)ASB_MAX_SUB * ctx->Fp * 16))) return rc;
-    if ((rc = asb_alloc(ctx, &ctx->Wq3, (size_t)ASB_MAX_SUB * ctx->Fp * 16))) return rc;
-    if ((rc = asb_alloc(ctx, &ctx->wn2t3, (size_t)16 * ASB_MAX_SUB))) return rc;
-    if ((rc = asb_alloc(ctx, &ctx->tile_counter, (size_t)16))) return rc;
-    // weights: constants (mode < 100) or pseudo-random in (-0.05, 0.05) (mode >= 100: mode - 100 is the mode proper) -- the
-    // f64 MFMA rate of this part depends on how many operand bits toggle
-    const bool random_w = mode >= 100;
-    if (random_w) mode -= 100;
-    std::vector<double> ones((size_t)ASB_MAX_SUB * ctx->Fp * 16, 1.0e-3);
-    if (random_w) {
-        unsigned long long z = 0x9E3779B97F4A7C15ull;
-        for (double& v : ones) {
-            z = z * 6364136223846793005ull + 1442695040888963407ull;
-            v = ((double)(z >> 11) / 9007199254740992.0 - 0.5) * 0.1;
-        }
-    }
-    ASB_HIP(ctx, hipMemcpy(ctx->Wq3, ones.data(), ones.size() * sizeof(double), hipMemcpyHostToDevice));
-    for (double& v : ones) v = 1.0e-3;
-    ASB_HIP(ctx, hipMemcpy(ctx->wn2t3, ones.data(), 16 * ASB_MAX_SUB * sizeof(double), hipMemcpyHostToDevice));
-    WideArgs wa{};
-    for (int ct = 0; ct < nct; ++ct) { wa.kb[ct] = 16 * ct; wa.nc[ct] = 16; }
-    hipEvent_t e0, e1;
-    ASB_HIP(ctx, hipEventCreate(&e0));
-    ASB_HIP(ctx, hipEventCreate(&e1));
-    float best = 1e30f;
-    for (int r = 0; r < reps; ++r) {
-        ASB_HIP(ctx, hipMemsetAsync(ctx->tile_counter, 0, 16 * sizeof(unsigned), ctx->stream));
-        ASB_HIP(ctx, hipEventRecord(e0, ctx->stream));
-        rc = ASB_ERR_ARG;
-#define ASB_PROBE_CASE(N)                                                           \
-        if (nct == N && mode < 10) rc = mode == 0 ? l2w_probe_launch<N, 0>(ctx, wa) : (mode == 1 ? l2w_probe_launch<N, 1>(ctx, wa) : l2w_probe_launch<N, 2>(ctx, wa));
-        ASB_PROBE_CASE(2) ASB_PROBE_CASE(3) ASB_PROBE_CASE(4)
-#undef ASB_PROBE_CASE
-        if (nct == 4 && mode >= 20) {          // k_project_l2d<4, 3>: 20 = as it runs, 23 = no X loads in the loop, 24 = nor LDS reads, 25 = no stage sync
-            const long long rows = 3 * ctx->n_loc;
-#define ASB_L2D_PROBE(M)                                                                                                        \
-            {                                                                                                                   \
-                const size_t lds3 = ((size_t)3 * 4 * 3 * 4 * 128 + 4) * sizeof(double);                                         \
-                const long long ngr = (rows + 15) / 16;                                                                         \
-                ASB_HIP(ctx, hipFuncSetAttribute((const void*)k_project_l2d<4, 3, 1, 3, M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3)); \
-                hipLaunchKernelGGL((k_project_l2d<4, 3, 1, 3, M>), dim3((unsigned)(ngr < ctx->n_cu ? ngr : ctx->n_cu)), dim3(512), lds3, ctx->stream, \
-                                   ctx->X, rows, (int)ctx->Fp, ctx->Wq3, ctx->wn2t3, wa, ctx->comps, rows);                     \
-            }
-            if (mode == 23) ASB_L2D_PROBE(3) else if (mode == 24) ASB_L2D_PROBE(4) else if (mode == 25) ASB_L2D_PROBE(5) else ASB_L2D_PROBE(0)
-#undef ASB_L2D_PROBE
-            rc = ASB_OK;
-        }
-        if (rc) return rc;
-        ASB_HIP(ctx, hipEventRecord(e1, ctx->stream));
-        ASB_HIP(ctx, hipEventSynchronize(e1));
-        float ms = 0.f;
-        ASB_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
-        if (ms < best) best = ms;
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    *ms_out = best;
-    return ASB_OK;
-}
-
 static int launch_project_l2(asb_ctx* ctx, int ncols, double* out) {
     const long long rows = 3 * ctx->n_loc;
     int rc;
     if ((rc = asb_alloc(ctx, &ctx->Wq, (size_t)ctx->Fp * 16))) return rc;
     if ((rc = asb_alloc(ctx, &ctx->tile_counter, (size_t)16))) return rc;
     hipLaunchKernelGGL(k_build_wq, dim3(64), dim3(256), 0, ctx->stream, ctx->Wt, (int)ctx->Fp, ctx->Wq, ctx->tile_counter);
-    const int variant = ctx->l2_variant;       // 4 (default): two waves (one 128-thread block) per 64-row tile; 5: four; 6: <= 256 registers
     const long long ntiles = (rows + 63) / 64;
     size_t slot;
     if ((rc = prof_begin(ctx, slot))) return rc;
-    if (variant == 6)
-        hipLaunchKernelGGL((k_project_l2s<4, 2, 2, 1, 2>), dim3((unsigned)(ntiles < 4 * ctx->n_cu ? ntiles : 4 * ctx->n_cu)), dim3(128), 0, ctx->stream, ctx->X, rows, (int)ctx->Fp, ctx->Wq,
-                           ctx->wn2t, ncols, out, rows, ctx->tile_counter);
-    else if (variant == 5)      // four waves per tile: loses at the barriers what it gains at the end of the launch
-        hipLaunchKernelGGL((k_project_l2s<4, 2, 4, 1>), dim3((unsigned)(ntiles < 2 * ctx->n_cu ? ntiles : 2 * ctx->n_cu)), dim3(256), 0, ctx->stream, ctx->X, rows, (int)ctx->Fp, ctx->Wq,
-                           ctx->wn2t, ncols, out, rows, ctx->tile_counter);
-    else
-        hipLaunchKernelGGL((k_project_l2s<4, 2, 2, 1>), dim3((unsigned)(ntiles < 4 * ctx->n_cu ? ntiles : 4 * ctx->n_cu)), dim3(128), 0, ctx->stream, ctx->X, rows, (int)ctx->Fp, ctx->Wq,
-                           ctx->wn2t, ncols, out, rows, ctx->tile_counter);
+    // two waves (one 128-thread block) per 64-row tile (four waves per tile lost at the barriers what they gained at the end of the launch)
+    hipLaunchKernelGGL((k_project_l2s<4, 2, 2, 1>), dim3((unsigned)(ntiles < 4 * ctx->n_cu ? ntiles : 4 * ctx->n_cu)), dim3(128), 0, ctx->stream, ctx->X, rows, (int)ctx->Fp, ctx->Wq,
+                       ctx->wn2t, ncols, out, rows, ctx->tile_counter);
     if ((rc = prof_end(ctx, slot))) return rc;
     ASB_CHECK_LAUNCH(ctx);
     return ASB_OK;
@@ -2966,6 +2807,7 @@ static int coop_buffers(asb_ctx* ctx, int* cgrid_all, size_t* n_words) {
     return asb_alloc(ctx, &ctx->coop_rec, *n_words);
 }
 static int launch_panel_multi_any(asb_ctx* ctx, int grid, const MultiArgs& ma, bool* launched, PanelState* sub, bool writeback);
+constexpr int SPEC_W_RANK = 24;       // k_panel_multi: blocks ranked below it publish their w ahead of the exchange
 
 template <int NJ>
 static int launch_panel_multi(asb_ctx* ctx, int grid, const MultiArgs& ma, bool* launched, PanelState* sub, bool writeback) {
@@ -2974,36 +2816,10 @@ static int launch_panel_multi(asb_ctx* ctx, int grid, const MultiArgs& ma, bool*
     if (per_cu < 1) { *launched = false; return ASB_OK; }
     if ((long long)per_cu * ctx->n_cu < grid) grid = per_cu * ctx->n_cu;      // the kernel refuses panels with more candidates
     unsigned long long* words = (unsigned long long*)ctx->coop_rec;
-    if (ctx->coop_launch == 1) {
-        // A COOPERATIVE launch (ASB_COOP_LAUNCH=1) makes the runtime assert what the plain launch infers from the occupancy
-        // query -- that all blocks are resident at once -- and refuse instead of running when they cannot be.  Not the default:
-        // the cooperative path serialises against every other queue of the process; where the stream (or the device)
-        // does not take it the launch falls back to the plain form, whose poll limit turns a surprise into an error, not a hang.
-        const double* a0 = ctx->candR;
-        int a1 = (int)ctx->F, a2 = (int)ctx->Fp;
-        double *a3 = ctx->W, *a4 = ctx->scal;
-        MultiArgs a5 = ma;
-        const PanelState* a6 = ctx->pstate;
-        PanelState* a7 = sub;
-        const long long* a8 = ctx->cand_idx;
-        unsigned* a9 = ctx->coop_bar;
-        unsigned long long *a10 = words, *a11 = words + (size_t)3 * grid * 2, *a11b = a11 + (size_t)3 * (ctx->Fp + 8);
-        double* a12 = writeback ? ctx->candR : (double*)nullptr;
-        int a13 = ctx->coop_test_stall, a14 = ctx->spec_w_rank;
-        void* args[] = {&a0, &a1, &a2, &a3, &a4, &a5, &a6, &a7, &a8, &a9, &a10, &a11, &a11b, &a12, &a13, &a14};
-        const hipError_t e = hipLaunchCooperativeKernel((const void*)k_panel_multi<NJ>, dim3(grid), dim3(256), args, 0, ctx->stream);
-        if (e == hipSuccess) {
-            *launched = true;
-            ctx->n_coop_launches++;
-            return ASB_OK;
-        }
-        (void)hipGetLastError();
-        ctx->coop_launch = -1;                // this context's stream / device does not take cooperative launches
-    }
     hipLaunchKernelGGL(k_panel_multi<NJ>, dim3(grid), dim3(256), 0, ctx->stream, ctx->candR, (int)ctx->F, (int)ctx->Fp, ctx->W, ctx->scal,
                        ma, ctx->pstate, sub, ctx->cand_idx, ctx->coop_bar, words, words + (size_t)3 * grid * 2,
                        words + (size_t)3 * grid * 2 + (size_t)3 * (ctx->Fp + 8), writeback ? ctx->candR : (double*)nullptr,
-                       ctx->coop_test_stall, ctx->spec_w_rank);
+                       ctx->coop_test_stall, SPEC_W_RANK);
     ASB_CHECK_LAUNCH(ctx);
     *launched = true;
     ctx->n_coop_launches++;
@@ -3117,8 +2933,8 @@ extern "C" int asb_panel_run(asb_ctx* ctx, int64_t k0, int steps, int global_all
             return rc;
         }
     }
-    if (coop && getenv("ASB_DEBUG_PANELS")) print_multi_timeline(ctx, (int)h.committed);
-    if (getenv("ASB_DEBUG_PANELS")) {
+    if (coop && asb_debug_panels()) print_multi_timeline(ctx, (int)h.committed);
+    if (asb_debug_panels()) {
         double sc[8];
         (void)hipMemcpy(sc, ctx->scalar_dev, sizeof(sc), hipMemcpyDeviceToHost);
         std::vector<double> ce((size_t)h.n_cand);
@@ -3298,125 +3114,19 @@ __global__ __launch_bounds__(256) void k_apply_tmp(double* __restrict__ E, const
     for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < n; v += (long long)gridDim.x * 256) E[v] = Etmp[v];
 }
 
-// ---- the checks of ALL tiles of a read in ONE launch (round 4; k_correct_rows<true> x ntile -> k_check_tiles): with weights
+// ---- the checks of ALL tiles of a read in ONE launch (round 4; k_correct_rows<true> x ntile -> k_check_tiles_w): with weights
 // orthogonalised before the pass a check is a streaming read of the tile's columns, and what a later tile sees of an earlier one
-// is only the energies it would have left -- so one thread per vertex walks the tiles in order, carrying the energy AS IF every
-// tile so far stood (the chain discards everything behind a tile that did not), and leaves per tile: the tentative energies,
-// the block records and column sums, and the first rejected step (atomicMin into the tile's PanelState).  The arithmetic per
-// tile is k_correct_rows<true>'s, term by term.  k_tiles_decide (one block) is k_tile_decide for all tiles in order;
-// k_apply_tiles adopts the energies and records of the LAST tile that stood in full.  Four tiles: 3 launches instead of 12.
+// is only the energies it would have left -- so the tiles are walked in order, carrying the energy AS IF every tile so far stood
+// (the chain discards everything behind a tile that did not), and the kernel leaves per tile: the tentative energies, the block
+// records and column sums, and the first rejected step (atomicMin into the tile's PanelState).  The arithmetic per tile is
+// k_correct_rows<true>'s, term by term.  k_tiles_decide (one block) is k_tile_decide for all tiles in order; k_apply_tiles
+// adopts the energies and records of the LAST tile that stood in full.  Four tiles: 3 launches instead of 12.
 #define ASB_CHK_TILES 4
 struct CheckOut { double* etmp; double* pmax; long long* pidx; double* psum; double* colpart; };
-__global__ __launch_bounds__(256, 2) void k_check_tiles(const double* __restrict__ comps, long long comp_stride, long long n_vert, WideArgs wa,
-                                                     int ntile, const double* __restrict__ wn2t3, const double* __restrict__ E,
-                                                     const double* __restrict__ Ecl, const double* __restrict__ E2,
-                                                     const double* __restrict__ sc, PanelState* __restrict__ st, CheckOut out) {
-    __shared__ double sh[4 * 16];
-    __shared__ double sh_m[4];
-    __shared__ long long sh_i[4];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    int viol[ASB_CHK_TILES];
-    double bmax[ASB_CHK_TILES], bsum[ASB_CHK_TILES], csum[ASB_CHK_TILES][16];
-    long long bidx[ASB_CHK_TILES];
-#pragma unroll
-    for (int ct = 0; ct < ASB_CHK_TILES; ++ct) {
-        viol[ct] = ASB_PANEL_COLS; bmax[ct] = -1.0; bsum[ct] = 0.0; bidx[ct] = 0x7fffffffffffffffLL;
-#pragma unroll
-        for (int t = 0; t < 16; ++t) csum[ct][t] = 0.0;
-    }
-    for (long long v = (long long)blockIdx.x * 256 + tid; v < n_vert; v += (long long)gridDim.x * 256) {
-        double e = E[v];
-        const double es = Ecl ? Ecl[v] : e;
-        const bool outside = !(es > sc[SC_TAU]) && !(E2 && in_guess(es, E2[v], sc)) && !in_div(es, v, sc);
-#pragma unroll
-        for (int ct = 0; ct < ASB_CHK_TILES; ++ct) {
-            if (ct >= ntile) break;
-            const int ncols = wa.nc[ct];
-            const double* base = comps + wa.kb[ct] * comp_stride + 3 * v;
-            const PanelState* sp = st + ct;
-            const double margin = sp->margin;
-            const int proven = (int)sp->proven;
-            const double e_start = e;
-            double loss = 0.0;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {                // (eight columns' loads in flight at a time: 24 doubles per thread)
-                double c[8][3];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int t = 8 * h + u;
-                    const bool on = t < ncols;
-                    c[u][0] = on ? base[(long long)t * comp_stride] : 0.0;
-                    c[u][1] = on ? base[(long long)t * comp_stride + 1] : 0.0;
-                    c[u][2] = on ? base[(long long)t * comp_stride + 2] : 0.0;
-                }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int t = 8 * h + u;
-                    if (t < ncols) {
-                        if (outside && t >= proven && t < viol[ct] && !(sp->e_win[t] > e + margin)) viol[ct] = t;
-                        const double q = ((c[u][0] * c[u][0] + c[u][1] * c[u][1]) + c[u][2] * c[u][2]) * wn2t3[16 * ct + t];
-                        e -= q;
-                        loss += q;
-                        csum[ct][t] += q;
-                    }
-                }
-            }
-            double en = e_start - loss;                  // exactly k_commit_energy's arithmetic
-            if (en < 0.0) en = 0.0;
-            out.etmp[(long long)ct * n_vert + v] = en;
-            bsum[ct] += en;
-            if (am_better(en, v, bmax[ct], bidx[ct])) { bmax[ct] = en; bidx[ct] = v; }
-            e = en;                                      // what the next tile reads once this one has been adopted
-        }
-    }
-#pragma unroll
-    for (int ct = 0; ct < ASB_CHK_TILES; ++ct) {
-        if (ct >= ntile) break;                          // (uniform)
-        int vl = viol[ct];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const int ov = __shfl_xor(vl, o, 64);
-            vl = ov < vl ? ov : vl;
-        }
-        if (lane == 0 && vl < ASB_PANEL_COLS) atomicMin(reinterpret_cast<long long*>(&st[ct].spec_ok), (long long)vl);
-#pragma unroll
-        for (int t = 0; t < 16; ++t) csum[ct][t] = wave_sum(csum[ct][t]);
-        double bs = wave_sum(bsum[ct]), bm = bmax[ct];
-        long long bi = bidx[ct];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const double om = __shfl_xor(bm, o, 64);
-            const long long oi = __shfl_xor(bi, o, 64);
-            if (am_better(om, oi, bm, bi)) { bm = om; bi = oi; }
-        }
-        __syncthreads();                                 // the previous tile's reads of sh are done
-        if (lane == 0) {
-#pragma unroll
-            for (int t = 0; t < 16; ++t) sh[wv * 16 + t] = csum[ct][t];
-            sh_m[wv] = bm; sh_i[wv] = bi;
-        }
-        // (the block's sum of energies goes through the same LDS slots one tile later: a fifth array would do as well)
-        __syncthreads();
-        if (tid < 16)
-            out.colpart[((long long)ct * gridDim.x + blockIdx.x) * 16 + tid] = ((sh[tid] + sh[16 + tid]) + sh[32 + tid]) + sh[48 + tid];
-        if (tid == 64) {
-            double m = sh_m[0];
-            long long ix = sh_i[0];
-            for (int w = 1; w < 4; ++w)
-                if (am_better(sh_m[w], sh_i[w], m, ix)) { m = sh_m[w]; ix = sh_i[w]; }
-            out.pmax[(long long)ct * gridDim.x + blockIdx.x] = m;
-            out.pidx[(long long)ct * gridDim.x + blockIdx.x] = ix;
-        }
-        __syncthreads();
-        if (lane == 0) sh[wv] = bs;
-        __syncthreads();
-        if (tid == 0) out.psum[(long long)ct * gridDim.x + blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
-    }
-}
-// The same with ONE WAVE PER TILE: block = 4 waves over the same 64 vertices, wave ct loads tile ct's columns (48 loads per lane in
-// flight instead of eight dependent batches of 24), the tiles' losses meet through LDS, and every wave walks the (three-step) chain
-// of clamped energies up to its own tile before it checks its columns -- term by term the arithmetic of k_check_tiles.  Each wave
-// reduces its own tile's records: no cross-wave reduction.  62 -> 3x us per read at config 4.
+// ONE WAVE PER TILE: block = 4 waves over the same 64 vertices, wave ct loads tile ct's columns (48 loads per lane in flight; one
+// thread per vertex walking the tiles had eight dependent batches of 24), the tiles' losses meet through LDS, and every wave
+// walks the (three-step) chain of clamped energies up to its own tile before it checks its columns.  Each wave reduces its own
+// tile's records: no cross-wave reduction.  62 -> 3x us per read at config 4.
 __global__ __launch_bounds__(256) void k_check_tiles_w(const double* __restrict__ comps, long long comp_stride, long long n_vert, WideArgs wa,
                                                        int ntile, const double* __restrict__ wn2t3, const double* __restrict__ E,
                                                        const double* __restrict__ Ecl, const double* __restrict__ E2,
@@ -3733,7 +3443,7 @@ static int multi_chain_run(asb_ctx* ctx, long long k, long long k1, int nsub_max
     if (!launched) return ASB_OK;
     unsigned long long sum[9], seq = 0;
     if ((rc = fetch_multi_begin(ctx, &seq))) return rc;
-    if (spec_ntile && seq && ctx->spec_pass && ctx->spec_budget >= ASB_PANEL_COLS && ctx->pre_orth && ctx->correct_rows) {
+    if (spec_ntile && seq && ctx->spec_budget >= ASB_PANEL_COLS && ctx->pre_orth && ctx->correct_rows) {
         WideArgs wa{};
         int nt = 0;
         for (int sp = 0; sp < n; ++sp) {
@@ -3750,7 +3460,7 @@ static int multi_chain_run(asb_ctx* ctx, long long k, long long k1, int nsub_max
     if ((rc = fetch_multi_end(ctx, seq, sum))) return rc;
     ctx->n_panels++;
     ctx->run_coop_used = 1;
-    if (getenv("ASB_DEBUG_PANELS")) print_multi_timeline(ctx, (int)(sum[0] & 0xffffffffu) + 16 * (n - 1));
+    if (asb_debug_panels()) print_multi_timeline(ctx, (int)(sum[0] & 0xffffffffu) + 16 * (n - 1));
     int nt = 0;
     for (int sp = 0; sp < n; ++sp) {
         const long long committed = (long long)(sum[sp] & 0xffffffffu), prov = (long long)(sum[sp] >> 32) - 1;
@@ -3780,15 +3490,11 @@ static int tiles_enqueue(asb_ctx* ctx, int ntile, const long long* kb, const int
     if ((rc = asb_alloc(ctx, &ctx->tile_res, (size_t)ASB_MAX_SUB + 2))) return rc;
     long long cwr = (ctx->n_loc + 63) / 64;
     // (two blocks per CU, grid-strided: the one-block k_tile_decide sums a partial per block and column)
-    static const int bpc = getenv("ASB_CHECK_BLOCKS_PER_CU") ? atoi(getenv("ASB_CHECK_BLOCKS_PER_CU")) : 2;
-    const long long rcap = (long long)(bpc < 1 ? 1 : (bpc > 8 ? 8 : bpc)) * ctx->n_cu;
+    const long long rcap = 2LL * ctx->n_cu;
     const int rgrid = (int)(cwr < rcap ? cwr : rcap);
     long long cw = (ctx->n_loc + 255) / 256;
     const int cgrid = (int)(cw < ctx->nblk_cap ? cw : ctx->nblk_cap);
-    static const int fused = getenv("ASB_CHECK_FUSED") ? atoi(getenv("ASB_CHECK_FUSED")) : 2;
-    if (fused && ntile <= ASB_CHK_TILES) {
-        long long cb = (ctx->n_loc + 255) / 256;
-        int fgrid = (int)(cb < ctx->nblk_cap ? cb : ctx->nblk_cap);
+    if (ntile <= ASB_CHK_TILES) {                        // one launch for all tiles; more tiles: the per-tile chain below
         if ((rc = asb_alloc(ctx, &ctx->e_tmp4, (size_t)ASB_CHK_TILES * ctx->n_loc))) return rc;
         if ((rc = asb_alloc(ctx, &ctx->chk_rec, (size_t)ASB_CHK_TILES * ctx->nblk_cap * 18))) return rc;
         if ((rc = asb_alloc(ctx, &ctx->chk_idx, (size_t)ASB_CHK_TILES * ctx->nblk_cap))) return rc;
@@ -3800,15 +3506,12 @@ static int tiles_enqueue(asb_ctx* ctx, int ntile, const long long* kb, const int
             wa.nc[ct] = nc[ct];
             if (st[ct] != st[0] + ct) ASB_FAIL(ctx, ASB_ERR_ARG, "tiles_enqueue: the tiles' states are not contiguous");
         }
-        if (fused >= 2) {                                // one wave per tile (blocks of 64 vertices)
-            long long cg = (ctx->n_loc + 63) / 64;           // (two blocks per CU, grid-strided: the one-block decision sums a record per block)
-            const long long cgc = 2LL * ctx->n_cu < ctx->nblk_cap ? 2LL * ctx->n_cu : ctx->nblk_cap;
-            fgrid = (int)(cg < cgc ? cg : cgc);
-            hipLaunchKernelGGL(k_check_tiles_w, dim3(fgrid), dim3(256), 0, ctx->stream, ctx->comps, (long long)(3 * ctx->n_loc),
-                               (long long)ctx->n_loc, wa, ntile, ctx->wn2t3, ctx->energy, ctx->e_class, ctx->sel_e2, ctx->scalar_dev, st[0], co);
-        } else
-        hipLaunchKernelGGL(k_check_tiles, dim3(fgrid), dim3(256), 0, ctx->stream, ctx->comps, (long long)(3 * ctx->n_loc), (long long)ctx->n_loc,
-                           wa, ntile, ctx->wn2t3, ctx->energy, ctx->e_class, ctx->sel_e2, ctx->scalar_dev, st[0], co);
+        // one wave per tile, blocks of 64 vertices (two blocks per CU, grid-strided: the one-block decision sums a record per block)
+        const long long cg = (ctx->n_loc + 63) / 64;
+        const long long cgc = 2LL * ctx->n_cu < ctx->nblk_cap ? 2LL * ctx->n_cu : ctx->nblk_cap;
+        const int fgrid = (int)(cg < cgc ? cg : cgc);
+        hipLaunchKernelGGL(k_check_tiles_w, dim3(fgrid), dim3(256), 0, ctx->stream, ctx->comps, (long long)(3 * ctx->n_loc),
+                           (long long)ctx->n_loc, wa, ntile, ctx->wn2t3, ctx->energy, ctx->e_class, ctx->sel_e2, ctx->scalar_dev, st[0], co);
         hipLaunchKernelGGL(k_tiles_decide, dim3(1), dim3(1024), 0, ctx->stream, co.colpart, fgrid, ntile, wa, ctx->scal, st[0], ctx->tile_res);
         hipLaunchKernelGGL(k_apply_tiles, dim3(cgrid), dim3(256), 0, ctx->stream, ctx->energy, (long long)ctx->n_loc, fgrid, co, ctx->tile_res,
                            ctx->pmax, ctx->pidx, ctx->psum);
@@ -3926,7 +3629,7 @@ static int double_panel(asb_ctx* ctx, long long k, long long k1, int64_t* done_o
             ctx->n_spec_steps += nc[ct] - proven[ct];
             ctx->n_spec_kept += kept > proven[ct] ? kept - proven[ct] : 0;
             total += kept;
-            if (getenv("ASB_DEBUG_PANELS"))
+            if (asb_debug_panels())
                 fprintf(stderr, "[asb] panel at k=%lld tile %d: %d proven + %lld of %d unproven steps kept\n", k, ct, proven[ct],
                         (long long)(kept > proven[ct] ? kept - proven[ct] : 0), nc[ct] - proven[ct]);
             if (ct >= 1) {
@@ -3943,7 +3646,7 @@ static int double_panel(asb_ctx* ctx, long long k, long long k1, int64_t* done_o
         ctx->n_spec_steps += nc[ct] - proven[ct];
         ctx->n_spec_kept += kept > proven[ct] ? kept - proven[ct] : 0;
         total += kept;
-        if (getenv("ASB_DEBUG_PANELS"))
+        if (asb_debug_panels())
             fprintf(stderr, "[asb] panel at k=%lld tile %d: %d proven + %lld of %d unproven steps kept\n", k, ct, proven[ct],
                     (long long)(kept > proven[ct] ? kept - proven[ct] : 0), nc[ct] - proven[ct]);
         if (ct >= 1) {                                // adapt the later sub-panels' lengths to what stands
@@ -3993,7 +3696,7 @@ static int double_panel(asb_ctx* ctx, long long k, long long k1, int64_t* done_o
         }
         {
             const int nm = ntile < 1 ? 1 : (ntile > 4 ? 4 : ntile);
-            if (ctx->cost_cnt[nm] < 4 && read_ms > 0.0 && !getenv("ASB_DEBUG_PANELS")) {
+            if (ctx->cost_cnt[nm] < 4 && read_ms > 0.0 && !asb_debug_panels()) {
                 ctx->cost_nt[nm] = (ctx->cost_nt[nm] < 0.0 || read_ms < ctx->cost_nt[nm]) ? read_ms : ctx->cost_nt[nm];
                 ctx->cost_cnt[nm]++;
             }
@@ -4014,7 +3717,7 @@ static int double_panel(asb_ctx* ctx, long long k, long long k1, int64_t* done_o
         want_replay = !ctx->last_by_score;                  // look at the other kind again, ever more rarely while the verdict stands
         ctx->probe_after = ctx->probe_after < 64 ? 2 * ctx->probe_after : 64;
     }
-    if (getenv("ASB_DEBUG_PANELS") && ctx->read_by_score && ctx->sk_pred) {
+    if (asb_debug_panels() && ctx->read_by_score && ctx->sk_pred) {
         // how good was the replay that named this read's candidates?  its winners (local vertex ids) against the read's own
         long long pr[64];
         std::vector<double> sc4((size_t)(total + 1) * 4);
@@ -4031,7 +3734,7 @@ static int double_panel(asb_ctx* ctx, long long k, long long k1, int64_t* done_o
         fprintf(stderr, "[asb]   the replay named the first %d of the %lld winners kept; at the step that fell it had vertex %lld, the panel took %lld\n",
                 agree, (long long)total, total < 64 ? pr[total] + ctx->v0 : -1LL, gq);
     }
-    if (getenv("ASB_DEBUG_PANELS"))
+    if (asb_debug_panels())
         fprintf(stderr, "[asb] read at k=%lld (%s candidates) kept %lld: components per ms plain %.1f, predicted %.1f -> %s next\n", k,
                 ctx->read_by_score ? "predicted" : "plain", (long long)total, ctx->rate_plain, ctx->rate_sketch,
                 want_replay ? "replay" : "plain");
@@ -4039,8 +3742,7 @@ static int double_panel(asb_ctx* ctx, long long k, long long k1, int64_t* done_o
         long long ncols = 0;
         for (int ct = 0; ct < ntile; ++ct) ncols += nc[ct];
         const long long left = ncols - total;
-        static const int sk_min_cols = getenv("ASB_SKETCH_MIN_COLS") ? atoi(getenv("ASB_SKETCH_MIN_COLS")) : 8;
-        if (left >= sk_min_cols && ctx->n_loc > ctx->m_cap) {        // (above one co-resident launch the replay runs on the largest energies)
+        if (left >= 8 && ctx->n_loc > ctx->m_cap) {        // (above one co-resident launch the replay runs on the largest energies)
             const long long ks = k + total, todo = k1 - ks;
             const int r = (int)(left < 64 ? left : 64), steps = (int)(todo < 64 ? todo : 64);
             const auto t_rep0 = std::chrono::steady_clock::now();
@@ -4054,7 +3756,7 @@ static int double_panel(asb_ctx* ctx, long long k, long long k1, int64_t* done_o
             unsigned fl[4] = {0, 0, 0, 0};
             if ((rc = fetch_words(ctx, ctx->sk_flags, 2, fl))) return rc;
             const bool replayed = fl[2] != 0 && fl[1] == 0;
-            if (replayed && ctx->cost_replay_cnt < 4 && steps == 64 && !getenv("ASB_DEBUG_PANELS")) {
+            if (replayed && ctx->cost_replay_cnt < 4 && steps == 64 && !asb_debug_panels()) {
                 const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_rep0).count();
                 ctx->cost_replay = (ctx->cost_replay < 0.0 || ms < ctx->cost_replay) ? ms : ctx->cost_replay;
                 ctx->cost_replay_cnt++;
@@ -4066,7 +3768,7 @@ static int double_panel(asb_ctx* ctx, long long k, long long k1, int64_t* done_o
             } else if (fl[3]) {
                 ctx->sketch_run_off = true;
             }
-            if (getenv("ASB_DEBUG_PANELS"))
+            if (asb_debug_panels())
                 fprintf(stderr, "[asb] sketch of %d columns at k=%lld holds %.3f of the residual: %s\n", r, ks,
                         [&] { float f; memcpy(&f, &fl[0], 4); return (double)f; }(), replayed ? "replayed" : (fl[3] ? "holds too little of the residual: candidates by energy" : "exchange timed out"));
         }
@@ -4384,8 +4086,7 @@ static int guess_thresholds(asb_ctx* ctx, int world, bool with_energy) {
     gt.m_cap[ASB_DIV_Q] = md + md / 8;
     gt.div_seed = (double)(ctx->n_panels + ctx->n_refresh + 1);
     const int nq = with_energy ? ASB_NQ : ASB_NG;
-    static const int ucb = getenv("ASB_GUESS_UCB") ? atoi(getenv("ASB_GUESS_UCB")) : 1;      // 0: without the confidence-bound family
-    unsigned qmask = ucb ? 0xffffffffu : ~(1u << (ASB_NG - 1));
+    unsigned qmask = 0xffffffffu;
     if (md < 8) qmask &= ~(1u << ASB_DIV_Q);
     for (int level = 1; level <= 2; ++level) {
         hipLaunchKernelGGL(k_hist_multi, dim3(hist_grid(ctx)), dim3(256), 0, ctx->stream, ctx->energy, ctx->EV, (long long)ctx->n_loc,
@@ -4408,10 +4109,9 @@ static int score_thresholds(asb_ctx* ctx, bool with_score = true, long long m_di
     GuessTargets gt;
     // (a third of the candidates by energy: the replay names who comes CLOSE to winning under its model, the energies who is large
     // now -- eight low-rank tensors: 16.0 ms / 6.25 reads in the mean with a third or a half by energy, 17.0 / 6.5 with a twelfth)
-    static const int me_div = getenv("ASB_SKETCH_ME_DIV") ? atoi(getenv("ASB_SKETCH_ME_DIV")) : 3;
     // with_score: ms by the replay's scores, me by energy (+ m_div by the diversity family beside them); without: a PLAIN read
     // behind a rejection -- m_target - m_div by energy, m_div (half) energy-weighted random (in_div)
-    const long long me = with_score ? ctx->m_target / (me_div > 1 ? me_div : 2) : ctx->m_target - m_div, ms = ctx->m_target - me;
+    const long long me = with_score ? ctx->m_target / 3 : ctx->m_target - m_div, ms = ctx->m_target - me;
     for (int q = 0; q < ASB_NQ; ++q) {
         gt.g[q] = q == ASB_NG ? 1.0 : 0.0;
         gt.h[q] = 0.0;
@@ -4532,7 +4232,7 @@ extern "C" int asb_project_switch_residual(asb_ctx* ctx, int64_t k) {
     ctx->sel_e2 = nullptr;
     ctx->k_done = k;
     ctx->k_switch = k;
-    if (getenv("ASB_DEBUG_PANELS"))
+    if (asb_debug_panels())
         fprintf(stderr, "[asb] k=%lld: %lld reads of X so far -- the run continues in the residual loop\n", (long long)k,
                 (long long)(ctx->n_panels + ctx->n_refresh));
     return ASB_OK;
@@ -4617,7 +4317,7 @@ int asb_project_run(asb_ctx* ctx, int64_t k0, int64_t k1) {
             // a kept step saves 1/16 of a pass over X (~80 us on config 4), a rejected one costs one panel step (~14 us):
             // keep trying the full panel as long as anything stands, back off only after complete failures
             ctx->spec_budget = gain > 0 ? ASB_PANEL_COLS : (ctx->spec_budget / 2 > 2 ? ctx->spec_budget / 2 : 2);
-            if (getenv("ASB_DEBUG_PANELS"))
+            if (asb_debug_panels())
                 fprintf(stderr, "[asb] panel at k=%lld: %lld proven + %lld of %lld unproven steps kept\n", k, (long long)proven,
                         (long long)gain, (long long)tried);
             if (done > 0) {
@@ -4670,28 +4370,26 @@ int asb_project_results(asb_ctx* ctx, double* comps, double* weigs, int64_t* idx
     // own round trip when the destination is pageable) -- the weights below are the only copy of a run's results
     bool published = false;
     unsigned long long seq = 0;
-    if (ctx->host_poll) {
-        if (ctx->res_pin_count < n_scal + 16) {
-            if (ctx->res_pin) (void)hipHostFree(ctx->res_pin);
+    if (ctx->res_pin_count < n_scal + 16) {
+        if (ctx->res_pin) (void)hipHostFree(ctx->res_pin);
+        ctx->res_pin = nullptr;
+        ctx->res_pin_dev = nullptr;
+        if (hipHostMalloc((void**)&ctx->res_pin, (n_scal + 16) * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped) == hipSuccess) {
+            ctx->res_pin_count = n_scal + 16;
+            ctx->res_pin[0] = 0.0;
+            if (hipHostGetDevicePointer((void**)&ctx->res_pin_dev, ctx->res_pin, 0) != hipSuccess) ctx->res_pin_dev = nullptr;
+        } else {
+            (void)hipGetLastError();
             ctx->res_pin = nullptr;
-            ctx->res_pin_dev = nullptr;
-            if (hipHostMalloc((void**)&ctx->res_pin, (n_scal + 16) * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped) == hipSuccess) {
-                ctx->res_pin_count = n_scal + 16;
-                ctx->res_pin[0] = 0.0;
-                if (hipHostGetDevicePointer((void**)&ctx->res_pin_dev, ctx->res_pin, 0) != hipSuccess) ctx->res_pin_dev = nullptr;
-            } else {
-                (void)hipGetLastError();
-                ctx->res_pin = nullptr;
-                ctx->res_pin_count = 0;
-            }
+            ctx->res_pin_count = 0;
         }
-        if (ctx->res_pin_dev) {
-            seq = ++ctx->pin_seq;
-            hipLaunchKernelGGL(k_publish_results, dim3(1), dim3(256), 0, ctx->stream, ctx->scal, (long long)n_scal, ctx->scalar_dev,
-                               ctx->res_pin_dev, seq);
-            ASB_CHECK_LAUNCH(ctx);
-            published = true;
-        }
+    }
+    if (ctx->res_pin_dev) {
+        seq = ++ctx->pin_seq;
+        hipLaunchKernelGGL(k_publish_results, dim3(1), dim3(256), 0, ctx->stream, ctx->scal, (long long)n_scal, ctx->scalar_dev,
+                           ctx->res_pin_dev, seq);
+        ASB_CHECK_LAUNCH(ctx);
+        published = true;
     }
     if (!published) {
         ASB_HIP(ctx, hipMemcpyAsync(h.data(), ctx->scal, h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -4710,14 +4408,7 @@ int asb_project_results(asb_ctx* ctx, double* comps, double* weigs, int64_t* idx
         ASB_HIP(ctx, hipMemcpyAsync(weigs, ctx->w_fk, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     }
     if (published) {
-        volatile unsigned long long* word = reinterpret_cast<volatile unsigned long long*>(ctx->res_pin);
-        const auto t0 = std::chrono::steady_clock::now();
-        bool arrived = false;
-        for (unsigned spins = 0;; ++spins) {
-            if (*word == seq) { arrived = true; break; }
-            if ((spins & 1023) == 1023 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 4.0) break;
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
+        const bool arrived = pin_wait(ctx->res_pin, seq, 4.0);
         if (!arrived || comps || weigs) ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));      // (the copies above; a fault shows here)
         memcpy(h.data(), ctx->res_pin + 2, n_scal * sizeof(double));
         memcpy(sc, ctx->res_pin + 2 + n_scal, sizeof(sc));

@@ -484,7 +484,7 @@ int asb_sketch_predict(asb_ctx* ctx, const double* cols, long long stride, const
         if ((rc = asb_alloc(ctx, &ctx->sk_counts, (size_t)4))) return rc;
         ASB_HIP(ctx, hipMemsetAsync(ctx->sk_counts, 0, 4 * sizeof(unsigned), ctx->stream));
     }
-    static const float min_share = getenv("ASB_SKETCH_MIN_SHARE") ? (float)atof(getenv("ASB_SKETCH_MIN_SHARE")) : 0.15f;
+    constexpr float min_share = 0.15f;
     ASB_HIP(ctx, hipMemsetAsync(ctx->sk_words, 0xFF, n_words * sizeof(unsigned long long), ctx->stream));
     ASB_HIP(ctx, hipMemsetAsync(ctx->sk_flags, 0, 4 * sizeof(unsigned), ctx->stream));
     ASB_HIP(ctx, hipMemsetAsync(ctx->sk_pred, 0xFF, 64 * sizeof(long long), ctx->stream));
@@ -494,7 +494,7 @@ int asb_sketch_predict(asb_ctx* ctx, const double* cols, long long stride, const
     ASB_CHECK_LAUNCH(ctx);
     ctx->sk_test_stall = 0;
     ctx->n_sketch_runs++;
-    if (getenv("ASB_DEBUG_PANELS")) {
+    if (asb_debug_panels()) {
         unsigned long long tlh[64 * 6];
         unsigned flh[4] = {0, 0, 0, 0};
         (void)hipStreamSynchronize(ctx->stream);

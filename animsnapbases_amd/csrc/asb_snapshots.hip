@@ -296,31 +296,22 @@ extern "C" int asb_create(int device_id, void* hip_stream, asb_ctx** out) {
         ctx->own_stream = true;
     }
     ctx->n_cu = prop.multiProcessorCount;
-    if (const char* pk = getenv("ASB_PROJECT_KERNEL")) ctx->project_kernel = atoi(pk);
-    if (const char* pv = getenv("ASB_L2_VARIANT")) ctx->l2_variant = atoi(pv);
     if (const char* pc = getenv("ASB_PANEL_COOP")) ctx->panel_coop = atoi(pc);
     if (const char* ts = getenv("ASB_COOP_TEST_STALL")) ctx->coop_test_stall = atoi(ts);
     if (const char* er = getenv("ASB_E0_REUSE")) ctx->e0_reuse = atoi(er);
     if (const char* er = getenv("ASB_FIRST_PANEL_MEAN")) ctx->first_panel_mean = atoi(er);
-    if (const char* hp = getenv("ASB_HOST_POLL")) ctx->host_poll = atoi(hp);
     if (const char* cr = getenv("ASB_CORRECT_ROWS")) ctx->correct_rows = atoi(cr);
-    if (const char* sp = getenv("ASB_SUPER_PANELS")) ctx->super_panels = atoi(sp);
     if (const char* sp = getenv("ASB_SPEC_PANELS")) ctx->spec_panels = atoi(sp);
-    if (const char* gc = getenv("ASB_GATHER_CPT")) ctx->gather_cpt = atoi(gc);
     if (const char* dp = getenv("ASB_DOUBLE_PANELS")) ctx->double_panels = atoi(dp);
     if (const char* dp = getenv("ASB_SUB_PANELS")) ctx->sub_panels = atoi(dp);
     if (const char* dp = getenv("ASB_PRE_ORTH")) ctx->pre_orth = atoi(dp);
     if (const char* dp = getenv("ASB_TILE_CHAIN")) ctx->tile_chain = atoi(dp);
     if (const char* dp = getenv("ASB_SUB_CHAIN")) ctx->sub_chain = atoi(dp);
-    if (const char* dp = getenv("ASB_COOP_LAUNCH")) ctx->coop_launch = atoi(dp) ? 1 : 0;
-    if (const char* dp = getenv("ASB_SPEC_PASS")) ctx->spec_pass = atoi(dp);
-    if (const char* dp = getenv("ASB_SPEC_W_RANK")) ctx->spec_w_rank = atoi(dp);
     if (const char* sk = getenv("ASB_SKETCH")) ctx->sketch = atoi(sk);
     if (const char* sf = getenv("ASB_STALL_FALLBACK")) ctx->stall_fallback = atoi(sf);
     if (const char* dv = getenv("ASB_DIVERSE")) ctx->diverse = atoi(dv);
     if (const char* sk = getenv("ASB_SKETCH_TEST_STALL")) ctx->sk_test_stall = atoi(sk);
     if (const char* dp = getenv("ASB_SUB_FIRST")) ctx->sub_first = atoi(dp) < 1 ? 1 : atoi(dp);
-    if (const char* bt = getenv("ASB_BAND_TARGET")) { ctx->band_target = atoll(bt); ctx->band_cap = ctx->band_target * 4 / 3; }
     ctx->nblk_cap = prop.multiProcessorCount * 8;   // grid cap for streaming passes (guide: G11)
     int rc;
     if ((rc = asb_alloc(ctx, &ctx->pmax, (size_t)ctx->nblk_cap))) return rc;
@@ -597,7 +588,7 @@ extern "C" int asb_snapshots_scale(asb_ctx* ctx, double a) {
     ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     // squared coefficient of variation of the per-vertex energies outside the constant direction
     ctx->ev_cv2 = (h[4] > 0.0 && ctx->n_loc > 1) ? (double)ctx->n_loc * h[5] / (h[4] * h[4]) - 1.0 : 0.0;
-    if (getenv("ASB_DEBUG_PANELS")) fprintf(stderr, "[asb] energies outside the constant direction: squared coefficient of variation %.3f over %lld vertices\n", ctx->ev_cv2, (long long)ctx->n_loc);
+    if (asb_debug_panels()) fprintf(stderr, "[asb] energies outside the constant direction: squared coefficient of variation %.3f over %lld vertices\n", ctx->ev_cv2, (long long)ctx->n_loc);
     ctx->mean_frac = h[0] > 0.0 ? h[2] / h[0] : 0.0;
     ctx->mean_energy = h[2];
     ctx->prep_normx2 = h[0];

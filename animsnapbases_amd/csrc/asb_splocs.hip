@@ -18,8 +18,6 @@ typedef double d4 __attribute__((ext_vector_type(4)));
 
 // defined in asb_project.hip
 int asb_project_columns_wide(asb_ctx* ctx, const double* Wfk, int64_t ldw, int64_t k0, int ncols, double* out_rows, const double* col_scale);
-int asb_project_columns(asb_ctx* ctx, const double* Wfk, int64_t ldw, int64_t k0, int ncols, double* out_rows,
-                        const double* col_scale);
 
 // --------------------------------------------------------------------------------------
 // k_bcd: the block-coordinate-descent sweep over the K weight columns (:144-156), one block.
@@ -397,8 +395,7 @@ extern "C" int asb_splocs_gram(asb_ctx* ctx, double* P_dev, double* M_dev, doubl
     // P = X^T C^T is the one pass over X of an outer iteration: on the 128 x 128-tile MFMA kernel of the POD's Gram matrix (two
     // operands, split over row slabs) where the shapes allow -- the one-wave-per-16 x 16-tile kernel takes ~0.4 ms for config 3's
     // 44 379 x 1000 by 44 379 x 64 (it re-reads X once per 16 columns of C)
-    static const int big = getenv("ASB_SPLOCS_GRAM_BIG") ? atoi(getenv("ASB_SPLOCS_GRAM_BIG")) : 1;
-    if (big && K >= 32 && !(K & 1)) rc = asb_gemm_tn_big(ctx, ctx->X, ctx->Fp, s->Ct, K, n3, (int)ctx->F, (int)K, Pout);
+    if (K >= 32 && !(K & 1)) rc = asb_gemm_tn_big(ctx, ctx->X, ctx->Fp, s->Ct, K, n3, (int)ctx->F, (int)K, Pout);
     else rc = asb_gemm_tn(ctx, ctx->X, ctx->Fp, s->Ct, K, n3, (int)ctx->F, (int)K, Pout);
     if (rc) return rc;
     if ((rc = asb_gemm_tn(ctx, s->Ct, K, s->Ct, K, n3, (int)K, (int)K, Mout))) return rc;
@@ -522,12 +519,10 @@ static int splocs_admm_run(asb_ctx* ctx, double rho, int n_iter) {
     const int64_t K = s->K, n3 = 3 * ctx->n_loc, kn = K * ctx->n_loc;
     // c = W^T X  (K x 3n): the deflation's projection kernel, 16 columns per pass over X
     // (round 4: 64 columns per pass through the panel reads' four-tile kernel; config 3: 4 x 89 us + 8 small launches -> one pass)
-    static const int wide = getenv("ASB_SPLOCS_WIDE") ? atoi(getenv("ASB_SPLOCS_WIDE")) : 1;
-    const int step = wide ? 64 : 16;
+    constexpr int step = 64;
     for (int64_t k0 = 0; k0 < K; k0 += step) {
         const int nc = (int)((K - k0) < step ? (K - k0) : step);
-        int rc = wide ? asb_project_columns_wide(ctx, s->Wfk, K, k0, nc, s->c + (size_t)k0 * n3, nullptr)
-                      : asb_project_columns(ctx, s->Wfk, K, k0, nc, s->c + (size_t)k0 * n3, nullptr);
+        int rc = asb_project_columns_wide(ctx, s->Wfk, K, k0, nc, s->c + (size_t)k0 * n3, nullptr);
         if (rc) return rc;
     }
     if (!s->defer_status) ASB_HIP(ctx, hipMemsetAsync(s->status, 0, 4 * sizeof(int), ctx->stream));
@@ -545,8 +540,7 @@ static int splocs_admm_run(asb_ctx* ctx, double rho, int n_iter) {
     const long long n = (long long)K * n3;
     const int eg = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
     const int pg = (int)((kn + 255) / 256 < 4096 ? (kn + 255) / 256 : 4096);
-    static const int fused = getenv("ASB_ADMM_FUSED") ? atoi(getenv("ASB_ADMM_FUSED")) : 1;
-    if (fused && K <= 64 && n_iter > 0) {
+    if (K <= 64 && n_iter > 0) {
         hipLaunchKernelGGL(k_admm_fused, dim3((unsigned)((ctx->n_loc + 15) / 16)), dim3(256), 0, ctx->stream, s->c, s->Z, s->U, s->Ginv,
                            s->Lambda, rho, (int)K, (long long)ctx->n_loc, n_iter);
         n_iter = 0;

@@ -61,7 +61,7 @@ class Comm(object):
 
             self._torch = torch
             backend = self.dist.get_backend(group)
-            self._staged = bool(backend == "gloo" and torch.cuda.is_available() and os.environ.get("ASB_GLOO_STAGED", "1") != "0")
+            self._staged = bool(backend == "gloo" and torch.cuda.is_available())
             self._dev = torch.device("cuda", torch.cuda.current_device()) if (backend == "nccl" or self._staged) else torch.device("cpu")
             if backend == "nccl":
                 self.stream_handle = int(torch.cuda.current_stream().cuda_stream)

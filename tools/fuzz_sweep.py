@@ -15,7 +15,7 @@ bad = 0
 t0 = time.time()
 for seed in range(first, first + count):
     rng = np.random.default_rng(seed)
-    big = "--big" in sys.argv                 # shards large enough for super-panels (ASB_SUPER_PANELS=1)
+    big = "--big" in sys.argv                 # shards large enough for several sub-panels per read
     N = int(rng.integers(20000, 70000)) if big else int(rng.integers(1, 6000))
     F = int(rng.integers(8, 150)) if big else int(rng.integers(1, 700))
     if "--bigk" in sys.argv:                  # reads with four sub-panels (K >= 64): odd frame counts, ragged shards

@@ -1,4 +1,4 @@
-"""config 3 (bench.py's leg, no CPU baseline): ms of the compute and of the set-up, for A/B runs (ASB_ADMM_FUSED=0 ...)."""
+"""config 3 (bench.py's leg, no CPU baseline): ms of the compute and of the set-up, for A/B runs."""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import torch
