@@ -297,6 +297,16 @@ struct asb_ctx {
     double* is_part = nullptr;        // per-block partials + the reduced row
     long long* is_off = nullptr;      // C offsets per sweep point; M and C offsets per row of C
     int* is_int = nullptr;            // rp per sweep point; npt and coordinate per row of C
+    // on-mesh accuracy maps (asb_onmesh.hip)
+    int *om_tris = nullptr, *om_ptr = nullptr, *om_star = nullptr;    // triangles (M, 3); vertex-star CSR: offsets (n + 1), triangles
+    int64_t om_verts = 0;             // vertices of the uploaded mesh (0: none)
+    double* om_invm = nullptr;        // (n_loc) 1 / massL
+    double* om_vpart = nullptr;       // (frame tiles, n_loc) per-vertex sums of the error pass
+    double* om_fpart = nullptr;       // per block: numerators | denominators of its tile's frames
+    double* om_spart = nullptr;       // per block [-min, max, NaN seen]: error pass | normal pass
+    double* om_out = nullptr;         // accum_norm | accum_angle | per-frame numerators | denominators | statistics
+    double* om_scratch = nullptr;     // (3*n_loc, cw) reconstruction of one chunk of frames
+    double *om_fe = nullptr, *om_ang = nullptr;   // (frames, n_loc) maps, only when asked for
 
     // ---- profiling of the dominant streaming kernel ----
     bool prof = false;

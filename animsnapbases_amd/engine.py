@@ -482,6 +482,47 @@ class HipEngine(object):
                                            ptr(mx), ptr(norms)))
         return sums, mx, norms
 
+    # ------------------------------------------------------------------ on-mesh accuracy maps
+    def onmesh_mesh(self, tris):
+        """Uploads the triangles (M, 3) of the whole mesh with their vertex-star CSR (utils.vertex_star_csr); a repeated
+        upload of the same triangles to this context is skipped."""
+        from .utils import vertex_star_csr
+        tris = np.ascontiguousarray(tris, dtype=np.int64)
+        if tris.ndim != 2 or tris.shape[1] != 3:
+            raise ValueError("triangles of shape %s: (M, 3) expected" % (tris.shape,))
+        cached = getattr(self, "_onmesh_tris", None)
+        if cached is not None and cached[0] == self.n_loc and np.array_equal(cached[1], tris):
+            return
+        self._onmesh_tris = None
+        if tris.size and (tris.min() < 0 or tris.max() >= self.n_loc):
+            raise ValueError("triangles name vertices outside 0..%d" % (self.n_loc - 1))
+        sptr, star = vertex_star_csr(tris, self.n_loc)
+        self._ck(self.lib.asb_onmesh_mesh(self.h, ptr(tris), tris.shape[0], ptr(sptr), ptr(star), self.v0, self.n_loc))
+        self._onmesh_tris = (self.n_loc, tris.copy())
+
+    def onmesh_run(self, which, r, f0, f1, fj, normals, inv_massL, add_mean, psf, denom, per_frame=False):
+        """One r-component reconstruction of the training (which 0) or held-out (1) tensor over range(f0, f1, fj): this
+        shard's dict of accum_norm (n_loc), mesh_num / mesh_den (F_sel), stats (10, see asb.h), with ``normals`` accum_angle
+        (n_loc), with ``per_frame`` the (F_sel, n_loc) maps frame_err and angle."""
+        n_sel = len(range(int(f0), int(f1), int(fj)))
+        n = self.n_loc
+        out = dict(accum_norm=np.empty(n), mesh_num=np.empty(n_sel), mesh_den=np.empty(n_sel), stats=np.empty(10))
+        if normals:
+            out["accum_angle"] = np.empty(n)
+        if per_frame:
+            out["frame_err"] = np.empty((n_sel, n))
+            if normals:
+                out["angle"] = np.empty((n_sel, n))
+        if inv_massL is not None:
+            inv_massL = np.ascontiguousarray(inv_massL, dtype=np.float64)
+            assert inv_massL.shape == (self.N_glob,)
+        self._ck(self.lib.asb_onmesh_run(self.h, int(which), int(r), int(f0), int(f1), int(fj), int(bool(normals)),
+                                         ptr(inv_massL), int(bool(add_mean)), float(psf), float(denom),
+                                         ptr(out["accum_norm"]), ptr(out["mesh_num"]), ptr(out["mesh_den"]),
+                                         ptr(out.get("accum_angle")), ptr(out["stats"]), ptr(out.get("frame_err")),
+                                         ptr(out.get("angle"))))
+        return out
+
     # ------------------------------------------------------------------ SPLOCS
     def splocs_begin(self):
         self._ck(self.lib.asb_splocs_begin(self.h))

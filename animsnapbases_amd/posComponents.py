@@ -57,6 +57,7 @@ class posComponents:  # Components == bases
 
         self._comps = None            # host copy (cache of the device-resident basis, or user-assigned)
         self._comps_on_device = False  # True: the authoritative (K, n_loc, 3) basis is in HBM
+        self._comps_post_processed = False     # True once post_process_components has un-scaled the basis
         self.weigs = None
         self.ortho_comps = None
         self.smooth_min_dist = param.vertPos_smooth_min_dist
@@ -91,6 +92,7 @@ class posComponents:  # Components == bases
     def comps(self, value):
         self._comps = value
         self._comps_on_device = False
+        self._comps_post_processed = False
 
     # ------------------------------------------------------------------ statics (same as the reference)
     @staticmethod
@@ -306,6 +308,7 @@ class posComponents:  # Components == bases
     def compute_components_store_singvalues(self):
         """posComponents.py:258-272."""
         headerSing = ['component', 'singVal', 'norm_R']
+        self._comps_post_processed = False
         file_name = os.path.join(self.param.vertPos_output_directory,
                                  self.param.name + "_posBases_pcaExtraction_singValues_errorNorm")
         if self.storeSingVal:
@@ -330,6 +333,7 @@ class posComponents:  # Components == bases
         eng, comm = snaps._engine, snaps._comm
         v0, n_loc = snaps._shards[comm.rank]
         self._comps_streamed = False    # (the device basis is about to change: a later read copies it afresh)
+        self._comps_post_processed = True       # (on_mesh_accuracy needs the basis in the tensor's space)
         if not self._comps_on_device:
             if self._comps is None:
                 raise ValueError("no components: run compute_components_store_singvalues first")
@@ -497,6 +501,92 @@ class posComponents:  # Components == bases
             rel = np.sqrt(sums) / np.sqrt(n2)[None, :]
             max_err = mx / tmax
         return fro_err.tolist(), max_err.tolist(), rel[:, 0].tolist(), rel[:, 1].tolist(), rel[:, 2].tolist()
+
+    def on_mesh_accuracy(self, r, frame_start=0, frame_end=None, frame_jump=1, animation="train", normals=True,
+                         per_frame=False):
+        """Extra (not in the reference's class): the on-mesh accuracy measures of ``compute_accuracy``
+        (generate_figures/onMesh_accuracyMeasures.py:61-151) for the r-component reconstruction that
+        ``reconstruction_errors`` uses for the same ``animation``, over the frames range(frame_start, frame_end, frame_jump),
+        computed on the device in world space (mass weighting, mean row and scale undone).  With
+        denom = sqrt(3 (frame_end - frame_start) N) (:70) the dict holds
+
+        ``accum_norm`` (N,)      sum over the frames of frame_err[f, v] = |x - x_r|^2 / |x|^2 / denom (:116, :120)
+        ``mesh_err`` (F_sel,)    |x - x_r|_F / |x|_F / denom of each frame (:117)
+        ``accum_angle`` (N,)     with ``normals``: sum over the frames of the angle in degrees between the area-weighted
+                                 per-vertex normals of the full and the reduced mesh (:73-90, :122-125)
+        ``frame_err``, ``angle`` (F_sel, N), only with ``per_frame``
+        ``stats`` (14,)          one CSV row without its first column, see ``store_on_mesh_measures``.
+
+        A vertex in no triangle or with a zero normal has angle NaN, one with |x| = 0 an inf or NaN error, and the statistics
+        carry them as NumPy's would.  Every rank returns the same dict; ``normals`` needs the triangles
+        (``pos_snapshots.tris``) and one rank."""
+        snaps = self.pos_snapshots
+        eng, comm = snaps._engine, snaps._comm
+        if isinstance(animation, str) and animation not in ("train", "test"):
+            raise ValueError("animation must be 'train', 'test' or an (F', N, 3) array, not %r" % animation)
+        if getattr(self, "_comps_post_processed", False):
+            raise ValueError("the basis was un-scaled by post_process_components: the maps need it in the tensor's space "
+                             "(call on_mesh_accuracy before post-processing, or recompute the components)")
+        if normals and snaps.tris is None:
+            raise ValueError("normals=True needs the mesh triangles (pos_snapshots.tris)")
+        if normals and comm.multi:
+            raise NotImplementedError("normals=True on several ranks: triangles straddle the vertex shards and no halo of "
+                                      "reconstructed positions is built")
+        K = self._device_basis()
+        train = isinstance(animation, str) and animation == "train"
+        if not 0 <= r <= K:
+            raise ValueError("r = %d is outside 0..%d" % (r, K))
+        if train:
+            if self.weigs is None or r > self.weigs.shape[1]:
+                raise ValueError("no greedy weights for r = %d: run compute_components_store_singvalues first" % r)
+            F = snaps.frs
+        else:
+            Y = snaps.test_verts if isinstance(animation, str) else animation
+            self._heldout_prepare(Y)
+            F = np.asarray(Y).shape[0]
+        frame_end = F if frame_end is None else frame_end
+        if frame_jump < 1 or frame_start < 0 or frame_end > F or frame_start >= frame_end:
+            raise ValueError("range(%d, %d, %d) is not a selection of the %d frames" % (frame_start, frame_end, frame_jump, F))
+        N = snaps.nVerts
+        n_sel = len(range(frame_start, frame_end, frame_jump))
+        denom = float(np.sqrt(3 * (frame_end - frame_start) * N))
+        if normals:
+            eng.onmesh_mesh(snaps.tris)
+        loc = eng.onmesh_run(0 if train else 1, r, frame_start, frame_end, frame_jump, normals, snaps.invMassL,
+                             snaps._standarize, snaps.pre_scale_factor, denom, per_frame)
+        out = {"accum_norm": comm.all_gather_rows(loc["accum_norm"], N, axis=0)}
+        nd = comm.allreduce_sum(np.concatenate([loc["mesh_num"], loc["mesh_den"]]))
+        with errstate(divide='ignore', invalid='ignore'):
+            out["mesh_err"] = np.sqrt(nd[:n_sel]) / np.sqrt(nd[n_sel:]) / denom
+        st = loc["stats"]
+        sums = comm.allreduce_sum([st[1]])            # (angles: one rank)
+        hi = comm.allreduce_max([-st[0], st[2], -st[3], st[4]])
+        cnt = float(n_sel) * N
+        stats = [-hi[2], sums[0] / cnt, hi[3], sums[0]]
+        stats += [st[8], st[6] / cnt, st[9], st[6]] if normals else [np.nan] * 4
+        stats += [-hi[0], sums[0] / N, hi[1]]
+        stats += [st[5], st[6] / N, st[7]] if normals else [np.nan] * 3
+        out["stats"] = np.array(stats, dtype=np.float64)
+        if normals:
+            out["accum_angle"] = loc["accum_angle"]
+        if per_frame:
+            out["frame_err"] = comm.all_gather_rows(loc["frame_err"], N, axis=1)
+            if normals:
+                out["angle"] = loc["angle"]
+        return out
+
+    def store_on_mesh_measures(self, r_values, output_dir, case="_test_on_training_set", **range_args):
+        """Extra: writes ``_on_mesh_measures<case>.csv`` with the header of onMesh_accuracyMeasures.py:95-98 and one row per r,
+        composed as its commented-out writer does (:132-137): r; min / mean / max / sum of frame_err; the same of angle;
+        min / mean / max of accum_norm; min / mean / max of accum_angle.  ``range_args`` go to ``on_mesh_accuracy``.  The
+        statistics come from the device pass: the (F_sel, N) maps are not downloaded.  Returns the rows."""
+        rows = [[int(r)] + self.on_mesh_accuracy(r, **range_args)["stats"].tolist() for r in r_values]
+        if self.pos_snapshots._comm.rank == 0:
+            with open(os.path.join(output_dir, "_on_mesh_measures" + case) + '.csv', 'w', encoding='UTF8') as acc_file:
+                writer = csv.writer(acc_file)
+                writer.writerow(_u.ON_MESH_HEADER)
+                writer.writerows(rows)
+        return rows
 
     def project_animation(self, verts=None):
         """Extra (not in the reference): the (F', K) least-squares weights of an (F', N, 3) animation (None: the test

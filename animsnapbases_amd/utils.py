@@ -279,6 +279,28 @@ def mesh_edges(simplices):
     return e[np.lexsort((e[:, 0], e[:, 1]))]
 
 
+def vertex_star_csr(tris, n_verts):
+    """The vertex stars of a triangle list as CSR: ``ptr`` (n_verts + 1) and ``star`` (3 M) int64, ``star[ptr[v]:ptr[v + 1]]``
+    the triangles that have v as a corner in increasing triangle number, one entry per corner (a triangle that names v twice
+    is listed twice: it is added twice to v's normal, as the per-corner sum of ``igl.per_vertex_normals`` does).  A vertex in
+    no triangle has an empty range."""
+    T = np.asarray(tris, dtype=np.int64).reshape(-1, 3)
+    n_verts = int(n_verts)
+    if T.size and (T.min() < 0 or T.max() >= n_verts):
+        raise ValueError("triangles name vertices outside 0..%d" % (n_verts - 1))
+    corners = T.ravel()
+    order = np.argsort(corners, kind="stable")          # stable: corners are stored triangle by triangle
+    ptr = np.zeros(n_verts + 1, dtype=np.int64)
+    np.cumsum(np.bincount(corners, minlength=n_verts), out=ptr[1:])
+    return ptr, np.ascontiguousarray(order // 3, dtype=np.int64)
+
+
+ON_MESH_HEADER = ['numComponent', 'norm_error_min', 'norm_error_mean', 'norm_error_max', 'norm_error_sum',
+                  'angle_error_min', 'angle_error_mean', 'angle_error_max', 'angle_error_sum',
+                  "accum_norm_min", "accum_norm_meann", "accum_norm_max",
+                  "accum_angle_min", "accum_angle_mean", "accum_angle_max"]     # onMesh_accuracyMeasures.py:95-98, spelling included
+
+
 def read_triangle_mesh(path):
     """(vertices, triangles) of an ``.obj`` or ``.off`` file (what the reference reads with ``igl.read_triangle_mesh``)."""
     ext = os.path.splitext(path)[1].lower()

@@ -580,6 +580,32 @@ int asb_rows_gather(asb_ctx* ctx, int which, const int64_t* gidx, int64_t n, dou
 int asb_interp_sweep(asb_ctx* ctx, int which, const int64_t* rp, const int64_t* npt, int64_t S, const double* M, const double* B,
                      int64_t nb, double* sums_out, double* max_out, double* norms_out);
 
+/* ------------------------------------------------- on-mesh accuracy maps ---- */
+/* compute_accuracy (generate_figures/onMesh_accuracyMeasures.py:61-151) on the resident tensor, in world space:
+ * x = (T / psf + mean) / massL_v of the tensor, x_r the same of R_r = A[:, :r] B[:r] (A, B as in asb_recon_sweep).
+ * asb_onmesh_mesh: the triangles (host, n_tris x 3) and the vertex-star CSR -- star_ptr (n_loc + 1) offsets, star_tri
+ * (3 n_tris) the incident triangles of each vertex in increasing triangle number, one entry per corner -- of the WHOLE mesh:
+ * v0 = 0 and n_loc = N_glob (normals across vertex shards are not built).  Every index is checked; kept until the next call. */
+int asb_onmesh_mesh(asb_ctx* ctx, const int64_t* tris, int64_t n_tris, const int64_t* star_ptr, const int64_t* star_tri,
+                    int64_t v0, int64_t n_loc);
+/* One reconstruction of r components over the frames range(f0, f1, fj) (n_sel of them), `which` as in asb_recon_sweep.
+ * inv_massL (host, N_glob, or NULL): 1 / massL; add_mean != 0: the mean row is added back; psf: the scale the tensor was
+ * multiplied by (1 when not standardised); denom: sqrt(3 (f1 - f0) N_glob) (:70).  This shard's values:
+ *   accum_norm_out (n_loc)   sum_f frame_err[f, v], frame_err = |x - x_r|^2 / |x|^2 / denom (:116, :120)
+ *   mesh_num_out, mesh_den_out (n_sel)   sum_v |x - x_r|^2 and sum_v |x|^2 of each frame (:117 = sqrt(num / den) / denom)
+ *   accum_angle_out (n_loc)  sum_f angle[f, v] in degrees between the area-weighted per-vertex normals (sum of the incident
+ *                            triangles' (b - a) x (c - a), cosine clipped to [-1, 1]) of x and x_r (:73-90, :122-125);
+ *                            only with want_normals != 0, which needs asb_onmesh_mesh
+ *   stats_out (10)           accum_norm min, sum, max; frame_err min, max; accum_angle min, sum, max; angle min, max
+ *                            (NaN-propagating like numpy; the sum of a map is the sum of its accumulated vector)
+ *   frame_err_out, angle_out (n_sel x n_loc, may be NULL)   the maps themselves.
+ * One read of the tensor for the error pass; the normal pass runs in chunks of frames through a bounded scratch.
+ * Deterministic (fixed-order reductions, no atomics).  Any output pointer may be NULL. */
+int asb_onmesh_run(asb_ctx* ctx, int which, int64_t r, int64_t f0, int64_t f1, int64_t fj, int want_normals,
+                   const double* inv_massL, int add_mean, double psf, double denom, double* accum_norm_out,
+                   double* mesh_num_out, double* mesh_den_out, double* accum_angle_out, double* stats_out,
+                   double* frame_err_out, double* angle_out);
+
 /* ------------------------------------------------ SPLOCS refinement ----------- */
 /* posComponents.splocs_glob_optimization, snapbases/posComponents.py:132-189.
  * State after a residual-mode deflation: C = comps, W = weigs, U = 0 (:135-139).  One outer
