@@ -196,7 +196,6 @@ struct asb_ctx {
                                            // the projection kernel needs more than 256 registers and loses what the saved read gains)
     int sub_first = 4;                     // sub-panels of the first read (ASB_SUB_FIRST); then adapted: sub_cur
     int sub_cur = 0;
-    int sub_ntile = 0;                     // tiles of the read in progress (multi-rank steps: asb_panel_sub_*)
     int chain_timed_out = 0;               // the last one-launch run of a read's sub-panels met a poll that did not complete
     // the read in progress of the multi-rank driver (asb_panel_read_*): its tiles, whether its pass is already enqueued
     long long rd_k0 = 0;

@@ -2783,7 +2783,7 @@ __global__ __launch_bounds__(256, (NJ > 16 ? 1 : 2)) void k_panel_multi(const do
     // sub-panels that were not reached: "ran, committed nothing" (proven = -1 would read as a launch that did not finish)
     if (blockIdx.x == 0 && tid == 0)
         for (int q = sp; q < ma.nsub; ++q) { sub[q].proven = 0; sub[q].done = 1; }
-    // launches that continue on the same candidates (one sub-panel per launch: the multi-rank driver, ASB_SUB_CHAIN=0):
+    // launches that continue on the same candidates (one sub-panel per launch: double_panel with ASB_SUB_CHAIN=0):
     // the deflated rows become the next start rows -- behind the last step, past every abort exit
     if (rows_out != nullptr && have) {
         double* row = rows_out + s * 3 * (long long)Fp;
@@ -3533,6 +3533,65 @@ static int tiles_enqueue(asb_ctx* ctx, int ntile, const long long* kb, const int
     *cgrid_out = cgrid;
     return ASB_OK;
 }
+// ---- the host steps of a read of X with several sub-panels, shared by double_panel (one rank, inside the library) and
+// asb_panel_read_run / _commit (several ranks, driven by _panels.py)
+// the operands and states of up to ASB_MAX_SUB tiles
+static int read_buffers(asb_ctx* ctx) {
+    int rc;
+    if ((rc = asb_alloc(ctx, &ctx->Wt3, (size_t)ASB_MAX_SUB * ctx->Fp * 16))) return rc;
+    if ((rc = asb_alloc(ctx, &ctx->Wq3, (size_t)ASB_MAX_SUB * ctx->Fp * 16))) return rc;
+    if ((rc = asb_alloc(ctx, &ctx->wn2t3, (size_t)16 * ASB_MAX_SUB))) return rc;
+    if ((rc = asb_alloc(ctx, &ctx->tile_counter, (size_t)16))) return rc;
+    if ((rc = asb_alloc(ctx, &ctx->pstate2, (size_t)ASB_MAX_SUB))) return rc;
+    return asb_alloc(ctx, &ctx->e_class, (size_t)ctx->n_loc);
+}
+// who is a candidate is decided by the energies NOW (behind the selection); the later tiles' checks run after the earlier
+// tiles' updates, and a shard that ran ahead of the ranks' verdict goes back to these
+static int read_snapshot(asb_ctx* ctx) {
+    ASB_HIP(ctx, hipMemcpyAsync(ctx->e_class, ctx->energy, (size_t)ctx->n_loc * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    return ASB_OK;
+}
+// the pass over X for tiles [k0 + 16 ct, + nc[ct]) -- unless it is already running: enqueued behind the panel kernel on the
+// expected counts spec_nc[0 .. spec_ntile), which cover the reached ones -- and, checks: the checks of all tiles behind it
+static int read_enqueue(asb_ctx* ctx, long long k0, int ntile, const int* nc, int spec_ntile, const int* spec_nc, bool checks, int* rgrid,
+                        int* cgrid) {
+    int rc;
+    long long kb[ASB_MAX_SUB];
+    PanelState* st[ASB_MAX_SUB];
+    WideArgs wa{};
+    for (int ct = 0; ct < ASB_MAX_SUB; ++ct) {
+        kb[ct] = wa.kb[ct] = k0 + (long long)ct * ASB_PANEL_COLS;
+        st[ct] = ctx->pstate2 + ct;
+        wa.nc[ct] = ct < ntile ? nc[ct] : 0;
+    }
+    bool covered = spec_ntile >= ntile;
+    for (int ct = 0; covered && ct < ntile; ++ct) covered = spec_nc[ct] >= nc[ct];
+    if (!covered) {
+        if ((rc = dbl_build_tiles(ctx, ntile, wa))) return rc;
+        if ((rc = launch_wide(ctx, ntile, wa))) return rc;
+    }
+    return checks ? tiles_enqueue(ctx, ntile, kb, nc, st, rgrid, cgrid) : ASB_OK;
+}
+// energies / column sums of the first `cols` columns of tile ct, whose energies the checks left untouched
+static void commit_head(asb_ctx* ctx, int ct, long long kb, int cols, int cgrid) {
+    hipLaunchKernelGGL(k_commit_energy, dim3(cgrid), dim3(256), 0, ctx->stream, ctx->comps, (long long)(3 * ctx->n_loc),
+                       (long long)ctx->n_loc, (int)kb, ctx->pstate2 + ct, ctx->wn2t3 + 16 * ct, ctx->energy, ctx->pmax, ctx->pidx,
+                       ctx->psum, ctx->colpart, cols);
+    ctx->nblk = cgrid;
+    hipLaunchKernelGGL(k_colsum, dim3(1), dim3(1024), 0, ctx->stream, ctx->colpart, ctx->nblk, cols, kb, ctx->scal, (PanelState*)nullptr);
+}
+// statistics and the next read's step budget once `kept` of the nc columns of tile ct (the first `proven` certain) stand
+static void tile_account(asb_ctx* ctx, long long k, int ct, int nc, int proven, int64_t kept) {
+    ctx->n_spec_steps += nc - proven;
+    ctx->n_spec_kept += kept > proven ? kept - proven : 0;
+    if (asb_debug_panels())
+        fprintf(stderr, "[asb] panel at k=%lld tile %d: %d proven + %lld of %d unproven steps kept\n", k, ct, proven,
+                (long long)(kept > proven ? kept - proven : 0), nc - proven);
+    if (ct >= 1) {                                    // adapt the later sub-panels' lengths to what stands
+        const int want = (int)kept + 2;
+        ctx->sub_budget[ct] = want < 4 ? 4 : (want > ASB_PANEL_COLS ? ASB_PANEL_COLS : want);
+    }
+}
 static int panel_candidates(asb_ctx* ctx, long long k, int stalled);
 static int double_panel(asb_ctx* ctx, long long k, long long k1, int64_t* done_out) {
     int rc;
@@ -3540,16 +3599,10 @@ static int double_panel(asb_ctx* ctx, long long k, long long k1, int64_t* done_o
     const int nsub_lim = ctx->sub_panels < 1 ? 1 : (ctx->sub_panels > ASB_MAX_SUB ? ASB_MAX_SUB : ctx->sub_panels);
     if (ctx->sub_cur < 1) ctx->sub_cur = nsub_lim < ctx->sub_first ? nsub_lim : ctx->sub_first;
     const int nsub_max = ctx->sub_cur < nsub_lim ? ctx->sub_cur : nsub_lim;
-    if ((rc = asb_alloc(ctx, &ctx->Wt3, (size_t)ASB_MAX_SUB * ctx->Fp * 16))) return rc;
-    if ((rc = asb_alloc(ctx, &ctx->Wq3, (size_t)ASB_MAX_SUB * ctx->Fp * 16))) return rc;
-    if ((rc = asb_alloc(ctx, &ctx->wn2t3, (size_t)16 * ASB_MAX_SUB))) return rc;
-    if ((rc = asb_alloc(ctx, &ctx->tile_counter, (size_t)16))) return rc;
-    if ((rc = asb_alloc(ctx, &ctx->pstate2, (size_t)ASB_MAX_SUB))) return rc;
-    if ((rc = asb_alloc(ctx, &ctx->e_class, (size_t)ctx->n_loc))) return rc;
+    if ((rc = read_buffers(ctx))) return rc;
     const auto t_read0 = std::chrono::steady_clock::now();
     if ((rc = panel_candidates(ctx, k, 0))) return rc;
-    // who is a candidate is decided by the energies NOW; the later tiles' checks run after the earlier tiles' updates
-    ASB_HIP(ctx, hipMemcpyAsync(ctx->e_class, ctx->energy, (size_t)ctx->n_loc * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    if ((rc = read_snapshot(ctx))) return rc;
     long long kb[ASB_MAX_SUB];
     int nc[ASB_MAX_SUB] = {0}, proven[ASB_MAX_SUB] = {0};
     for (int sp = 0; sp < ASB_MAX_SUB; ++sp) kb[sp] = k + (long long)sp * ASB_PANEL_COLS;
@@ -3588,71 +3641,35 @@ static int double_panel(asb_ctx* ctx, long long k, long long k1, int64_t* done_o
         // as they were) and may go on unproven
         if (ran < ASB_PANEL_COLS || !ctx->run_coop_used || !ctx->spec_panels) break;
     }
-    PanelState* st[ASB_MAX_SUB];
-    for (int ct = 0; ct < ntile; ++ct) st[ct] = ctx->pstate2 + ct;      // (k_panel_multi writes them there; the one-by-one loop copies)
-    // one read of X for all tiles
-    WideArgs wa{};
-    for (int ct = 0; ct < ntile; ++ct) {
-        wa.kb[ct] = kb[ct];
-        wa.nc[ct] = nc[ct];
-    }
-    // (the pass may already be running: enqueued behind the panel kernel on the expected counts, which cover the reached ones)
-    bool covered = chained_runs && spec_ntile >= ntile;
-    for (int ct = 0; covered && ct < ntile; ++ct) covered = spec_nc[ct] >= nc[ct];
-    if (!covered) {
-        if ((rc = dbl_build_tiles(ctx, ntile, wa))) return rc;
-        if ((rc = launch_wide(ctx, ntile, wa))) return rc;
-    }
+    // one read of X for all tiles (their states are in pstate2: k_panel_multi writes them there, the one-by-one loop copies);
+    // chained: the checks of all tiles enqueued back to back behind it, ONE host read
     int64_t total = 0;
-    int full = 0;
+    int full = 0, rgrid = 0, cgrid = 0;
     bool rejected = false;
     const bool chained = ctx->pre_orth && ctx->correct_rows && ctx->tile_chain;
+    if ((rc = read_enqueue(ctx, k, ntile, nc, chained_runs ? spec_ntile : 0, spec_nc, chained, &rgrid, &cgrid))) return rc;
     if (chained) {
-        // all tiles enqueued back to back, ONE host read
-        int rgrid = 0, cgrid = 0;
-        if ((rc = tiles_enqueue(ctx, ntile, kb, nc, st, &rgrid, &cgrid))) return rc;
         long long res[ASB_MAX_SUB + 1];
         if ((rc = fetch_words(ctx, ctx->tile_res, ASB_MAX_SUB + 1, res))) return rc;
         ctx->nblk = rgrid;                           // the records of the last tile that stood in full
         for (int ct = 0; ct < ntile; ++ct) {
             int64_t kept = res[ct] < 0 ? 0 : res[ct];
             if (res[ct] >= 0 && kept < nc[ct]) {     // this tile did not stand in full: its energies are untouched, commit the head
-                hipLaunchKernelGGL(k_commit_energy, dim3(cgrid), dim3(256), 0, ctx->stream, ctx->comps, (long long)(3 * ctx->n_loc),
-                                   (long long)ctx->n_loc, (int)kb[ct], st[ct], ctx->wn2t3 + 16 * ct, ctx->energy, ctx->pmax, ctx->pidx,
-                                   ctx->psum, ctx->colpart, (int)kept);
-                ctx->nblk = cgrid;
-                hipLaunchKernelGGL(k_colsum, dim3(1), dim3(1024), 0, ctx->stream, ctx->colpart, ctx->nblk, (int)kept, kb[ct], ctx->scal,
-                                   (PanelState*)nullptr);
+                commit_head(ctx, ct, kb[ct], (int)kept, cgrid);
                 ASB_CHECK_LAUNCH(ctx);
             }
             if (res[ct] < 0) break;                  // behind a tile that did not stand
-            ctx->n_spec_steps += nc[ct] - proven[ct];
-            ctx->n_spec_kept += kept > proven[ct] ? kept - proven[ct] : 0;
+            tile_account(ctx, k, ct, nc[ct], proven[ct], kept);
             total += kept;
-            if (asb_debug_panels())
-                fprintf(stderr, "[asb] panel at k=%lld tile %d: %d proven + %lld of %d unproven steps kept\n", k, ct, proven[ct],
-                        (long long)(kept > proven[ct] ? kept - proven[ct] : 0), nc[ct] - proven[ct]);
-            if (ct >= 1) {
-                const int want = (int)kept + 2;
-                ctx->sub_budget[ct] = want < 4 ? 4 : (want > ASB_PANEL_COLS ? ASB_PANEL_COLS : want);
-            }
             if (kept < nc[ct]) { rejected = true; break; }
             ++full;
         }
     }
     for (int ct = 0; ct < ntile && !chained; ++ct) {
         int64_t kept = 0;
-        if ((rc = spec_tile_finish(ctx, ct, kb[ct], nc[ct], st[ct], &kept))) return rc;
-        ctx->n_spec_steps += nc[ct] - proven[ct];
-        ctx->n_spec_kept += kept > proven[ct] ? kept - proven[ct] : 0;
+        if ((rc = spec_tile_finish(ctx, ct, kb[ct], nc[ct], ctx->pstate2 + ct, &kept))) return rc;
+        tile_account(ctx, k, ct, nc[ct], proven[ct], kept);
         total += kept;
-        if (asb_debug_panels())
-            fprintf(stderr, "[asb] panel at k=%lld tile %d: %d proven + %lld of %d unproven steps kept\n", k, ct, proven[ct],
-                    (long long)(kept > proven[ct] ? kept - proven[ct] : 0), nc[ct] - proven[ct]);
-        if (ct >= 1) {                                // adapt the later sub-panels' lengths to what stands
-            const int want = (int)kept + 2;
-            ctx->sub_budget[ct] = want < 4 ? 4 : (want > ASB_PANEL_COLS ? ASB_PANEL_COLS : want);
-        }
         if (kept < nc[ct]) { rejected = true; break; }      // what follows was built on a rejected step
         ++full;
     }
@@ -3797,92 +3814,6 @@ static int double_panel(asb_ctx* ctx, long long k, long long k1, int64_t* done_o
     return ASB_OK;
 }
 
-// ---- the same read of X with several sub-panels, in steps, for the multi-rank driver (_panels.py): every rank runs the
-// sub-panels on the identical assembled candidates, projects its shard once, and the tiles are checked one at a time with
-// a min over the ranks in between (the driver's all-reduce of the device word)
-// (every sub-panel's state is copied to pstate2[sp] right behind its run: what a later launch -- which re-arms pstate --
-// does or does not commit cannot change which record a tile is checked against)
-static PanelState* sub_state(asb_ctx* ctx, int ct) { return ctx->pstate2 + ct; }
-extern "C" int asb_panel_sub_run(asb_ctx* ctx, int sp, int64_t k0, int steps, int spec_max, int64_t* ran, int64_t* proven, int* may_continue) {
-    if (!ctx || !ctx->candR || ctx->mode != ASB_DEFLATE_PROJECT || !ran || !proven || !may_continue) return ASB_ERR_ARG;
-    if (sp < 0 || sp >= ASB_MAX_SUB || spec_max < 0) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_panel_sub_run: bad sub-panel");
-    int rc;
-    if (sp == 0) {
-        if ((rc = asb_alloc(ctx, &ctx->Wt3, (size_t)ASB_MAX_SUB * ctx->Fp * 16))) return rc;
-        if ((rc = asb_alloc(ctx, &ctx->Wq3, (size_t)ASB_MAX_SUB * ctx->Fp * 16))) return rc;
-        if ((rc = asb_alloc(ctx, &ctx->wn2t3, (size_t)16 * ASB_MAX_SUB))) return rc;
-        if ((rc = asb_alloc(ctx, &ctx->tile_counter, (size_t)16))) return rc;
-        if ((rc = asb_alloc(ctx, &ctx->pstate2, (size_t)ASB_MAX_SUB))) return rc;
-        if ((rc = asb_alloc(ctx, &ctx->e_class, (size_t)ctx->n_loc))) return rc;
-        ASB_HIP(ctx, hipMemcpyAsync(ctx->e_class, ctx->energy, (size_t)ctx->n_loc * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    ctx->run_writeback = 1;
-    ctx->run_spec_max = ctx->spec_panels ? spec_max : 0;
-    rc = asb_panel_run(ctx, k0, steps, 0, 1, ran);
-    ctx->run_writeback = 0;
-    ctx->run_spec_max = 0;
-    if (rc) return rc;
-    ASB_HIP(ctx, hipMemcpyAsync(ctx->pstate2 + sp, ctx->pstate, sizeof(PanelState), hipMemcpyDeviceToDevice, ctx->stream));
-    if (sp > 0) ctx->n_panels--;                          // statistics count reads of X
-    *proven = ctx->run_proven;
-    *may_continue = (*ran == ASB_PANEL_COLS && ctx->run_coop_used && ctx->spec_panels) ? 1 : 0;
-    return ASB_OK;
-}
-extern "C" int asb_panel_sub_project(asb_ctx* ctx, int64_t k0, int ntile, const int* nc) {
-    if (!ctx || !ctx->energy || ctx->mode != ASB_DEFLATE_PROJECT || !nc || ntile < 1 || ntile > ASB_MAX_SUB) return ASB_ERR_ARG;
-    WideArgs wa{};
-    for (int ct = 0; ct < ntile; ++ct) {
-        if (nc[ct] < 1 || nc[ct] > ASB_PANEL_COLS || k0 + 16 * ct + nc[ct] > ctx->K) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_panel_sub_project: bad range");
-        wa.kb[ct] = k0 + 16 * ct;
-        wa.nc[ct] = nc[ct];
-    }
-    int rc;
-    if ((rc = dbl_build_tiles(ctx, ntile, wa))) return rc;
-    ctx->sub_ntile = ntile;
-    return launch_wide(ctx, ntile, wa);
-}
-extern "C" int asb_panel_sub_check(asb_ctx* ctx, int ct, int64_t kb, int nc, double* first_rejected_dev) {
-    if (!ctx || !ctx->energy || ctx->mode != ASB_DEFLATE_PROJECT || !first_rejected_dev || ct < 0 || ct >= ctx->sub_ntile) return ASB_ERR_ARG;
-    PanelState* st = sub_state(ctx, ct);
-    const double* Wt = ctx->Wt3 + (size_t)ct * ctx->Fp * 16;
-    const int pre = (ctx->pre_orth && ctx->correct_rows) ? 1 : 0;
-    if (!pre)
-        hipLaunchKernelGGL(k_panel_gram, dim3((unsigned)(kb + nc)), dim3(256), 0, ctx->stream, ctx->W, Wt, (int)ctx->Fp, ctx->gram,
-                           ctx->gram_s, ctx->wn2t3 + 16 * ct);
-    if (ctx->correct_rows) {
-        long long cwr = (ctx->n_loc + 63) / 64;
-        hipLaunchKernelGGL(k_correct_rows<true>, dim3((unsigned)(cwr < ctx->nblk_cap ? cwr : ctx->nblk_cap)), dim3(192), 0, ctx->stream,
-                           ctx->comps, (long long)(3 * ctx->n_loc), (long long)ctx->n_loc, (int)kb, nc, ctx->gram_s, ctx->wn2t3 + 16 * ct,
-                           ctx->energy, ctx->pmax, ctx->pidx, ctx->psum, ctx->colpart, st, ctx->scalar_dev, ctx->sel_e2, ctx->e_class, pre);
-    } else {
-        long long cw = (ctx->n_loc + 255) / 256;
-        hipLaunchKernelGGL(k_correct<true>, dim3((unsigned)(cw < ctx->nblk_cap ? cw : ctx->nblk_cap)), dim3(256), 0, ctx->stream, ctx->comps,
-                           (long long)(3 * ctx->n_loc), (long long)ctx->n_loc, (int)kb, nc, ctx->gram, ctx->wn2t3 + 16 * ct, ctx->energy,
-                           ctx->pmax, ctx->pidx, ctx->psum, ctx->colpart, (const long long*)nullptr, (const PanelState*)nullptr,
-                           (long long)0, st, ctx->scalar_dev, ctx->sel_e2, ctx->e_class);
-    }
-    hipLaunchKernelGGL(k_spec_count, dim3(1), dim3(1), 0, ctx->stream, st, nc, first_rejected_dev);
-    ASB_CHECK_LAUNCH(ctx);
-    return ASB_OK;
-}
-extern "C" int asb_panel_sub_commit(asb_ctx* ctx, int ct, int64_t kb, int nc, int kept) {
-    if (!ctx || !ctx->energy || ctx->mode != ASB_DEFLATE_PROJECT || ct < 0 || ct >= ctx->sub_ntile || kept < 0 || kept > nc) return ASB_ERR_ARG;
-    PanelState* st = sub_state(ctx, ct);
-    long long cw = (ctx->n_loc + 255) / 256;
-    const int cgrid = (int)(cw < ctx->nblk_cap ? cw : ctx->nblk_cap);
-    hipLaunchKernelGGL(k_commit_energy, dim3(cgrid), dim3(256), 0, ctx->stream, ctx->comps, (long long)(3 * ctx->n_loc),
-                       (long long)ctx->n_loc, (int)kb, st, ctx->wn2t3 + 16 * ct, ctx->energy, ctx->pmax, ctx->pidx, ctx->psum,
-                       ctx->colpart, kept);
-    ctx->nblk = cgrid;
-    hipLaunchKernelGGL(k_colsum, dim3(1), dim3(1024), 0, ctx->stream, ctx->colpart, ctx->nblk, kept, (long long)kb, ctx->scal,
-                       (PanelState*)nullptr);
-    ASB_CHECK_LAUNCH(ctx);
-    if (kept > 0) ctx->k_done = kb + kept;
-    ctx->n_spec_steps += nc;
-    ctx->n_spec_kept += kept;
-    return ASB_OK;
-}
-
 // ---- round 4: the multi-rank read in THREE calls and ONE exchange, level with the single-rank chain.
 //   asb_panel_read_run     all sub-panels of the read in ONE launch of k_panel_multi on the ASSEMBLED candidates (identical on
 //                          every rank, so the nine-word summary is too), the read's pass over this shard enqueued behind it on
@@ -3912,14 +3843,9 @@ extern "C" int asb_panel_read_run(asb_ctx* ctx, int64_t k0, int64_t k1, int nsub
     if (!(coop_fits(ctx) && ctx->spec_panels && ctx->pre_orth && ctx->correct_rows))
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_panel_read_run needs the co-resident panel kernel (and F <= 2048)");
     int rc;
-    if ((rc = asb_alloc(ctx, &ctx->Wt3, (size_t)ASB_MAX_SUB * ctx->Fp * 16))) return rc;
-    if ((rc = asb_alloc(ctx, &ctx->Wq3, (size_t)ASB_MAX_SUB * ctx->Fp * 16))) return rc;
-    if ((rc = asb_alloc(ctx, &ctx->wn2t3, (size_t)16 * ASB_MAX_SUB))) return rc;
-    if ((rc = asb_alloc(ctx, &ctx->tile_counter, (size_t)16))) return rc;
-    if ((rc = asb_alloc(ctx, &ctx->pstate2, (size_t)ASB_MAX_SUB))) return rc;
-    if ((rc = asb_alloc(ctx, &ctx->e_class, (size_t)ctx->n_loc))) return rc;
+    if ((rc = read_buffers(ctx))) return rc;
     if ((rc = asb_alloc(ctx, &ctx->tile_res, (size_t)ASB_MAX_SUB + 2))) return rc;
-    ASB_HIP(ctx, hipMemcpyAsync(ctx->e_class, ctx->energy, (size_t)ctx->n_loc * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    if ((rc = read_snapshot(ctx))) return rc;
     const int save_budget = ctx->spec_budget;
     int save_sub[8];
     for (int q = 0; q < 8; ++q) { save_sub[q] = ctx->sub_budget[q]; if (sub_budget) ctx->sub_budget[q] = sub_budget[q]; }
@@ -3944,26 +3870,16 @@ extern "C" int asb_panel_read_run(asb_ctx* ctx, int64_t k0, int64_t k1, int nsub
         }
         ntile = 0;
     }
-    long long kb[ASB_MAX_SUB];
-    PanelState* st[ASB_MAX_SUB];
     for (int ct = 0; ct < ASB_MAX_SUB; ++ct) {
-        kb[ct] = k0 + (long long)ct * ASB_PANEL_COLS;
-        st[ct] = ctx->pstate2 + ct;
-        wa.kb[ct] = kb[ct];
+        wa.kb[ct] = k0 + (long long)ct * ASB_PANEL_COLS;
         wa.nc[ct] = ct < ntile ? nc[ct] : 0;
     }
     ctx->rd_k0 = k0;
     ctx->rd_ntile = ntile;
     for (int ct = 0; ct < 8; ++ct) { ctx->rd_nc[ct] = ct < ntile ? nc[ct] : 0; ctx->rd_proven[ct] = ct < ntile ? proven[ct] : 0; }
     if (ntile > 0) {
-        bool covered = spec_ntile >= ntile;
-        for (int ct = 0; covered && ct < ntile; ++ct) covered = spec_nc[ct] >= nc[ct];
-        if (!covered) {
-            if ((rc = dbl_build_tiles(ctx, ntile, wa))) return rc;
-            if ((rc = launch_wide(ctx, ntile, wa))) return rc;
-        }
         int rgrid = 0, cgrid = 0;
-        if ((rc = tiles_enqueue(ctx, ntile, kb, nc, st, &rgrid, &cgrid))) return rc;
+        if ((rc = read_enqueue(ctx, k0, ntile, nc, spec_ntile, spec_nc, true, &rgrid, &cgrid))) return rc;
         ctx->rd_rgrid = rgrid;
     }
     hipLaunchKernelGGL(k_read_words, dim3(1), dim3(64), 0, ctx->stream, ctx->tile_res, ntile, wa, status, words_dev);
@@ -4003,14 +3919,7 @@ extern "C" int asb_panel_read_commit(asb_ctx* ctx, const double* words, int64_t*
     int g_full = 0;
     while (g_full < nstand && keep[g_full] == ctx->rd_nc[g_full]) ++g_full;
     int64_t total = 0;
-    auto commit_cols = [&](int ct, int cols) {
-        hipLaunchKernelGGL(k_commit_energy, dim3(cgrid), dim3(256), 0, ctx->stream, ctx->comps, (long long)(3 * ctx->n_loc),
-                           (long long)ctx->n_loc, (int)(ctx->rd_k0 + 16 * ct), ctx->pstate2 + ct, ctx->wn2t3 + 16 * ct, ctx->energy, ctx->pmax,
-                           ctx->pidx, ctx->psum, ctx->colpart, cols);
-        ctx->nblk = cgrid;
-        hipLaunchKernelGGL(k_colsum, dim3(1), dim3(1024), 0, ctx->stream, ctx->colpart, ctx->nblk, cols, (long long)(ctx->rd_k0 + 16 * ct),
-                           ctx->scal, (PanelState*)nullptr);
-    };
+    auto commit_cols = [&](int ct, int cols) { commit_head(ctx, ct, ctx->rd_k0 + 16 * ct, cols, cgrid); };
     if (l_full > g_full) {
         // this shard ran ahead of the verdict: back to the energies at the start of the read, then the verdict column by column
         ASB_HIP(ctx, hipMemcpyAsync(ctx->energy, ctx->e_class, (size_t)ctx->n_loc * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));

@@ -17,7 +17,9 @@ def _view(ptr, n):
 
 
 class FakeEngine(object):
-    device_exchange = False          # exchange records are CPU tensors
+    # exchange records are CPU tensors; to the panel driver (_panels.py) this also says what the double cannot do: no guessed
+    # first panel (panel_guess_*), no leaving the projection mode in mid-run (project_switch_residual: the stall rule is off)
+    device_exchange = False
 
     def __init__(self):
         self.F = self.n_loc = self.v0 = self.N_glob = self.K = 0

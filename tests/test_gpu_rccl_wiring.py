@@ -157,8 +157,8 @@ def test_pod_deim_through_rccl(rccl_comm, tmp_path):
 
 
 def test_config4_full_size_vs_reference_through_rccl(rccl_comm, tmp_path):
-    """The headline configuration through the MULTI-RANK protocol (every collective issued, candidates assembled, sub-panels
-    through asb_panel_sub_*) against the unmodified reference's run on the same input (tests/golden/c4_*.npz)."""
+    """The headline configuration through the MULTI-RANK protocol (every collective issued, candidates assembled, the sub-panels
+    of a read in one launch and one exchange: asb_panel_read_run / _commit) against the unmodified reference's run on the same input (tests/golden/c4_*.npz)."""
     from animsnapbases_amd import posComponents, posSnapshots
     from conftest import load_golden
     from config_fixtures import c4_frames, make_param

@@ -285,3 +285,69 @@ def test_multirank_read_in_one_exchange_on_structured_data(world, kind):
             assert relerr(rec, pre["snapTensor"]) < 1e-9
     for o in outs[1:]:           # every rank ends with the same replicated results
         assert np.array_equal(o[0], outs[0][0]) and np.array_equal(o[2], outs[0][2]) and np.array_equal(o[1], outs[0][1])
+
+
+@pytest.mark.parametrize("kind", ["noise", "lowrank"])
+def test_multirank_read_costs_one_min_allreduce(kind):
+    """The collectives of the two-rank driver (animsnapbases_amd/_panels.py) on the device, recorded by a wrapper around the
+    communicator: uniform noise (F = 64, N = 9000) and the low-rank tensor of the test above (N = 12001, F = 96, rank 20), K = 40
+    -- reads with several sub-panels, and on the second shards that disagree about a tile.
+    How many min-all-reduces there must be follows from the driver and the library, not from a recorded run:
+      * deflate_stats()['panels'] counts every completed launch of the panel kernel for a read: one per asb_panel_read_run
+        (multi_chain_run) and one per asb_panel_run[_spec] (a launch that timed out is taken back: coop_fallbacks counts those);
+      * a read in one launch (_read_one_launch) is followed by exactly ONE min-all-reduce, of nine words;
+      * a plain read (_read_plain: HipEngine.panel_run / panel_run_spec, counted here) is followed, while the lock-step check
+        of the co-resident kernel is on (several ranks, no fallback), by exactly one min-all-reduce of ONE word.
+    So nine-word min-all-reduces = panels - plain reads, one-word ones = plain reads."""
+    import contextlib
+    import io
+    from animsnapbases_amd import HipEngine, posComponents, posSnapshots
+    from thread_comm import RecordingComm, run_ranks
+    if kind == "noise":
+        N, F, K = 9000, 64, 40
+        verts = np.random.default_rng(17).uniform(-1, 1, size=(F, N, 3))
+    else:
+        N, F, K = 12001, 96, 40
+        verts = orc.synth_snapshots(np.random.default_rng(28).normal(size=(N, 3)), F, rank=20, noise=1e-4, decay=0.9, seed=3)
+    param = _param(K)
+
+    def rank_fn(rank, comm):
+        comm = RecordingComm(comm)
+        eng = HipEngine(0, stream=0)
+        plain, tiles, rejected = [0], [], []
+
+        def counted(fn):
+            def call(*args):
+                plain[0] += 1
+                return fn(*args)
+            return call
+        eng.panel_run, eng.panel_run_spec = counted(eng.panel_run), counted(eng.panel_run_spec)
+        read_run, read_commit = eng.panel_read_run, eng.panel_read_commit
+        eng.panel_read_run = lambda *a: tiles.append(read_run(*a)) or tiles[-1]
+        eng.panel_read_commit = lambda *a: rejected.append(read_commit(*a)) or rejected[-1]
+        with contextlib.redirect_stdout(io.StringIO()):
+            snaps = posSnapshots.from_arrays(verts, None, "first", standarize=True, massWeight=False, engine=eng, comm=comm)
+            n_before = len(comm.calls)
+            comp = posComponents(param, snaps)
+            comp.deflate_mode = "project"
+            comp.compute_components_store_singvalues()
+        return (comp.selected_vertices.copy(), comm.calls[n_before:], eng.deflate_stats(), plain[0], [t[0] for t in tiles],
+                [bool(r[2]) for r in rejected])
+
+    outs = run_ranks(2, rank_fn)
+    pre = orc.prepare_snapshots(verts, "first", True)
+    ref = orc.extract_k_components(pre["snapTensor"], K)
+    sig = ref["measures"][:, 1]
+    good = int(np.argmax(sig < 1e-7 * sig[0])) if np.any(sig < 1e-7 * sig[0]) else K
+    for idx, calls, st, plain, ntiles, rej in outs:
+        mins = [n for name, n in calls if name == "allreduce_min_tensor"]
+        print(kind, "panels", st["panels"], "refreshes", st["refreshes"], "plain reads", plain, "tiles per read", ntiles, "rejections", rej,
+              "min-all-reduces", mins, "residual switch at", st["residual_switch_at"])
+        assert idx[:good].tolist() == ref["idx"][:good].tolist()
+        assert calls == outs[0][1]                          # the ranks issued the same collectives in the same order
+        assert st["coop_fallbacks"] == 0, st
+        assert max(ntiles) > 1, ntiles                      # some read had several sub-panels
+        if kind == "lowrank":
+            assert any(rej), rej                            # ... and some tile did not stand in full
+        assert mins.count(9) == st["panels"] - plain and mins.count(9) == len(ntiles)
+        assert mins.count(1) == plain and len(mins) == st["panels"]

@@ -187,3 +187,47 @@ def test_comm_collectives_gloo(world):
     """The small-value collectives of Comm (cached exchange tensors, all_reduce / all_gather_into_tensor only)."""
     import torch.multiprocessing as mp
     mp.spawn(_comm_worker, args=(world, _free_port()), nprocs=world, join=True)
+
+
+# The collectives of deflate_panels_multirank on the CPU test double, as recorded at the commit before the driver was cut into
+# phases: (name, payload elements) in call order.  The run covers the start-up exchange (4 words), per read the all-gather of the
+# exported energies (M_CAP + 1 = 25) and the packed all-gather of rows + ids (73 = 3 F + 1 words per candidate of the rank with
+# the most), and, with unproven steps on, the host-side min of the pass's verdicts (allreduce_max of one negated word) behind five
+# of the six reads; without them eleven shorter reads.  No read ends in a refresh here.
+_READ = [("all_gather_into", 25), ("all_gather_into", 584), ("allreduce_max", 1)]
+_COLLECTIVES = {
+    "1": [("all_gather_ints", 4), ("all_gather_into", 25), ("all_gather_into", 657), ("allreduce_max", 1)] + 4 * _READ
+         + [("all_gather_into", 25), ("all_gather_into", 511)],
+    "0": [("all_gather_ints", 4)] + [c for n in (657, 730, 511, 584, 584, 438, 584, 438, 584, 438, 511)
+                                     for c in (("all_gather_into", 25), ("all_gather_into", n))],
+}
+_COUNTS = {"1": {"all_gather_ints": 1, "all_gather_into": 12, "allreduce_max": 5}, "0": {"all_gather_ints": 1, "all_gather_into": 22}}
+
+
+@pytest.mark.parametrize("spec", ["1", "0"])
+def test_panel_driver_issues_the_recorded_collectives(spec, monkeypatch):
+    """Two thread ranks drive deflate_panels_multirank on the CPU test double (uniform noise, F = 24, N = 600 -- above the
+    double's panel capacity, so thresholds and the rows all-gather run --, K = 20) through a communicator that records every
+    collective: the sequence, on both ranks, is the recorded one, with and without unproven steps."""
+    import collections
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from animsnapbases_amd._panels import deflate_panels_multirank
+    from fake_engine import FakeEngine
+    from thread_comm import RecordingComm, run_ranks
+
+    monkeypatch.setenv("ASB_SPEC_PANELS", spec)
+    F, N, K = 24, 600, 20
+    X = np.random.default_rng(11).uniform(-1, 1, size=(F, N, 3))
+
+    def rank_fn(rank, comm):
+        comm = RecordingComm(comm)
+        eng = FakeEngine()
+        eng.upload(X, *comm.my_shard(N))
+        eng.deflate_begin(K, False, 1)
+        assert deflate_panels_multirank(eng, comm, N, K) == K
+        return comm.calls
+
+    for calls in run_ranks(2, rank_fn, device="cpu"):
+        assert calls == _COLLECTIVES[spec]
+        assert dict(collections.Counter(name for name, _ in calls)) == _COUNTS[spec]

@@ -27,13 +27,13 @@ class _Hub(object):
 
 
 class ThreadComm(object):
-    def __init__(self, hub, rank):
+    def __init__(self, hub, rank, device="cuda:0"):
         import torch
 
         self.hub, self.rank, self.world = hub, rank, hub.world
         self.multi = self.world > 1
         self._torch = torch
-        self._dev = torch.device("cuda", 0)
+        self._dev = torch.device(device)           # "cpu": the CPU test double of the engine (tests/fake_engine.py)
         self.on_engine_stream = False       # the emulated collectives run on torch's stream behind device-wide syncs
 
     def shards(self, N):
@@ -43,7 +43,8 @@ class ThreadComm(object):
         return self.shards(N)[self.rank]
 
     def _sync(self):
-        self._torch.cuda.synchronize()
+        if self._dev.type == "cuda":
+            self._torch.cuda.synchronize()
 
     def allreduce_sum(self, values):
         a = np.atleast_1d(np.asarray(values, dtype=np.float64))
@@ -116,14 +117,34 @@ class ThreadComm(object):
         self.hub.bar.wait()
 
 
-def run_ranks(world, fn):
+class RecordingComm(object):
+    """Wraps a communicator and records, in order, (name, payload elements) of every collective called through it."""
+    PAYLOAD = {"allreduce_sum": 0, "allreduce_max": 0, "all_gather_ints": 0, "allreduce_tensor": 0, "allreduce_min_tensor": 0,
+               "all_gather_into": 1, "all_gather_records": 0, "global_argmax": 0, "all_gather_rows": 0}
+
+    def __init__(self, comm):
+        self._comm, self.calls = comm, []
+
+    def __getattr__(self, name):
+        fn = getattr(self._comm, name)
+        if name not in self.PAYLOAD:
+            return fn
+
+        def recorded(*args, **kwargs):
+            p = args[self.PAYLOAD[name]]
+            self.calls.append((name, int(p.numel()) if hasattr(p, "numel") else int(np.size(p))))
+            return fn(*args, **kwargs)
+        return recorded
+
+
+def run_ranks(world, fn, device="cuda:0"):
     """Runs fn(rank, comm) on `world` threads; re-raises the first failure."""
     hub = _Hub(world)
     errs, outs = [], [None] * world
 
     def body(r):
         try:
-            outs[r] = fn(r, ThreadComm(hub, r))
+            outs[r] = fn(r, ThreadComm(hub, r, device))
         except BaseException as e:          # noqa: BLE001 - surfaced to the test below
             errs.append(e)
             hub.bar.abort()
