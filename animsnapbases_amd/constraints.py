@@ -144,6 +144,23 @@ class nonlinearSnapshots:
         self._frames_device, self._keepalive = frames_device, keepalive
         self._engine, self._comm = engine, comm if comm is not None else Comm()
         self._shards = None
+        self._p_of_kind = None              # from_positions: p of the projected element kind (config() keeps it)
+
+    @classmethod
+    def from_positions(cls, param, pos_snapshots, kind, elements=None, **kw):
+        """Extra (not in the reference): the constraint-projection snapshots of a position animation that is already in HBM
+        -- ``pos_snapshots.constraint_projections(kind, elements, **kw)`` (projective_dynamics/Constraint_projections.py's
+        ``get_pi`` on the device) adopted through ``frames_device``; the tensor is kept alive by the instance.  Call
+        ``config()`` / ``snapshots_prepare()`` as usual afterwards; ``constraintsSize`` is this kind's p, whatever
+        ``param.constProj_p_size`` says.  One rank only."""
+        from .projections import KINDS
+        tensor, F, rows = pos_snapshots.constraint_projections(kind, elements, **kw)
+        self = cls(param, frames_device=(tensor.data_ptr(), F, rows), keepalive=tensor)
+        self.constraintsSize = self._p_of_kind = KINDS[kind][0]
+        self.frs = F
+        self.projection_kind = kind
+        self.bending_indices = pos_snapshots.bending_indices
+        return self
 
     # the prepared tensor lives on the device; (F, ep, 3) on read
     @property
@@ -166,7 +183,7 @@ class nonlinearSnapshots:
         self.dim = getattr(p, "constProj_dim", 3)
         self.mass_file = getattr(p, "constProj_masses_file", "")
         self.frs = p.constProj_numFrames
-        self.constraintsSize = p.constProj_p_size
+        self.constraintsSize = self._p_of_kind if self._p_of_kind else p.constProj_p_size
         self.ele_type = getattr(p, "constProj_element_type", "")
         constProj_output_directory = getattr(p, "constProj_output_directory", "")
 

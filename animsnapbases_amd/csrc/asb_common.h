@@ -306,6 +306,12 @@ struct asb_ctx {
     double* om_out = nullptr;         // accum_norm | accum_angle | per-frame numerators | denominators | statistics
     double* om_scratch = nullptr;     // (3*n_loc, cw) reconstruction of one chunk of frames
     double *om_fe = nullptr, *om_ang = nullptr;   // (frames, n_loc) maps, only when asked for
+    // constraint projections of the resident positions (asb_cproj.hip)
+    int cp_kind = -1;                 // element kind of the last asb_cproj_setup (-1: none)
+    int64_t cp_n = 0, cp_verts = 0;   // its elements; the vertices its indices were checked against
+    int *cp_idx = nullptr, *cp_sptr = nullptr, *cp_sidx = nullptr;    // indices (cp_n x width); verts_bending: star CSR
+    double* cp_table = nullptr;       // per-element tables (+ the star edges' weights)
+    double* cp_invm = nullptr;        // (n_loc) 1 / massL
 
     // ---- profiling of the dominant streaming kernel ----
     bool prof = false;

@@ -1,0 +1,396 @@
+// Constraint-projection snapshots from the resident position tensor: per element and frame the projection `get_pi` of the
+// reference's five element constraints (projective_dynamics/Constraint_projections.py: edge spring :291-312, triangle strain
+// :407-426, tetrahedron strain :534-554, tetrahedron deformation gradient :669-687, vertex bending :197-215), written as the
+// (F', n_elem p, 3) tensor that Simulators.py:655-724 stacks, without the simulator's Python loop over elements and frames.
+//
+// World space as in asb_onmesh.hip: x = (T * (1 / psf) + mean) * (1 / massL_v), same arguments, same reciprocals.
+//
+// Reads: the tensor is vertex-major (row 3 v + d, frames contiguous), so lanes run along the selected frames.  A wave owns one
+// element x 64 frames: the element's indices and table are the same in every lane (scalar loads), each of its 2 - 4 vertices'
+// rows is a coalesced 512-byte load (frame_jump 1).  Writes: the output is frame-major, so a block of CP_EB elements x 64
+// frames stages its p x 3 results in LDS, one row of CP_EB * 3p + 1 doubles per frame (the odd row length spreads the 64 lanes
+// of a column store over all banks), and then writes per frame the block's contiguous run of elements x 3p doubles.
+//
+// SVD: per thread, in registers, one-sided (Hestenes) Jacobi on F itself -- column pairs of A = F V are rotated until
+// orthogonal, the column norms are the singular values, u_i = a_i / sigma_i -- with a fixed bound on the sweeps and an early
+// out.  F^T F is never formed: the closed-form eigen-solve of it squares the condition number and loses sigma_3 below
+// 1e-8 sigma_1.  Every result is a function of F: sum_i g(sigma_i) u_i v_i^T does not depend on the order or signs the sweeps
+// end with.  A (frame, element) is computed by one thread from its own loads only and nothing is accumulated across threads:
+// no atomics, repeated calls and sub-ranges of frames are bit-identical.
+#include "asb_common.h"
+
+#include <vector>
+
+#define CP_EB 16            // elements per block
+#define CP_WAVES 4
+#define CP_SWEEPS 12        // bound on the Jacobi sweeps (3 x 3 converges in 4 - 6)
+#define CP_TOL 4.440892098500626e-16        // columns count as orthogonal at |a_p . a_q| <= CP_TOL |a_p| |a_q|
+
+enum { CP_EDGE = 0, CP_TRI = 1, CP_TET_STRAIN = 2, CP_TET_DEFGRAD = 3, CP_BEND = 4 };
+
+template <int KIND> struct CpShape;
+template <> struct CpShape<CP_EDGE> { static constexpr int NV = 2, P = 1, TW = 1; };
+template <> struct CpShape<CP_TRI> { static constexpr int NV = 3, P = 2, TW = 10; };
+template <> struct CpShape<CP_TET_STRAIN> { static constexpr int NV = 4, P = 3, TW = 9; };
+template <> struct CpShape<CP_TET_DEFGRAD> { static constexpr int NV = 4, P = 3, TW = 9; };
+template <> struct CpShape<CP_BEND> { static constexpr int NV = 1, P = 1, TW = 5; };
+
+struct CpWorld {
+    const double* T;
+    long long ldt;
+    const double* mean;
+    const double* invm;
+    double inv_psf;
+};
+
+__device__ __forceinline__ void cp_pos(const CpWorld& w, long long f, int v, double (&x)[3]) {
+    const double im = w.invm ? w.invm[v] : 1.0;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) x[d] = (w.T[(3LL * v + d) * w.ldt + f] * w.inv_psf + (w.mean ? w.mean[3LL * v + d] : 0.0)) * im;
+}
+
+// one Jacobi rotation of the columns p, q of A (N rows) and of V (N rows): true when it rotated
+template <int N>
+__device__ __forceinline__ bool cp_rotate(double (&A)[N][N], double (&V)[N][N], int p, int q) {
+    double al = 0.0, be = 0.0, ga = 0.0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        al = fma(A[i][p], A[i][p], al);
+        be = fma(A[i][q], A[i][q], be);
+        ga = fma(A[i][p], A[i][q], ga);
+    }
+    if (!(fabs(ga) > CP_TOL * sqrt(al * be))) return false;
+    const double zeta = (be - al) / (2.0 * ga);
+    const double t = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+    const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const double ap = A[i][p], aq = A[i][q], vp = V[i][p], vq = V[i][q];
+        A[i][p] = c * ap - s * aq;
+        A[i][q] = s * ap + c * aq;
+        V[i][p] = c * vp - s * vq;
+        V[i][q] = s * vp + c * vq;
+    }
+    return true;
+}
+
+// F V = A with orthogonal columns; sig[i] = |a_i|; A's columns are normalised to u_i.  A column of norm 0 is completed to
+// the unit vector that makes det(U) det(V) = +1 (any choice is a valid SVD there; this one is the non-inverted one).
+__device__ __forceinline__ void cp_svd3(double (&A)[3][3], double (&V)[3][3], double (&sig)[3]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+    for (int sw = 0; sw < CP_SWEEPS; ++sw) {
+        bool r = cp_rotate<3>(A, V, 0, 1);
+        r |= cp_rotate<3>(A, V, 0, 2);
+        r |= cp_rotate<3>(A, V, 1, 2);
+        if (!r) break;
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        sig[j] = sqrt(A[0][j] * A[0][j] + A[1][j] * A[1][j] + A[2][j] * A[2][j]);
+        if (sig[j] > 0.0) {
+            const double inv = 1.0 / sig[j];
+            A[0][j] *= inv, A[1][j] *= inv, A[2][j] *= inv;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        if (sig[j] > 0.0) continue;
+        const int a = (j + 1) % 3, b = (j + 2) % 3;
+        if (sig[a] > 0.0 && sig[b] > 0.0) {         // u_j = +- u_a x u_b with the sign of det V
+            const double dv = V[0][0] * (V[1][1] * V[2][2] - V[1][2] * V[2][1]) - V[0][1] * (V[1][0] * V[2][2] - V[1][2] * V[2][0]) +
+                              V[0][2] * (V[1][0] * V[2][1] - V[1][1] * V[2][0]);
+            const double sg = dv < 0.0 ? -1.0 : 1.0;
+            A[0][j] = sg * (A[1][a] * A[2][b] - A[2][a] * A[1][b]);
+            A[1][j] = sg * (A[2][a] * A[0][b] - A[0][a] * A[2][b]);
+            A[2][j] = sg * (A[0][a] * A[1][b] - A[1][a] * A[0][b]);
+        } else {                                    // rank <= 1: no direction is preferred, u_j = v_j
+            A[0][j] = V[0][j], A[1][j] = V[1][j], A[2][j] = V[2][j];
+        }
+    }
+}
+
+__device__ __forceinline__ double cp_det3(const double (&M)[3][3]) {
+    return M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) +
+           M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
+}
+
+__device__ __forceinline__ double cp_clip(double s, double lo, double hi) { return fmin(fmax(s, lo), hi); }
+
+// ---------------------------------------------------------------- the five projections: r[3 p] of one (element, frame)
+__device__ __forceinline__ void cp_edge(const CpWorld& w, long long f, const int* __restrict__ ix, const double* __restrict__ tb,
+                                        double (&r)[3]) {
+    double a[3], b[3];
+    cp_pos(w, f, ix[0], a);
+    cp_pos(w, f, ix[1], b);
+    const double s0 = b[0] - a[0], s1 = b[1] - a[1], s2 = b[2] - a[2];
+    const double len = sqrt(s0 * s0 + s1 * s1 + s2 * s2);
+    // 0.5 (pi2 - pi1) of :306-311 is 0.5 d s / |s|; |s| = 0 (:303-304: no projection) gives 0 / 0 = NaN, what storing the
+    // reference's None in a float row gives
+    const double g = 0.5 * tb[0] / len;
+    r[0] = len == 0.0 ? NAN : g * s0;
+    r[1] = len == 0.0 ? NAN : g * s1;
+    r[2] = len == 0.0 ? NAN : g * s2;
+}
+
+__device__ __forceinline__ void cp_tri(const CpWorld& w, long long f, const int* __restrict__ ix, const double* __restrict__ tb,
+                                       double smin, double smax, double (&r)[6]) {
+    double q1[3], q2[3], q3[3];
+    cp_pos(w, f, ix[0], q1);
+    cp_pos(w, f, ix[1], q2);
+    cp_pos(w, f, ix[2], q3);
+    // tb: P (3 x 2) row-major, DmInv (2 x 2) row-major.  Ds2 = P^T [q2 - q1, q3 - q1], F = Ds2 DmInv
+    double ds[2][2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        ds[j][0] = tb[j] * (q2[0] - q1[0]) + tb[2 + j] * (q2[1] - q1[1]) + tb[4 + j] * (q2[2] - q1[2]);
+        ds[j][1] = tb[j] * (q3[0] - q1[0]) + tb[2 + j] * (q3[1] - q1[1]) + tb[4 + j] * (q3[2] - q1[2]);
+    }
+    double A[2][2], V[2][2] = {{1.0, 0.0}, {0.0, 1.0}};
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) A[i][j] = ds[i][0] * tb[6 + j] + ds[i][1] * tb[8 + j];
+    for (int sw = 0; sw < CP_SWEEPS; ++sw)
+        if (!cp_rotate<2>(A, V, 0, 1)) break;
+    double sg[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        sg[j] = sqrt(A[0][j] * A[0][j] + A[1][j] * A[1][j]);
+        if (sg[j] > 0.0) {
+            const double inv = 1.0 / sg[j];
+            A[0][j] *= inv, A[1][j] *= inv;
+        }
+    }
+    const double dv = V[0][0] * V[1][1] - V[0][1] * V[1][0] < 0.0 ? -1.0 : 1.0;
+    if (!(sg[0] > 0.0) && !(sg[1] > 0.0)) {
+        A[0][0] = V[0][0], A[1][0] = V[1][0], A[0][1] = V[0][1], A[1][1] = V[1][1];
+    } else if (!(sg[1] > 0.0)) {                    // u_1 = the quarter turn of u_0, signed so that det U det V = +1
+        A[0][1] = -dv * A[1][0], A[1][1] = dv * A[0][0];
+    } else if (!(sg[0] > 0.0)) {
+        A[0][0] = dv * A[1][1], A[1][0] = -dv * A[0][1];
+    }
+    const double c0 = cp_clip(sg[0], smin, smax), c1 = cp_clip(sg[1], smin, smax);
+    double Fh[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) Fh[i][j] = c0 * A[i][0] * V[j][0] + c1 * A[i][1] * V[j][1];
+    // pi = (P Fhat)^T: row a, column c = sum_b P[c][b] Fhat[b][a]
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) r[3 * a + c] = tb[2 * c] * Fh[0][a] + tb[2 * c + 1] * Fh[1][a];
+}
+
+template <int KIND>
+__device__ __forceinline__ void cp_tet(const CpWorld& w, long long f, const int* __restrict__ ix, const double* __restrict__ tb,
+                                       double smin, double smax, double (&r)[9]) {
+    double q[4][3];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) cp_pos(w, f, ix[i], q[i]);
+    double A[3][3], V[3][3], sg[3], Fm[3][3];
+    // F = [q1 - q4, q2 - q4, q3 - q4] DmInv
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            A[i][j] = (q[0][i] - q[3][i]) * tb[j] + (q[1][i] - q[3][i]) * tb[3 + j] + (q[2][i] - q[3][i]) * tb[6 + j];
+            Fm[i][j] = A[i][j];
+        }
+    cp_svd3(A, V, sg);
+    if (KIND == CP_TET_STRAIN) {
+        const bool inverted = cp_det3(Fm) < 0.0;                    // (:550-551): the SMALLEST singular value changes sign
+        int lo = sg[1] < sg[0] ? 1 : 0;
+        if (sg[2] <= sg[lo]) lo = 2;
+        double c[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            c[j] = cp_clip(sg[j], smin, smax);
+            if (inverted && j == lo) c[j] = -c[j];
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) r[3 * i + j] = c[0] * A[i][0] * V[j][0] + c[1] * A[i][1] * V[j][1] + c[2] * A[i][2] * V[j][2];
+    } else {
+        double R[3][3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) R[i][j] = A[i][0] * V[j][0] + A[i][1] * V[j][1] + A[i][2] * V[j][2];
+        if (cp_det3(R) < 0.0) R[0][2] = -R[0][2], R[1][2] = -R[1][2], R[2][2] = -R[2][2];      // (:684-685): third COLUMN of R
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) r[3 * i + j] = R[j][i];                                  // (:687) R^T
+    }
+}
+
+__device__ __forceinline__ void cp_bend(const CpWorld& w, long long f, int v, const double* __restrict__ tb, const int* __restrict__ nb,
+                                        const double* __restrict__ wt, int e0, int e1, double (&r)[3]) {
+    double x[3], y[3], ss[3] = {0.0, 0.0, 0.0};
+    cp_pos(w, f, v, x);
+    for (int e = e0; e < e1; ++e) {                 // (:201-202) in the star's edge order
+        cp_pos(w, f, nb[e], y);
+        const double we = wt[e];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) ss[d] += (x[d] - y[d]) * we;
+    }
+    const double nrm = sqrt(ss[0] * ss[0] + ss[1] * ss[1] + ss[2] * ss[2]);
+    const double rmc = tb[0];
+    const double g = rmc / nrm;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) r[d] = nrm < 1e-10 ? tb[1 + d] * rmc : ss[d] * g;                // (:205-208)
+    const double dot = tb[1] * r[0] + tb[2] * r[1] + tb[3] * r[2];
+    if (nrm > 1e-5 && dot * tb[4] < 0.0) r[0] = -r[0], r[1] = -r[1], r[2] = -r[2];              // (:210-213)
+}
+
+// grid (element blocks, frame tiles); out (n_sel, n_elem * P, 3)
+template <int KIND>
+__global__ __launch_bounds__(64 * CP_WAVES) void k_cproj(CpWorld w, const int* __restrict__ idx, const double* __restrict__ table,
+                                                         const int* __restrict__ sptr, const int* __restrict__ sidx,
+                                                         const double* __restrict__ swt, long long n_elem, int f0, int fj, int n_sel,
+                                                         double smin, double smax, double* __restrict__ out) {
+    constexpr int NV = CpShape<KIND>::NV, P3 = 3 * CpShape<KIND>::P, TW = CpShape<KIND>::TW;
+    constexpr int RUN = CP_EB * P3, ROW = RUN + 1;
+    __shared__ double stage[64 * ROW];
+    const int lane = threadIdx.x & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int s0 = (int)blockIdx.y * 64;
+    // a lane past the last selected frame recomputes frame f0 (an address inside the tensor); its row is never written out
+    const long long f = (long long)f0 + (long long)(s0 + lane < n_sel ? s0 + lane : 0) * fj;
+    const long long e_base = (long long)blockIdx.x * CP_EB;
+    for (int j = wid; j < CP_EB; j += CP_WAVES) {
+        const long long e = e_base + j;
+        if (e >= n_elem) break;                     // the same in every lane
+        double r[P3];
+        const int* ix = idx + e * NV;
+        const double* tb = table + e * TW;
+        if constexpr (KIND == CP_EDGE) cp_edge(w, f, ix, tb, r);
+        else if constexpr (KIND == CP_TRI) cp_tri(w, f, ix, tb, smin, smax, r);
+        else if constexpr (KIND == CP_BEND) cp_bend(w, f, ix[0], tb, sidx, swt, sptr[e], sptr[e + 1], r);
+        else cp_tet<KIND>(w, f, ix, tb, smin, smax, r);
+#pragma unroll
+        for (int k = 0; k < P3; ++k) stage[lane * ROW + j * P3 + k] = r[k];
+    }
+    __syncthreads();
+    const int ne = n_elem - e_base < CP_EB ? (int)(n_elem - e_base) : CP_EB;
+    const int nf = n_sel - s0 < 64 ? n_sel - s0 : 64;
+    const int run = ne * P3;
+    const long long row_len = n_elem * P3;
+    for (int i = threadIdx.x; i < 64 * RUN; i += 64 * CP_WAVES) {
+        const int fl = i / RUN, k = i % RUN;
+        if (fl < nf && k < run) out[(long long)(s0 + fl) * row_len + e_base * P3 + k] = stage[fl * ROW + k];
+    }
+}
+
+// The element kind of the next asb_cproj_run calls: indices (n_elem x NV), tables (n_elem x TW; verts_bending: followed by the
+// star edges' weights) and, for verts_bending, the star CSR.  Every index the kernel follows is checked against the vertices
+// of the resident tensor here.  Replaces the previous set-up of this context.
+extern "C" int asb_cproj_setup(asb_ctx* ctx, int kind, int64_t n_elem, const int64_t* idx, const double* table, const int64_t* star_ptr,
+                               const int64_t* star_idx) {
+    if (!ctx || !idx || !table || n_elem < 1) return ASB_ERR_ARG;
+    if (kind < CP_EDGE || kind > CP_BEND) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cproj_setup: unknown kind %d", kind);
+    if (!ctx->X || ctx->n_loc < 1) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cproj_setup: no snapshots on the device");
+    if (ctx->v0 != 0 || ctx->n_loc != ctx->N_glob)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cproj_setup: vertices [%lld, +%lld) of %lld: elements straddle vertex shards, one rank only",
+                 (long long)ctx->v0, (long long)ctx->n_loc, (long long)ctx->N_glob);
+    static const int NV[5] = {2, 3, 4, 4, 1}, TW[5] = {1, 10, 9, 9, 5};
+    const int nv = NV[kind], tw = TW[kind];
+    const long long n_loc = ctx->n_loc;
+    if (n_loc > 0x7fffffffLL || n_elem > 0x7fffffffLL / 16) ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_cproj_setup: too large for 32-bit indices");
+    ctx->cp_kind = -1;
+    std::vector<int> i32((size_t)n_elem * nv), p32, s32;
+    for (int64_t i = 0; i < n_elem * nv; ++i) {
+        if (idx[i] < 0 || idx[i] >= n_loc)
+            ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cproj_setup: element %lld names vertex %lld of %lld", (long long)(i / nv), (long long)idx[i], n_loc);
+        i32[i] = (int)idx[i];
+    }
+    int64_t nnz = 0;
+    if (kind == CP_BEND) {
+        if (!star_ptr || !star_idx) return ASB_ERR_ARG;
+        if (star_ptr[0] != 0) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cproj_setup: the star offsets do not start at 0");
+        for (int64_t v = 0; v < n_elem; ++v)
+            if (star_ptr[v + 1] < star_ptr[v]) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cproj_setup: star offsets decrease at element %lld", (long long)v);
+        nnz = star_ptr[n_elem];
+        if (nnz > 0x7fffffffLL) ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_cproj_setup: too many star edges for 32-bit indices");
+        p32.resize((size_t)n_elem + 1);
+        s32.resize((size_t)nnz);
+        for (int64_t v = 0; v <= n_elem; ++v) p32[v] = (int)star_ptr[v];
+        for (int64_t i = 0; i < nnz; ++i) {
+            if (star_idx[i] < 0 || star_idx[i] >= n_loc)
+                ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cproj_setup: star edge %lld names vertex %lld of %lld", (long long)i, (long long)star_idx[i], n_loc);
+            s32[i] = (int)star_idx[i];
+        }
+    }
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    const size_t n_table = (size_t)n_elem * tw + (size_t)nnz;
+    int rc;
+    if ((rc = asb_alloc(ctx, &ctx->cp_idx, i32.size()))) return rc;
+    if ((rc = asb_alloc(ctx, &ctx->cp_table, n_table))) return rc;
+    if ((rc = asb_alloc(ctx, &ctx->cp_sptr, p32.size() + 1))) return rc;
+    if ((rc = asb_alloc(ctx, &ctx->cp_sidx, s32.size() + 1))) return rc;
+    ASB_HIP(ctx, hipMemcpyAsync(ctx->cp_idx, i32.data(), i32.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    ASB_HIP(ctx, hipMemcpyAsync(ctx->cp_table, table, n_table * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (!p32.empty()) ASB_HIP(ctx, hipMemcpyAsync(ctx->cp_sptr, p32.data(), p32.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    if (!s32.empty()) ASB_HIP(ctx, hipMemcpyAsync(ctx->cp_sidx, s32.data(), s32.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));          // (the staging vectors die here)
+    ctx->cp_kind = kind;
+    ctx->cp_n = n_elem;
+    ctx->cp_verts = n_loc;
+    return ASB_OK;
+}
+
+template <int KIND>
+static void cp_launch(asb_ctx* ctx, const CpWorld& w, int f0, int fj, int n_sel, double smin, double smax, double* out) {
+    const dim3 grid((unsigned)((ctx->cp_n + CP_EB - 1) / CP_EB), (unsigned)((n_sel + 63) / 64));
+    hipLaunchKernelGGL(k_cproj<KIND>, grid, dim3(64 * CP_WAVES), 0, ctx->stream, w, ctx->cp_idx, ctx->cp_table, ctx->cp_sptr, ctx->cp_sidx,
+                       ctx->cp_table + (size_t)ctx->cp_n * CpShape<KIND>::TW, (long long)ctx->cp_n, f0, fj, n_sel, smin, smax, out);
+}
+
+extern "C" int asb_cproj_run(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean, double psf,
+                             double sigma_min, double sigma_max, double* out_dev) {
+    if (!ctx || !out_dev) return ASB_ERR_ARG;
+    if (ctx->cp_kind < 0 || !ctx->X || ctx->cp_verts != ctx->n_loc || ctx->v0 != 0 || ctx->n_loc != ctx->N_glob)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cproj_run: no element set-up for the resident tensor (asb_cproj_setup)");
+    CpWorld w;
+    int64_t F;
+    if (which == 0) {
+        w.T = ctx->X, w.ldt = ctx->Fp, F = ctx->F;
+    } else if (which == 1) {
+        if (!ctx->ho_Y) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cproj_run: no held-out animation on the device (asb_heldout_upload)");
+        w.T = ctx->ho_Y, w.ldt = ctx->ho_Fp, F = ctx->ho_F;
+    } else {
+        return ASB_ERR_ARG;
+    }
+    if (f0 < 0 || f1 > F || f0 >= f1 || fj < 1)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cproj_run: range(%lld, %lld, %lld) is not a selection of the %lld frames", (long long)f0,
+                 (long long)f1, (long long)fj, (long long)F);
+    if (add_mean && !ctx->have_mean) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cproj_run: no mean on the device");
+    if (!(psf > 0.0)) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cproj_run: scale %g", psf);
+    if (!(sigma_min <= sigma_max)) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cproj_run: sigma_min %g > sigma_max %g", sigma_min, sigma_max);
+    const int64_t n_sel = (f1 - f0 + fj - 1) / fj;
+    if ((n_sel + 63) / 64 > 65535) ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_cproj_run: %lld frames in one call (at most %d)", (long long)n_sel, 65535 * 64);
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    int rc;
+    if (inv_massL) {
+        if ((rc = asb_alloc(ctx, &ctx->cp_invm, (size_t)ctx->n_loc))) return rc;
+        ASB_HIP(ctx, hipMemcpyAsync(ctx->cp_invm, inv_massL, (size_t)ctx->n_loc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    }
+    w.mean = add_mean ? ctx->mean : nullptr;
+    w.invm = inv_massL ? ctx->cp_invm : nullptr;
+    w.inv_psf = 1.0 / psf;
+    switch (ctx->cp_kind) {
+        case CP_EDGE: cp_launch<CP_EDGE>(ctx, w, (int)f0, (int)fj, (int)n_sel, sigma_min, sigma_max, out_dev); break;
+        case CP_TRI: cp_launch<CP_TRI>(ctx, w, (int)f0, (int)fj, (int)n_sel, sigma_min, sigma_max, out_dev); break;
+        case CP_TET_STRAIN: cp_launch<CP_TET_STRAIN>(ctx, w, (int)f0, (int)fj, (int)n_sel, sigma_min, sigma_max, out_dev); break;
+        case CP_TET_DEFGRAD: cp_launch<CP_TET_DEFGRAD>(ctx, w, (int)f0, (int)fj, (int)n_sel, sigma_min, sigma_max, out_dev); break;
+        default: cp_launch<CP_BEND>(ctx, w, (int)f0, (int)fj, (int)n_sel, sigma_min, sigma_max, out_dev); break;
+    }
+    ASB_CHECK_LAUNCH(ctx);
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the caller owns out_dev and may read it on any stream
+    return ASB_OK;
+}

@@ -507,6 +507,21 @@ class HipEngine(object):
                                          ptr(out.get("angle"))))
         return out
 
+    # ------------------------------------------------------------------ constraint projections of the resident positions
+    def cproj_setup(self, setup):
+        """Uploads one element kind (a ``projections.ProjectionSetup``); replaces the previous one of this context."""
+        self._ck(self.lib.asb_cproj_setup(self.h, int(setup.code), int(setup.n_elem), ptr(setup.idx), ptr(setup.table),
+                                          ptr(setup.star_ptr), ptr(setup.star_idx)))
+
+    def cproj_run(self, which, f0, f1, fj, inv_massL, add_mean, psf, sigma_min, sigma_max, out_dev_ptr):
+        """The projections of the frames range(f0, f1, fj) of the training (which 0) or held-out (1) tensor into the caller's
+        device buffer of (F', rows, 3) float64."""
+        if inv_massL is not None:
+            inv_massL = np.ascontiguousarray(inv_massL, dtype=np.float64)
+            assert inv_massL.shape == (self.N_glob,)
+        self._ck(self.lib.asb_cproj_run(self.h, int(which), int(f0), int(f1), int(fj), ptr(inv_massL), int(bool(add_mean)),
+                                        float(psf), float(sigma_min), float(sigma_max), ctypes.c_void_p(int(out_dev_ptr))))
+
     # ------------------------------------------------------------------ SPLOCS
     def splocs_begin(self):
         self._ck(self.lib.asb_splocs_begin(self.h))

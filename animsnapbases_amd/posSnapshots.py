@@ -11,6 +11,7 @@ import sys
 
 import numpy as np
 
+from . import projections as _proj
 from . import utils as _u
 from .distributed import Comm
 from .engine import HipEngine
@@ -50,6 +51,7 @@ class posSnapshots:
         self._snapTensor = None
         self.compute_geodesic_distance = None
         self.tet_mesh = tet_mesh_file
+        self.bending_indices = None             # constraint_projections("verts_bending"): the constrained vertices
 
         # ---- device side ----
         self._comm = comm if comm is not None else Comm()
@@ -100,6 +102,71 @@ class posSnapshots:
     @snapTensor.setter
     def snapTensor(self, value):
         self._snapTensor = value
+
+    # ------------------------------------------------------------------ extras: constraint projections of the animation
+    def constraint_projections(self, kind, elements=None, rest_positions=None, sigma_min=1.0, sigma_max=1.0, animation="train",
+                               frame_start=0, frame_end=None, frame_jump=1):
+        """Extra (not in the reference's class): the constraint-projection snapshots the reference's projective-dynamics
+        simulator records (Simulators.py:655-724) -- ``get_pi`` of every element for every frame
+        (projective_dynamics/Constraint_projections.py) -- computed on the device from the resident animation in world space
+        (mass weighting, mean row and scale undone), for the frames range(frame_start, frame_end, frame_jump).
+
+        ``kind``: "edge_spring" (elements (E, 2)), "tris_strain" ((T, 3)), "tets_strain" / "tets_deformation_gradient"
+        ((T, 4)) or "verts_bending" (elements: the (M, 3) triangles, None = ``self.tris``; the constrained vertices are left
+        in ``self.bending_indices``).  ``rest_positions`` (N, 3): default frame 0 of the world-space input.  ``sigma_min`` /
+        ``sigma_max``: the clamp of the strain kinds.  ``animation``: "train", "test" (``test_verts``) or an (F', N, 3) array.
+
+        Returns ``(tensor, F', rows)``: a ``torch.float64`` device tensor (F', rows, 3), rows = elements x p, allocated here
+        through torch and owned by the caller (what ``nonlinearSnapshots(frames_device=...)`` adopts).  One rank only."""
+        if kind not in _proj.KINDS:
+            raise ValueError("unknown projection kind %r: one of %s" % (kind, ", ".join(sorted(_proj.KINDS))))
+        if self._comm.multi:
+            raise NotImplementedError("constraint_projections on several ranks: elements straddle the vertex shards and no "
+                                      "halo of positions is built")
+        if not sigma_min <= sigma_max:
+            raise ValueError("sigma_min %r > sigma_max %r" % (sigma_min, sigma_max))
+        if isinstance(animation, str) and animation not in ("train", "test"):
+            raise ValueError("animation must be 'train', 'test' or an (F', N, 3) array, not %r" % (animation,))
+        if elements is None:
+            if kind != "verts_bending" or self.tris is None:
+                raise ValueError("%s: no elements given%s" % (kind, " and the snapshots have no triangles" if kind == "verts_bending" else ""))
+            elements = self.tris
+        train = isinstance(animation, str) and animation == "train"
+        Y = None
+        if train:
+            F = self.frs
+        else:
+            Y = self.test_verts if isinstance(animation, str) else animation
+            if Y is None:
+                raise ValueError("no test animation (test_verts is None)")
+            Y = np.asarray(Y, dtype=np.float64)
+            if Y.ndim != 3 or Y.shape[1:] != (self.nVerts, 3) or Y.shape[0] < 1:
+                raise ValueError("held-out animation of shape %s: (F', %d, 3) expected" % (Y.shape, self.nVerts))
+            F = Y.shape[0]
+        frame_end = F if frame_end is None else frame_end
+        if frame_jump < 1 or frame_start < 0 or frame_end > F or frame_start >= frame_end:
+            raise ValueError("empty frame range: range(%r, %r, %r) selects none of the %d frames"
+                             % (frame_start, frame_end, frame_jump, F))
+        if rest_positions is None:
+            if self.verts is not None:
+                rest_positions = self.verts[0]
+            else:                                   # an adopted device tensor: frame 0 back in world space
+                rest_positions = self.snapTensor[0] / self.pre_scale_factor + (self.mean if self._standarize else 0.0)
+        rest = np.asarray(rest_positions, dtype=np.float64)
+        if rest.shape != (self.nVerts, 3):
+            raise ValueError("rest positions of shape %s: (%d, 3) expected" % (rest.shape, self.nVerts))
+        setup = _proj.build_setup(kind, elements, rest)
+        import torch
+        eng = self._engine
+        if Y is not None:
+            eng.heldout_upload(Y, self.massL, self._standarize, self.pre_scale_factor)
+        eng.cproj_setup(setup)
+        n_sel = len(range(frame_start, frame_end, frame_jump))
+        out = torch.empty((n_sel, setup.rows, 3), dtype=torch.float64, device="cuda:%d" % eng.device_id)
+        eng.cproj_run(0 if train else 1, frame_start, frame_end, frame_jump, self.invMassL, self._standarize,
+                      self.pre_scale_factor, sigma_min, sigma_max, out.data_ptr())
+        self.bending_indices = setup.bending_indices
+        return out, n_sel, setup.rows
 
     # ------------------------------------------------------------------ reference methods
     @log_time("")

@@ -1,0 +1,254 @@
+"""Rest-pose set-up of the reference's five element projections (projective_dynamics/Constraint_projections.py), restated
+from their definitions for the device kernel of csrc/asb_cproj.hip, plus a NumPy restatement of the per-frame projection
+(``project_host``) that the timing tool uses for scale.
+
+Per element kind: p rows per element, the index width and the per-element table the kernel reads.
+
+  kind                        p  indices  table (doubles per element)
+  edge_spring                 1  (E, 2)   1: rest length d (:280)
+  tris_strain                 2  (T, 3)   10: the 3 x 2 frame P (:368-376) row-major, then the 2 x 2 DmInv (:379-381)
+  tets_strain                 3  (T, 4)   9: DmInv of Dm = [p1 - p4, p2 - p4, p3 - p4] (:496-505)
+  tets_deformation_gradient   3  (T, 4)   9: the same DmInv (:635-639)
+  verts_bending               1  (n, 1)   5: rest mean-curvature norm, averaged triangle normal, dot_with_normal (:178-186);
+                                          behind the n x 5 block the cotangent weights / Voronoi-area third of every star
+                                          edge (:156-169), in the order of the star CSR
+
+The star CSR of ``verts_bending`` lists, per constrained vertex, the neighbour ``v2`` of every star edge in the order
+``DeformableMesh.vertex_star`` finds them (:1129-1162): the per-frame sum (:201-202) runs in that order.
+
+Every projection is a function of the deformation gradient itself: no singular vector is returned, so the sign and ordering
+choices of an SVD routine never show.
+"""
+import numpy as np
+
+# kind -> (p, vertices per element, table doubles per element, code of the C ABI)
+KINDS = {
+    "edge_spring": (1, 2, 1, 0),
+    "tris_strain": (2, 3, 10, 1),
+    "tets_strain": (3, 4, 9, 2),
+    "tets_deformation_gradient": (3, 4, 9, 3),
+    "verts_bending": (1, 1, 5, 4),
+}
+
+
+class ProjectionSetup(object):
+    """What ``asb_cproj_setup`` uploads: ``idx`` (n, width) int64, ``table`` (flat float64), for ``verts_bending`` the star
+    CSR ``star_ptr`` (n + 1) / ``star_idx`` (nnz) and ``bending_indices`` (the constrained vertices, Simulators.py:312)."""
+
+    def __init__(self, kind, idx, table, star_ptr=None, star_idx=None, bending_indices=None, parts=None):
+        self.kind = kind
+        self.p, self.width, self.table_width, self.code = KINDS[kind]
+        self.idx = np.ascontiguousarray(idx, dtype=np.int64)
+        self.table = np.ascontiguousarray(table, dtype=np.float64).reshape(-1)
+        self.star_ptr = None if star_ptr is None else np.ascontiguousarray(star_ptr, dtype=np.int64)
+        self.star_idx = None if star_idx is None else np.ascontiguousarray(star_idx, dtype=np.int64)
+        self.bending_indices = bending_indices
+        self.parts = parts or {}            # the named rest tables (tests, project_host)
+        self.n_elem = int(self.idx.shape[0])
+        self.rows = self.n_elem * self.p
+
+
+def _check_elements(kind, elements, n_verts):
+    width = 3 if kind == "verts_bending" else KINDS[kind][1]
+    el = np.asarray(elements)
+    if el.ndim != 2 or el.shape[1] != width:
+        raise ValueError("%s: elements of shape %s, (n, %d) expected" % (kind, el.shape, width))
+    if el.shape[0] < 1:
+        raise ValueError("%s: no elements" % kind)
+    if not np.issubdtype(el.dtype, np.integer):
+        raise ValueError("%s: elements must be integers, not %s" % (kind, el.dtype))
+    el = el.astype(np.int64)
+    if el.min() < 0 or el.max() >= n_verts:
+        bad = int(el.max()) if el.max() >= n_verts else int(el.min())
+        raise ValueError("%s: an element names vertex %d, the animation has vertices 0..%d" % (kind, bad, n_verts - 1))
+    return el
+
+
+def edge_spring_tables(rest, edges):
+    """Rest length d = |x_v0 - x_v1| (:279-280)."""
+    d = np.linalg.norm(rest[edges[:, 0]] - rest[edges[:, 1]], axis=1)
+    if (d == 0).any():
+        raise ValueError("edge_spring: degenerate rest element %d: rest edge length is 0" % int(np.flatnonzero(d == 0)[0]))
+    return d
+
+
+def tris_strain_tables(rest, tris):
+    """The tangent frame P (3 x 2: the normalised first edge, the second edge orthogonalised against it, :368-376) and the
+    inverse of the rest edges in that frame (:379-381)."""
+    p1, p2, p3 = rest[tris[:, 0]], rest[tris[:, 1]], rest[tris[:, 2]]
+    e1, e2 = p2 - p1, p3 - p1
+    n1 = np.linalg.norm(e1, axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        c0 = e1 / n1[:, None]
+        c1 = e2 - np.einsum("ij,ij->i", e2, c0)[:, None] * c0
+        n2 = np.linalg.norm(c1, axis=1)
+        c1 = c1 / n2[:, None]
+    P = np.stack([c0, c1], axis=2)                                  # (T, 3, 2)
+    Dm = np.einsum("tij,tik->tjk", P, np.stack([e1, e2], axis=2))   # P^T [e1 e2]  (T, 2, 2)
+    det = Dm[:, 0, 0] * Dm[:, 1, 1] - Dm[:, 0, 1] * Dm[:, 1, 0]
+    bad = ~(np.isfinite(det) & (det != 0))
+    if bad.any():
+        raise ValueError("tris_strain: degenerate rest element %d: |det Dm| is 0" % int(np.flatnonzero(bad)[0]))
+    return P, np.linalg.inv(Dm)
+
+
+def tets_tables(rest, tets, kind="tets_strain"):
+    """DmInv of Dm = [p1 - p4, p2 - p4, p3 - p4] as columns (:502-504, :638-639)."""
+    p4 = rest[tets[:, 3]]
+    Dm = np.stack([rest[tets[:, 0]] - p4, rest[tets[:, 1]] - p4, rest[tets[:, 2]] - p4], axis=2)
+    det = np.linalg.det(Dm)
+    if (det == 0).any():
+        raise ValueError("%s: degenerate rest element %d: |det Dm| is 0" % (kind, int(np.flatnonzero(det == 0)[0])))
+    return np.linalg.inv(Dm)
+
+
+def vertex_stars(tris, n_verts):
+    """Per vertex the star edges [v2, vOtherT1, t1, vOtherT2, t2] in the order ``DeformableMesh.vertex_star`` appends them
+    (:1129-1162): triangles in order, their corners in order, the two other corners in order; a second triangle on a known
+    neighbour fills (t2, vOtherT2), a later one overwrites them."""
+    stars = [[] for _ in range(n_verts)]
+    where = [dict() for _ in range(n_verts)]
+    for t, tri in enumerate(np.asarray(tris, dtype=np.int64)):
+        for v in range(3):
+            vi = int(tri[v])
+            for ov in range(3):
+                if ov == v:
+                    continue
+                nb, third = int(tri[ov]), int(tri[3 - (v + ov)])
+                k = where[vi].get(nb)
+                if k is None:
+                    where[vi][nb] = len(stars[vi])
+                    stars[vi].append([nb, third, t, -1, -1])
+                else:
+                    stars[vi][k][3], stars[vi][k][4] = third, t
+    return stars
+
+
+def _angle_at(a, b, c):
+    """Angle at b between (a - b) and (c - b) (:138-143)."""
+    u, v = a - b, c - b
+    return np.arccos(np.clip(np.dot(u, v) / (np.linalg.norm(u) * np.linalg.norm(v)), -1, 1))
+
+
+def bending_tables(rest, tris):
+    """``add_vertex_bending_constraint`` (:1196-1223): the vertices whose star edges all have two triangles, and per such
+    vertex the cotangent weights over a third of the incident triangle area (:156-169, :1086-1104), the norm of the rest
+    mean-curvature vector, the average of the star triangles' unit normals and its product with that vector (:178-186)."""
+    rest = np.asarray(rest, dtype=np.float64)
+    tris = np.asarray(tris, dtype=np.int64)
+    n = rest.shape[0]
+    area = np.zeros(n)
+    for tri in tris:                                                # (:1095-1104)
+        a = 0.5 * np.linalg.norm(np.cross(rest[tri[1]] - rest[tri[0]], rest[tri[2]] - rest[tri[0]])) / 3.0
+        for vi in tri:
+            area[vi] += a
+    area[area < 1e-7] = 1e-7
+    stars = vertex_stars(tris, n)
+    ids, ptr, v2s, wts, rmc, nrm, dwn = [], [0], [], [], [], [], []
+    for v in range(n):
+        star = stars[v]
+        if not star or any(e[4] < 0 for e in star):
+            continue
+        w, seen, tl = [], set(), []
+        for nb, o1, t1, o2, t2 in star:
+            cot = 0.5 / np.tan(_angle_at(rest[v], rest[o1], rest[nb])) + 0.5 / np.tan(_angle_at(rest[v], rest[o2], rest[nb]))
+            w.append(cot / area[v])
+            for t in (t1, t2):
+                if t not in seen:
+                    seen.add(t)
+                    tl.append(t)
+        mc = np.zeros(3)
+        for (nb, _o1, _t1, _o2, _t2), wi in zip(star, w):
+            mc += (rest[v] - rest[nb]) * wi
+        normals = []
+        for t in tl:                                                # (:145-154)
+            a, b, c = rest[tris[t]]
+            nn = np.cross(b - a, c - a)
+            ln = np.linalg.norm(nn)
+            if ln > 1e-10:
+                normals.append(nn / ln)
+        tn = np.mean(normals, axis=0) if normals else np.array([0.0, 0.0, 1.0])
+        ids.append(v)
+        v2s += [e[0] for e in star]
+        wts += w
+        ptr.append(len(v2s))
+        rmc.append(np.linalg.norm(mc))
+        nrm.append(tn)
+        dwn.append(tn @ mc)
+    return dict(indices=np.array(ids, dtype=np.int64), star_ptr=np.array(ptr, dtype=np.int64),
+                star_idx=np.array(v2s, dtype=np.int64), weights=np.array(wts, dtype=np.float64),
+                rest_curvature=np.array(rmc, dtype=np.float64), normal=np.array(nrm, dtype=np.float64).reshape(-1, 3),
+                dot_with_normal=np.array(dwn, dtype=np.float64))
+
+
+def build_setup(kind, elements, rest_positions):
+    """The upload of one element kind for rest positions (N, 3).  ``elements``: the index array of the table above; for
+    ``verts_bending`` the (M, 3) triangles of the mesh.  Raises ValueError for an unknown kind, a wrong element width, an index
+    outside the mesh or a degenerate rest element."""
+    if kind not in KINDS:
+        raise ValueError("unknown projection kind %r: one of %s" % (kind, ", ".join(sorted(KINDS))))
+    rest = np.asarray(rest_positions, dtype=np.float64)
+    if rest.ndim != 2 or rest.shape[1] != 3:
+        raise ValueError("rest positions of shape %s: (N, 3) expected" % (rest.shape,))
+    el = _check_elements(kind, elements, rest.shape[0])
+    if kind == "edge_spring":
+        d = edge_spring_tables(rest, el)
+        return ProjectionSetup(kind, el, d, parts=dict(d=d))
+    if kind == "tris_strain":
+        P, DmInv = tris_strain_tables(rest, el)
+        table = np.concatenate([P.reshape(-1, 6), DmInv.reshape(-1, 4)], axis=1)
+        return ProjectionSetup(kind, el, table, parts=dict(P=P, DmInv=DmInv))
+    if kind in ("tets_strain", "tets_deformation_gradient"):
+        DmInv = tets_tables(rest, el, kind)
+        return ProjectionSetup(kind, el, DmInv.reshape(-1, 9), parts=dict(DmInv=DmInv))
+    b = bending_tables(rest, el)
+    if b["indices"].shape[0] == 0:
+        raise ValueError("verts_bending: no vertex of the mesh has a closed star (every star edge needs two triangles)")
+    head = np.concatenate([b["rest_curvature"][:, None], b["normal"], b["dot_with_normal"][:, None]], axis=1)
+    return ProjectionSetup(kind, b["indices"][:, None], np.concatenate([head.reshape(-1), b["weights"]]), b["star_ptr"],
+                           b["star_idx"], bending_indices=b["indices"], parts=b)
+
+
+def project_host(setup, positions, sigma_min=1.0, sigma_max=1.0):
+    """NumPy restatement of ``get_pi`` for every element and frame: positions (F, N, 3) -> (F, n p, 3).  For scale and for
+    checks on small shapes only; the product path is the device kernel."""
+    X = np.asarray(positions, dtype=np.float64)
+    F = X.shape[0]
+    idx, kind, q = setup.idx, setup.kind, setup.parts
+    if kind == "edge_spring":                                        # (:297-311): 0.5 (pi2 - pi1) = 0.5 d s / |s|
+        s = X[:, idx[:, 1]] - X[:, idx[:, 0]]
+        ln = np.linalg.norm(s, axis=2)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return 0.5 * q["d"][None, :, None] * s / ln[..., None]
+    if kind == "tris_strain":                                        # (:411-425)
+        Ds = np.stack([X[:, idx[:, 1]] - X[:, idx[:, 0]], X[:, idx[:, 2]] - X[:, idx[:, 0]]], axis=3)
+        Fm = np.einsum("tij,ftik->ftjk", q["P"], Ds) @ q["DmInv"][None]
+        U, s, Vt = np.linalg.svd(Fm)
+        Fh = (U * np.clip(s, sigma_min, sigma_max)[..., None, :]) @ Vt
+        pi = np.swapaxes(np.einsum("tij,ftjk->ftik", q["P"], Fh), 2, 3)
+        return pi.reshape(F, -1, 3)
+    if kind in ("tets_strain", "tets_deformation_gradient"):         # (:538-554, :673-687)
+        x4 = X[:, idx[:, 3]]
+        Ds = np.stack([X[:, idx[:, 0]] - x4, X[:, idx[:, 1]] - x4, X[:, idx[:, 2]] - x4], axis=3)
+        Fm = Ds @ q["DmInv"][None]
+        U, s, Vt = np.linalg.svd(Fm)
+        if kind == "tets_strain":
+            s = np.clip(s, sigma_min, sigma_max)
+            s[..., 2] = np.where(np.linalg.det(Fm) < 0.0, -s[..., 2], s[..., 2])
+            return ((U * s[..., None, :]) @ Vt).reshape(F, -1, 3)
+        R = U @ Vt
+        R[..., 2] = np.where((np.linalg.det(R) < 0)[..., None], -R[..., 2], R[..., 2])
+        return np.swapaxes(R, 2, 3).reshape(F, -1, 3)
+    out = np.empty((F, setup.n_elem, 3))                            # verts_bending (:199-215)
+    ptr, v2, w = q["star_ptr"], q["star_idx"], q["weights"]
+    for i, v in enumerate(q["indices"]):
+        ss = np.zeros((F, 3))
+        for e in range(ptr[i], ptr[i + 1]):
+            ss += (X[:, v] - X[:, v2[e]]) * w[e]
+        nrm = np.linalg.norm(ss, axis=1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            corr = np.where((nrm < 1e-10)[:, None], q["normal"][i][None] * q["rest_curvature"][i],
+                            ss * (q["rest_curvature"][i] / nrm)[:, None])
+        flip = (nrm > 1e-5) & ((corr @ q["normal"][i]) * q["dot_with_normal"][i] < 0)
+        out[:, i] = np.where(flip[:, None], -corr, corr)
+    return out

@@ -591,6 +591,25 @@ int asb_onmesh_run(asb_ctx* ctx, int which, int64_t r, int64_t f0, int64_t f1, i
                    double* mesh_num_out, double* mesh_den_out, double* accum_angle_out, double* stats_out,
                    double* frame_err_out, double* angle_out);
 
+/* ------------------------------- constraint projections of resident positions ---- */
+/* The per-element projections `get_pi` of projective_dynamics/Constraint_projections.py for every frame of the resident
+ * position tensor, written in the layout of the simulator's stacked_p (Simulators.py:655-724).  One rank: v0 = 0 and
+ * n_loc = N_glob.  kind: 0 edge_spring (p = 1; idx n x 2; table n x 1: rest length), 1 tris_strain (p = 2; idx n x 3; table
+ * n x 10: the 3 x 2 tangent frame P, then the 2 x 2 DmInv, both row-major), 2 tets_strain and 3 tets_deformation_gradient
+ * (p = 3; idx n x 4; table n x 9: DmInv row-major), 4 verts_bending (p = 1; idx n x 1: the constrained vertices; table n x 5:
+ * rest mean-curvature norm, averaged triangle normal, dot_with_normal -- followed by one weight per star edge; star_ptr
+ * (n + 1) and star_idx (the neighbour v2 of each star edge, in the reference's edge order) are needed for this kind only).
+ * All arrays on the host.  Every index is checked against the vertices of the tensor; kept until the next call. */
+int asb_cproj_setup(asb_ctx* ctx, int kind, int64_t n_elem, const int64_t* idx, const double* table, const int64_t* star_ptr,
+                    const int64_t* star_idx);
+/* The projections of the frames range(f0, f1, fj) (n_sel of them) of the training (which 0) or held-out (1) tensor, from
+ * world positions x = (T / psf + mean) / massL_v formed as asb_onmesh_run forms them (same arguments).  sigma_min / sigma_max:
+ * the clamp of the two strain kinds.  out_dev: caller-owned DEVICE memory, (n_sel, n_elem p, 3) doubles.  A zero-length edge
+ * writes NaN.  Deterministic: no atomics, sub-ranges equal the matching slices of a full run bit for bit.  Returns after the
+ * stream has drained. */
+int asb_cproj_run(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean, double psf,
+                  double sigma_min, double sigma_max, double* out_dev);
+
 /* ------------------------------------------------ SPLOCS refinement ----------- */
 /* posComponents.splocs_glob_optimization, snapbases/posComponents.py:132-189.
  * State after a residual-mode deflation: C = comps, W = weigs, U = 0 (:135-139).  One outer
