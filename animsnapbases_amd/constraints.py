@@ -145,21 +145,28 @@ class nonlinearSnapshots:
         self._engine, self._comm = engine, comm if comm is not None else Comm()
         self._shards = None
         self._p_of_kind = None              # from_positions: p of the projected element kind (config() keeps it)
+        self.assembly_ST = None             # from_positions(wi=...): the kind's weighted S^T (constraintsComponents.config)
 
     @classmethod
-    def from_positions(cls, param, pos_snapshots, kind, elements=None, **kw):
+    def from_positions(cls, param, pos_snapshots, kind, elements=None, wi=None, **kw):
         """Extra (not in the reference): the constraint-projection snapshots of a position animation that is already in HBM
         -- ``pos_snapshots.constraint_projections(kind, elements, **kw)`` (projective_dynamics/Constraint_projections.py's
         ``get_pi`` on the device) adopted through ``frames_device``; the tensor is kept alive by the instance.  Call
         ``config()`` / ``snapshots_prepare()`` as usual afterwards; ``constraintsSize`` is this kind's p, whatever
-        ``param.constProj_p_size`` says.  One rank only."""
+        ``param.constProj_p_size`` says.  ``wi``: the constraint weight; when given, the kind's weighted differential
+        operator S^T assembled from the rest tables is kept as ``self.assembly_ST`` and ``constraintsComponents.config()``
+        takes it as its ``St`` unless a ``constProj_weightedSt`` file is configured.  One rank only."""
         from .projections import KINDS
+        if wi is not None:
+            kw["wi"] = wi
         tensor, F, rows = pos_snapshots.constraint_projections(kind, elements, **kw)
         self = cls(param, frames_device=(tensor.data_ptr(), F, rows), keepalive=tensor)
         self.constraintsSize = self._p_of_kind = KINDS[kind][0]
         self.frs = F
         self.projection_kind = kind
         self.bending_indices = pos_snapshots.bending_indices
+        if wi is not None:
+            self.assembly_ST = pos_snapshots.assembly_ST[kind]
         return self
 
     # the prepared tensor lives on the device; (F, ep, 3) on read
@@ -412,7 +419,8 @@ class constraintsComponents:  # Components == bases
                file_name_sing="_constrprojBases_pcaExtraction_singValues"):
         """constraintsComponents.py:61-74; the weighted S^T operator (``constProj_weightedSt``, an .npz holding a scipy
         sparse matrix under ``costProj_St_key``) is read when configured -- 'pca_blocks_with_St' and the position-space
-        interpolation error use it (``self.St`` may also be assigned directly)."""
+        interpolation error use it (``self.St`` may also be assigned directly).  Without such a file the S^T that
+        ``nonlinearSnapshots.from_positions(wi=...)`` assembled is taken."""
         p = self.param
         self.basesType = getattr(p, "constProj_bases_interpolation_type", "")
         self.support = getattr(p, "constProj_support", "global")
@@ -423,6 +431,8 @@ class constraintsComponents:  # Components == bases
         st_file = getattr(p, "constProj_weightedSt", None)
         if st_file:
             self.St = read_sparse_matrix(st_file, ".npz", key=getattr(p, "costProj_St_key", None))
+        elif getattr(self.nonlinearSnapshots, "assembly_ST", None) is not None:
+            self.St = self.nonlinearSnapshots.assembly_ST
 
     def _elements_around(self, v):
         """The elements the reference lists around position-space vertex v (constraintsComponents.py:182-194, 682-697)."""

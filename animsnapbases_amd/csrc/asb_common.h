@@ -312,6 +312,9 @@ struct asb_ctx {
     int *cp_idx = nullptr, *cp_sptr = nullptr, *cp_sidx = nullptr;    // indices (cp_n x width); verts_bending: star CSR
     double* cp_table = nullptr;       // per-element tables (+ the star edges' weights)
     double* cp_invm = nullptr;        // (n_loc) 1 / massL
+    int *cf_ptr = nullptr, *cf_idx = nullptr;     // asb_cforce_run: the CSR of S^T (n_loc + 1 offsets, columns)
+    double* cf_val = nullptr;         // its values
+    double* cf_scratch = nullptr;     // (3 * cp_n * p, cw) element-major projections of one chunk of frames
 
     // ---- profiling of the dominant streaming kernel ----
     bool prof = false;

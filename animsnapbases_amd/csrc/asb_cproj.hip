@@ -394,3 +394,190 @@ extern "C" int asb_cproj_run(asb_ctx* ctx, int which, int64_t f0, int64_t f1, in
     ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the caller owns out_dev and may read it on any stream
     return ASB_OK;
 }
+
+// ---------------------------------------------------------------- constraint forces b = S^T p of the resident animation
+// b[f] = S^T p(q_f), (n_sel, N, 3) frame-major (Simulators.py:643-724, one kind's term), in chunks of cw selected frames so
+// that p is never formed at full size.  Per chunk, in stream order:
+//   k_cproj_em   the projections of the chunk, ELEMENT-major: scratch row (e P + i) 3 + d holds cw doubles, one per frame of
+//                the chunk.  Same per-thread routines, same world positions, same wave = one element x 64 frames as k_cproj;
+//                every store is a coalesced 512-byte run, so no LDS transposition.
+//   k_st_apply   a wave owns one vertex x 64 frames: it walks the vertex's row of S^T in ascending column order (indices and
+//                values are the same in every lane), accumulates the three coordinates by f64 FMA in that order from
+//                coalesced reads of the scratch rows, and a block of CF_VB vertices x 64 frames stages its results in LDS
+//                (odd row length) to write per frame its contiguous run of CF_VB * 3 doubles -- a plain read-modify-write
+//                of the block's own entries when accumulating.
+// An (frame, vertex) entry is summed by one thread in a fixed order and no thread touches another's entry: no atomics;
+// repeated calls, sub-ranges and any chunk width give the same bits.  A NaN of a collapsed edge reaches the vertices whose
+// row stores that column (S^T stores no zeros: the edge's two vertices) and nothing else.
+#define CF_VB 16                                // vertices per block of k_st_apply
+#define CF_SCRATCH_BYTES (256ull << 20)         // bound on the element-major scratch of one chunk
+
+template <int KIND>
+__global__ __launch_bounds__(64 * CP_WAVES) void k_cproj_em(CpWorld w, const int* __restrict__ idx, const double* __restrict__ table,
+                                                            const int* __restrict__ sptr, const int* __restrict__ sidx,
+                                                            const double* __restrict__ swt, long long n_elem, int f0, int fj, int c0,
+                                                            int cn, int cw, double smin, double smax, double* __restrict__ S) {
+    constexpr int NV = CpShape<KIND>::NV, P3 = 3 * CpShape<KIND>::P, TW = CpShape<KIND>::TW;
+    const int lane = threadIdx.x & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int col = (int)blockIdx.y * 64 + lane;            // frame of the chunk: selected frame c0 + col
+    const bool ok = col < cn;
+    // a lane past the chunk's last frame recomputes frame f0 (an address inside the tensor) and stores nothing
+    const long long f = (long long)f0 + (long long)(ok ? c0 + col : 0) * fj;
+    const long long e_base = (long long)blockIdx.x * CP_EB;
+    for (int j = wid; j < CP_EB; j += CP_WAVES) {
+        const long long e = e_base + j;
+        if (e >= n_elem) break;                     // the same in every lane
+        double r[P3];
+        const int* ix = idx + e * NV;
+        const double* tb = table + e * TW;
+        if constexpr (KIND == CP_EDGE) cp_edge(w, f, ix, tb, r);
+        else if constexpr (KIND == CP_TRI) cp_tri(w, f, ix, tb, smin, smax, r);
+        else if constexpr (KIND == CP_BEND) cp_bend(w, f, ix[0], tb, sidx, swt, sptr[e], sptr[e + 1], r);
+        else cp_tet<KIND>(w, f, ix, tb, smin, smax, r);
+        if (ok) {
+#pragma unroll
+            for (int k = 0; k < P3; ++k) S[(e * P3 + k) * cw + col] = r[k];
+        }
+    }
+}
+
+// grid (vertex blocks, frame tiles of the chunk); out (n_sel, N, 3), rows c0 .. c0 + cn of it
+__global__ __launch_bounds__(64 * CP_WAVES) void k_st_apply(const int* __restrict__ ptr, const int* __restrict__ ci,
+                                                            const double* __restrict__ val, const double* __restrict__ S, int cw,
+                                                            int c0, int cn, long long n_verts, int accumulate,
+                                                            double* __restrict__ out) {
+    constexpr int RUN = CF_VB * 3, ROW = RUN + 1;
+    __shared__ double stage[64 * ROW];
+    const int lane = threadIdx.x & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int t0 = (int)blockIdx.y * 64;
+    const int col = t0 + lane;
+    const bool ok = col < cn;
+    const long long v_base = (long long)blockIdx.x * CF_VB;
+    for (int j = wid; j < CF_VB; j += CP_WAVES) {
+        const long long v = v_base + j;
+        if (v >= n_verts) break;                    // the same in every lane
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+        const int t1 = ptr[v + 1];
+        for (int t = ptr[v]; t < t1; ++t) {         // ascending columns
+            const double s = val[t];
+            if (ok) {
+                const double* row = S + 3LL * ci[t] * cw + col;
+                a0 = fma(s, row[0], a0);
+                a1 = fma(s, row[cw], a1);
+                a2 = fma(s, row[2LL * cw], a2);
+            }
+        }
+        stage[lane * ROW + j * 3 + 0] = a0;
+        stage[lane * ROW + j * 3 + 1] = a1;
+        stage[lane * ROW + j * 3 + 2] = a2;
+    }
+    __syncthreads();
+    const int nv = n_verts - v_base < CF_VB ? (int)(n_verts - v_base) : CF_VB;
+    const int nf = cn - t0 < 64 ? cn - t0 : 64;
+    const int run = nv * 3;
+    for (int i = threadIdx.x; i < 64 * RUN; i += 64 * CP_WAVES) {
+        const int fl = i / RUN, k = i % RUN;
+        if (fl < nf && k < run) {
+            double* o = out + ((long long)(c0 + t0 + fl) * n_verts + v_base) * 3 + k;
+            *o = accumulate ? *o + stage[fl * ROW + k] : stage[fl * ROW + k];
+        }
+    }
+}
+
+template <int KIND>
+static void cf_launch(asb_ctx* ctx, const CpWorld& w, int f0, int fj, int c0, int cn, int cw, double smin, double smax) {
+    const dim3 grid((unsigned)((ctx->cp_n + CP_EB - 1) / CP_EB), (unsigned)((cn + 63) / 64));
+    hipLaunchKernelGGL(k_cproj_em<KIND>, grid, dim3(64 * CP_WAVES), 0, ctx->stream, w, ctx->cp_idx, ctx->cp_table, ctx->cp_sptr,
+                       ctx->cp_sidx, ctx->cp_table + (size_t)ctx->cp_n * CpShape<KIND>::TW, (long long)ctx->cp_n, f0, fj, c0, cn, cw, smin,
+                       smax, ctx->cf_scratch);
+}
+
+extern "C" int asb_cforce_run(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean,
+                              double psf, double sigma_min, double sigma_max, int64_t n_rows, const int64_t* indptr,
+                              const int64_t* indices, const double* data, int accumulate, int64_t chunk_frames, double* out_dev) {
+    if (!ctx || !out_dev || !indptr || n_rows < 1) return ASB_ERR_ARG;
+    if (ctx->cp_kind < 0 || !ctx->X || ctx->cp_verts != ctx->n_loc || ctx->v0 != 0 || ctx->n_loc != ctx->N_glob)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: no element set-up for the resident tensor (asb_cproj_setup)");
+    CpWorld w;
+    int64_t F;
+    if (which == 0) {
+        w.T = ctx->X, w.ldt = ctx->Fp, F = ctx->F;
+    } else if (which == 1) {
+        if (!ctx->ho_Y) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: no held-out animation on the device (asb_heldout_upload)");
+        w.T = ctx->ho_Y, w.ldt = ctx->ho_Fp, F = ctx->ho_F;
+    } else {
+        return ASB_ERR_ARG;
+    }
+    if (f0 < 0 || f1 > F || f0 >= f1 || fj < 1)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: range(%lld, %lld, %lld) is not a selection of the %lld frames", (long long)f0,
+                 (long long)f1, (long long)fj, (long long)F);
+    if (add_mean && !ctx->have_mean) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: no mean on the device");
+    if (!(psf > 0.0)) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: scale %g", psf);
+    if (!(sigma_min <= sigma_max)) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: sigma_min %g > sigma_max %g", sigma_min, sigma_max);
+    if (chunk_frames < 0) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: chunk_frames %lld", (long long)chunk_frames);
+    const int64_t n_sel = (f1 - f0 + fj - 1) / fj;
+    if ((n_sel + 63) / 64 > 65535) ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_cforce_run: %lld frames in one call (at most %d)", (long long)n_sel, 65535 * 64);
+    // ---- the CSR of S^T: one row per vertex of the tensor, columns = rows of the stacked projections, ascending in a row
+    static const int PK[5] = {1, 2, 3, 3, 1};
+    const long long n_cols = (long long)ctx->cp_n * PK[ctx->cp_kind];
+    if (n_rows != ctx->n_loc)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: S^T has %lld rows, the tensor %lld vertices", (long long)n_rows, (long long)ctx->n_loc);
+    if (indptr[0] != 0) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: the row offsets of S^T do not start at 0");
+    for (int64_t v = 0; v < n_rows; ++v)
+        if (indptr[v + 1] < indptr[v]) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: row offsets of S^T decrease at row %lld", (long long)v);
+    const int64_t nnz = indptr[n_rows];
+    if (nnz > 0x7fffffffLL) ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_cforce_run: too many entries of S^T for 32-bit indices");
+    if (nnz > 0 && (!indices || !data)) return ASB_ERR_ARG;
+    std::vector<int> p32((size_t)n_rows + 1), c32((size_t)nnz);
+    for (int64_t v = 0; v <= n_rows; ++v) p32[v] = (int)indptr[v];
+    for (int64_t v = 0; v < n_rows; ++v)
+        for (int64_t t = indptr[v]; t < indptr[v + 1]; ++t) {
+            if (indices[t] < 0 || indices[t] >= n_cols)
+                ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: row %lld of S^T names column %lld of %lld", (long long)v, (long long)indices[t], n_cols);
+            if (t > indptr[v] && indices[t] <= indices[t - 1])
+                ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: the columns of row %lld of S^T are not ascending", (long long)v);
+            c32[t] = (int)indices[t];
+        }
+    // ---- chunk width: whole 128-byte lines per scratch row, the scratch within CF_SCRATCH_BYTES, whole waves if it can
+    long long cw = (long long)(CF_SCRATCH_BYTES / (24ull * (unsigned long long)n_cols));
+    cw = cw >= 64 ? cw / 64 * 64 : (cw >= 16 ? cw / 16 * 16 : 16);
+    if (chunk_frames > 0 && (chunk_frames + 15) / 16 * 16 < cw) cw = (chunk_frames + 15) / 16 * 16;
+    const long long span = (n_sel + 15) / 16 * 16;
+    if (cw > span) cw = span;
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    int rc;
+    if ((rc = asb_alloc(ctx, &ctx->cf_ptr, p32.size()))) return rc;
+    if ((rc = asb_alloc(ctx, &ctx->cf_idx, c32.size() + 1))) return rc;
+    if ((rc = asb_alloc(ctx, &ctx->cf_val, c32.size() + 1))) return rc;
+    if ((rc = asb_alloc(ctx, &ctx->cf_scratch, (size_t)3 * n_cols * cw))) return rc;
+    ASB_HIP(ctx, hipMemcpyAsync(ctx->cf_ptr, p32.data(), p32.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    if (nnz > 0) {
+        ASB_HIP(ctx, hipMemcpyAsync(ctx->cf_idx, c32.data(), c32.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        ASB_HIP(ctx, hipMemcpyAsync(ctx->cf_val, data, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (inv_massL) {
+        if ((rc = asb_alloc(ctx, &ctx->cp_invm, (size_t)ctx->n_loc))) return rc;
+        ASB_HIP(ctx, hipMemcpyAsync(ctx->cp_invm, inv_massL, (size_t)ctx->n_loc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    }
+    w.mean = add_mean ? ctx->mean : nullptr;
+    w.invm = inv_massL ? ctx->cp_invm : nullptr;
+    w.inv_psf = 1.0 / psf;
+    const unsigned gv = (unsigned)((n_rows + CF_VB - 1) / CF_VB);
+    for (long long c0 = 0; c0 < n_sel; c0 += cw) {
+        const int cn = (int)(c0 + cw < n_sel ? cw : n_sel - c0);
+        switch (ctx->cp_kind) {
+            case CP_EDGE: cf_launch<CP_EDGE>(ctx, w, (int)f0, (int)fj, (int)c0, cn, (int)cw, sigma_min, sigma_max); break;
+            case CP_TRI: cf_launch<CP_TRI>(ctx, w, (int)f0, (int)fj, (int)c0, cn, (int)cw, sigma_min, sigma_max); break;
+            case CP_TET_STRAIN: cf_launch<CP_TET_STRAIN>(ctx, w, (int)f0, (int)fj, (int)c0, cn, (int)cw, sigma_min, sigma_max); break;
+            case CP_TET_DEFGRAD: cf_launch<CP_TET_DEFGRAD>(ctx, w, (int)f0, (int)fj, (int)c0, cn, (int)cw, sigma_min, sigma_max); break;
+            default: cf_launch<CP_BEND>(ctx, w, (int)f0, (int)fj, (int)c0, cn, (int)cw, sigma_min, sigma_max); break;
+        }
+        hipLaunchKernelGGL(k_st_apply, dim3(gv, (unsigned)((cn + 63) / 64)), dim3(64 * CP_WAVES), 0, ctx->stream, ctx->cf_ptr, ctx->cf_idx,
+                           ctx->cf_val, ctx->cf_scratch, (int)cw, (int)c0, cn, (long long)n_rows, accumulate ? 1 : 0, out_dev);
+    }
+    ASB_CHECK_LAUNCH(ctx);
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the staging vectors die here; the caller owns out_dev
+    return ASB_OK;
+}

@@ -522,6 +522,21 @@ class HipEngine(object):
         self._ck(self.lib.asb_cproj_run(self.h, int(which), int(f0), int(f1), int(fj), ptr(inv_massL), int(bool(add_mean)),
                                         float(psf), float(sigma_min), float(sigma_max), ctypes.c_void_p(int(out_dev_ptr))))
 
+    def cforce_run(self, which, f0, f1, fj, inv_massL, add_mean, psf, sigma_min, sigma_max, St, accumulate, chunk_frames, out_dev_ptr):
+        """The constraint forces S^T p of the same frames for the kind of the last ``cproj_setup`` into (or, ``accumulate``,
+        onto) the caller's device buffer of (F', N, 3) float64.  ``St``: scipy CSR (N, rows) with sorted indices;
+        ``chunk_frames``: frames per pass, 0 = automatic."""
+        if inv_massL is not None:
+            inv_massL = np.ascontiguousarray(inv_massL, dtype=np.float64)
+            assert inv_massL.shape == (self.N_glob,)
+        indptr = np.ascontiguousarray(St.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(St.indices, dtype=np.int64)
+        data = np.ascontiguousarray(St.data, dtype=np.float64)
+        self._ck(self.lib.asb_cforce_run(self.h, int(which), int(f0), int(f1), int(fj), ptr(inv_massL), int(bool(add_mean)),
+                                         float(psf), float(sigma_min), float(sigma_max), int(St.shape[0]), ptr(indptr),
+                                         ptr(indices), ptr(data), int(bool(accumulate)), int(chunk_frames),
+                                         ctypes.c_void_p(int(out_dev_ptr))))
+
     # ------------------------------------------------------------------ SPLOCS
     def splocs_begin(self):
         self._ck(self.lib.asb_splocs_begin(self.h))

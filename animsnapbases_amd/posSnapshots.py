@@ -52,6 +52,7 @@ class posSnapshots:
         self.compute_geodesic_distance = None
         self.tet_mesh = tet_mesh_file
         self.bending_indices = None             # constraint_projections("verts_bending"): the constrained vertices
+        self.assembly_ST = None                 # constraint_forces / constraint_projections(wi=...): kind -> S^T (CSR)
 
         # ---- device side ----
         self._comm = comm if comm is not None else Comm()
@@ -104,20 +105,9 @@ class posSnapshots:
         self._snapTensor = value
 
     # ------------------------------------------------------------------ extras: constraint projections of the animation
-    def constraint_projections(self, kind, elements=None, rest_positions=None, sigma_min=1.0, sigma_max=1.0, animation="train",
-                               frame_start=0, frame_end=None, frame_jump=1):
-        """Extra (not in the reference's class): the constraint-projection snapshots the reference's projective-dynamics
-        simulator records (Simulators.py:655-724) -- ``get_pi`` of every element for every frame
-        (projective_dynamics/Constraint_projections.py) -- computed on the device from the resident animation in world space
-        (mass weighting, mean row and scale undone), for the frames range(frame_start, frame_end, frame_jump).
-
-        ``kind``: "edge_spring" (elements (E, 2)), "tris_strain" ((T, 3)), "tets_strain" / "tets_deformation_gradient"
-        ((T, 4)) or "verts_bending" (elements: the (M, 3) triangles, None = ``self.tris``; the constrained vertices are left
-        in ``self.bending_indices``).  ``rest_positions`` (N, 3): default frame 0 of the world-space input.  ``sigma_min`` /
-        ``sigma_max``: the clamp of the strain kinds.  ``animation``: "train", "test" (``test_verts``) or an (F', N, 3) array.
-
-        Returns ``(tensor, F', rows)``: a ``torch.float64`` device tensor (F', rows, 3), rows = elements x p, allocated here
-        through torch and owned by the caller (what ``nonlinearSnapshots(frames_device=...)`` adopts).  One rank only."""
+    def _cproj_args(self, kind, elements, rest_positions, sigma_min, sigma_max, animation, frame_start, frame_end, frame_jump):
+        """The checks shared by ``constraint_projections`` and ``constraint_forces``: the rest set-up of the kind, the held-out
+        animation (None: the training tensor) and the end of the frame range."""
         if kind not in _proj.KINDS:
             raise ValueError("unknown projection kind %r: one of %s" % (kind, ", ".join(sorted(_proj.KINDS))))
         if self._comm.multi:
@@ -155,7 +145,27 @@ class posSnapshots:
         rest = np.asarray(rest_positions, dtype=np.float64)
         if rest.shape != (self.nVerts, 3):
             raise ValueError("rest positions of shape %s: (%d, 3) expected" % (rest.shape, self.nVerts))
-        setup = _proj.build_setup(kind, elements, rest)
+        return _proj.build_setup(kind, elements, rest), Y, frame_end
+
+    def constraint_projections(self, kind, elements=None, rest_positions=None, sigma_min=1.0, sigma_max=1.0, animation="train",
+                               frame_start=0, frame_end=None, frame_jump=1, wi=None):
+        """Extra (not in the reference's class): the constraint-projection snapshots the reference's projective-dynamics
+        simulator records (Simulators.py:655-724) -- ``get_pi`` of every element for every frame
+        (projective_dynamics/Constraint_projections.py) -- computed on the device from the resident animation in world space
+        (mass weighting, mean row and scale undone), for the frames range(frame_start, frame_end, frame_jump).
+
+        ``kind``: "edge_spring" (elements (E, 2)), "tris_strain" ((T, 3)), "tets_strain" / "tets_deformation_gradient"
+        ((T, 4)) or "verts_bending" (elements: the (M, 3) triangles, None = ``self.tris``; the constrained vertices are left
+        in ``self.bending_indices``).  ``rest_positions`` (N, 3): default frame 0 of the world-space input.  ``sigma_min`` /
+        ``sigma_max``: the clamp of the strain kinds.  ``animation``: "train", "test" (``test_verts``) or an (F', N, 3) array.
+        ``wi``: the constraint weight; when given, the kind's weighted differential operator S^T (``projections.assembly_ST``)
+        is left in ``self.assembly_ST[kind]``.
+
+        Returns ``(tensor, F', rows)``: a ``torch.float64`` device tensor (F', rows, 3), rows = elements x p, allocated here
+        through torch and owned by the caller (what ``nonlinearSnapshots(frames_device=...)`` adopts).  One rank only."""
+        setup, Y, frame_end = self._cproj_args(kind, elements, rest_positions, sigma_min, sigma_max, animation, frame_start,
+                                               frame_end, frame_jump)
+        St = None if wi is None else _proj.assembly_ST(setup, self.nVerts, wi)
         import torch
         eng = self._engine
         if Y is not None:
@@ -163,10 +173,60 @@ class posSnapshots:
         eng.cproj_setup(setup)
         n_sel = len(range(frame_start, frame_end, frame_jump))
         out = torch.empty((n_sel, setup.rows, 3), dtype=torch.float64, device="cuda:%d" % eng.device_id)
-        eng.cproj_run(0 if train else 1, frame_start, frame_end, frame_jump, self.invMassL, self._standarize,
+        eng.cproj_run(0 if Y is None else 1, frame_start, frame_end, frame_jump, self.invMassL, self._standarize,
                       self.pre_scale_factor, sigma_min, sigma_max, out.data_ptr())
         self.bending_indices = setup.bending_indices
+        if St is not None:
+            self.assembly_ST = {kind: St}
         return out, n_sel, setup.rows
+
+    def constraint_forces(self, kinds, animation="train", frame_start=0, frame_end=None, frame_jump=1, chunk_frames=None):
+        """Extra (not in the reference's class): the constraint term of the global step's right-hand side,
+        b[f] = sum_k S_k^T p_k(q_f) (``get_sum_ST_p``, Simulators.py:643-724), for the frames
+        range(frame_start, frame_end, frame_jump) of the resident animation -- on the device, the projections p never formed
+        at full size and never downloaded.
+
+        ``kinds``: a non-empty list of dicts ``{"kind", "elements", "wi": 1.0, "rest_positions": None, "sigma_min": 1.0,
+        "sigma_max": 1.0}`` with the meanings of ``constraint_projections``; a kind may be listed once.  The terms are added
+        in list order.  ``chunk_frames``: frames per pass of the device (rounded up to a multiple of 16; None: as many as a
+        256 MB scratch holds), which bounds the scratch and changes no bit of the result.
+
+        Returns ``(tensor, F')``: a ``torch.float64`` device tensor (F', N, 3) in world space, allocated here through torch
+        and owned by the caller -- the layout ``posSnapshots.from_device`` adopts.  Leaves ``self.assembly_ST`` (kind -> CSR)
+        and ``self.bending_indices``.  One rank only."""
+        if not isinstance(kinds, (list, tuple)) or len(kinds) == 0:
+            raise ValueError("constraint_forces: kinds must be a non-empty list of dicts, not %r" % (kinds,))
+        if chunk_frames is not None and (int(chunk_frames) != chunk_frames or chunk_frames < 1):
+            raise ValueError("constraint_forces: chunk_frames %r: a positive number of frames or None" % (chunk_frames,))
+        known = ("kind", "elements", "wi", "rest_positions", "sigma_min", "sigma_max")
+        plan, Y, end = [], None, frame_end
+        for spec in kinds:
+            if not isinstance(spec, dict) or "kind" not in spec:
+                raise ValueError("constraint_forces: every entry of kinds is a dict with a 'kind', not %r" % (spec,))
+            extra = sorted(set(spec) - set(known))
+            if extra:
+                raise ValueError("constraint_forces: unknown key %r (one of %s)" % (extra[0], ", ".join(known)))
+            kind, smin, smax = spec["kind"], spec.get("sigma_min", 1.0), spec.get("sigma_max", 1.0)
+            setup, Y, end = self._cproj_args(kind, spec.get("elements"), spec.get("rest_positions"), smin, smax, animation,
+                                             frame_start, frame_end, frame_jump)
+            if any(kind == q[0] for q in plan):
+                raise ValueError("constraint_forces: kind %r is listed twice" % (kind,))
+            plan.append((kind, setup, _proj.assembly_ST(setup, self.nVerts, spec.get("wi", 1.0)), smin, smax))
+        import torch
+        eng = self._engine
+        if Y is not None:
+            eng.heldout_upload(Y, self.massL, self._standarize, self.pre_scale_factor)
+        n_sel = len(range(frame_start, end, frame_jump))
+        out = torch.empty((n_sel, self.nVerts, 3), dtype=torch.float64, device="cuda:%d" % eng.device_id)
+        for i, (kind, setup, St, smin, smax) in enumerate(plan):
+            eng.cproj_setup(setup)
+            eng.cforce_run(0 if Y is None else 1, frame_start, end, frame_jump, self.invMassL, self._standarize,
+                           self.pre_scale_factor, smin, smax, St, i > 0, 0 if chunk_frames is None else int(chunk_frames),
+                           out.data_ptr())
+        self.assembly_ST = {q[0]: q[2] for q in plan}
+        bend = [q[1].bending_indices for q in plan if q[0] == "verts_bending"]
+        self.bending_indices = bend[0] if bend else None
+        return out, n_sel
 
     # ------------------------------------------------------------------ reference methods
     @log_time("")

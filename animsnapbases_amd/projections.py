@@ -102,6 +102,18 @@ def tets_tables(rest, tets, kind="tets_strain"):
     return np.linalg.inv(Dm)
 
 
+def tris_rest_area(rest, tris, P):
+    """A0 = det(P^T [p2 - p1, p3 - p1]) / 2, the signed rest area in the tangent frame (:383)."""
+    e = np.stack([rest[tris[:, 1]] - rest[tris[:, 0]], rest[tris[:, 2]] - rest[tris[:, 0]]], axis=2)
+    return 0.5 * np.linalg.det(np.einsum("tij,tik->tjk", P, e))
+
+
+def tets_rest_volume(rest, tets):
+    """V0 = det(Dm) / 6, the signed rest volume (:506, :640)."""
+    p4 = rest[tets[:, 3]]
+    return np.linalg.det(np.stack([rest[tets[:, 0]] - p4, rest[tets[:, 1]] - p4, rest[tets[:, 2]] - p4], axis=2)) / 6.0
+
+
 def vertex_stars(tris, n_verts):
     """Per vertex the star edges [v2, vOtherT1, t1, vOtherT2, t2] in the order ``DeformableMesh.vertex_star`` appends them
     (:1129-1162): triangles in order, their corners in order, the two other corners in order; a second triangle on a known
@@ -144,7 +156,7 @@ def bending_tables(rest, tris):
             area[vi] += a
     area[area < 1e-7] = 1e-7
     stars = vertex_stars(tris, n)
-    ids, ptr, v2s, wts, rmc, nrm, dwn = [], [0], [], [], [], [], []
+    ids, ptr, v2s, wts, rmc, nrm, dwn, vor = [], [0], [], [], [], [], [], []
     for v in range(n):
         star = stars[v]
         if not star or any(e[4] < 0 for e in star):
@@ -175,10 +187,11 @@ def bending_tables(rest, tris):
         rmc.append(np.linalg.norm(mc))
         nrm.append(tn)
         dwn.append(tn @ mc)
+        vor.append(area[v])
     return dict(indices=np.array(ids, dtype=np.int64), star_ptr=np.array(ptr, dtype=np.int64),
                 star_idx=np.array(v2s, dtype=np.int64), weights=np.array(wts, dtype=np.float64),
                 rest_curvature=np.array(rmc, dtype=np.float64), normal=np.array(nrm, dtype=np.float64).reshape(-1, 3),
-                dot_with_normal=np.array(dwn, dtype=np.float64))
+                dot_with_normal=np.array(dwn, dtype=np.float64), voronoi_area=np.array(vor, dtype=np.float64))
 
 
 def build_setup(kind, elements, rest_positions):
@@ -197,16 +210,61 @@ def build_setup(kind, elements, rest_positions):
     if kind == "tris_strain":
         P, DmInv = tris_strain_tables(rest, el)
         table = np.concatenate([P.reshape(-1, 6), DmInv.reshape(-1, 4)], axis=1)
-        return ProjectionSetup(kind, el, table, parts=dict(P=P, DmInv=DmInv))
+        return ProjectionSetup(kind, el, table, parts=dict(P=P, DmInv=DmInv, A0=tris_rest_area(rest, el, P)))
     if kind in ("tets_strain", "tets_deformation_gradient"):
         DmInv = tets_tables(rest, el, kind)
-        return ProjectionSetup(kind, el, DmInv.reshape(-1, 9), parts=dict(DmInv=DmInv))
+        return ProjectionSetup(kind, el, DmInv.reshape(-1, 9), parts=dict(DmInv=DmInv, V0=tets_rest_volume(rest, el)))
     b = bending_tables(rest, el)
     if b["indices"].shape[0] == 0:
         raise ValueError("verts_bending: no vertex of the mesh has a closed star (every star edge needs two triangles)")
     head = np.concatenate([b["rest_curvature"][:, None], b["normal"], b["dot_with_normal"][:, None]], axis=1)
     return ProjectionSetup(kind, b["indices"][:, None], np.concatenate([head.reshape(-1), b["weights"]]), b["star_ptr"],
                            b["star_idx"], bending_indices=b["indices"], parts=b)
+
+
+def assembly_ST(setup, n_verts, wi=1.0):
+    """The weighted differential operator S^T of one element kind, (n_verts, setup.rows) CSR with sorted indices: what the
+    reference's ``*_assembly_ST`` hold (:1221-1284), restated from the rest tables of ``build_setup``.  Column c belongs to
+    row c of the stacked projections, so ``assembly_ST @ p[f]`` is the kind's term of the global step's right-hand side
+    (Simulators.py:643-724).
+
+      edge_spring   column e: -wi at v0, +wi at v1 (:285-289)
+      tris_strain   columns 2 e + j: G[j] = [DmInv^T | -rowsum(DmInv^T)][j] on (v1, v2, v3), times wi |A0| (:383-405)
+      tets_*        columns 3 e + j: the same with the 3 x 3 DmInv on (v1 .. v4), times wi |V0| (:505-532, :640-667)
+      verts_bending column i: wi_v sum(w) at the constrained vertex, -wi_v w_j at every star neighbour (:189-195), with the
+                    constraint's own weight wi_v = wi * (a third of the incident triangle area, :119, :1216)
+
+    Entries that are exactly zero are not stored; contributions to one (row, column) are summed."""
+    from scipy import sparse
+    wi = float(wi)
+    if not np.isfinite(wi):
+        raise ValueError("%s: the constraint weight wi must be finite, not %r" % (setup.kind, wi))
+    n_verts = int(n_verts)
+    if setup.idx.max() >= n_verts or (setup.star_idx is not None and setup.star_idx.size and setup.star_idx.max() >= n_verts):
+        raise ValueError("%s: an element names vertex %d, S^T has %d rows" % (setup.kind, int(setup.idx.max()), n_verts))
+    kind, idx, q, n = setup.kind, setup.idx, setup.parts, setup.n_elem
+    if kind == "edge_spring":
+        row, col = idx.reshape(-1), np.repeat(np.arange(n), 2)
+        val = np.tile([-wi, wi], n)
+    elif kind == "verts_bending":
+        ptr, w = q["star_ptr"], q["weights"]
+        deg = np.diff(ptr)
+        row = np.concatenate([q["indices"], q["star_idx"]])
+        col = np.concatenate([np.arange(n), np.repeat(np.arange(n), deg)])
+        wv = wi * q["voronoi_area"]
+        val = np.concatenate([np.array([w[ptr[i]:ptr[i + 1]].sum() for i in range(n)]) * wv, -w * np.repeat(wv, deg)])
+    else:
+        p, nv = setup.p, setup.width
+        DmInvT = np.swapaxes(q["DmInv"], 1, 2)
+        G = np.concatenate([DmInvT, -DmInvT.sum(axis=2)[:, :, None]], axis=2)          # (n, p, nv): G[e, j, corner]
+        G = G * wi * np.abs(q["A0"] if kind == "tris_strain" else q["V0"])[:, None, None]
+        row = np.broadcast_to(idx[:, None, :], (n, p, nv)).reshape(-1)
+        col = np.broadcast_to((p * np.arange(n)[:, None] + np.arange(p)[None, :])[:, :, None], (n, p, nv)).reshape(-1)
+        val = G.reshape(-1)
+    St = sparse.coo_matrix((val, (row, col)), shape=(n_verts, setup.rows)).tocsr()     # (sums duplicates)
+    St.eliminate_zeros()
+    St.sort_indices()
+    return St
 
 
 def project_host(setup, positions, sigma_min=1.0, sigma_max=1.0):

@@ -609,6 +609,17 @@ int asb_cproj_setup(asb_ctx* ctx, int kind, int64_t n_elem, const int64_t* idx, 
  * stream has drained. */
 int asb_cproj_run(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean, double psf,
                   double sigma_min, double sigma_max, double* out_dev);
+/* The constraint forces b[f] = S^T p(q_f) of the same frames for the kind of the preceding asb_cproj_setup: the term of that
+ * kind in the global step's right-hand side (get_sum_ST_p, Simulators.py:643-724), without forming p at full size.  The first
+ * ten arguments are those of asb_cproj_run.  S^T: HOST CSR with n_rows = the tensor's vertices, columns = rows of the stacked
+ * projections (< n_elem p), strictly ascending in every row; it is checked before use.  out_dev: caller-owned DEVICE memory,
+ * (n_sel, n_rows, 3) doubles.  accumulate 0: every entry is written (0.0 where a vertex's row is empty); 1: added to what is
+ * there.  chunk_frames: frames per pass (rounded up to a multiple of 16; 0 or too large: the most a 256 MB scratch of
+ * (3 n_elem p) rows holds).  Deterministic: no atomics, every entry is summed by one thread over ascending columns, so
+ * sub-ranges, repeats and any chunk_frames give the same bits.  Returns after the stream has drained. */
+int asb_cforce_run(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean, double psf,
+                   double sigma_min, double sigma_max, int64_t n_rows, const int64_t* indptr, const int64_t* indices,
+                   const double* data, int accumulate, int64_t chunk_frames, double* out_dev);
 
 /* ------------------------------------------------ SPLOCS refinement ----------- */
 /* posComponents.splocs_glob_optimization, snapbases/posComponents.py:132-189.
