@@ -196,6 +196,8 @@ PROTOTYPES = {
                                  c_i64, c_i64]),
     "asb_test_transpose": (c_int, [ctypes.c_void_p, c_dp, c_i64, c_i64, c_dp, c_i64]),
     "asb_test_sym_eig": (c_int, [ctypes.c_void_p, c_dp, c_i64, c_dp, c_dp, ctypes.POINTER(c_int)]),
+    "asb_test_splocs_install": (c_int, [ctypes.c_void_p, c_dp, c_dp, c_dp]),
+    "asb_test_splocs_state": (c_int, [ctypes.c_void_p, c_dp, c_dp, c_dp, c_dp, c_dp]),
 }
 
 

@@ -640,6 +640,34 @@ extern "C" int asb_splocs_results(asb_ctx* ctx, double* C_out, double* W_out) {
     return ASB_OK;
 }
 
+// test hooks (tests/test_gpu_splocs_phases.py): the state between two phases, host arrays, every pointer optional.
+// install: C (K, n_loc, 3), W (F, K) frame-major and U (K, n_loc, 3) replace what asb_splocs_begin left
+extern "C" int asb_test_splocs_install(asb_ctx* ctx, const double* C, const double* W, const double* U) {
+    if (!ctx || !ctx->splocs) return ASB_ERR_ARG;
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    asb_splocs* s = ctx->splocs;
+    const size_t kn3 = (size_t)s->K * 3 * ctx->n_loc * sizeof(double);
+    if (C) ASB_HIP(ctx, hipMemcpyAsync(s->C, C, kn3, hipMemcpyHostToDevice, ctx->stream));
+    if (W) ASB_HIP(ctx, hipMemcpyAsync(s->Wfk, W, (size_t)ctx->F * s->K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (U) ASB_HIP(ctx, hipMemcpyAsync(s->U, U, kn3, hipMemcpyHostToDevice, ctx->stream));
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ASB_OK;
+}
+// state: U (K, n_loc, 3), Lambda (K, n_loc), G = W^T W and Ginv = (G + rho I)^-1 (K, K), c = W^T X (K, 3 n_loc) as the last phase left them
+extern "C" int asb_test_splocs_state(asb_ctx* ctx, double* U, double* Lambda, double* G, double* Ginv, double* c) {
+    if (!ctx || !ctx->splocs) return ASB_ERR_ARG;
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    asb_splocs* s = ctx->splocs;
+    const size_t K = (size_t)s->K, n = (size_t)ctx->n_loc, d = sizeof(double);
+    if (U) ASB_HIP(ctx, hipMemcpyAsync(U, s->U, K * 3 * n * d, hipMemcpyDeviceToHost, ctx->stream));
+    if (Lambda) ASB_HIP(ctx, hipMemcpyAsync(Lambda, s->Lambda, K * n * d, hipMemcpyDeviceToHost, ctx->stream));
+    if (G) ASB_HIP(ctx, hipMemcpyAsync(G, s->G, K * K * d, hipMemcpyDeviceToHost, ctx->stream));
+    if (Ginv) ASB_HIP(ctx, hipMemcpyAsync(Ginv, s->Ginv, K * K * d, hipMemcpyDeviceToHost, ctx->stream));
+    if (c) ASB_HIP(ctx, hipMemcpyAsync(c, s->c, K * 3 * n * d, hipMemcpyDeviceToHost, ctx->stream));
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ASB_OK;
+}
+
 void asb_splocs_free(asb_ctx* ctx) {
     if (ctx->splocs) {
         delete ctx->splocs;       // device buffers are released through ctx->alloc_bytes

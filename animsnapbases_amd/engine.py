@@ -881,6 +881,25 @@ class HipEngine(object):
         assert recs.ndim == 2 and recs.shape[1] == self.xchg_len()
         self._ck(self.lib.asb_test_pick_records(self.h, int(k), ptr(recs), recs.shape[0]))
 
+    # the SPLOCS state between two phases (tests/test_gpu_splocs_phases.py), after splocs_begin
+    def test_splocs_install(self, C=None, W=None, U=None):
+        """Overwrites the SPLOCS state: C (K, n_loc, 3), W (F, K), U (K, n_loc, 3); None leaves a piece as it is."""
+        arrs = []
+        for a, shape in ((C, (self.K, self.n_loc, 3)), (W, (self.F, self.K)), (U, (self.K, self.n_loc, 3))):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                assert a.shape == shape, (a.shape, shape)
+            arrs.append(a)
+        self._ck(self.lib.asb_test_splocs_install(self.h, ptr(arrs[0]), ptr(arrs[1]), ptr(arrs[2])))
+
+    def test_splocs_state(self):
+        """dict: U (K, n_loc, 3), Lambda (K, n_loc), G and Ginv (K, K), c (K, 3 n_loc) as the last phase left them."""
+        K, n = self.K, self.n_loc
+        out = dict(U=np.empty((K, n, 3)), Lambda=np.empty((K, n)), G=np.empty((K, K)), Ginv=np.empty((K, K)), c=np.empty((K, 3 * n)))
+        self._ck(self.lib.asb_test_splocs_state(self.h, ptr(out["U"]), ptr(out["Lambda"]), ptr(out["G"]), ptr(out["Ginv"]),
+                                                ptr(out["c"])))
+        return out
+
     def snapshots_affine(self, inv_scale, add_mean, rowscale_loc=None):
         if rowscale_loc is not None:
             rowscale_loc = np.ascontiguousarray(rowscale_loc, dtype=np.float64)

@@ -625,7 +625,9 @@ int asb_cforce_run(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, 
 /* posComponents.splocs_glob_optimization, snapbases/posComponents.py:132-189.
  * State after a residual-mode deflation: C = comps, W = weigs, U = 0 (:135-139).  One outer
  * iteration = weights -> (host support maps) -> admm -> gram -> objective.  The F x 3N
- * residual is never formed (see csrc/asb_splocs.hip).  K <= 128. */
+ * residual is never formed (see csrc/asb_splocs.hip).  No limit on K of its own: K <= 64 runs the ADMM loop in one fused
+ * launch, larger K the unfused loop (tested up to K = 136); the weight sweep spreads over blocks while 64 rows of W fit the
+ * LDS (K <= 298) and runs in one block beyond. */
 int asb_splocs_begin(asb_ctx* ctx);
 /* P = X C^T (F x K) and M = C C^T (K x K) of this shard for the CURRENT C, into the
  * caller's device buffers (to be all-reduced over ranks) or into the context when NULL.
@@ -710,6 +712,12 @@ int asb_test_gemm_tn(asb_ctx* ctx, int form, const double* X, int64_t ldx, int64
                      int64_t I, int64_t J, double* out, int64_t so_i, int64_t so_j, int64_t out_len, int64_t I_split);
 int asb_test_transpose(asb_ctx* ctx, const double* in, int64_t rows, int64_t cols, double* out, int64_t out_len);
 int asb_test_sym_eig(asb_ctx* ctx, const double* A, int64_t n, double* lam, double* V, int* status);
+/* test hooks of the SPLOCS phases (tests/test_gpu_splocs_phases.py), after asb_splocs_begin; host arrays, every pointer optional.
+ * asb_test_splocs_install: overwrites the state: C (K, n_loc, 3), W (F, K) frame-major, U (K, n_loc, 3).
+ * asb_test_splocs_state: what the last phase left: U (K, n_loc, 3), Lambda (K, n_loc), G = W^T W and Ginv = (G + rho I)^-1 (K, K),
+ * c = W^T X (K, 3 n_loc).  G is written by asb_splocs_weights, the others by asb_splocs_admm(_fields). */
+int asb_test_splocs_install(asb_ctx* ctx, const double* C, const double* W, const double* U);
+int asb_test_splocs_state(asb_ctx* ctx, double* U, double* Lambda, double* G, double* Ginv, double* c);
 
 #ifdef __cplusplus
 }
