@@ -379,11 +379,6 @@ int asb_deflate_apply_dev(asb_ctx* ctx, int64_t k, const double* s_dev);      //
 // G = X^T X (n x n, both triangles) for a tall row-major X: LDS-tiled f64 MFMA kernel (asb_linalg.hip)
 int asb_syrk_tn(asb_ctx* ctx, const double* X, long long ld, long long R, int n, double* out);
 int asb_gemm_tn_big(asb_ctx* ctx, const double* X, long long ldx, const double* Y, long long ldy, long long R, int I, int J, double* out);
-// test hooks (asb_linalg.hip): a device copy of n host doubles (nullptr: NaN) with `slack` NaN behind it; the result's copy back
-// after the stream drains, freeing f0 .. f2 whatever happened (rc: the status so far, passed through)
-int asb_test_stage(asb_ctx* ctx, const double* h, size_t n, size_t slack, double** d);
-int asb_test_finish(asb_ctx* ctx, int rc, double* out_dev, double* out_host, size_t out_len, double* f0, double* f1, double* f2);
-
 #define ASB_CHECK_LAUNCH(ctx) ASB_HIP(ctx, hipGetLastError())
 
 // ASB_DEBUG_PANELS: the panel loop's trace on stderr (changes no result); read once per process
@@ -420,6 +415,35 @@ static inline int asb_alloc(asb_ctx* ctx, T** p, size_t count) {
     ctx->alloc_bytes[(void*)p] = want;
     return ASB_OK;
 }
+
+// A device buffer that lives inside one call: freed when it goes out of scope (hipFree waits for the device, so work still in
+// flight on the buffer is safe), unless release() has handed it to the context.  Buffers that outlive a call go through asb_alloc.
+template <typename T>
+struct asb_tmp {
+    asb_tmp() = default;
+    asb_tmp(const asb_tmp&) = delete;
+    asb_tmp& operator=(const asb_tmp&) = delete;
+    ~asb_tmp() { if (p) (void)hipFree(p); }
+    int alloc(asb_ctx* ctx, size_t count) {          // (an earlier allocation of this owner is freed first)
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        ASB_HIP(ctx, hipMalloc((void**)&p, count * sizeof(T)));
+        return ASB_OK;
+    }
+    T* get() const { return p; }
+    T* release() { T* q = p; p = nullptr; return q; }
+
+private:
+    T* p = nullptr;
+};
+
+// asb_snapshots.hip: the shard [v0, v0 + n_loc) of a host tensor (F, N_glob, 3) and of its mass vector, staged on the device
+int asb_stage_shard(asb_ctx* ctx, const double* X, int64_t F, int64_t N_glob, int64_t v0, int64_t n_loc, const double* massL,
+                    asb_tmp<double>& stage, asb_tmp<double>& mdev);
+// test hooks on host arrays (asb_linalg.hip): a device copy of n host doubles (nullptr: NaN) with `slack` NaN behind it; the
+// copy back of out_len doubles after the stream drains (rc: the status so far, passed through)
+int asb_test_stage(asb_ctx* ctx, const double* h, size_t n, size_t slack, asb_tmp<double>& d);
+int asb_test_finish(asb_ctx* ctx, int rc, const double* out_dev, double* out_host, size_t out_len);
 
 int asb_dl_begin(asb_ctx* ctx);          // asb_linalg.hip
 // component rows [dl_done, k_to) are final: copy them to the pinned buffer on the copy stream, behind what the main stream

@@ -401,14 +401,14 @@ extern "C" int asb_test_eig3_dev(asb_ctx* ctx, int fast, const double* a6, int64
     if (!ctx || !a6 || !out4) return ASB_ERR_ARG;
     if (n < 1 || n > (1 << 24) || out_len < 4 * n) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_eig3_dev: n = %lld, out_len = %lld", (long long)n, (long long)out_len);
     ASB_HIP(ctx, hipSetDevice(ctx->dev));
-    double *da = nullptr, *dout = nullptr;
-    int rc = asb_test_stage(ctx, a6, (size_t)n * 6, 64, &da);
-    if (!rc) rc = asb_test_stage(ctx, out4, (size_t)out_len, 0, &dout);
+    asb_tmp<double> da, dout;
+    int rc = asb_test_stage(ctx, a6, (size_t)n * 6, 64, da);
+    if (!rc) rc = asb_test_stage(ctx, out4, (size_t)out_len, 0, dout);
     if (!rc) {
-        hipLaunchKernelGGL(k_test_eig3, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, da, (long long)n, fast, dout);
+        hipLaunchKernelGGL(k_test_eig3, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, da.get(), (long long)n, fast, dout.get());
         if (hipGetLastError() != hipSuccess) rc = ASB_ERR_HIP;
     }
-    return asb_test_finish(ctx, rc, dout, out4, (size_t)out_len, da, dout, nullptr);
+    return asb_test_finish(ctx, rc, dout.get(), out4, (size_t)out_len);
 }
 
 // component k from the caller: w (F doubles; the padding of the row is zeroed here), |w|^2 as given, then the UPDATE pass of
@@ -462,8 +462,8 @@ extern "C" int asb_test_pick_records(asb_ctx* ctx, int64_t k, const double* recs
     if (!ctx || !ctx->R || !recs) return ASB_ERR_ARG;
     if (n_rec < 1 || n_rec > 16) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_pick_records: %lld records", (long long)n_rec);
     ASB_HIP(ctx, hipSetDevice(ctx->dev));
-    double* d = nullptr;
-    int rc = asb_test_stage(ctx, recs, (size_t)n_rec * (2 + 3 * ctx->Fp), 64, &d);
-    if (!rc) rc = asb_deflate_pick(ctx, k, d, n_rec);
-    return asb_test_finish(ctx, rc, nullptr, nullptr, 0, d, nullptr, nullptr);
+    asb_tmp<double> d;
+    int rc = asb_test_stage(ctx, recs, (size_t)n_rec * (2 + 3 * ctx->Fp), 64, d);
+    if (!rc) rc = asb_deflate_pick(ctx, k, d.get(), n_rec);
+    return asb_test_finish(ctx, rc, nullptr, nullptr, 0);
 }

@@ -591,10 +591,10 @@ extern "C" int asb_test_gemm_nn(asb_ctx* ctx, const double* A, int64_t lda, cons
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_gemm_nn: M = %lld, N = %lld, Kc = %lld, lda = %lld, ldb = %lld, ldc = %lld, c_len = %lld",
                  (long long)M, (long long)N, (long long)Kc, (long long)lda, (long long)ldb, (long long)ldc, (long long)c_len);
     ASB_HIP(ctx, hipSetDevice(ctx->dev));
-    double *da = nullptr, *db = nullptr, *dc = nullptr;
-    int rc = asb_test_stage(ctx, A, (size_t)M * lda, 256, &da);
-    if (!rc) rc = asb_test_stage(ctx, B, (size_t)Kc * ldb, 256, &db);
-    if (!rc) rc = asb_test_stage(ctx, C, (size_t)c_len, 0, &dc);
-    if (!rc) rc = asb_gemm_nn(ctx, da, lda, db, ldb, dc, ldc, (int)M, (int)N, (int)Kc, alpha, beta, tri);
-    return asb_test_finish(ctx, rc, dc, C, (size_t)c_len, da, db, dc);
+    asb_tmp<double> da, db, dc;
+    int rc = asb_test_stage(ctx, A, (size_t)M * lda, 256, da);
+    if (!rc) rc = asb_test_stage(ctx, B, (size_t)Kc * ldb, 256, db);
+    if (!rc) rc = asb_test_stage(ctx, C, (size_t)c_len, 0, dc);
+    if (!rc) rc = asb_gemm_nn(ctx, da.get(), lda, db.get(), ldb, dc.get(), ldc, (int)M, (int)N, (int)Kc, alpha, beta, tri);
+    return asb_test_finish(ctx, rc, dc.get(), C, (size_t)c_len);
 }

@@ -674,7 +674,7 @@ static int bt_factor(asb_ctx* ctx, asb_geo* G, asb_bt& bt, const int* rp, const 
     bt.E.assign(ns, nullptr);
     bt.Et.assign(ns, nullptr);
     int rc;
-    double* Ct = nullptr;                      // A_{k-1,k} (sp_{k-1} x sp_k): scratch, sized for the largest pair
+    asb_tmp<double> Ct;                        // A_{k-1,k} (sp_{k-1} x sp_k): scratch, sized for the largest pair
     size_t ct_cap = 0;
     for (int k = 0; k < ns; ++k) {
         const int sp = G->bt_sz[k], s = ptr[k + 1] - ptr[k];
@@ -692,26 +692,24 @@ static int bt_factor(asb_ctx* ctx, asb_geo* G, asb_bt& bt, const int* rp, const 
             ASB_HIP(ctx, hipMalloc((void**)&bt.Et[k], (size_t)sp * spm * sizeof(double)));
             const size_t need = (size_t)sp * spm;
             if (need > ct_cap) {
-                if (Ct) (void)hipFree(Ct);
-                ASB_HIP(ctx, hipMalloc((void**)&Ct, 2 * need * sizeof(double)));
+                if ((rc = Ct.alloc(ctx, 2 * need))) return rc;
                 ct_cap = need;
             }
-            double* C = Ct + ct_cap;           // A_{k,k-1} (sp x sp_{k-1})
-            ASB_HIP(ctx, hipMemsetAsync(Ct, 0, 2 * ct_cap * sizeof(double), ctx->stream));
+            double* C = Ct.get() + ct_cap;     // A_{k,k-1} (sp x sp_{k-1})
+            ASB_HIP(ctx, hipMemsetAsync(Ct.get(), 0, 2 * ct_cap * sizeof(double), ctx->stream));
             hipLaunchKernelGGL(k_csr_block_dense, dim3(grid), dim3(256), 0, ctx->stream, rp, ci, va, ptr[k], s, ptr[k - 1], sm, C, spm, sp, 0);
             const int gridm = (spm + 3) / 4 < 2048 ? (spm + 3) / 4 : 2048;
-            hipLaunchKernelGGL(k_csr_block_dense, dim3(gridm), dim3(256), 0, ctx->stream, rp, ci, va, ptr[k - 1], sm, ptr[k], s, Ct, sp, spm, 0);
+            hipLaunchKernelGGL(k_csr_block_dense, dim3(gridm), dim3(256), 0, ctx->stream, rp, ci, va, ptr[k - 1], sm, ptr[k], s, Ct.get(), sp, spm, 0);
             ASB_CHECK_LAUNCH(ctx);
             // E_k = A_{k,k-1} D_{k-1}^-1 ; D_k -= E_k A_{k-1,k}
             if ((rc = asb_gemm_nn(ctx, C, spm, bt.Dinv[k - 1], spm, bt.E[k], spm, sp, spm, spm, 1.0, 0.0))) return rc;
-            if ((rc = asb_gemm_nn(ctx, bt.E[k], spm, Ct, sp, bt.Dinv[k], sp, sp, sp, spm, -1.0, 1.0))) return rc;
+            if ((rc = asb_gemm_nn(ctx, bt.E[k], spm, Ct.get(), sp, bt.Dinv[k], sp, sp, sp, spm, -1.0, 1.0))) return rc;
             if ((rc = asb_transpose(ctx, bt.E[k], sp, spm, bt.Et[k]))) return rc;
         }
         ASB_CHECK_LAUNCH(ctx);
         if ((rc = asb_dense_spd_inverse(ctx, bt.Dinv[k], sp))) return rc;
     }
     ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (Ct) (void)hipFree(Ct);
     return ASB_OK;
 }
 
@@ -752,23 +750,24 @@ extern "C" int asb_geodesic_bt_setup(asb_ctx* ctx, int nslab, const int* slab_pt
     if ((rc = asb_alloc(ctx, &G->bt_w, (size_t)G->bt_npad * GB))) return rc;
     ASB_HIP(ctx, hipMemcpyAsync(G->bt_pos, pos.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     // the permuted matrices go to the device for the block extraction only
-    auto up = [&](const int* rp, const int* ci, const double* va, int*& drp, int*& dci, double*& dva) -> int {
+    auto up = [&](const int* rp, const int* ci, const double* va, asb_tmp<int>& drp, asb_tmp<int>& dci, asb_tmp<double>& dva) -> int {
         const long long nnz = rp[n];
-        ASB_HIP(ctx, hipMalloc((void**)&drp, (size_t)(n + 1) * sizeof(int)));
-        ASB_HIP(ctx, hipMalloc((void**)&dci, (size_t)(nnz > 0 ? nnz : 1) * sizeof(int)));
-        ASB_HIP(ctx, hipMalloc((void**)&dva, (size_t)(nnz > 0 ? nnz : 1) * sizeof(double)));
-        ASB_HIP(ctx, hipMemcpyAsync(drp, rp, (size_t)(n + 1) * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        ASB_HIP(ctx, hipMemcpyAsync(dci, ci, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        ASB_HIP(ctx, hipMemcpyAsync(dva, va, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        int r;
+        if ((r = drp.alloc(ctx, (size_t)(n + 1)))) return r;
+        if ((r = dci.alloc(ctx, (size_t)(nnz > 0 ? nnz : 1)))) return r;
+        if ((r = dva.alloc(ctx, (size_t)(nnz > 0 ? nnz : 1)))) return r;
+        ASB_HIP(ctx, hipMemcpyAsync(drp.get(), rp, (size_t)(n + 1) * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        ASB_HIP(ctx, hipMemcpyAsync(dci.get(), ci, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        ASB_HIP(ctx, hipMemcpyAsync(dva.get(), va, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
         return ASB_OK;
     };
-    int *hrp = nullptr, *hci = nullptr, *lrp = nullptr, *lci = nullptr;
-    double *hva = nullptr, *lva = nullptr;
+    asb_tmp<int> hrp, hci, lrp, lci;
+    asb_tmp<double> hva, lva;
     auto body = [&]() -> int {
         int r;
         if ((r = up(heat_rp, heat_ci, heat_v, hrp, hci, hva))) return r;
         if ((r = up(lap_rp, lap_ci, lap_v, lrp, lci, lva))) return r;
-        if ((r = bt_factor(ctx, G, G->Hbt, hrp, hci, hva, ptr, -1, 0.0))) return r;
+        if ((r = bt_factor(ctx, G, G->Hbt, hrp.get(), hci.get(), hva.get(), ptr, -1, 0.0))) return r;
         // ground the LAST vertex of the permuted numbering with the mean diagonal of -L (keeps the conditioning)
         double gamma = 0.0;
         for (int q = 0; q < n; ++q)
@@ -776,12 +775,10 @@ extern "C" int asb_geodesic_bt_setup(asb_ctx* ctx, int nslab, const int* slab_pt
                 if (lap_ci[j] == q) gamma += lap_v[j];
         gamma /= n;
         if (!(gamma > 0.0)) ASB_FAIL(ctx, ASB_ERR_NUMERIC, "slab geodesics: the Laplacian has a non-positive mean diagonal");
-        return bt_factor(ctx, G, G->Pbt, lrp, lci, lva, ptr, n - 1, gamma);
+        return bt_factor(ctx, G, G->Pbt, lrp.get(), lci.get(), lva.get(), ptr, n - 1, gamma);
     };
     rc = body();
     (void)hipStreamSynchronize(ctx->stream);
-    for (void* p : {(void*)hrp, (void*)hci, (void*)hva, (void*)lrp, (void*)lci, (void*)lva})
-        if (p) (void)hipFree(p);
     if (rc) return rc;
     G->bt = true;
     G->dense = false;

@@ -95,23 +95,19 @@ __global__ __launch_bounds__(256) void k_apply_rbm(double* __restrict__ frames, 
 extern "C" int asb_align_frames(asb_ctx* ctx, double* frames, int64_t F, int64_t N, int rigid, double* T_out) {
     if (!ctx || !frames || F < 1 || N < 1) return ASB_ERR_ARG;
     ASB_HIP(ctx, hipSetDevice(ctx->dev));
-    double *d = nullptr, *T = nullptr;
+    asb_tmp<double> d, T;
     const size_t bytes = (size_t)F * N * 3 * sizeof(double);
-    ASB_HIP(ctx, hipMalloc((void**)&d, bytes));
-    hipError_t e = hipMalloc((void**)&T, (size_t)F * 16 * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpyAsync(d, frames, bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_procrustes, dim3((unsigned)F), dim3(256), 0, ctx->stream, d, (long long)N, rigid, T);
-        long long bx = (N + 255) / 256;
-        hipLaunchKernelGGL(k_apply_rbm, dim3((unsigned)(bx < 1024 ? bx : 1024), (unsigned)F), dim3(256), 0, ctx->stream, d,
-                           (long long)N, T);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(frames, d, bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && T_out) e = hipMemcpyAsync(T_out, T, (size_t)F * 16 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
-    if (T) (void)hipFree(T);
-    if (e != hipSuccess) ASB_FAIL(ctx, ASB_ERR_HIP, "asb_align_frames: %s", hipGetErrorString(e));
+    int rc;
+    if ((rc = d.alloc(ctx, (size_t)F * N * 3))) return rc;
+    if ((rc = T.alloc(ctx, (size_t)F * 16))) return rc;
+    ASB_HIP(ctx, hipMemcpyAsync(d.get(), frames, bytes, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_procrustes, dim3((unsigned)F), dim3(256), 0, ctx->stream, d.get(), (long long)N, rigid, T.get());
+    long long bx = (N + 255) / 256;
+    hipLaunchKernelGGL(k_apply_rbm, dim3((unsigned)(bx < 1024 ? bx : 1024), (unsigned)F), dim3(256), 0, ctx->stream, d.get(),
+                       (long long)N, T.get());
+    ASB_CHECK_LAUNCH(ctx);
+    ASB_HIP(ctx, hipMemcpyAsync(frames, d.get(), bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (T_out) ASB_HIP(ctx, hipMemcpyAsync(T_out, T.get(), (size_t)F * 16 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return ASB_OK;
 }

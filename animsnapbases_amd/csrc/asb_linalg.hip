@@ -582,21 +582,17 @@ extern "C" int asb_components_transform(asb_ctx* ctx, const double* T_host) {
 extern "C" int asb_components_expand(asb_ctx* ctx, const double* coef_host, int64_t r, int64_t Fo, double* out_host) {
     if (!ctx || !ctx->comps || !coef_host || !out_host || r < 1 || r > ctx->K || Fo < 1) return ASB_ERR_ARG;
     const int64_t n = ctx->n_loc;
-    double *dc = nullptr, *dout = nullptr;
-    ASB_HIP(ctx, hipMalloc((void**)&dc, (size_t)3 * r * Fo * sizeof(double)));
-    hipError_t e = hipMalloc((void**)&dout, (size_t)Fo * 3 * n * sizeof(double));
-    int rc = ASB_OK;
-    if (e == hipSuccess) e = hipMemcpyAsync(dc, coef_host, (size_t)3 * r * Fo * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    for (int l = 0; l < 3 && e == hipSuccess && rc == ASB_OK; ++l)
-        rc = asb_gemm_tn_s(ctx, ctx->comps + l, 3 * n, 3, dc + (size_t)l * r * Fo, Fo, r, (int)n, (int)Fo, dout + l, 3, 3 * n,
-                           (long long)ctx->N_glob);
-    if (e == hipSuccess && rc == ASB_OK)
-        e = hipMemcpyAsync(out_host, dout, (size_t)Fo * 3 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(dc);
-    if (dout) (void)hipFree(dout);
-    if (rc) return rc;
-    if (e != hipSuccess) ASB_FAIL(ctx, ASB_ERR_HIP, "asb_components_expand: %s", hipGetErrorString(e));
+    asb_tmp<double> dc, dout;
+    int rc;
+    if ((rc = dc.alloc(ctx, (size_t)3 * r * Fo))) return rc;
+    if ((rc = dout.alloc(ctx, (size_t)Fo * 3 * n))) return rc;
+    ASB_HIP(ctx, hipMemcpyAsync(dc.get(), coef_host, (size_t)3 * r * Fo * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    for (int l = 0; l < 3; ++l)
+        if ((rc = asb_gemm_tn_s(ctx, ctx->comps + l, 3 * n, 3, dc.get() + (size_t)l * r * Fo, Fo, r, (int)n, (int)Fo, dout.get() + l, 3,
+                                3 * n, (long long)ctx->N_glob)))
+            return rc;
+    ASB_HIP(ctx, hipMemcpyAsync(out_host, dout.get(), (size_t)Fo * 3 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return ASB_OK;
 }
 
@@ -720,27 +716,19 @@ extern "C" int asb_components_pinned(asb_ctx* ctx, double** out) {
 // ---- test hooks on host arrays (tests/test_gpu_dense_blocks.py) ----------------------------------------------------------
 // A device copy of a host array of n doubles with `slack` NaN behind it (h == nullptr: n NaN too), so that a read past an
 // operand shows in the result; the buffers are the hook's own, not the production callers' padded ones.
-int asb_test_stage(asb_ctx* ctx, const double* h, size_t n, size_t slack, double** d) {
-    *d = nullptr;
-    ASB_HIP(ctx, hipMalloc((void**)d, (n + slack) * sizeof(double)));
-    hipError_t e = hipMemsetAsync(*d, 0xff, (n + slack) * sizeof(double), ctx->stream);       // all bits set: a NaN
-    if (e == hipSuccess && h && n) e = hipMemcpyAsync(*d, h, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-        (void)hipFree(*d);
-        *d = nullptr;
-        ASB_FAIL(ctx, ASB_ERR_HIP, "asb_test_stage: %s", hipGetErrorString(e));
-    }
+int asb_test_stage(asb_ctx* ctx, const double* h, size_t n, size_t slack, asb_tmp<double>& d) {
+    int rc;
+    if ((rc = d.alloc(ctx, n + slack))) return rc;
+    ASB_HIP(ctx, hipMemsetAsync(d.get(), 0xff, (n + slack) * sizeof(double), ctx->stream));       // all bits set: a NaN
+    if (h && n) ASB_HIP(ctx, hipMemcpyAsync(d.get(), h, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return ASB_OK;
 }
-// out_len doubles device -> host after the stream has drained; frees the listed buffers whatever happened
-int asb_test_finish(asb_ctx* ctx, int rc, double* out_dev, double* out_host, size_t out_len, double* f0, double* f1, double* f2) {
+// out_len doubles device -> host after the stream has drained (out_host == nullptr: the drain only)
+int asb_test_finish(asb_ctx* ctx, int rc, const double* out_dev, double* out_host, size_t out_len) {
     hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (rc == ASB_OK && e == hipSuccess && out_host) e = hipMemcpy(out_host, out_dev, out_len * sizeof(double), hipMemcpyDeviceToHost);
-    (void)hipFree(f0);
-    (void)hipFree(f1);
-    (void)hipFree(f2);
     if (rc) return rc;
+    if (e == hipSuccess && out_host) e = hipMemcpy(out_host, out_dev, out_len * sizeof(double), hipMemcpyDeviceToHost);
     if (e != hipSuccess) ASB_FAIL(ctx, ASB_ERR_HIP, "asb test hook: %s", hipGetErrorString(e));
     return ASB_OK;
 }
@@ -757,16 +745,16 @@ extern "C" int asb_test_gemm_tn(asb_ctx* ctx, int form, const double* X, int64_t
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_gemm_tn: form %d, R = %lld, I = %lld, J = %lld, ldx = %lld, ldy = %lld, out_len = %lld",
                  form, (long long)R, (long long)I, (long long)J, (long long)ldx, (long long)ldy, (long long)out_len);
     ASB_HIP(ctx, hipSetDevice(ctx->dev));
-    double *dx = nullptr, *dy = nullptr, *dout = nullptr;
-    int rc = asb_test_stage(ctx, X, (size_t)R * ldx, 256, &dx);
-    if (!rc && form != 2) rc = asb_test_stage(ctx, Y, (size_t)R * ldy, 256, &dy);
-    if (!rc) rc = asb_test_stage(ctx, out, (size_t)out_len, 0, &dout);
+    asb_tmp<double> dx, dy, dout;
+    int rc = asb_test_stage(ctx, X, (size_t)R * ldx, 256, dx);
+    if (!rc && form != 2) rc = asb_test_stage(ctx, Y, (size_t)R * ldy, 256, dy);
+    if (!rc) rc = asb_test_stage(ctx, out, (size_t)out_len, 0, dout);
     if (!rc) {
-        if (form == 0) rc = asb_gemm_tn_s(ctx, dx, ldx, sx, dy, ldy, R, (int)I, (int)J, dout, so_i, so_j, I_split);
-        else if (form == 1) rc = asb_gemm_tn_big(ctx, dx, ldx, dy, ldy, R, (int)I, (int)J, dout);
-        else rc = asb_syrk_tn(ctx, dx, ldx, R, (int)I, dout);
+        if (form == 0) rc = asb_gemm_tn_s(ctx, dx.get(), ldx, sx, dy.get(), ldy, R, (int)I, (int)J, dout.get(), so_i, so_j, I_split);
+        else if (form == 1) rc = asb_gemm_tn_big(ctx, dx.get(), ldx, dy.get(), ldy, R, (int)I, (int)J, dout.get());
+        else rc = asb_syrk_tn(ctx, dx.get(), ldx, R, (int)I, dout.get());
     }
-    return asb_test_finish(ctx, rc, dout, out, (size_t)out_len, dx, dy, dout);
+    return asb_test_finish(ctx, rc, dout.get(), out, (size_t)out_len);
 }
 
 // in (rows x cols) -> out[c rows + r]; the whole of out (out_len >= rows cols) round-trips
@@ -775,11 +763,11 @@ extern "C" int asb_test_transpose(asb_ctx* ctx, const double* in, int64_t rows, 
     if (rows < 1 || cols < 1 || rows * cols > out_len || (rows + 31) / 32 > 65535)
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_transpose: %lld x %lld, out_len = %lld", (long long)rows, (long long)cols, (long long)out_len);
     ASB_HIP(ctx, hipSetDevice(ctx->dev));
-    double *din = nullptr, *dout = nullptr;
-    int rc = asb_test_stage(ctx, in, (size_t)rows * cols, 256, &din);
-    if (!rc) rc = asb_test_stage(ctx, out, (size_t)out_len, 0, &dout);
-    if (!rc) rc = asb_transpose(ctx, din, rows, cols, dout);
-    return asb_test_finish(ctx, rc, dout, out, (size_t)out_len, din, dout, nullptr);
+    asb_tmp<double> din, dout;
+    int rc = asb_test_stage(ctx, in, (size_t)rows * cols, 256, din);
+    if (!rc) rc = asb_test_stage(ctx, out, (size_t)out_len, 0, dout);
+    if (!rc) rc = asb_transpose(ctx, din.get(), rows, cols, dout.get());
+    return asb_test_finish(ctx, rc, dout.get(), out, (size_t)out_len);
 }
 
 // the one-block Jacobi solver (n <= 128) on a host matrix: lam (n) descending, V (n x n) eigenvectors as columns;
@@ -788,14 +776,14 @@ extern "C" int asb_test_sym_eig(asb_ctx* ctx, const double* A, int64_t n, double
     if (!ctx || !A || !lam || !V || !status) return ASB_ERR_ARG;
     if (n < 1 || n > 128) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_sym_eig: n = %lld (the one-block solver takes 1 .. 128)", (long long)n);
     ASB_HIP(ctx, hipSetDevice(ctx->dev));
-    double *da = nullptr, *dv = nullptr;
-    int rc = asb_test_stage(ctx, A, (size_t)n * n, 256, &da);
-    if (!rc) rc = asb_test_stage(ctx, nullptr, (size_t)n * n + n, 0, &dv);         // V, then lam
-    if (!rc) rc = asb_sym_eig(ctx, da, (int)n, dv + (size_t)n * n, dv);
+    asb_tmp<double> da, dv;
+    int rc = asb_test_stage(ctx, A, (size_t)n * n, 256, da);
+    if (!rc) rc = asb_test_stage(ctx, nullptr, (size_t)n * n + n, 0, dv);         // V, then lam
+    if (!rc) rc = asb_sym_eig(ctx, da.get(), (int)n, dv.get() + (size_t)n * n, dv.get());
     int st[4] = {0, 0, 0, 0};
     if (!rc && hipMemcpyAsync(st, ctx->la_status, sizeof(st), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = ASB_ERR_HIP;
     std::vector<double> h((size_t)n * n + n);
-    rc = asb_test_finish(ctx, rc, dv, h.data(), h.size(), da, dv, nullptr);
+    rc = asb_test_finish(ctx, rc, dv.get(), h.data(), h.size());
     if (rc) return rc;
     std::copy(h.begin(), h.begin() + n * n, V);
     std::copy(h.begin() + n * n, h.end(), lam);

@@ -455,29 +455,37 @@ extern "C" int asb_pod_deflate_begin(asb_ctx* ctx, const double* B_dev, int64_t 
     int rc;
     // the kept rows join the earlier levels' (pod_u1 grows: old content first)
     const size_t have = (size_t)ctx->pod_u1_rows * n3, add = (size_t)keep * n3;
-    double* u1 = nullptr;
-    ASB_HIP(ctx, hipMalloc((void**)&u1, (have + add) * sizeof(double)));
-    if (have) ASB_HIP(ctx, hipMemcpyAsync(u1, ctx->pod_u1, have * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    ASB_HIP(ctx, hipMemcpyAsync(u1 + have, ctx->comps, add * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    asb_tmp<double> u1;
+    if ((rc = u1.alloc(ctx, have + add))) return rc;
+    if (have) ASB_HIP(ctx, hipMemcpyAsync(u1.get(), ctx->pod_u1, have * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    ASB_HIP(ctx, hipMemcpyAsync(u1.get() + have, ctx->comps, add * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // u1 is complete: it replaces pod_u1, whose first pod_u1_rows rows are unchanged; the count follows once the level stands
     if (ctx->pod_u1) (void)hipFree(ctx->pod_u1);
-    ctx->pod_u1 = u1;
-    ctx->pod_u1_rows += keep;
+    ctx->pod_u1 = u1.release();
     // B_1 = U_1^T A in sorted order = the gathered rows of the rotated B; oct_1 = U_1^T (3n x keep)
     if ((rc = asb_alloc(ctx, &ctx->pod_vn, (size_t)F * K))) return rc;
     hipLaunchKernelGGL(k_gather_b, dim3(1024), dim3(256), 0, ctx->stream, B, (int)F, (int)keep, ctx->jac_where, ctx->pod_vn);
     ASB_CHECK_LAUNCH(ctx);
     if ((rc = asb_alloc(ctx, &ctx->comps2, (size_t)K * n3))) return rc;
     if ((rc = asb_transpose(ctx, ctx->comps, keep, n3, ctx->comps2))) return rc;          // (3n x keep)
-    // A_2 = A - oct_1 B_1 into the second snapshot buffer
+    // A_2 = A - oct_1 B_1 into the second snapshot buffer (the first level allocates and fills it; later levels deflate it in
+    // place); the context switches to it only once everything is enqueued
     const size_t nx = (size_t)n3 * ctx->Fp;
+    asb_tmp<double> xd;
+    double* X_deflated = ctx->X_deflated;
+    if (!X_deflated) {
+        if ((rc = xd.alloc(ctx, nx))) return rc;
+        X_deflated = xd.get();
+        ASB_HIP(ctx, hipMemcpyAsync(X_deflated, ctx->X, nx * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    if ((rc = asb_gemm_nn(ctx, ctx->comps2, keep, ctx->pod_vn, F, X_deflated, ctx->Fp, (int)n3, (int)F, (int)keep, -1.0, 1.0))) return rc;
     if (!ctx->X_deflated) {
-        ASB_HIP(ctx, hipMalloc((void**)&ctx->X_deflated, nx * sizeof(double)));
-        ASB_HIP(ctx, hipMemcpyAsync(ctx->X_deflated, ctx->X, nx * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+        ctx->X_deflated = xd.release();
         ctx->X_original = ctx->X;
         ctx->X = ctx->X_deflated;
     }
-    if ((rc = asb_gemm_nn(ctx, ctx->comps2, keep, ctx->pod_vn, F, ctx->X, ctx->Fp, (int)n3, (int)F, (int)keep, -1.0, 1.0))) return rc;
+    ctx->pod_u1_rows += keep;
     ctx->e0_valid = false;
     ctx->ev_valid = false;
     return ASB_OK;
@@ -488,16 +496,17 @@ extern "C" int asb_pod_deflate_end(asb_ctx* ctx, int64_t last) {
     const int64_t n3 = 3 * ctx->n_loc;
     if (last < 0 || last > ctx->K) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pod_deflate_end: last = %lld of %lld", (long long)last, (long long)ctx->K);
     const int64_t Kt = ctx->pod_u1_rows + last;
-    double* nb = nullptr;
-    ASB_HIP(ctx, hipMalloc((void**)&nb, (size_t)Kt * n3 * sizeof(double)));
-    ASB_HIP(ctx, hipMemcpyAsync(nb, ctx->pod_u1, (size_t)ctx->pod_u1_rows * n3 * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    asb_tmp<double> nb;
+    int rc;
+    if ((rc = nb.alloc(ctx, (size_t)Kt * n3))) return rc;
+    ASB_HIP(ctx, hipMemcpyAsync(nb.get(), ctx->pod_u1, (size_t)ctx->pod_u1_rows * n3 * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     if (last)
-        ASB_HIP(ctx, hipMemcpyAsync(nb + (size_t)ctx->pod_u1_rows * n3, ctx->comps, (size_t)last * n3 * sizeof(double),
+        ASB_HIP(ctx, hipMemcpyAsync(nb.get() + (size_t)ctx->pod_u1_rows * n3, ctx->comps, (size_t)last * n3 * sizeof(double),
                                     hipMemcpyDeviceToDevice, ctx->stream));
     ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     // the context's basis buffer is replaced (asb_alloc's bookkeeping follows the pointer variable)
     if (ctx->comps) (void)hipFree(ctx->comps);
-    ctx->comps = nb;
+    ctx->comps = nb.release();
     ctx->alloc_bytes[(void*)&ctx->comps] = (size_t)Kt * n3 * sizeof(double);
     ctx->K = Kt;
     ctx->X = ctx->X_original;

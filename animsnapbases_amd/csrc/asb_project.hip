@@ -1831,32 +1831,17 @@ extern "C" int asb_test_project_columns(asb_ctx* ctx, const double* W_host, int6
                  (long long)ldw, (long long)out_cols, path);
     ASB_HIP(ctx, hipSetDevice(ctx->dev));
     const size_t rows = (size_t)3 * ctx->n_loc, nw = (size_t)ctx->F * ldw, no = (size_t)out_cols * rows;
-    double *W = nullptr, *sc = nullptr, *out = nullptr;
-    hipError_t e = hipMalloc((void**)&W, nw * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&out, no * sizeof(double));
-    if (e == hipSuccess && col_scale_host) e = hipMalloc((void**)&sc, (size_t)ldw * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(W, W_host, nw * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(out, out_host, no * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess && sc) e = hipMemcpy(sc, col_scale_host, (size_t)ldw * sizeof(double), hipMemcpyHostToDevice);
-    int rc = ASB_OK;
-    if (e == hipSuccess) {
-        if (path == 1) {
-            rc = asb_project_columns_wide(ctx, W, ldw, k0, ncols, out, sc);
-        } else {
-            for (int j = 0; j < ncols && rc == ASB_OK; j += ASB_PANEL_COLS) {
-                const int nc = ncols - j < ASB_PANEL_COLS ? ncols - j : ASB_PANEL_COLS;
-                rc = asb_project_columns(ctx, W, ldw, k0 + j, nc, out + (size_t)j * rows, sc);
-            }
+    asb_tmp<double> W, out, sc;
+    int rc = asb_test_stage(ctx, W_host, nw, 0, W);
+    if (!rc) rc = asb_test_stage(ctx, out_host, no, 0, out);
+    if (!rc && col_scale_host) rc = asb_test_stage(ctx, col_scale_host, (size_t)ldw, 0, sc);
+    if (!rc && path == 1) rc = asb_project_columns_wide(ctx, W.get(), ldw, k0, ncols, out.get(), sc.get());
+    if (path == 0)
+        for (int j = 0; j < ncols && rc == ASB_OK; j += ASB_PANEL_COLS) {
+            const int nc = ncols - j < ASB_PANEL_COLS ? ncols - j : ASB_PANEL_COLS;
+            rc = asb_project_columns(ctx, W.get(), ldw, k0 + j, nc, out.get() + (size_t)j * rows, sc.get());
         }
-        e = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess) e = hipMemcpy(out_host, out, no * sizeof(double), hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(W);
-    (void)hipFree(out);
-    if (sc) (void)hipFree(sc);
-    if (rc) return rc;
-    if (e != hipSuccess) ASB_FAIL(ctx, ASB_ERR_HIP, "asb_test_project_columns: %s", hipGetErrorString(e));
-    return ASB_OK;
+    return asb_test_finish(ctx, rc, out.get(), out_host, no);
 }
 
 // start of a run on a tensor whose initial energies are known (E0): scal <- 0, hist <- 0, energy <- E0, range scalars restored --

@@ -196,23 +196,12 @@ extern "C" int asb_heldout_upload(asb_ctx* ctx, const double* Y, int64_t F, int6
     ctx->ho_Fp = Fp;
     ctx->ho_K = 0;
     ASB_HIP(ctx, hipMemsetAsync(ctx->ho_Y, 0, (size_t)rows * Fp * sizeof(double), ctx->stream));
-    double *stage = nullptr, *mdev = nullptr;
-    ASB_HIP(ctx, hipMalloc((void**)&stage, (size_t)F * rows * sizeof(double)));
-    hipError_t e = hipMemcpy2DAsync(stage, rows * sizeof(double), Y + v0 * 3, (size_t)N_glob * 3 * sizeof(double), rows * sizeof(double),
-                                    (size_t)F, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && massL) {
-        e = hipMalloc((void**)&mdev, (size_t)n_loc * sizeof(double));
-        if (e == hipSuccess) e = hipMemcpyAsync(mdev, massL + v0, (size_t)n_loc * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_heldout_prep, dim3(grid_for(rows * F)), dim3(256), 0, ctx->stream, stage, (long long)F, (long long)n_loc,
-                           mdev, ctx->mean, subtract, pre_scale_factor, ctx->ho_Y, Fp);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    }
-    (void)hipFree(stage);
-    if (mdev) (void)hipFree(mdev);
-    if (e != hipSuccess) ASB_FAIL(ctx, ASB_ERR_HIP, "asb_heldout_upload: %s", hipGetErrorString(e));
+    asb_tmp<double> stage, mdev;
+    if ((rc = asb_stage_shard(ctx, Y, F, N_glob, v0, n_loc, massL, stage, mdev))) return rc;
+    hipLaunchKernelGGL(k_heldout_prep, dim3(grid_for(rows * F)), dim3(256), 0, ctx->stream, stage.get(), (long long)F, (long long)n_loc,
+                       mdev.get(), ctx->mean, subtract, pre_scale_factor, ctx->ho_Y, Fp);
+    ASB_CHECK_LAUNCH(ctx);
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return ASB_OK;
 }
 

@@ -600,61 +600,48 @@ int asb_chol_tinv_dev(asb_ctx* ctx, const double* G, int K, double* Tt, int* sta
 extern "C" int asb_test_tridiag_eig(asb_ctx* ctx, const double* d, const double* e, int64_t n, int64_t k, double* lam_desc,
                                     double* Z, int64_t* n_bad) {
     if (!ctx || !d || !lam_desc || n < 1 || k < 0 || k > n || (n > 1 && !e) || (k > 0 && !Z)) return ASB_ERR_ARG;
-    double *dd = nullptr, *dl = nullptr, *dz = nullptr;
-    ASB_HIP(ctx, hipMalloc((void**)&dd, (size_t)2 * n * sizeof(double)));
-    ASB_HIP(ctx, hipMalloc((void**)&dl, (size_t)n * sizeof(double)));
-    ASB_HIP(ctx, hipMalloc((void**)&dz, (size_t)(k > 0 ? n * k : 1) * sizeof(double)));
-    ASB_HIP(ctx, hipMemcpyAsync(dd, d, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (n > 1) ASB_HIP(ctx, hipMemcpyAsync(dd + n, e, (size_t)(n - 1) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    asb_tmp<double> dd, dl, dz;
+    int rc = asb_test_stage(ctx, nullptr, (size_t)2 * n, 0, dd);          // d, then e
+    if (!rc) rc = asb_test_stage(ctx, nullptr, (size_t)n, 0, dl);
+    if (!rc) rc = asb_test_stage(ctx, nullptr, (size_t)(k > 0 ? n * k : 1), 0, dz);
+    if (rc) return rc;
+    ASB_HIP(ctx, hipMemcpyAsync(dd.get(), d, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (n > 1) ASB_HIP(ctx, hipMemcpyAsync(dd.get() + n, e, (size_t)(n - 1) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     int bad = 0;
-    int rc = asb_tri_eig_dev(ctx, dd, dd + n, (int)n, (int)k, dl, dz, &bad);
-    if (rc == ASB_OK) {
-        (void)hipMemcpyAsync(lam_desc, dl, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-        if (k > 0) (void)hipMemcpyAsync(Z, dz, (size_t)n * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-        (void)hipStreamSynchronize(ctx->stream);
-    }
+    rc = asb_tri_eig_dev(ctx, dd.get(), dd.get() + n, (int)n, (int)k, dl.get(), dz.get(), &bad);
+    rc = asb_test_finish(ctx, rc, dl.get(), lam_desc, (size_t)n);
+    if (k > 0) rc = asb_test_finish(ctx, rc, dz.get(), Z, (size_t)n * k);
     if (n_bad) *n_bad = bad;
-    (void)hipFree(dd); (void)hipFree(dl); (void)hipFree(dz);
     return rc;
 }
 
 extern "C" int asb_test_jacobi_rows(asb_ctx* ctx, const double* A, int64_t nv, int64_t m, double* U /* nv x nv, columns */,
                                     double* sig, int64_t* sweeps) {
     if (!ctx || !A || !sig || nv < 1 || m < 1) return ASB_ERR_ARG;
-    double *da = nullptr, *dq = nullptr, *ds = nullptr;
-    ASB_HIP(ctx, hipMalloc((void**)&da, (size_t)nv * m * sizeof(double)));
-    ASB_HIP(ctx, hipMalloc((void**)&dq, (size_t)nv * nv * sizeof(double)));
-    ASB_HIP(ctx, hipMalloc((void**)&ds, (size_t)nv * sizeof(double)));
-    ASB_HIP(ctx, hipMemcpyAsync(da, A, (size_t)nv * m * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    asb_tmp<double> da, dq, ds;
+    int rc = asb_test_stage(ctx, A, (size_t)nv * m, 0, da);
+    if (!rc) rc = asb_test_stage(ctx, nullptr, (size_t)nv * nv, 0, dq);
+    if (!rc) rc = asb_test_stage(ctx, nullptr, (size_t)nv, 0, ds);
     int sw = 0;
-    int rc = asb_jacobi_rows_dev(ctx, da, (int)nv, (int)m, m, U ? dq : nullptr, 1, ds, &sw);
-    if (rc == ASB_OK) {
-        (void)hipMemcpyAsync(sig, ds, (size_t)nv * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-        if (U) (void)hipMemcpyAsync(U, dq, (size_t)nv * nv * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-        (void)hipStreamSynchronize(ctx->stream);
-    }
+    if (!rc) rc = asb_jacobi_rows_dev(ctx, da.get(), (int)nv, (int)m, m, U ? dq.get() : nullptr, 1, ds.get(), &sw);
+    rc = asb_test_finish(ctx, rc, ds.get(), sig, (size_t)nv);
+    if (U) rc = asb_test_finish(ctx, rc, dq.get(), U, (size_t)nv * nv);
     if (sweeps) *sweeps = sw;
-    (void)hipFree(da); (void)hipFree(dq); (void)hipFree(ds);
     return rc;
 }
 
 extern "C" int asb_test_chol_tinv(asb_ctx* ctx, const double* G, int64_t K, double* Tt) {
     if (!ctx || !G || !Tt || K < 1) return ASB_ERR_ARG;
-    double *dg = nullptr, *dt = nullptr;
+    asb_tmp<double> dg, dt;
     int rc;
     if ((rc = asb_alloc(ctx, &ctx->la_status, (size_t)4))) return rc;
-    ASB_HIP(ctx, hipMalloc((void**)&dg, (size_t)K * K * sizeof(double)));
-    ASB_HIP(ctx, hipMalloc((void**)&dt, (size_t)K * K * sizeof(double)));
-    ASB_HIP(ctx, hipMemcpyAsync(dg, G, (size_t)K * K * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = asb_test_stage(ctx, G, (size_t)K * K, 0, dg))) return rc;
+    if ((rc = asb_test_stage(ctx, nullptr, (size_t)K * K, 0, dt))) return rc;
     ASB_HIP(ctx, hipMemsetAsync(ctx->la_status, 0, 4 * sizeof(int), ctx->stream));
-    rc = asb_chol_tinv_dev(ctx, dg, (int)K, dt, ctx->la_status);
+    if ((rc = asb_chol_tinv_dev(ctx, dg.get(), (int)K, dt.get(), ctx->la_status))) return rc;
     int st[4] = {0, 0, 0, 0};
-    if (rc == ASB_OK) {
-        (void)hipMemcpyAsync(Tt, dt, (size_t)K * K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-        (void)hipMemcpyAsync(st, ctx->la_status, sizeof(st), hipMemcpyDeviceToHost, ctx->stream);
-        (void)hipStreamSynchronize(ctx->stream);
-    }
-    (void)hipFree(dg); (void)hipFree(dt);
-    if (rc == ASB_OK && st[0]) ASB_FAIL(ctx, ASB_ERR_NUMERIC, "Cholesky: the matrix is not positive definite");
-    return rc;
+    ASB_HIP(ctx, hipMemcpyAsync(st, ctx->la_status, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = asb_test_finish(ctx, rc, dt.get(), Tt, (size_t)K * K))) return rc;
+    if (st[0]) ASB_FAIL(ctx, ASB_ERR_NUMERIC, "Cholesky: the matrix is not positive definite");
+    return ASB_OK;
 }

@@ -410,51 +410,6 @@ static int transpose_in(asb_ctx* ctx, const double* stage_dev, const double* mas
     return ASB_OK;
 }
 
-extern "C" int asb_snapshots_upload(asb_ctx* ctx, const double* X, int64_t F, int64_t N_glob, int64_t v0,
-                                    int64_t n_loc, const double* massL) {
-    if (!ctx || !X) return ASB_ERR_ARG;
-    ASB_HIP(ctx, hipSetDevice(ctx->dev));
-    int rc = set_shape(ctx, F, N_glob, v0, n_loc);
-    if (rc) return rc;
-    double* stage = nullptr;
-    double* mdev = nullptr;
-    const size_t C = (size_t)n_loc * 3;
-    ASB_HIP(ctx, hipMalloc((void**)&stage, (size_t)F * C * sizeof(double)));
-    hipError_t e = hipMemcpy2DAsync(stage, C * sizeof(double), X + v0 * 3, (size_t)N_glob * 3 * sizeof(double),
-                                    C * sizeof(double), (size_t)F, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && massL) {
-        e = hipMalloc((void**)&mdev, (size_t)n_loc * sizeof(double));
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(mdev, massL + v0, (size_t)n_loc * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    }
-    if (e == hipSuccess) {
-        rc = transpose_in(ctx, stage, mdev);
-        e = hipStreamSynchronize(ctx->stream);
-    }
-    (void)hipFree(stage);
-    if (mdev) (void)hipFree(mdev);
-    if (e != hipSuccess) ASB_FAIL(ctx, ASB_ERR_HIP, "asb_snapshots_upload: %s", hipGetErrorString(e));
-    return rc;
-}
-
-extern "C" int asb_snapshots_adopt_dev(asb_ctx* ctx, const double* X_dev, int64_t F, int64_t n_loc,
-                                       const double* massL_loc, int64_t v0, int64_t N_glob) {
-    if (!ctx || !X_dev) return ASB_ERR_ARG;
-    ASB_HIP(ctx, hipSetDevice(ctx->dev));
-    int rc = set_shape(ctx, F, N_glob, v0, n_loc);
-    if (rc) return rc;
-    double* mdev = nullptr;
-    if (massL_loc) {
-        ASB_HIP(ctx, hipMalloc((void**)&mdev, (size_t)n_loc * sizeof(double)));
-        ASB_HIP(ctx, hipMemcpyAsync(mdev, massL_loc, (size_t)n_loc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    }
-    rc = transpose_in(ctx, X_dev, mdev);
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (mdev) (void)hipFree(mdev);
-    if (e != hipSuccess) ASB_FAIL(ctx, ASB_ERR_HIP, "asb_snapshots_adopt_dev: %s", hipGetErrorString(e));
-    return rc;
-}
-
 // layout change + rest shape (+ its subtraction) in one go; sums_out[0] = sum(x), sums_out[1] = sum(x^2) of the shard as it
 // stands afterwards (rest_shape 1, "average", needs the column means first: the separate sweeps, sums_out[1] = -1)
 static int transpose_rest(asb_ctx* ctx, const double* stage_dev, const double* massL_dev, int rest_shape, int subtract, double* sums_out) {
@@ -480,51 +435,65 @@ static int transpose_rest(asb_ctx* ctx, const double* stage_dev, const double* m
     return ASB_OK;
 }
 
+// The shard [v0, v0 + n_loc) of a host tensor (F, N_glob, 3) into `stage` (F, 3 n_loc) and, when massL (N_glob, host) is
+// given, the shard's entries of it into `mdev`; both copies are enqueued on the context's stream
+int asb_stage_shard(asb_ctx* ctx, const double* X, int64_t F, int64_t N_glob, int64_t v0, int64_t n_loc, const double* massL,
+                    asb_tmp<double>& stage, asb_tmp<double>& mdev) {
+    const size_t C = (size_t)n_loc * 3;
+    int rc;
+    if ((rc = stage.alloc(ctx, (size_t)F * C))) return rc;
+    ASB_HIP(ctx, hipMemcpy2DAsync(stage.get(), C * sizeof(double), X + v0 * 3, (size_t)N_glob * 3 * sizeof(double), C * sizeof(double),
+                                  (size_t)F, hipMemcpyHostToDevice, ctx->stream));
+    if (!massL) return ASB_OK;
+    if ((rc = mdev.alloc(ctx, (size_t)n_loc))) return rc;
+    ASB_HIP(ctx, hipMemcpyAsync(mdev.get(), massL + v0, (size_t)n_loc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    return ASB_OK;
+}
+
+// The four ingest calls.  The shard is staged from a host tensor of N_glob vertices (X_host; massL indexed globally) or is a
+// device tensor already (X_dev; massL holds the shard's entries only).  sums_out != nullptr: the rest shape goes with the
+// layout change (transpose_rest), and X is cleared beforehand only where that takes the separate sweeps.
+static int ingest(asb_ctx* ctx, const double* X_host, const double* X_dev, int64_t F, int64_t N_glob, int64_t v0, int64_t n_loc,
+                  const double* massL, int rest_shape, int subtract, double* sums_out) {
+    if (sums_out && rest_shape != 0 && rest_shape != 1) ASB_FAIL(ctx, ASB_ERR_ARG, "unknown rest shape code %d", rest_shape);
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    int rc = set_shape(ctx, F, N_glob, v0, n_loc, !sums_out || rest_shape != 0);
+    if (rc) return rc;
+    asb_tmp<double> stage, mdev;
+    if (X_host) {
+        if ((rc = asb_stage_shard(ctx, X_host, F, N_glob, v0, n_loc, massL, stage, mdev))) return rc;
+        X_dev = stage.get();
+    } else if (massL) {
+        if ((rc = mdev.alloc(ctx, (size_t)n_loc))) return rc;
+        ASB_HIP(ctx, hipMemcpyAsync(mdev.get(), massL, (size_t)n_loc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    }
+    rc = sums_out ? transpose_rest(ctx, X_dev, mdev.get(), rest_shape, subtract, sums_out) : transpose_in(ctx, X_dev, mdev.get());
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return rc;
+}
+
+extern "C" int asb_snapshots_upload(asb_ctx* ctx, const double* X, int64_t F, int64_t N_glob, int64_t v0,
+                                    int64_t n_loc, const double* massL) {
+    if (!ctx || !X) return ASB_ERR_ARG;
+    return ingest(ctx, X, nullptr, F, N_glob, v0, n_loc, massL, 0, 0, nullptr);
+}
+
+extern "C" int asb_snapshots_adopt_dev(asb_ctx* ctx, const double* X_dev, int64_t F, int64_t n_loc,
+                                       const double* massL_loc, int64_t v0, int64_t N_glob) {
+    if (!ctx || !X_dev) return ASB_ERR_ARG;
+    return ingest(ctx, nullptr, X_dev, F, N_glob, v0, n_loc, massL_loc, 0, 0, nullptr);
+}
+
 extern "C" int asb_snapshots_upload_rest(asb_ctx* ctx, const double* X, int64_t F, int64_t N_glob, int64_t v0, int64_t n_loc,
                                          const double* massL, int rest_shape, int subtract, double* sums_out) {
     if (!ctx || !X || !sums_out) return ASB_ERR_ARG;
-    if (rest_shape != 0 && rest_shape != 1) ASB_FAIL(ctx, ASB_ERR_ARG, "unknown rest shape code %d", rest_shape);
-    ASB_HIP(ctx, hipSetDevice(ctx->dev));
-    int rc = set_shape(ctx, F, N_glob, v0, n_loc, rest_shape != 0);
-    if (rc) return rc;
-    double* stage = nullptr;
-    double* mdev = nullptr;
-    const size_t C = (size_t)n_loc * 3;
-    ASB_HIP(ctx, hipMalloc((void**)&stage, (size_t)F * C * sizeof(double)));
-    hipError_t e = hipMemcpy2DAsync(stage, C * sizeof(double), X + v0 * 3, (size_t)N_glob * 3 * sizeof(double),
-                                    C * sizeof(double), (size_t)F, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && massL) {
-        e = hipMalloc((void**)&mdev, (size_t)n_loc * sizeof(double));
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(mdev, massL + v0, (size_t)n_loc * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    }
-    if (e == hipSuccess) {
-        rc = transpose_rest(ctx, stage, mdev, rest_shape, subtract, sums_out);
-        e = hipStreamSynchronize(ctx->stream);
-    }
-    (void)hipFree(stage);
-    if (mdev) (void)hipFree(mdev);
-    if (e != hipSuccess) ASB_FAIL(ctx, ASB_ERR_HIP, "asb_snapshots_upload_rest: %s", hipGetErrorString(e));
-    return rc;
+    return ingest(ctx, X, nullptr, F, N_glob, v0, n_loc, massL, rest_shape, subtract, sums_out);
 }
 
 extern "C" int asb_snapshots_adopt_dev_rest(asb_ctx* ctx, const double* X_dev, int64_t F, int64_t n_loc, const double* massL_loc,
                                             int64_t v0, int64_t N_glob, int rest_shape, int subtract, double* sums_out) {
     if (!ctx || !X_dev || !sums_out) return ASB_ERR_ARG;
-    if (rest_shape != 0 && rest_shape != 1) ASB_FAIL(ctx, ASB_ERR_ARG, "unknown rest shape code %d", rest_shape);
-    ASB_HIP(ctx, hipSetDevice(ctx->dev));
-    int rc = set_shape(ctx, F, N_glob, v0, n_loc, rest_shape != 0);
-    if (rc) return rc;
-    double* mdev = nullptr;
-    if (massL_loc) {
-        ASB_HIP(ctx, hipMalloc((void**)&mdev, (size_t)n_loc * sizeof(double)));
-        ASB_HIP(ctx, hipMemcpyAsync(mdev, massL_loc, (size_t)n_loc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    }
-    rc = transpose_rest(ctx, X_dev, mdev, rest_shape, subtract, sums_out);
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (mdev) (void)hipFree(mdev);
-    if (e != hipSuccess) ASB_FAIL(ctx, ASB_ERR_HIP, "asb_snapshots_adopt_dev_rest: %s", hipGetErrorString(e));
-    return rc;
+    return ingest(ctx, nullptr, X_dev, F, N_glob, v0, n_loc, massL_loc, rest_shape, subtract, sums_out);
 }
 
 static int finish_sum(asb_ctx* ctx, int nblk, double* out_host) {
@@ -607,17 +576,15 @@ extern "C" int asb_snapshots_get_mean(asb_ctx* ctx, double* mean_out) {
 // (C, Fp) vertex-major device tensor -> host (F, C)
 int asb_download_vertex_major(asb_ctx* ctx, const double* src, double* out) {
     const long long C = ctx->n_loc * 3;
-    double* stage = nullptr;
-    ASB_HIP(ctx, hipMalloc((void**)&stage, (size_t)ctx->F * C * sizeof(double)));
+    asb_tmp<double> stage;
+    int rc;
+    if ((rc = stage.alloc(ctx, (size_t)ctx->F * C))) return rc;
     dim3 grid((unsigned)((ctx->F + 31) / 32), (unsigned)((C + 31) / 32));
     hipLaunchKernelGGL(k_transpose, grid, dim3(256), 0, ctx->stream, src, C, (long long)ctx->F, (long long)ctx->Fp,
-                       stage, C, (const double*)nullptr, 0);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(out, stage, (size_t)ctx->F * C * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(stage);
-    if (e != hipSuccess) ASB_FAIL(ctx, ASB_ERR_HIP, "download: %s", hipGetErrorString(e));
+                       stage.get(), C, (const double*)nullptr, 0);
+    ASB_CHECK_LAUNCH(ctx);
+    ASB_HIP(ctx, hipMemcpyAsync(out, stage.get(), (size_t)ctx->F * C * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return ASB_OK;
 }
 
