@@ -198,6 +198,10 @@ PROTOTYPES = {
     "asb_test_sym_eig": (c_int, [ctypes.c_void_p, c_dp, c_i64, c_dp, c_dp, ctypes.POINTER(c_int)]),
     "asb_test_splocs_install": (c_int, [ctypes.c_void_p, c_dp, c_dp, c_dp]),
     "asb_test_splocs_state": (c_int, [ctypes.c_void_p, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "asb_test_slab_gemm64": (c_int, [ctypes.c_void_p, c_dp, c_i64, c_dp, c_dp, c_i64, c_i64, c_dbl, c_dbl, c_int]),
+    "asb_test_geodesic_field1": (c_int, [ctypes.c_void_p, c_i64, c_dp]),
+    "asb_test_support_weights": (c_int, [ctypes.c_void_p, c_dp, c_i64, c_i64, c_i64, c_dbl, c_dbl, c_dp]),
+    "asb_test_geodesic_cached": (c_int, [ctypes.c_void_p, c_i64, c_dp]),
 }
 
 

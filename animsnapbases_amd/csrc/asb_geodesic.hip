@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256) void k_cg_direction(int rows, int nblk_in, con
     const double beta = (first || old == 0.0 || !(rrn > tol2 * rz[4 * GB + lane])) ? 0.0 : rzn / old;      // (rrn: every block sums the same partials)
     for (int i = blockIdx.x * 4 + wid; i < rows; i += gridDim.x * 4) {
         const long long e = (long long)i * GB + lane;
-        p[e] = z[e] + beta * p[e];
+        p[e] = beta == 0.0 ? z[e] : z[e] + beta * p[e];      // (the first direction must not read p: it holds whatever the last batch left, NaN in its unused columns)
     }
     __threadfence();
     if (blockIdx.x == gridDim.x - 1 && wid == 0) {       // staged: see k_cg_commit
@@ -996,6 +996,8 @@ static int geodesic_solve1_dense(asb_ctx* ctx, const long long* src_dev) {
 // distances from each of nsrc (<= 64) source vertices: out (nsrc, n), host.  iters (optional): CG iterations of the two solves.
 extern "C" int asb_geodesic_solve(asb_ctx* ctx, const int64_t* sources, int nsrc, double tol, double* out, int* iters) {
     if (!ctx || !ctx->geo || !sources || nsrc < 1 || nsrc > GB || !out) return ASB_ERR_ARG;
+    for (int c = 0; c < nsrc; ++c)         // (k_set_sources / k_gather_sources index with the id as it is)
+        if (sources[c] < 0 || sources[c] >= ctx->geo->n) ASB_FAIL(ctx, ASB_ERR_ARG, "geodesic source %lld outside the mesh", (long long)sources[c]);
     if (!(tol >= 1e-14)) tol = 1e-14;      // below the rounding floor CG only wanders (and can blow up)
     int rc;
     if ((rc = asb_alloc(ctx, &ctx->geo_src, (size_t)GB))) return rc;
@@ -1079,6 +1081,67 @@ extern "C" int asb_deflate_apply_geodesic(asb_ctx* ctx, int64_t k, double dmin, 
                        dmin, dmax, ctx->s_dev);
     ASB_CHECK_LAUNCH(ctx);
     return asb_deflate_apply_dev(ctx, k, ctx->s_dev);
+}
+
+// ---- test hooks on host arrays (tests/test_gpu_geodesic_small.py): read-only with respect to the solver's state --------------
+// out (M x 64, in and out) = beta out + alpha A (M x lda, the leading Kc columns) Z (Kc x 64) through slab_gemm64 with `nct`
+// column tiles; A and Z travel with NaN behind them
+extern "C" int asb_test_slab_gemm64(asb_ctx* ctx, const double* A, int64_t lda, const double* Z, double* out, int64_t M, int64_t Kc,
+                                    double alpha, double beta, int nct) {
+    if (!ctx || !A || !Z || !out) return ASB_ERR_ARG;
+    if (M < 16 || Kc < 16 || M > 1 << 20 || Kc > 1 << 20 || ((M | Kc) & 15) || lda < Kc || (lda & 3) || lda > 1 << 24)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_slab_gemm64: M = %lld, Kc = %lld (multiples of 16), lda = %lld (a multiple of 4, >= Kc)",
+                 (long long)M, (long long)Kc, (long long)lda);
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    asb_tmp<double> da, dz, dout;
+    int rc = asb_test_stage(ctx, A, (size_t)M * lda, 256, da);
+    if (!rc) rc = asb_test_stage(ctx, Z, (size_t)Kc * GB, 256, dz);
+    if (!rc) rc = asb_test_stage(ctx, out, (size_t)M * GB, 0, dout);
+    if (!rc) rc = slab_gemm64(ctx, da.get(), lda, dz.get(), dout.get(), (int)M, (int)Kc, alpha, beta, nct);
+    return asb_test_finish(ctx, rc, dout.get(), out, (size_t)M * GB);
+}
+// the field asb_deflate_apply_geodesic computes for its source, for a source id given on the host: phi_out (n)
+extern "C" int asb_test_geodesic_field1(asb_ctx* ctx, int64_t src, double* phi_out) {
+    if (!ctx || !ctx->geo || !phi_out) return ASB_ERR_ARG;
+    asb_geo* G = ctx->geo;
+    if (src < 0 || src >= G->n) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_geodesic_field1: source %lld outside the mesh", (long long)src);
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    int rc;
+    if ((rc = asb_alloc(ctx, &ctx->geo_src, (size_t)GB))) return rc;
+    const long long s = src;
+    ASB_HIP(ctx, hipMemcpyAsync(ctx->geo_src, &s, sizeof(s), hipMemcpyHostToDevice, ctx->stream));
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (G->dense) rc = geodesic_solve1_dense(ctx, ctx->geo_src);
+    else rc = geodesic_solve_dev(ctx, ctx->geo_src, 1, 1e-13, nullptr, nullptr);
+    return asb_test_finish(ctx, rc, ctx->geo_out, phi_out, (size_t)G->n);
+}
+// s_out (n_loc) = k_support_weights on phi (n, host) for the shard [v0, v0 + n_loc), launched as asb_deflate_apply_geodesic does
+extern "C" int asb_test_support_weights(asb_ctx* ctx, const double* phi, int64_t n, int64_t v0, int64_t n_loc, double dmin, double dmax,
+                                        double* s_out) {
+    if (!ctx || !phi || !s_out) return ASB_ERR_ARG;
+    if (n < 1 || n > 1 << 28 || v0 < 0 || n_loc < 1 || v0 + n_loc > n || !(dmax > dmin) || !(dmax - dmin < 1.0e300))
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_support_weights: n = %lld, shard [%lld, %lld), distances (%g, %g)", (long long)n,
+                 (long long)v0, (long long)(v0 + n_loc), dmin, dmax);
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    asb_tmp<double> dphi, ds;
+    int rc = asb_test_stage(ctx, phi, (size_t)n, 256, dphi);
+    if (!rc) rc = asb_test_stage(ctx, nullptr, (size_t)n_loc, 0, ds);
+    if (!rc) {
+        const int grid = (int)((n_loc + 255) / 256 < 1024 ? (n_loc + 255) / 256 : 1024);
+        hipLaunchKernelGGL(k_support_weights, dim3(grid), dim3(256), 0, ctx->stream, dphi.get(), (long long)v0, (long long)n_loc, dmin,
+                           dmax, ds.get());
+        if (hipGetLastError() != hipSuccess) rc = ASB_ERR_HIP;
+    }
+    return asb_test_finish(ctx, rc, ds.get(), s_out, (size_t)n_loc);
+}
+// out (n) = the cached field of `slot` as asb_splocs.hip reads it
+extern "C" int asb_test_geodesic_cached(asb_ctx* ctx, int64_t slot, double* out) {
+    if (!ctx || !out) return ASB_ERR_ARG;
+    long long n = 0;
+    const double* f = asb_geo_cached_field(ctx, (long long)slot, &n);
+    if (!f) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_geodesic_cached: no cached field in slot %lld", (long long)slot);
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    return asb_test_finish(ctx, ASB_OK, f, out, (size_t)n);
 }
 
 void asb_geo_free(asb_ctx* ctx) {

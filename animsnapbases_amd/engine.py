@@ -900,6 +900,34 @@ class HipEngine(object):
                                                 ptr(out["c"])))
         return out
 
+    # the device geodesics on small meshes (tests/test_gpu_geodesic_small.py); none of these changes the solver's state
+    def test_slab_gemm64(self, A, Z, out, Kc, alpha=1.0, beta=0.0, nct=4):
+        """out (M, 64) = beta out + alpha A[:, :Kc] Z (Kc, 64) through slab_gemm64, in place; A (M, lda) 2-D contiguous."""
+        for a in (A, Z, out):
+            assert a.dtype == np.float64 and a.flags.c_contiguous and a.ndim == 2
+        assert Z.shape == (Kc, 64) and out.shape == (A.shape[0], 64)
+        self._ck(self.lib.asb_test_slab_gemm64(self.h, ptr(A), A.shape[1], ptr(Z), ptr(out), A.shape[0], int(Kc), float(alpha),
+                                               float(beta), int(nct)))
+        return out
+
+    def test_geodesic_field1(self, src):
+        """(n,) the distance field apply_geodesic solves for its source, for a source given here."""
+        phi = np.empty(self._geo_n)
+        self._ck(self.lib.asb_test_geodesic_field1(self.h, int(src), ptr(phi)))
+        return phi
+
+    def test_support_weights(self, phi, v0, n_loc, dmin, dmax):
+        phi = np.ascontiguousarray(phi, dtype=np.float64)
+        s = np.empty(max(int(n_loc), 0))
+        self._ck(self.lib.asb_test_support_weights(self.h, ptr(phi), phi.shape[0], int(v0), int(n_loc), float(dmin), float(dmax),
+                                                   ptr(s)))
+        return s
+
+    def test_geodesic_cached(self, slot):
+        out = np.empty(self._geo_n)
+        self._ck(self.lib.asb_test_geodesic_cached(self.h, int(slot), ptr(out)))
+        return out
+
     def snapshots_affine(self, inv_scale, add_mean, rowscale_loc=None):
         if rowscale_loc is not None:
             rowscale_loc = np.ascontiguousarray(rowscale_loc, dtype=np.float64)

@@ -718,6 +718,19 @@ int asb_test_sym_eig(asb_ctx* ctx, const double* A, int64_t n, double* lam, doub
  * c = W^T X (K, 3 n_loc).  G is written by asb_splocs_weights, the others by asb_splocs_admm(_fields). */
 int asb_test_splocs_install(asb_ctx* ctx, const double* C, const double* W, const double* U);
 int asb_test_splocs_state(asb_ctx* ctx, double* U, double* Lambda, double* G, double* Ginv, double* c);
+/* test hooks of the device geodesics (tests/test_gpu_geodesic_small.py); host arrays, no solver state is changed.
+ * asb_test_slab_gemm64: out (M x 64, in and out) = beta out + alpha A (M x lda, Kc columns used) Z (Kc x 64) on the slab sweeps'
+ * product kernel with nct (clamped to 1 .. 4) column tiles of 16: columns >= 16 nct stay as they are.  M, Kc multiples of 16.
+ * asb_test_geodesic_field1: phi_out (n) = the field asb_deflate_apply_geodesic solves for its source, for a source given here
+ * (dense mode: the single-source path; otherwise the batch solver with one source).
+ * asb_test_support_weights: s_out (n_loc) = 1 - (clip(phi[v0 + i], dmin, dmax) - dmin) / (dmax - dmin) on the device, phi (n) host.
+ * asb_test_geodesic_cached: out (n) = the cached field of `slot`; ASB_ERR_ARG where there is none. */
+int asb_test_slab_gemm64(asb_ctx* ctx, const double* A, int64_t lda, const double* Z, double* out, int64_t M, int64_t Kc,
+                         double alpha, double beta, int nct);
+int asb_test_geodesic_field1(asb_ctx* ctx, int64_t src, double* phi_out);
+int asb_test_support_weights(asb_ctx* ctx, const double* phi, int64_t n, int64_t v0, int64_t n_loc, double dmin, double dmax,
+                             double* s_out);
+int asb_test_geodesic_cached(asb_ctx* ctx, int64_t slot, double* out);
 
 #ifdef __cplusplus
 }

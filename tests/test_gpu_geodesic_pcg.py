@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden, relerr
+from geodesic_cases import torus as _torus
 from oracle import asb_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -28,17 +29,6 @@ def test_two_level_pcg_on_the_bunny_vs_superlu():
         assert relerr(phi[q], ref(s)) < 1e-8
     assert geo.n_aggregates > 500
     eng.close()
-
-
-def _torus(nu, nv, R=0.4, r=0.15):
-    """A quasi-uniform triangle mesh with nu * nv vertices (a regular grid bent into a torus)."""
-    th, ph = 2 * np.pi * np.arange(nu) / nu, 2 * np.pi * np.arange(nv) / nv
-    T, P = np.meshgrid(th, ph, indexing="ij")
-    V = np.stack([(R + r * np.cos(P)) * np.cos(T), (R + r * np.cos(P)) * np.sin(T), r * np.sin(P)], -1).reshape(-1, 3)
-    i, j = np.meshgrid(np.arange(nu), np.arange(nv), indexing="ij")
-    a, b = (i * nv + j).ravel(), (((i + 1) % nu) * nv + j).ravel()
-    c, d = (i * nv + (j + 1) % nv).ravel(), (((i + 1) % nu) * nv + (j + 1) % nv).ravel()
-    return V, np.concatenate([np.stack([a, b, c], 1), np.stack([b, d, c], 1)]).astype(np.int64)
 
 
 @pytest.mark.parametrize("mode", ["auto", "device"])
