@@ -951,10 +951,12 @@ class constraintsComponents:  # Components == bases
                 th.join()
                 if "exc" in box:
                     raise box["exc"]
-                Pt_d, maxabs, bad = box["out"]
+                out = box["out"]
                 test_linear_dependency_grams(G, K, lambda j: self.comps[:, :, j].T, lams=lams)
             else:
-                Pt_d, maxabs, bad = eng.deim_run()
+                out = eng.deim_run()
+            # (None: K beyond the solve kernel's LDS, nothing ran on the device -- the host loop below)
+            Pt_d, maxabs, bad = out if out is not None else (None, None, 1)
             if bad and os.environ.get("ASB_DEBUG_DEIM"):
                 print("[asb] DEIM: the device loop's verification failed at a step: host loop", file=sys.stderr)
             if not bad:

@@ -576,8 +576,8 @@ __global__ __launch_bounds__(256) void k_deim_residual(const double* __restrict_
 // whose leading k x k block is (Mx[i][:k, :k])^-1, carried along by the bordering (Schur complement) update -- what the
 // reference recomputes from scratch with lstsq at every step (:829).
 // k_deim_solve (one block per dimension): grows the inverse by last step's point / vector, then coef[i] = Minv b with
-// b = Mx[i][:k, k]; the solve is verified (|M x - b| against rounding level), a failure raises flags[0] and the caller
-// repeats the loop with the reference's lstsq on the host.
+// b = Mx[i][:k, k], refined once by its own residual; the solve is verified (|M x - b| of the unrefined x against rounding
+// level), a failure raises flags[0] and the caller repeats the loop with the reference's lstsq on the host.
 // Both the matrices of points (Mx, and MxT[i][j][m] = Mx[i][m][j]) and the inverse (Minv and its transpose MinvT) are kept in
 // two layouts so that every product below reads consecutive words across a wave.
 // 1024 threads: thread (r = tid % 256, part = tid / 256) takes every fourth term of row r's dot products (four times shorter
@@ -669,7 +669,6 @@ __global__ __launch_bounds__(DS_T) void k_deim_solve(const double* __restrict__ 
     for (int r = tid; r < k; r += DS_T) {
         const double sx = (pu[r] + pu[K + r]) + (pu[2 * K + r] + pu[3 * K + r]);
         x[r] = sx;
-        coef[(size_t)i * k + r] = sx;
         nx2 += sx * sx;
         nb2 += b[r] * b[r];
     }
@@ -685,8 +684,23 @@ __global__ __launch_bounds__(DS_T) void k_deim_solve(const double* __restrict__ 
     double res2 = 0.0;
     for (int r = tid; r < k; r += DS_T) {
         const double sr = (pw[r] + pw[K + r]) + (pw[2 * K + r] + pw[3 * K + r]) - b[r];
+        w[r] = sr;
         res2 += sr * sr;
     }
+    __syncthreads();
+    // one step of iterative refinement, coef = x - A (M x - b): the rounding of every earlier bordering step stays in A, and
+    // x = A b alone drifts from the fresh solve the reference makes (K = 257: the largest |r| of a run lay 33 times further
+    // from a longdouble model than the float64 fresh solves' did)
+    for (int r0 = 0; r0 < k; r0 += 256) {
+        const int r = r0 + lane_r;
+        double sd = 0.0;
+        if (r < k)
+            for (int q = part; q < k; q += 4) sd += AT[(size_t)q * K + r] * w[q];
+        if (r < k) pu[part * K + r] = sd;
+    }
+    __syncthreads();
+    for (int r = tid; r < k; r += DS_T)
+        coef[(size_t)i * k + r] = x[r] - ((pu[r] + pu[K + r]) + (pu[2 * K + r] + pu[3 * K + r]));
     double v[4] = {nb2, nx2, nm2, res2};
     block_sum<4>(v, red);
     if (tid == 0) {
@@ -695,11 +709,14 @@ __global__ __launch_bounds__(DS_T) void k_deim_solve(const double* __restrict__ 
     }
 }
 
-// reduces the residual kernel's partials to the step's point: Pt[k], its largest |r| entry, and row k of Mx
+// reduces the residual kernel's partials to the step's point: Pt[k], its largest |r| entry, and row k of Mx.  When a failed
+// solve left NaN coefficients no energy compares greater than the initial -1 and no row is named: row 0 is taken and
+// flags[0] raised (the caller repeats the loop on the host), instead of reading the basis at an index that does not exist.
 __global__ __launch_bounds__(256) void k_deim_pick(const double* __restrict__ pmax, const long long* __restrict__ pidx,
                                                    const double* __restrict__ pabs, int nblk, const double* __restrict__ comps,
                                                    long long n_vert, int K, int k, long long* __restrict__ Pt,
-                                                   double* __restrict__ maxabs, double* __restrict__ Mx, double* __restrict__ MxT) {
+                                                   double* __restrict__ maxabs, double* __restrict__ Mx, double* __restrict__ MxT,
+                                                   int* __restrict__ flags) {
     __shared__ double sh_d[256];
     __shared__ long long sh_i[256];
     __shared__ double sh_a[256];
@@ -721,8 +738,12 @@ __global__ __launch_bounds__(256) void k_deim_pick(const double* __restrict__ pm
         }
         __syncthreads();
     }
-    const long long idx = sh_i[0];
-    if (threadIdx.x == 0) { Pt[k] = idx; maxabs[k] = sh_a[0]; }
+    const bool none = sh_i[0] < 0 || sh_i[0] >= n_vert;
+    const long long idx = none ? 0 : sh_i[0];
+    if (threadIdx.x == 0) {
+        Pt[k] = idx; maxabs[k] = sh_a[0];
+        if (none) flags[0] = 1;
+    }
     for (int q = threadIdx.x; q < 3 * K; q += 256) {
         const int i = q / K, j = q % K;
         const double val = comps[(long long)j * 3 * n_vert + 3 * idx + i];
@@ -741,6 +762,16 @@ extern "C" int asb_deim_run(asb_ctx* ctx, int64_t* Pt_out, double* maxabs_out, i
     ASB_HIP(ctx, hipSetDevice(ctx->dev));         // (the host mirror calls this from a worker thread, beside its LAPACK rank check)
     const int K = (int)ctx->K;
     int rc;
+    // k_deim_solve keeps 11 K + 64 doubles in LDS: a basis too large for the device's block is refused before anything is
+    // allocated or launched (the caller has the host loop)
+    const size_t lds_solve = ((size_t)11 * K + 64) * sizeof(double);
+    int lds_max = 0;
+    hipFuncAttributes fa;
+    ASB_HIP(ctx, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->dev));
+    ASB_HIP(ctx, hipFuncGetAttributes(&fa, (const void*)k_deim_solve));
+    if (lds_solve + fa.sharedSizeBytes > (size_t)lds_max)
+        ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_deim_run: K = %d needs %zu bytes of LDS per block, the device has %d", K,
+                 lds_solve + fa.sharedSizeBytes, lds_max);
     if ((rc = asb_alloc(ctx, &ctx->deim_m, (size_t)12 * K * K + 4 * (size_t)K + 2048 * 2))) return rc;
     if ((rc = asb_alloc(ctx, &ctx->deim_pt, (size_t)K + 2048))) return rc;
     if ((rc = asb_alloc(ctx, &ctx->la_status, (size_t)4))) return rc;
@@ -757,7 +788,6 @@ extern "C" int asb_deim_run(asb_ctx* ctx, int64_t* Pt_out, double* maxabs_out, i
     ASB_HIP(ctx, hipMemsetAsync(ctx->la_status, 0, 4 * sizeof(int), ctx->stream));
     long long want = (ctx->n_loc + 255) / 256;
     const int grid = (int)(want < 1024 ? want : 1024);
-    const size_t lds_solve = ((size_t)11 * K + 64) * sizeof(double);
     if (lds_solve > 48 * 1024)
         ASB_HIP(ctx, hipFuncSetAttribute((const void*)k_deim_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_solve));
     for (int k = 0; k < K; ++k) {
@@ -767,7 +797,7 @@ extern "C" int asb_deim_run(asb_ctx* ctx, int64_t* Pt_out, double* maxabs_out, i
         hipLaunchKernelGGL(k_deim_residual, dim3(grid), dim3(256), (size_t)(3 * k + 1) * sizeof(double), ctx->stream, ctx->comps,
                            (long long)ctx->n_loc, k, coef, (long long)ctx->v0, pmax, pidx, pabs);
         hipLaunchKernelGGL(k_deim_pick, dim3(1), dim3(256), 0, ctx->stream, pmax, pidx, pabs, grid, ctx->comps, (long long)ctx->n_loc,
-                           K, k, Pt, maxabs, Mx, MxT);
+                           K, k, Pt, maxabs, Mx, MxT, ctx->la_status);
     }
     ASB_CHECK_LAUNCH(ctx);
     int st[4];

@@ -945,9 +945,13 @@ class HipEngine(object):
         return i.value, v.value
 
     def deim_run(self):
-        """The whole DEIM loop on the device (single rank): (Pt (K,), maxabs (K,), solve_failed)."""
+        """The whole DEIM loop on the device (single rank): (Pt (K,), maxabs (K,), solve_failed); None when K is too large
+        for the solve kernel's LDS (nothing was launched: the caller runs the host loop)."""
         Pt, ma, bad = np.empty(self.K, dtype=np.int64), np.empty(self.K), ctypes.c_int()
-        self._ck(self.lib.asb_deim_run(self.h, Pt.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ptr(ma), ctypes.byref(bad)))
+        rc = self.lib.asb_deim_run(self.h, Pt.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ptr(ma), ctypes.byref(bad))
+        if rc == _lib.ERR_LIMIT:
+            return None
+        self._ck(rc)
         return Pt, ma, bad.value
 
     def deim_block_step(self, k, p, coef, group):

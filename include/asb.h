@@ -509,7 +509,9 @@ int asb_deim_step(asb_ctx* ctx, int64_t k, const double* coef, int64_t* idx_out,
 /* deim (:797-860) entirely on the device, for a basis whose rows are all on this rank: Pt_out (K) = the interpolation rows in
  * order; maxabs_out (K) = the largest |residual| entry of each step (the reference stops with "zero residual" when
  * np.allclose(r, 0), i.e. <= 1e-8); the k x k systems are solved through a bordered inverse carried on the device and
- * verified -- *solve_failed != 0 means a check failed and the caller should fall back to asb_deim_step + lstsq (:829). */
+ * verified -- *solve_failed != 0 means a check failed (or no row could be named because the coefficients were not finite)
+ * and the caller should fall back to asb_deim_step + lstsq (:829).  Every Pt_out entry is a row of the basis either way.
+ * ASB_ERR_LIMIT, before anything is allocated or launched, when (11 K + 64) doubles exceed the device's LDS per block. */
 int asb_deim_run(asb_ctx* ctx, int64_t* Pt_out, double* maxabs_out, int* solve_failed);
 /* deim_blocksForm (:733-795) / geom_block_form_utilizing_differential_operator (:619-731, error in the constraint space):
  * residual of block k (p basis vectors) with the interpolation coefficients coef (host, 3 x (k p) x p; NULL at k = 0);
