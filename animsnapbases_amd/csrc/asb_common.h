@@ -131,12 +131,10 @@ struct asb_ctx {
     int64_t n_coop_fallbacks = 0;     // launches of k_panel_coop whose record exchange timed out (redone by the two-kernel loop)
     int64_t n_coop_launches = 0;      // launches of the co-resident panel kernel (k_panel_multi) in the last run
     int64_t max_read_kept = 0;        // most components one read of X (all its sub-panels) committed in the last run
-    // super-panels (asb_project.hip): how the next asb_panel_run behaves / what it did
-    int run_writeback = 0, run_theta_band = 0, run_coop_used = 0;
     int spec_panels = 1;              // ASB_SPEC_PANELS=0 -> provable steps only
-    int run_spec_max = 0;             // unproven steps the next asb_panel_run may take (0 outside asb_project_run)
     int spec_budget = 16;             // adapted to how many unproven steps survived in the last panels
-    long long run_proven = 0;         // provable head of the last asb_panel_run
+    // joins asb_panel_project_spec[_dev] to the asb_panel_commit that follows it: the provable head of the panel being checked
+    long long spec_proven = 0;
     double* w_fk = nullptr;                 // weights in the reference's (F, K) order for the read-back
     unsigned char* host_pin = nullptr;      // pinned (coherent, device-mapped) host memory for the small read-backs
     unsigned char* host_pin_dev = nullptr;  // its device address: tiny kernels publish state there, the host polls (asb_pin_alloc)
@@ -196,8 +194,8 @@ struct asb_ctx {
                                            // the projection kernel needs more than 256 registers and loses what the saved read gains)
     int sub_first = 4;                     // sub-panels of the first read (ASB_SUB_FIRST); then adapted: sub_cur
     int sub_cur = 0;
-    int chain_timed_out = 0;               // the last one-launch run of a read's sub-panels met a poll that did not complete
-    // the read in progress of the multi-rank driver (asb_panel_read_*): its tiles, whether its pass is already enqueued
+    // joins asb_panel_read_run to the asb_panel_read_commit that follows it (the multi-rank driver's read in progress): its tiles,
+    // the grid of its checks
     long long rd_k0 = 0;
     int rd_ntile = 0, rd_nc[8] = {0}, rd_proven[8] = {0}, rd_rgrid = 0;
     double* rd_words = nullptr;            // (8) per tile: columns that stand on this shard; [ASB_MAX_SUB]: status

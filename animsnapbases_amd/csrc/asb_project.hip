@@ -870,15 +870,16 @@ __global__ __launch_bounds__(256) void k_commit_energy(const double* __restrict_
 // otherwise takes out of the COEFFICIENTS after the pass (X w~_t = X w_t - sum_j (X w_j)(w_j . w_t) / |w_j|^2, which is the
 // correction with the uncorrected c_j in place of the corrected ones: a second-order difference) -- at the cost of
 // K x 16 x F flops instead of a sweep over all earlier coefficient columns.
-__global__ __launch_bounds__(256) void k_orth_wt(const double* __restrict__ W, const double* __restrict__ G,
-                                                 long long kb, int ncols, int Fp, double* __restrict__ Wt) {
+// (one body for the kernel of one tile and for the kernel of all tiles of a read, which passes tile blockIdx.y's operands;
+// i0 / stride: the thread's first element and the grid's stride along x, which the kernel reads and hands over)
+__device__ __forceinline__ void orth_wt_body(const double* W, const double* G, long long kb, int ncols, int Fp, double* Wt,
+                                             long long i0, long long stride) {
     const long long total = (long long)Fp * ASB_PANEL_COLS;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    for (long long i = i0; i < total; i += stride) {
         const int t = (int)(i % ASB_PANEL_COLS);
         const long long f = i / ASB_PANEL_COLS;
         if (t >= ncols) continue;
-        double s = 0.0;
-        double s2 = 0.0;
+        double s = 0.0, s2 = 0.0;
         long long j = 0;
         for (; j + 2 <= kb + t; j += 2) {          // G: already divided by |w_j|^2 (k_panel_gram)
             s += W[j * Fp + f] * G[j * 16 + t];
@@ -888,18 +889,27 @@ __global__ __launch_bounds__(256) void k_orth_wt(const double* __restrict__ W, c
         Wt[i] -= s + s2;
     }
 }
-__global__ __launch_bounds__(256) void k_build_wt(const double* __restrict__ W, const double* __restrict__ scal,
-                                                  long long k0, int ncols, int Fp, double* __restrict__ Wt,
-                                                  double* __restrict__ wn2) {
+__global__ __launch_bounds__(256) void k_orth_wt(const double* __restrict__ W, const double* __restrict__ G,
+                                                 long long kb, int ncols, int Fp, double* __restrict__ Wt) {
+    const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+    orth_wt_body(W, G, kb, ncols, Fp, Wt, i0, stride);
+}
+__device__ __forceinline__ void build_wt_body(const double* W, const double* scal, long long k0, int ncols, int Fp, double* Wt,
+                                              double* wn2, long long i0, long long stride) {
     const long long total = (long long)Fp * ASB_PANEL_COLS;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
+    for (long long i = i0; i < total; i += stride) {
         const int t = (int)(i % ASB_PANEL_COLS);
         const long long f = i / ASB_PANEL_COLS;
         Wt[i] = (t < ncols) ? W[(k0 + t) * Fp + f] : 0.0;
     }
     if (blockIdx.x == 0 && threadIdx.x < ASB_PANEL_COLS)
         wn2[threadIdx.x] = (threadIdx.x < ncols) ? scal[(k0 + threadIdx.x) * 4 + 1] : 1.0;
+}
+__global__ __launch_bounds__(256) void k_build_wt(const double* __restrict__ W, const double* __restrict__ scal,
+                                                  long long k0, int ncols, int Fp, double* __restrict__ Wt,
+                                                  double* __restrict__ wn2) {
+    const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+    build_wt_body(W, scal, k0, ncols, Fp, Wt, wn2, i0, stride);
 }
 
 // B-operand panel from a frame-major (F x ldw) matrix: columns k0 .. k0+ncols-1, unit norms
@@ -936,15 +946,29 @@ __device__ __forceinline__ int wt_perm(int f) { return (f & ~5) | ((f & 1) << 2)
 // 256 KB panel stays L2-resident.  No LDS, no partial tiles, one launch per pass; whole rows are streamed
 // (the access pattern measured at 5.7 TB/s by tools/probe_stream_patterns.hip).
 // --------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_build_wq(const double* __restrict__ Wt, int Fp, double* __restrict__ Wq,
-                                                  unsigned* __restrict__ tile_counter) {
-    if (blockIdx.x == 0 && threadIdx.x < 16) tile_counter[threadIdx.x] = 0u;      // the projection kernel's work queue
+__device__ __forceinline__ void build_wq_body(const double* Wt, int Fp, double* Wq, long long i0, long long stride) {
     const long long total = (long long)Fp * 16;
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
+    for (long long e = i0; e < total; e += stride) {
         const int j = (int)(e & 3), i = (int)((e >> 2) & 15), g = (int)((e >> 6) & 3);
         const long long chunk = e >> 8;
         Wq[e] = Wt[(chunk * 16 + 4 * g + j) * ASB_PANEL_COLS + i];
     }
+}
+__global__ __launch_bounds__(256) void k_build_wq(const double* __restrict__ Wt, int Fp, double* __restrict__ Wq,
+                                                  unsigned* __restrict__ tile_counter) {
+    if (blockIdx.x == 0 && threadIdx.x < 16) tile_counter[threadIdx.x] = 0u;      // the projection kernel's work queue
+    const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+    build_wq_body(Wt, Fp, Wq, i0, stride);
+}
+// the same for all tiles of a multi-tile pass in one launch (blockIdx.y = tile)
+__global__ __launch_bounds__(256) void k_build_wq_tiles(const double* __restrict__ Wt3, int Fp, double* __restrict__ Wq3,
+                                                        unsigned* __restrict__ tile_counter) {
+    const int ct = blockIdx.y;
+    if (blockIdx.x == 0 && ct == 0 && threadIdx.x < 16) tile_counter[threadIdx.x] = 0u;      // the projection kernel's work queue
+    const double* Wt = Wt3 + (size_t)ct * Fp * 16;
+    double* Wq = Wq3 + (size_t)ct * Fp * 16;
+    const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+    build_wq_body(Wt, Fp, Wq, i0, stride);
 }
 
 // k_project_l2s: the same product with S waves sharing one row tile (each takes every S-th group of G frame chunks and
@@ -1474,7 +1498,26 @@ static void launch_gather(asb_ctx* ctx, const StreamCfg& c, int grid, const long
     }
 }
 
-static void launch_project(asb_ctx* ctx, int ncols, double* out);
+static int launch_project_l2(asb_ctx* ctx, int ncols, double* out) {
+    const long long rows = 3 * ctx->n_loc;
+    int rc;
+    if ((rc = asb_alloc(ctx, &ctx->Wq, (size_t)ctx->Fp * 16))) return rc;
+    if ((rc = asb_alloc(ctx, &ctx->tile_counter, (size_t)16))) return rc;
+    hipLaunchKernelGGL(k_build_wq, dim3(64), dim3(256), 0, ctx->stream, ctx->Wt, (int)ctx->Fp, ctx->Wq, ctx->tile_counter);
+    const long long ntiles = (rows + 63) / 64;
+    size_t slot;
+    if ((rc = prof_begin(ctx, slot))) return rc;
+    // two waves (one 128-thread block) per 64-row tile (four waves per tile lost at the barriers what they gained at the end of the launch)
+    hipLaunchKernelGGL((k_project_l2s<4, 2, 2, 1>), dim3((unsigned)(ntiles < 4 * ctx->n_cu ? ntiles : 4 * ctx->n_cu)), dim3(128), 0, ctx->stream, ctx->X, rows, (int)ctx->Fp, ctx->Wq,
+                       ctx->wn2t, ncols, out, rows, ctx->tile_counter);
+    if ((rc = prof_end(ctx, slot))) return rc;
+    ASB_CHECK_LAUNCH(ctx);
+    return ASB_OK;
+}
+
+static void launch_project(asb_ctx* ctx, int ncols, double* out) {
+    (void)launch_project_l2(ctx, ncols, out);      // (errors surface through the launch check of the caller)
+}
 
 // Per-panel read-back of the panel state (and the panel kernel's flags) through pinned host memory: ONE wait, no staging
 // copy (a pageable destination costs an extra copy kernel and a second round trip for the flags).
@@ -1759,27 +1802,6 @@ static int launch_wide(asb_ctx* ctx, int ntile, const WideArgs& wa) {
     return ASB_OK;
 }
 
-static int launch_project_l2(asb_ctx* ctx, int ncols, double* out) {
-    const long long rows = 3 * ctx->n_loc;
-    int rc;
-    if ((rc = asb_alloc(ctx, &ctx->Wq, (size_t)ctx->Fp * 16))) return rc;
-    if ((rc = asb_alloc(ctx, &ctx->tile_counter, (size_t)16))) return rc;
-    hipLaunchKernelGGL(k_build_wq, dim3(64), dim3(256), 0, ctx->stream, ctx->Wt, (int)ctx->Fp, ctx->Wq, ctx->tile_counter);
-    const long long ntiles = (rows + 63) / 64;
-    size_t slot;
-    if ((rc = prof_begin(ctx, slot))) return rc;
-    // two waves (one 128-thread block) per 64-row tile (four waves per tile lost at the barriers what they gained at the end of the launch)
-    hipLaunchKernelGGL((k_project_l2s<4, 2, 2, 1>), dim3((unsigned)(ntiles < 4 * ctx->n_cu ? ntiles : 4 * ctx->n_cu)), dim3(128), 0, ctx->stream, ctx->X, rows, (int)ctx->Fp, ctx->Wq,
-                       ctx->wn2t, ncols, out, rows, ctx->tile_counter);
-    if ((rc = prof_end(ctx, slot))) return rc;
-    ASB_CHECK_LAUNCH(ctx);
-    return ASB_OK;
-}
-
-static void launch_project(asb_ctx* ctx, int ncols, double* out) {
-    (void)launch_project_l2(ctx, ncols, out);      // (errors surface through the launch check of the caller)
-}
-
 // out_rows (ncols, 3 n_loc) = X . Wfk[:, k0:k0+ncols] / col_scale[k0 + t]   (col_scale NULL: raw products;
 // used for c = W^T X of SPLOCS and for the POD back-projection U = A V S^-1)
 int asb_project_columns(asb_ctx* ctx, const double* Wfk, int64_t ldw, int64_t k0, int ncols, double* out_rows,
@@ -1794,7 +1816,6 @@ int asb_project_columns(asb_ctx* ctx, const double* Wfk, int64_t ldw, int64_t k0
     return ASB_OK;
 }
 
-__global__ void k_build_wq_tiles(const double* __restrict__ Wt3, int Fp, double* __restrict__ Wq3, unsigned* __restrict__ tile_counter);
 // the same product for up to 16 * ASB_MAX_SUB = 128 columns in ONE pass over X (the multi-tile kernels of the panel reads; SPLOCS'
 // c = W^T X, at most 64 columns, took four 16-column passes): out_rows[(k0 + j) - k0] for j < ncols
 int asb_project_columns_wide(asb_ctx* ctx, const double* Wfk, int64_t ldw, int64_t k0, int ncols, double* out_rows, const double* col_scale) {
@@ -2275,23 +2296,6 @@ __global__ __launch_bounds__(256) void k_assemble(const double* __restrict__ row
 }
 
 static int panel_assemble(asb_ctx* ctx, const double* rows_g, const long long* idx_g, const int64_t* counts, int world,
-                          int64_t maxcount, long long stride_rows, long long stride_idx);
-
-extern "C" int asb_panel_assemble(asb_ctx* ctx, const double* rows_g, const long long* idx_g, const int64_t* counts,
-                                  int world, int64_t maxcount) {
-    if (!ctx) return ASB_ERR_ARG;
-    return panel_assemble(ctx, rows_g, idx_g, counts, world, maxcount, (long long)maxcount * 3 * ctx->Fp, (long long)maxcount);
-}
-// the same from ONE all-gathered buffer: every rank's piece is its maxcount rows (3*Fp doubles each) followed by its
-// maxcount vertex ids (int64), i.e. maxcount * (3*Fp + 1) eight-byte words per rank
-extern "C" int asb_panel_assemble_packed(asb_ctx* ctx, const double* packed_g, const int64_t* counts, int world, int64_t maxcount) {
-    if (!ctx || !packed_g || maxcount < 0) return ASB_ERR_ARG;
-    const long long rl = 3 * ctx->Fp, stride = (long long)maxcount * (rl + 1);
-    return panel_assemble(ctx, packed_g, reinterpret_cast<const long long*>(packed_g + (long long)maxcount * rl), counts, world, maxcount,
-                          stride, stride);
-}
-
-static int panel_assemble(asb_ctx* ctx, const double* rows_g, const long long* idx_g, const int64_t* counts, int world,
                           int64_t maxcount, long long stride_rows, long long stride_idx) {
     if (!ctx || !ctx->candR || !rows_g || !idx_g || !counts) return ASB_ERR_ARG;
     if (world < 1 || world > 16) ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_panel_assemble: at most 16 ranks (got %d)", world);
@@ -2313,6 +2317,20 @@ static int panel_assemble(asb_ctx* ctx, const double* rows_g, const long long* i
     }
     ctx->n_slots_host = off;
     return ASB_OK;
+}
+
+extern "C" int asb_panel_assemble(asb_ctx* ctx, const double* rows_g, const long long* idx_g, const int64_t* counts,
+                                  int world, int64_t maxcount) {
+    if (!ctx) return ASB_ERR_ARG;
+    return panel_assemble(ctx, rows_g, idx_g, counts, world, maxcount, (long long)maxcount * 3 * ctx->Fp, (long long)maxcount);
+}
+// the same from ONE all-gathered buffer: every rank's piece is its maxcount rows (3*Fp doubles each) followed by its
+// maxcount vertex ids (int64), i.e. maxcount * (3*Fp + 1) eight-byte words per rank
+extern "C" int asb_panel_assemble_packed(asb_ctx* ctx, const double* packed_g, const int64_t* counts, int world, int64_t maxcount) {
+    if (!ctx || !packed_g || maxcount < 0) return ASB_ERR_ARG;
+    const long long rl = 3 * ctx->Fp, stride = (long long)maxcount * (rl + 1);
+    return panel_assemble(ctx, packed_g, reinterpret_cast<const long long*>(packed_g + (long long)maxcount * rl), counts, world, maxcount,
+                          stride, stride);
 }
 
 // --------------------------------------------------------------------------------------
@@ -2791,7 +2809,6 @@ static int coop_buffers(asb_ctx* ctx, int* cgrid_all, size_t* n_words) {
     if ((rc = asb_alloc(ctx, &ctx->coop_bar, (size_t)4 + 2 * 64 * 6))) return rc;
     return asb_alloc(ctx, &ctx->coop_rec, *n_words);
 }
-static int launch_panel_multi_any(asb_ctx* ctx, int grid, const MultiArgs& ma, bool* launched, PanelState* sub, bool writeback);
 constexpr int SPEC_W_RANK = 24;       // k_panel_multi: blocks ranked below it publish their w ahead of the exchange
 
 template <int NJ>
@@ -2830,61 +2847,82 @@ static void print_multi_timeline(asb_ctx* ctx, int nsteps) {
                 (tl[t * 6 + 4] - tl[t * 6 + 3]) * 0.01, (tl[t * 6 + 4] - tl[t * 6 + 0]) * 0.01);
 }
 
-// up to `steps` greedy steps on the context's candidate buffer (asb_panel_select with NULL
-// buffers, or asb_panel_assemble); returns the number of components committed.
-extern "C" int asb_panel_run(asb_ctx* ctx, int64_t k0, int steps, int global_all, int assembled, int64_t* committed) {
-    if (!ctx || !ctx->candR || ctx->mode != ASB_DEFLATE_PROJECT || !committed) return ASB_ERR_ARG;
+// One run of up to `steps` greedy steps on the context's candidate buffer (panel_run): everything it is told and
+// everything it reports -- nothing travels through the context.
+struct PanelRunIn {
+    long long k0 = 0;
+    int steps = 0;
+    int global_all = 0;      // every vertex is a candidate: nothing outside to bound
+    int assembled = 0;       // the candidate buffer was assembled from several ranks' pieces
+    int spec_max = 0;        // unproven steps the run may take behind its provable head
+    bool writeback = false;  // the panel kernel leaves the deflated rows in the buffer (a later sub-panel runs on them)
+    bool allow_coop = true;  // false: the two-kernel loop even where the co-resident kernel fits
+};
+struct PanelRunOut {
+    int64_t committed = 0;   // steps taken (-1: assembled candidates and the kernel's exchange timed out -- the driver redoes it)
+    long long proven = 0;    // length of their provable head
+    bool coop_used = false;  // they ran in the co-resident kernel
+};
+// up to `in.steps` greedy steps on the context's candidate buffer (asb_panel_select with NULL buffers, or asb_panel_assemble).
+// The co-resident kernel is tried first where it fits; a launch that has to be abandoned is redone by the two-kernel loop.
+static int panel_run(asb_ctx* ctx, const PanelRunIn& in, PanelRunOut* out) {
+    if (!ctx || !ctx->candR || ctx->mode != ASB_DEFLATE_PROJECT || !out) return ASB_ERR_ARG;
+    const long long k0 = in.k0;
+    const int steps = in.steps;
     if (steps < 1 || steps > ASB_PANEL_COLS || k0 < 0 || k0 + steps > ctx->K)
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_panel_run: bad range k0=%lld steps=%d", (long long)k0, steps);
     const StreamCfg c = ctx->cfg;
     int rc;
     if ((rc = asb_alloc(ctx, &ctx->cand_c, (size_t)ASB_PANEL_COLS * ctx->m_cap * 3))) return rc;
     if ((rc = asb_alloc(ctx, &ctx->slab_scratch, (size_t)3 * ctx->Fp))) return rc;
-    int cgrid_all = 0;
-    size_t n_words = 0;
-    const bool want_coop = coop_fits(ctx);
-    if (want_coop && (rc = coop_buffers(ctx, &cgrid_all, &n_words))) return rc;
-    const long long spec_max = want_coop && !global_all ? ctx->run_spec_max : 0;
-    hipLaunchKernelGGL(k_panel_arm, dim3(1), dim3(256), 0, ctx->stream, ctx->pstate, ctx->scalar_dev, global_all,
-                       (long long)(assembled ? ctx->n_slots_host : -1), ASB_MARGIN_REL, want_coop ? ctx->coop_bar : (unsigned*)nullptr,
-                       want_coop ? (unsigned long long*)ctx->coop_rec : (unsigned long long*)nullptr,
-                       want_coop ? 3 * cgrid_all * 2 + 3 * ((int)ctx->Fp + 8) : 0,
-                       ctx->run_theta_band, spec_max);
-    const int grid = stream_grid(ctx, c, ctx->m_cap);
+    PanelState h;
     bool coop = false;
-    if (want_coop) {      // the whole inner loop in one launch of co-resident blocks, rows in registers (one sub-panel)
-        MultiArgs ma{};
-        ma.kb[0] = k0;
-        ma.steps[0] = steps;
-        ma.spec_max[0] = (int)spec_max;
-        ma.nsub = 1;
-        if ((rc = launch_panel_multi_any(ctx, cgrid_all, ma, &coop, ctx->pstate, ctx->run_writeback != 0))) return rc;
-    }
-    if (assembled && !coop) {      // two-kernel loop: energies / partial records of the assembled buffer (rows came from other ranks)
-        StreamArgs a{ctx->candR, nullptr, nullptr, nullptr, nullptr, ctx->cand_e, ctx->cpmax, ctx->cpidx, ctx->cpsum,
-                     (long long)ctx->m_cap, ctx->pstate};
-        launch_stream(ctx, c, false, grid, a);
-        ctx->cnblk = grid;
-    }
-    for (int t = 0; t < (coop ? 0 : steps); ++t) {
-        const long long k = k0 + t;
-        hipLaunchKernelGGL(k_pick_panel, dim3(1), dim3(ASB_PP_T), 0, ctx->stream, ctx->candR, ctx->cand_c, (long long)ctx->m_cap,
-                           ctx->cpmax, ctx->cpidx, ctx->cnblk, (int)ctx->F, (int)ctx->Fp, ctx->W, ctx->scal, k,
-                           (long long)k0, ctx->pstate, ctx->cand_idx, ctx->slab_scratch);
-        if (t + 1 < steps) {          // the last step's dots would only feed a pick that never runs
-            launch_cand_dots(ctx, c, grid, k, t);
+    for (bool allow_coop = in.allow_coop;; allow_coop = false) {      // at most twice: the second time without the kernel
+        int cgrid_all = 0;
+        size_t n_words = 0;
+        const bool want_coop = allow_coop && coop_fits(ctx);
+        if (want_coop && (rc = coop_buffers(ctx, &cgrid_all, &n_words))) return rc;
+        const long long spec_max = want_coop && !in.global_all ? in.spec_max : 0;
+        hipLaunchKernelGGL(k_panel_arm, dim3(1), dim3(256), 0, ctx->stream, ctx->pstate, ctx->scalar_dev, in.global_all,
+                           (long long)(in.assembled ? ctx->n_slots_host : -1), ASB_MARGIN_REL, want_coop ? ctx->coop_bar : (unsigned*)nullptr,
+                           want_coop ? (unsigned long long*)ctx->coop_rec : (unsigned long long*)nullptr,
+                           want_coop ? 3 * cgrid_all * 2 + 3 * ((int)ctx->Fp + 8) : 0,
+                           0, spec_max);
+        const int grid = stream_grid(ctx, c, ctx->m_cap);
+        coop = false;
+        if (want_coop) {      // the whole inner loop in one launch of co-resident blocks, rows in registers (one sub-panel)
+            MultiArgs ma{};
+            ma.kb[0] = k0;
+            ma.steps[0] = steps;
+            ma.spec_max[0] = (int)spec_max;
+            ma.nsub = 1;
+            if ((rc = launch_panel_multi_any(ctx, cgrid_all, ma, &coop, ctx->pstate, in.writeback))) return rc;
+        }
+        if (in.assembled && !coop) {      // two-kernel loop: energies / partial records of the assembled buffer (rows came from other ranks)
+            StreamArgs a{ctx->candR, nullptr, nullptr, nullptr, nullptr, ctx->cand_e, ctx->cpmax, ctx->cpidx, ctx->cpsum,
+                         (long long)ctx->m_cap, ctx->pstate};
+            launch_stream(ctx, c, false, grid, a);
             ctx->cnblk = grid;
         }
-    }
-    ASB_CHECK_LAUNCH(ctx);
-    ctx->run_coop_used = coop ? 1 : 0;
-    PanelState h;
-    unsigned flags[4] = {0, 0, 0, 0};
-    if ((rc = read_panel_state(ctx, &h, coop ? flags : nullptr))) return rc;
-    *committed = h.committed;
-    ctx->run_proven = (h.proven < 0 || h.proven > h.committed) ? h.committed : h.proven;
-    ctx->n_panels++;
-    if (coop) {
+        for (int t = 0; t < (coop ? 0 : steps); ++t) {
+            const long long k = k0 + t;
+            hipLaunchKernelGGL(k_pick_panel, dim3(1), dim3(ASB_PP_T), 0, ctx->stream, ctx->candR, ctx->cand_c, (long long)ctx->m_cap,
+                               ctx->cpmax, ctx->cpidx, ctx->cnblk, (int)ctx->F, (int)ctx->Fp, ctx->W, ctx->scal, k,
+                               (long long)k0, ctx->pstate, ctx->cand_idx, ctx->slab_scratch);
+            if (t + 1 < steps) {          // the last step's dots would only feed a pick that never runs
+                launch_cand_dots(ctx, c, grid, k, t);
+                ctx->cnblk = grid;
+            }
+        }
+        ASB_CHECK_LAUNCH(ctx);
+        out->coop_used = coop;
+        unsigned flags[4] = {0, 0, 0, 0};
+        if ((rc = read_panel_state(ctx, &h, coop ? flags : nullptr))) return rc;
+        out->committed = h.committed;
+        out->proven = (h.proven < 0 || h.proven > h.committed) ? h.committed : h.proven;
+        ctx->n_panels++;
+        if (!coop || !(flags[1] || flags[2])) break;
+        ctx->n_panels--;                  // an abandoned launch is no read of X
         if (flags[1]) {
             // The record exchange did not complete: the kernel's blocks were not all resident at once -- another stream,
             // an RCCL kernel or a second context holds part of the GPU.  Every block has left through the abort flag (the
@@ -2895,28 +2933,16 @@ extern "C" int asb_panel_run(asb_ctx* ctx, int64_t k0, int steps, int global_all
             ctx->panel_coop = 0;
             ctx->coop_test_stall = 0;
             ctx->n_coop_fallbacks++;
-            if (assembled) {
+            if (in.assembled) {
                 // several ranks run this panel on identical data and must take identical decisions: the redo is the
                 // DRIVER's, on every rank together (committed = -1 tells it; see _panels.py)
-                ctx->n_panels--;
-                *committed = -1;
-                ctx->run_proven = 0;
+                out->committed = -1;
+                out->proven = 0;
                 return ASB_OK;
             }
-            ctx->n_panels--;
-            rc = asb_panel_run(ctx, k0, steps, global_all, assembled, committed);
-            ctx->run_coop_used = 0;
-            return rc;
         }
-        if (flags[2]) {               // more candidates than resident waves: this panel runs through the two-kernel loop
-            const int save = ctx->panel_coop;
-            ctx->panel_coop = 0;
-            ctx->n_panels--;
-            rc = asb_panel_run(ctx, k0, steps, global_all, assembled, committed);
-            ctx->panel_coop = save;
-            ctx->run_coop_used = 0;
-            return rc;
-        }
+        // (flags[2] alone: more candidates than resident waves -- this panel runs through the two-kernel loop, the context
+        // keeps the kernel for the next one)
     }
     if (coop && asb_debug_panels()) print_multi_timeline(ctx, (int)h.committed);
     if (asb_debug_panels()) {
@@ -2930,6 +2956,20 @@ extern "C" int asb_panel_run(asb_ctx* ctx, int64_t k0, int steps, int global_all
                         "max %.3f, 2nd %.3f, median %.3f, min %.3f\n", (long long)k0, h.n_cand, h.committed, h.theta,
                 m ? ce[m - 1] : 0.0, m > 1 ? ce[m - 2] : 0.0, m ? ce[m / 2] : 0.0, m ? ce[0] : 0.0);
     }
+    return ASB_OK;
+}
+// the C ABI of it: provable steps only; returns the number of components committed
+extern "C" int asb_panel_run(asb_ctx* ctx, int64_t k0, int steps, int global_all, int assembled, int64_t* committed) {
+    if (!committed) return ASB_ERR_ARG;
+    PanelRunIn in;
+    in.k0 = k0;
+    in.steps = steps;
+    in.global_all = global_all;
+    in.assembled = assembled;
+    PanelRunOut out;
+    const int rc = panel_run(ctx, in, &out);
+    if (rc) return rc;
+    *committed = out.committed;
     return ASB_OK;
 }
 
@@ -2949,11 +2989,17 @@ extern "C" int asb_panel_project(asb_ctx* ctx, int64_t k0, int ncols) {
 extern "C" int asb_panel_run_spec(asb_ctx* ctx, int64_t k0, int steps, int global_all, int assembled, int spec_max, int64_t* ran,
                                   int64_t* proven) {
     if (!ctx || !ran || !proven || spec_max < 0) return ASB_ERR_ARG;
-    ctx->run_spec_max = ctx->spec_panels ? spec_max : 0;
-    const int rc = asb_panel_run(ctx, k0, steps, global_all, assembled, ran);
-    ctx->run_spec_max = 0;
+    PanelRunIn in;
+    in.k0 = k0;
+    in.steps = steps;
+    in.global_all = global_all;
+    in.assembled = assembled;
+    in.spec_max = ctx->spec_panels ? spec_max : 0;
+    PanelRunOut out;
+    const int rc = panel_run(ctx, in, &out);
     if (rc) return rc;
-    *proven = ctx->run_proven;
+    *ran = out.committed;
+    *proven = out.proven;
     return ASB_OK;
 }
 // pass over X for all `ncols` steps of the panel (the first `proven` of them certain), coefficients written, energies
@@ -2965,7 +3011,7 @@ extern "C" int asb_panel_project_spec(asb_ctx* ctx, int64_t k0, int ncols, int p
     int rc = project_pass(ctx, k0, ncols, proven, nullptr, true);
     if (rc) return rc;
     ctx->n_spec_steps += ncols - proven;
-    ctx->run_proven = proven;
+    ctx->spec_proven = proven;
     PanelState h;
     if ((rc = read_panel_state(ctx, &h, nullptr))) return rc;
     *first_rejected = h.spec_ok < ncols ? h.spec_ok : ncols;
@@ -2983,7 +3029,7 @@ extern "C" int asb_panel_project_spec_dev(asb_ctx* ctx, int64_t k0, int ncols, i
     int rc = project_pass(ctx, k0, ncols, proven, nullptr, true);
     if (rc) return rc;
     ctx->n_spec_steps += ncols - proven;
-    ctx->run_proven = proven;
+    ctx->spec_proven = proven;
     hipLaunchKernelGGL(k_spec_count, dim3(1), dim3(1), 0, ctx->stream, ctx->pstate, ncols, first_rejected_dev);
     ASB_CHECK_LAUNCH(ctx);
     return ASB_OK;
@@ -2995,7 +3041,7 @@ extern "C" int asb_panel_commit(asb_ctx* ctx, int64_t k0, int kept) {
     int rc = project_commit(ctx, k0, kept, nullptr);
     if (rc) return rc;
     if (kept > 0) ctx->k_done = k0 + kept;
-    if (kept > ctx->run_proven) ctx->n_spec_kept += kept - ctx->run_proven;
+    if (kept > ctx->spec_proven) ctx->n_spec_kept += kept - ctx->spec_proven;
     return ASB_OK;
 }
 
@@ -3289,16 +3335,9 @@ static int spec_tile_finish(asb_ctx* ctx, int ct, long long kb, int nc, PanelSta
 // a few microseconds of work each, their cost is the launch
 __global__ __launch_bounds__(256) void k_build_wt_tiles(const double* __restrict__ W, const double* __restrict__ scal, WideArgs wa, int Fp,
                                                         double* __restrict__ Wt3, double* __restrict__ wn2t3) {
-    const int ct = blockIdx.y, ncols = wa.nc[ct];
-    const long long k0 = wa.kb[ct], total = (long long)Fp * ASB_PANEL_COLS;
-    double* Wt = Wt3 + (size_t)ct * Fp * 16;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int t = (int)(i % ASB_PANEL_COLS);
-        const long long f = i / ASB_PANEL_COLS;
-        Wt[i] = (t < ncols) ? W[(k0 + t) * Fp + f] : 0.0;
-    }
-    if (blockIdx.x == 0 && threadIdx.x < ASB_PANEL_COLS)
-        wn2t3[16 * ct + threadIdx.x] = (threadIdx.x < ncols) ? scal[(k0 + threadIdx.x) * 4 + 1] : 1.0;
+    const int ct = blockIdx.y;
+    const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+    build_wt_body(W, scal, wa.kb[ct], wa.nc[ct], Fp, Wt3 + (size_t)ct * Fp * 16, wn2t3 + 16 * ct, i0, stride);
 }
 // G3[ct][j][t] = (w_j . w_t) / |w_j|^2 for j < kb[ct] + nc[ct] (k_panel_gram with scal; K rows of 16 per tile)
 __global__ __launch_bounds__(256) void k_panel_gram_tiles(const double* __restrict__ W, const double* __restrict__ Wt3, int Fp, long long K,
@@ -3323,39 +3362,11 @@ __global__ __launch_bounds__(256) void k_panel_gram_tiles(const double* __restri
 }
 __global__ __launch_bounds__(256) void k_orth_wt_tiles(const double* __restrict__ W, const double* __restrict__ G3, long long K, WideArgs wa,
                                                        int Fp, double* __restrict__ Wt3) {
-    const int ct = blockIdx.y, ncols = wa.nc[ct];
-    const long long kb = wa.kb[ct], total = (long long)Fp * ASB_PANEL_COLS;
-    const double* G = G3 + (long long)ct * K * 16;
-    double* Wt = Wt3 + (size_t)ct * Fp * 16;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int t = (int)(i % ASB_PANEL_COLS);
-        const long long f = i / ASB_PANEL_COLS;
-        if (t >= ncols) continue;
-        double s = 0.0, s2 = 0.0;
-        long long j = 0;
-        for (; j + 2 <= kb + t; j += 2) {
-            s += W[j * Fp + f] * G[j * 16 + t];
-            s2 += W[(j + 1) * Fp + f] * G[(j + 1) * 16 + t];
-        }
-        if (j < kb + t) s += W[j * Fp + f] * G[j * 16 + t];
-        Wt[i] -= s + s2;
-    }
-}
-__global__ __launch_bounds__(256) void k_build_wq_tiles(const double* __restrict__ Wt3, int Fp, double* __restrict__ Wq3,
-                                                        unsigned* __restrict__ tile_counter) {
     const int ct = blockIdx.y;
-    if (blockIdx.x == 0 && ct == 0 && threadIdx.x < 16) tile_counter[threadIdx.x] = 0u;      // the projection kernel's work queue
-    const double* Wt = Wt3 + (size_t)ct * Fp * 16;
-    double* Wq = Wq3 + (size_t)ct * Fp * 16;
-    const long long total = (long long)Fp * 16;
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
-        const int j = (int)(e & 3), i = (int)((e >> 2) & 15), g = (int)((e >> 6) & 3);
-        const long long chunk = e >> 8;
-        Wq[e] = Wt[(chunk * 16 + 4 * g + j) * ASB_PANEL_COLS + i];
-    }
+    const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+    orth_wt_body(W, G3 + (long long)ct * K * 16, wa.kb[ct], wa.nc[ct], Fp, Wt3 + (size_t)ct * Fp * 16, i0, stride);
 }
 // the same through the per-tile kernels when the weights are not orthogonalised beforehand (ASB_PRE_ORTH=0 / ASB_CORRECT_ROWS=0)
-static int dbl_build_tiles(asb_ctx* ctx, int ntile, const WideArgs& wa);
 
 // operands of tile ct of a multi-sub-panel read; pre_orth: orthogonalised weights (k_orth_wt), see spec_tile_finish
 static void dbl_build_tile(asb_ctx* ctx, int ct, long long kb, int nc) {
@@ -3387,37 +3398,49 @@ static int dbl_build_tiles(asb_ctx* ctx, int ntile, const WideArgs& wa) {
     ASB_CHECK_LAUNCH(ctx);
     return ASB_OK;
 }
-// The sub-panels of a read in ONE launch (k_panel_multi): arm, kernel, one read of the summary.
-// *ntile = -1: the launch did not run to the end of its first sub-panel (exchange timed out / too many candidates): nothing
-// was committed, the caller takes the one-by-one path with its fallbacks.
-static int dbl_build_tiles(asb_ctx* ctx, int ntile, const WideArgs& wa);
-static int launch_wide(asb_ctx* ctx, int ntile, const WideArgs& wa);
-// spec_ntile / spec_nc (optional): the read's PASS is enqueued right behind the panel kernel on the column counts the
+// ---- the host steps of a read of X with several sub-panels, shared by double_panel (one rank, inside the library) and
+// asb_panel_read_run / _commit (several ranks, driven by _panels.py)
+// what such a read knows about its tiles, passed from step to step
+struct ReadState {
+    int ntile = 0;                                       // tiles (sub-panels that committed steps)
+    long long kb[ASB_MAX_SUB] = {0};                     // first component of tile ct
+    int nc[ASB_MAX_SUB] = {0}, proven[ASB_MAX_SUB] = {0};    // its columns, the provable head of them
+    int spec_ntile = 0, spec_nc[ASB_MAX_SUB] = {0};      // the tiles / columns a pass is already running for
+    int64_t total = 0;                                   // the verdict: components that stand,
+    int full = 0;                                        // tiles that stand in full,
+    bool rejected = false;                               // a tile lost columns
+};
+// The sub-panels of a read in ONE launch (k_panel_multi): arm, kernel, one read of the summary.  spec_budget: unproven steps of
+// the first sub-panel; sub_budget[sp]: steps given to the later ones.
+// rs.ntile = -1: the launch did not run to the end of its first sub-panel (exchange timed out / too many candidates): nothing
+// was committed, the caller takes the one-by-one path with its fallbacks.  *timed_out: a sub-panel met a poll that did not
+// complete (several ranks: the driver makes all of them leave the kernel together).
+// rs.spec_ntile / spec_nc: the read's PASS is enqueued right behind the panel kernel on the column counts the
 // sub-panels are EXPECTED to reach (their step budgets), before the host knows what they reached -- it runs while the host waits
 // for the summary instead of after it.  Safe: a sub-panel that ended early only means columns computed from rows of W nobody
 // wrote (they lie at and beyond the first column that is not committed, and a later tile exists only behind a FULL one, so no
 // committed column is ever orthogonalised against them); the caller checks the tiles on the counts really reached.
-static int multi_chain_run(asb_ctx* ctx, long long k, long long k1, int nsub_max, int* ntile, int* nc, int* proven,
-                           int* spec_ntile = nullptr, int* spec_nc = nullptr, bool assembled = false) {
+static int multi_chain_run(asb_ctx* ctx, long long k, long long k1, int nsub_max, int spec_budget, const int* sub_budget, bool assembled,
+                           ReadState& rs, bool* timed_out) {
     int rc;
-    *ntile = -1;
-    ctx->chain_timed_out = 0;
-    if (spec_ntile) *spec_ntile = 0;
-    int cgrid_all = 0;
-    size_t n_words = 0;
-    if ((rc = coop_buffers(ctx, &cgrid_all, &n_words))) return rc;
+    rs.ntile = -1;
+    rs.spec_ntile = 0;
+    *timed_out = false;
     MultiArgs ma{};
     int n = 0;
     for (int sp = 0; sp < nsub_max && sp < ASB_MAX_SUB && k + (long long)sp * ASB_PANEL_COLS < k1; ++sp) {
         const long long kb = k + (long long)sp * ASB_PANEL_COLS;
         int steps = (int)((k1 - kb) < ASB_PANEL_COLS ? (k1 - kb) : ASB_PANEL_COLS);
-        if (sp > 0 && steps > ctx->sub_budget[sp]) steps = ctx->sub_budget[sp];
+        if (sp > 0 && steps > sub_budget[sp]) steps = sub_budget[sp];
         ma.kb[n] = kb;
         ma.steps[n] = steps;
-        ma.spec_max[n] = sp == 0 ? ctx->spec_budget : ASB_PANEL_COLS;
+        ma.spec_max[n] = sp == 0 ? spec_budget : ASB_PANEL_COLS;
         ++n;
     }
     ma.nsub = n;
+    int cgrid_all = 0;
+    size_t n_words = 0;
+    if ((rc = coop_buffers(ctx, &cgrid_all, &n_words))) return rc;
     // records and the winner's weight buffers start out as "not written" (all bits set: filled by the arm kernel); the
     // speculative buffers are reset by their owners at the start of the panel kernel
     const int n_small = 3 * cgrid_all * 2 + 3 * ((int)ctx->Fp + 8);
@@ -3428,42 +3451,41 @@ static int multi_chain_run(asb_ctx* ctx, long long k, long long k1, int nsub_max
     if (!launched) return ASB_OK;
     unsigned long long sum[9], seq = 0;
     if ((rc = fetch_multi_begin(ctx, &seq))) return rc;
-    if (spec_ntile && seq && ctx->spec_budget >= ASB_PANEL_COLS && ctx->pre_orth && ctx->correct_rows) {
+    if (seq && spec_budget >= ASB_PANEL_COLS && ctx->pre_orth && ctx->correct_rows) {
         WideArgs wa{};
         int nt = 0;
         for (int sp = 0; sp < n; ++sp) {
             wa.kb[nt] = ma.kb[sp];
             wa.nc[nt] = ma.steps[sp];
-            spec_nc[nt] = ma.steps[sp];
+            rs.spec_nc[nt] = ma.steps[sp];
             ++nt;
             if (ma.steps[sp] < ASB_PANEL_COLS) break;
         }
         if ((rc = dbl_build_tiles(ctx, nt, wa))) return rc;
         if ((rc = launch_wide(ctx, nt, wa))) return rc;
-        *spec_ntile = nt;
+        rs.spec_ntile = nt;
     }
     if ((rc = fetch_multi_end(ctx, seq, sum))) return rc;
     ctx->n_panels++;
-    ctx->run_coop_used = 1;
     if (asb_debug_panels()) print_multi_timeline(ctx, (int)(sum[0] & 0xffffffffu) + 16 * (n - 1));
     int nt = 0;
     for (int sp = 0; sp < n; ++sp) {
         const long long committed = (long long)(sum[sp] & 0xffffffffu), prov = (long long)(sum[sp] >> 32) - 1;
         if (prov < 0) {                                  // the launch did not finish this sub-panel (sum[8] says why)
-            ctx->chain_timed_out = 1;                    // (several ranks: the driver makes all of them leave the kernel together)
-            if (sp == 0) return ASB_OK;                  // *ntile = -1: the one-by-one path meets the same and falls back
+            *timed_out = true;
+            if (sp == 0) return ASB_OK;                  // rs.ntile = -1: the one-by-one path meets the same and falls back
             ctx->panel_coop = 0;                         // a later one timed out: what stands stands, the context leaves the kernel
             ctx->coop_test_stall = 0;
             ctx->n_coop_fallbacks++;
             break;
         }
         if (committed <= 0) break;
-        nc[nt] = (int)committed;
-        proven[nt] = (int)(prov > committed ? committed : prov);
+        rs.nc[nt] = (int)committed;
+        rs.proven[nt] = (int)(prov > committed ? committed : prov);
         ++nt;
         if (committed < ASB_PANEL_COLS) break;
     }
-    *ntile = nt;
+    rs.ntile = nt;
     return ASB_OK;
 }
 // the checks of all tiles of a read, enqueued back to back (pre-orthogonalised weights, one-thread-per-row check): per tile the
@@ -3518,8 +3540,6 @@ static int tiles_enqueue(asb_ctx* ctx, int ntile, const long long* kb, const int
     *cgrid_out = cgrid;
     return ASB_OK;
 }
-// ---- the host steps of a read of X with several sub-panels, shared by double_panel (one rank, inside the library) and
-// asb_panel_read_run / _commit (several ranks, driven by _panels.py)
 // the operands and states of up to ASB_MAX_SUB tiles
 static int read_buffers(asb_ctx* ctx) {
     int rc;
@@ -3565,10 +3585,13 @@ static void commit_head(asb_ctx* ctx, int ct, long long kb, int cols, int cgrid)
     ctx->nblk = cgrid;
     hipLaunchKernelGGL(k_colsum, dim3(1), dim3(1024), 0, ctx->stream, ctx->colpart, ctx->nblk, cols, kb, ctx->scal, (PanelState*)nullptr);
 }
-// statistics and the next read's step budget once `kept` of the nc columns of tile ct (the first `proven` certain) stand
-static void tile_account(asb_ctx* ctx, long long k, int ct, int nc, int proven, int64_t kept) {
+// statistics once `kept` of the nc columns of a tile (the first `proven` certain) stand
+static void tile_stats(asb_ctx* ctx, int nc, int proven, int64_t kept) {
     ctx->n_spec_steps += nc - proven;
     ctx->n_spec_kept += kept > proven ? kept - proven : 0;
+}
+// one rank: the trace line of tile ct and the next read's step budget
+static void tile_adapt(asb_ctx* ctx, long long k, int ct, int nc, int proven, int64_t kept) {
     if (asb_debug_panels())
         fprintf(stderr, "[asb] panel at k=%lld tile %d: %d proven + %lld of %d unproven steps kept\n", k, ct, proven,
                 (long long)(kept > proven ? kept - proven : 0), nc - proven);
@@ -3577,104 +3600,132 @@ static void tile_account(asb_ctx* ctx, long long k, int ct, int nc, int proven, 
         ctx->sub_budget[ct] = want < 4 ? 4 : (want > ASB_PANEL_COLS ? ASB_PANEL_COLS : want);
     }
 }
-static int panel_candidates(asb_ctx* ctx, long long k, int stalled);
-static int double_panel(asb_ctx* ctx, long long k, long long k1, int64_t* done_out) {
-    int rc;
-    *done_out = 0;
-    const int nsub_lim = ctx->sub_panels < 1 ? 1 : (ctx->sub_panels > ASB_MAX_SUB ? ASB_MAX_SUB : ctx->sub_panels);
-    if (ctx->sub_cur < 1) ctx->sub_cur = nsub_lim < ctx->sub_first ? nsub_lim : ctx->sub_first;
-    const int nsub_max = ctx->sub_cur < nsub_lim ? ctx->sub_cur : nsub_lim;
-    if ((rc = read_buffers(ctx))) return rc;
-    const auto t_read0 = std::chrono::steady_clock::now();
-    if ((rc = panel_candidates(ctx, k, 0))) return rc;
-    if ((rc = read_snapshot(ctx))) return rc;
-    long long kb[ASB_MAX_SUB];
-    int nc[ASB_MAX_SUB] = {0}, proven[ASB_MAX_SUB] = {0};
-    for (int sp = 0; sp < ASB_MAX_SUB; ++sp) kb[sp] = k + (long long)sp * ASB_PANEL_COLS;
-    int ntile = 0, spec_ntile = 0, spec_nc[ASB_MAX_SUB] = {0};
-    bool chained_runs = false;
-    if (ctx->sub_chain && coop_fits(ctx) && ctx->spec_panels && nsub_max > 1) {
-        int nt = -1;
-        if ((rc = multi_chain_run(ctx, k, k1, nsub_max, &nt, nc, proven, &spec_ntile, spec_nc))) return rc;
-        if (nt == 0) return ASB_OK;                      // nothing committed: the caller's refresh / forced path
-        if (nt > 0) { ntile = nt; chained_runs = true; }
+// The verdict of a read whose checks ran as a chain on the device, for one rank and for several.  keep[ct]: the columns of
+// tile ct that stand on EVERY shard -- tiles stand in full while keep == nc, the first one below keeps its head, nothing
+// behind it.  local[ct]: what stands on THIS shard: its chain adopted the tentative energies of the tiles that stood in full
+// here, consecutively.  One rank is the case local == keep (several = false).  Fills rs.total / full / rejected.
+static int read_chain_verdict(asb_ctx* ctx, ReadState& rs, const int* keep, const int* local, int rgrid, int cgrid, bool several) {
+    int nstand = 0;                                      // tiles that take part
+    for (int ct = 0; ct < rs.ntile; ++ct) {
+        nstand = ct + 1;
+        if (keep[ct] < rs.nc[ct]) break;
     }
-    for (int sp = 0; !chained_runs && sp < nsub_max && kb[sp] < k1; ++sp) {
-        int steps = (int)((k1 - kb[sp]) < ASB_PANEL_COLS ? (k1 - kb[sp]) : ASB_PANEL_COLS);
+    int l_full = 0;
+    while (l_full < rs.ntile && local[l_full] == rs.nc[l_full]) {
+        // (a tile "not reached" locally also reads nc: it lies behind a local failure, so the loop has stopped before it)
+        ++l_full;
+    }
+    int g_full = 0;
+    while (g_full < nstand && keep[g_full] == rs.nc[g_full]) ++g_full;
+    if (several && l_full > g_full) {
+        // this shard ran ahead of the verdict: back to the energies at the start of the read, then the verdict column by column
+        ASB_HIP(ctx, hipMemcpyAsync(ctx->energy, ctx->e_class, (size_t)ctx->n_loc * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+        for (int ct = 0; ct < nstand; ++ct)
+            if (keep[ct] > 0) commit_head(ctx, ct, rs.kb[ct], keep[ct], cgrid);
+    } else {
+        // l_full == g_full (the minimum cannot stand where this shard did not): the full tiles are adopted -- the records are
+        // those of the last of them --, the partial one -- its energies untouched -- keeps its head (one rank: also an empty one)
+        ctx->nblk = rgrid;
+        if (g_full < nstand && (keep[g_full] > 0 || !several)) commit_head(ctx, g_full, rs.kb[g_full], keep[g_full], cgrid);
+    }
+    ASB_CHECK_LAUNCH(ctx);
+    rs.total = 0;
+    rs.full = 0;
+    rs.rejected = false;
+    for (int ct = 0; ct < nstand; ++ct) {
+        rs.total += keep[ct];
+        tile_stats(ctx, rs.nc[ct], rs.proven[ct], keep[ct]);
+        if (keep[ct] < rs.nc[ct]) rs.rejected = true; else ++rs.full;
+    }
+    return ASB_OK;
+}
+
+static int panel_candidates(asb_ctx* ctx, long long k, int stalled);
+// ---- one rank: a read of X in five steps
+// 1. the sub-panels, in one chained launch or one by one.  rs.ntile = 0 with *nothing = true: the first sub-panel committed
+// nothing (the caller's refresh / forced path)
+static int read_run_subpanels(asb_ctx* ctx, long long k, long long k1, int nsub_max, ReadState& rs, bool* chained_runs, bool* nothing) {
+    int rc;
+    *chained_runs = *nothing = false;
+    if (ctx->sub_chain && coop_fits(ctx) && ctx->spec_panels && nsub_max > 1) {
+        bool timed_out = false;
+        if ((rc = multi_chain_run(ctx, k, k1, nsub_max, ctx->spec_budget, ctx->sub_budget, false, rs, &timed_out))) return rc;
+        if (rs.ntile == 0) { *nothing = true; return ASB_OK; }
+        if (rs.ntile > 0) { *chained_runs = true; return ASB_OK; }
+        rs.ntile = 0;
+    }
+    for (int sp = 0; sp < nsub_max && rs.kb[sp] < k1; ++sp) {
+        PanelRunIn in;
+        in.k0 = rs.kb[sp];
+        in.steps = (int)((k1 - rs.kb[sp]) < ASB_PANEL_COLS ? (k1 - rs.kb[sp]) : ASB_PANEL_COLS);
         if (sp > 0) {
             // a later sub-panel runs on rows chosen for the first, mostly unproven (the bound on the vertices outside is the
             // stale one): it is given as many steps as the last ones kept (+2) -- a rejected step costs a panel step and
             // everything behind it
-            if (steps > ctx->sub_budget[sp]) steps = ctx->sub_budget[sp];
+            if (in.steps > ctx->sub_budget[sp]) in.steps = ctx->sub_budget[sp];
         }
-        int64_t ran = 0;
-        ctx->run_writeback = 1;
-        ctx->run_spec_max = ctx->spec_panels ? (sp == 0 ? ctx->spec_budget : ASB_PANEL_COLS) : 0;
-        rc = asb_panel_run(ctx, kb[sp], steps, 0, 0, &ran);      // sp > 0: same candidates, rows as the last sub-panel left them
-        ctx->run_writeback = 0;
-        ctx->run_spec_max = 0;
-        if (rc) return rc;
+        in.writeback = true;
+        in.spec_max = ctx->spec_panels ? (sp == 0 ? ctx->spec_budget : ASB_PANEL_COLS) : 0;
+        PanelRunOut ran;
+        if ((rc = panel_run(ctx, in, &ran))) return rc;      // sp > 0: same candidates, rows as the last sub-panel left them
         // this sub-panel's state (winner energies, provable head) is needed again after the pass; a later launch re-arms pstate
         ASB_HIP(ctx, hipMemcpyAsync(ctx->pstate2 + sp, ctx->pstate, sizeof(PanelState), hipMemcpyDeviceToDevice, ctx->stream));
         if (sp > 0) ctx->n_panels--;                     // statistics count reads of X
-        if (sp == 0 && ran == 0) return ASB_OK;          // the caller's refresh / forced path
-        if (ran == 0 || (sp > 0 && !ctx->run_coop_used)) break;
-        nc[sp] = (int)ran;
-        proven[sp] = (int)ctx->run_proven;
-        ntile = sp + 1;
+        if (sp == 0 && ran.committed == 0) { *nothing = true; return ASB_OK; }
+        if (ran.committed == 0 || (sp > 0 && !ran.coop_used)) break;
+        rs.nc[sp] = (int)ran.committed;
+        rs.proven[sp] = (int)ran.proven;
+        rs.ntile = sp + 1;
         // another sub-panel only behind a full one that ran in the co-resident kernel (the two-kernel loop leaves the rows
         // as they were) and may go on unproven
-        if (ran < ASB_PANEL_COLS || !ctx->run_coop_used || !ctx->spec_panels) break;
+        if (ran.committed < ASB_PANEL_COLS || !ran.coop_used || !ctx->spec_panels) break;
     }
-    // one read of X for all tiles (their states are in pstate2: k_panel_multi writes them there, the one-by-one loop copies);
-    // chained: the checks of all tiles enqueued back to back behind it, ONE host read
-    int64_t total = 0;
-    int full = 0, rgrid = 0, cgrid = 0;
-    bool rejected = false;
-    const bool chained = ctx->pre_orth && ctx->correct_rows && ctx->tile_chain;
-    if ((rc = read_enqueue(ctx, k, ntile, nc, chained_runs ? spec_ntile : 0, spec_nc, chained, &rgrid, &cgrid))) return rc;
+    return ASB_OK;
+}
+// 2. one read of X for all tiles (their states are in pstate2: k_panel_multi writes them there, the one-by-one loop copies) and
+// the verdict.  chained: the checks of all tiles enqueued back to back behind it, ONE host read; otherwise tile by tile
+static int read_verdict(asb_ctx* ctx, long long k, ReadState& rs, bool chained_runs, bool chained) {
+    int rc, rgrid = 0, cgrid = 0;
+    if ((rc = read_enqueue(ctx, k, rs.ntile, rs.nc, chained_runs ? rs.spec_ntile : 0, rs.spec_nc, chained, &rgrid, &cgrid))) return rc;
     if (chained) {
         long long res[ASB_MAX_SUB + 1];
         if ((rc = fetch_words(ctx, ctx->tile_res, ASB_MAX_SUB + 1, res))) return rc;
-        ctx->nblk = rgrid;                           // the records of the last tile that stood in full
-        for (int ct = 0; ct < ntile; ++ct) {
-            int64_t kept = res[ct] < 0 ? 0 : res[ct];
-            if (res[ct] >= 0 && kept < nc[ct]) {     // this tile did not stand in full: its energies are untouched, commit the head
-                commit_head(ctx, ct, kb[ct], (int)kept, cgrid);
-                ASB_CHECK_LAUNCH(ctx);
-            }
-            if (res[ct] < 0) break;                  // behind a tile that did not stand
-            tile_account(ctx, k, ct, nc[ct], proven[ct], kept);
-            total += kept;
-            if (kept < nc[ct]) { rejected = true; break; }
-            ++full;
-        }
+        int keep[ASB_MAX_SUB];
+        for (int ct = 0; ct < ASB_MAX_SUB; ++ct) keep[ct] = res[ct] < 0 ? 0 : (int)res[ct];      // (-1: behind a tile that did not stand)
+        if ((rc = read_chain_verdict(ctx, rs, keep, keep, rgrid, cgrid, false))) return rc;
+        for (int ct = 0; ct < rs.full + (rs.rejected ? 1 : 0); ++ct) tile_adapt(ctx, k, ct, rs.nc[ct], rs.proven[ct], keep[ct]);
     }
-    for (int ct = 0; ct < ntile && !chained; ++ct) {
+    for (int ct = 0; ct < rs.ntile && !chained; ++ct) {
         int64_t kept = 0;
-        if ((rc = spec_tile_finish(ctx, ct, kb[ct], nc[ct], ctx->pstate2 + ct, &kept))) return rc;
-        tile_account(ctx, k, ct, nc[ct], proven[ct], kept);
-        total += kept;
-        if (kept < nc[ct]) { rejected = true; break; }      // what follows was built on a rejected step
-        ++full;
+        if ((rc = spec_tile_finish(ctx, ct, rs.kb[ct], rs.nc[ct], ctx->pstate2 + ct, &kept))) return rc;
+        tile_stats(ctx, rs.nc[ct], rs.proven[ct], kept);
+        tile_adapt(ctx, k, ct, rs.nc[ct], rs.proven[ct], kept);
+        rs.total += kept;
+        if (kept < rs.nc[ct]) { rs.rejected = true; break; }      // what follows was built on a rejected step
+        ++rs.full;
     }
-    // (chained tiles: the host has just read the tile results, the read's GPU work is done)
-    const double read_ms = chained ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_read0).count() : -1.0;
-    // how many sub-panels the next read of X gets: twice as many after a read whose sub-panels all stood, what stood
-    // (+1) after a rejection -- a rejected sub-panel costs its panel steps and its share of the MFMA work
-    if (rejected) ctx->sub_cur = full + 1 < nsub_lim ? full + 1 : nsub_lim;
-    else if (ntile == nsub_max) ctx->sub_cur = 2 * nsub_max < nsub_lim ? 2 * nsub_max : nsub_lim;
-    if (total > 0) ctx->k_done = k + total;
-    if (total > ctx->max_read_kept) ctx->max_read_kept = total;
-    // Structured data: the ranking reshuffled under this read's candidates.  The columns of its rejected steps are a sketch
-    // of the residual of EVERY vertex (asb_sketch.hip): a greedy replay in that space names the next read's candidates, and
-    // the next read gets all its sub-panels again (its rejected columns are the sketch after it).
-    // Is a predicted read worth what it costs?  It reads X for all four sub-panels and pays the replay (about 2.9 ms at config 4's
-    // size) where a plain read behind a rejection takes one or two sub-panels (1.3 - 1.6 ms): on low-rank data it commits 4x the
-    // components, on a slowly decaying spectrum or on localised modes 1.3 - 1.5x (tools/structured_probe.py: 9 reads in 23.7 ms
-    // against 12 in 16.3, 16 in 42.9 against 23 in 30.3 when every rejection was answered by a replay).  So both kinds of read are
-    // rated, components per (modelled) millisecond, as exponential means; the better one is taken, the other tried again every
-    // sixth read.
+    if (rs.total > 0) ctx->k_done = k + rs.total;
+    if (rs.total > ctx->max_read_kept) ctx->max_read_kept = rs.total;
+    return ASB_OK;
+}
+// 3. how many sub-panels the next read of X gets: twice as many after a read whose sub-panels all stood, what stood
+// (+1) after a rejection -- a rejected sub-panel costs its panel steps and its share of the MFMA work
+static void read_adapt(asb_ctx* ctx, const ReadState& rs, int nsub_max, int nsub_lim) {
+    if (rs.rejected) ctx->sub_cur = rs.full + 1 < nsub_lim ? rs.full + 1 : nsub_lim;
+    else if (rs.ntile == nsub_max) ctx->sub_cur = 2 * nsub_max < nsub_lim ? 2 * nsub_max : nsub_lim;
+}
+// 4. Structured data: the ranking reshuffled under this read's candidates.  The columns of its rejected steps are a sketch
+// of the residual of EVERY vertex (asb_sketch.hip): a greedy replay in that space names the next read's candidates, and
+// the next read gets all its sub-panels again (its rejected columns are the sketch after it).
+// Is a predicted read worth what it costs?  It reads X for all four sub-panels and pays the replay (about 2.9 ms at config 4's
+// size) where a plain read behind a rejection takes one or two sub-panels (1.3 - 1.6 ms): on low-rank data it commits 4x the
+// components, on a slowly decaying spectrum or on localised modes 1.3 - 1.5x (tools/structured_probe.py: 9 reads in 23.7 ms
+// against 12 in 16.3, 16 in 42.9 against 23 in 30.3 when every rejection was answered by a replay).  So both kinds of read are
+// rated, components per (modelled) millisecond, as exponential means; the better one is taken, the other tried again every
+// sixth read.  read_ms: the host clock over this read (< 0: not measured).  Returns whether a replay should name the next candidates.
+static bool read_rate(asb_ctx* ctx, long long k, const ReadState& rs, double read_ms) {
+    const int ntile = rs.ntile;
+    const int64_t total = rs.total;
     {
         static const double pass_ms[5] = {0.0, 0.87, 1.0, 1.25, 1.41};
         // (a plain read is rated at the size the adaptation would have given it -- the sub-panels its kept steps fill -- not at the
@@ -3740,9 +3791,16 @@ static int double_panel(asb_ctx* ctx, long long k, long long k1, int64_t* done_o
         fprintf(stderr, "[asb] read at k=%lld (%s candidates) kept %lld: components per ms plain %.1f, predicted %.1f -> %s next\n", k,
                 ctx->read_by_score ? "predicted" : "plain", (long long)total, ctx->rate_plain, ctx->rate_sketch,
                 want_replay ? "replay" : "plain");
+    return want_replay;
+}
+// 5. what follows a rejection: a replay of the sketch, or the next read's sub-panels restored, or a diverse read
+static int read_followup(asb_ctx* ctx, long long k, long long k1, const ReadState& rs, bool want_replay, int nsub_lim) {
+    int rc;
+    const int64_t total = rs.total;
+    const bool rejected = rs.rejected;
     if (ctx->sketch && want_replay && !ctx->sketch_run_off && rejected && total > 0 && k + total < k1) {
         long long ncols = 0;
-        for (int ct = 0; ct < ntile; ++ct) ncols += nc[ct];
+        for (int ct = 0; ct < rs.ntile; ++ct) ncols += rs.nc[ct];
         const long long left = ncols - total;
         if (left >= 8 && ctx->n_loc > ctx->m_cap) {        // (above one co-resident launch the replay runs on the largest energies)
             const long long ks = k + total, todo = k1 - ks;
@@ -3795,7 +3853,32 @@ static int double_panel(asb_ctx* ctx, long long k, long long k1, int64_t* done_o
         ctx->sub_cur = nsub_lim;
         for (int sp = 0; sp < 8; ++sp) ctx->sub_budget[sp] = ASB_PANEL_COLS;
     }
-    *done_out = total;
+    return ASB_OK;
+}
+// one read of X with up to sub_cur sub-panels on one rank; *done_out = components it committed (0: nothing stood)
+static int double_panel(asb_ctx* ctx, long long k, long long k1, int64_t* done_out) {
+    int rc;
+    *done_out = 0;
+    const int nsub_lim = ctx->sub_panels < 1 ? 1 : (ctx->sub_panels > ASB_MAX_SUB ? ASB_MAX_SUB : ctx->sub_panels);
+    if (ctx->sub_cur < 1) ctx->sub_cur = nsub_lim < ctx->sub_first ? nsub_lim : ctx->sub_first;
+    const int nsub_max = ctx->sub_cur < nsub_lim ? ctx->sub_cur : nsub_lim;
+    if ((rc = read_buffers(ctx))) return rc;
+    const auto t_read0 = std::chrono::steady_clock::now();
+    if ((rc = panel_candidates(ctx, k, 0))) return rc;
+    if ((rc = read_snapshot(ctx))) return rc;
+    ReadState rs;
+    for (int sp = 0; sp < ASB_MAX_SUB; ++sp) rs.kb[sp] = k + (long long)sp * ASB_PANEL_COLS;
+    bool chained_runs = false, nothing = false;
+    if ((rc = read_run_subpanels(ctx, k, k1, nsub_max, rs, &chained_runs, &nothing))) return rc;
+    if (nothing) return ASB_OK;                          // nothing committed: the caller's refresh / forced path
+    const bool chained = ctx->pre_orth && ctx->correct_rows && ctx->tile_chain;
+    if ((rc = read_verdict(ctx, k, rs, chained_runs, chained))) return rc;
+    // (chained tiles: the host has just read the tile results, the read's GPU work is done)
+    const double read_ms = chained ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_read0).count() : -1.0;
+    read_adapt(ctx, rs, nsub_max, nsub_lim);
+    const bool want_replay = read_rate(ctx, k, rs, read_ms);
+    if ((rc = read_followup(ctx, k, k1, rs, want_replay, nsub_lim))) return rc;
+    *done_out = rs.total;
     return ASB_OK;
 }
 
@@ -3831,22 +3914,17 @@ extern "C" int asb_panel_read_run(asb_ctx* ctx, int64_t k0, int64_t k1, int nsub
     if ((rc = read_buffers(ctx))) return rc;
     if ((rc = asb_alloc(ctx, &ctx->tile_res, (size_t)ASB_MAX_SUB + 2))) return rc;
     if ((rc = read_snapshot(ctx))) return rc;
-    const int save_budget = ctx->spec_budget;
-    int save_sub[8];
-    for (int q = 0; q < 8; ++q) { save_sub[q] = ctx->sub_budget[q]; if (sub_budget) ctx->sub_budget[q] = sub_budget[q]; }
-    ctx->spec_budget = spec_budget;
-    int ntile = -1, nc[ASB_MAX_SUB] = {0}, proven[ASB_MAX_SUB] = {0}, spec_ntile = 0, spec_nc[ASB_MAX_SUB] = {0};
+    ReadState rs;
+    bool timed_out = false;
     const int nlim = nsub_max > ASB_MAX_SUB ? ASB_MAX_SUB : nsub_max;
-    rc = multi_chain_run(ctx, k0, k1, nlim, &ntile, nc, proven, &spec_ntile, spec_nc, true);
-    ctx->spec_budget = save_budget;
-    for (int q = 0; q < 8; ++q) ctx->sub_budget[q] = save_sub[q];
-    if (rc) return rc;
+    if ((rc = multi_chain_run(ctx, k0, k1, nlim, spec_budget, sub_budget ? sub_budget : ctx->sub_budget, true, rs, &timed_out))) return rc;
+    int ntile = rs.ntile;
+    const int *nc = rs.nc, *proven = rs.proven;
     WideArgs wa{};
     double status = 0.0;
-    if (ntile < 0 || ctx->chain_timed_out) {          // the exchange timed out on THIS rank: every rank must leave the kernel together
+    if (ntile < 0 || timed_out) {                     // the exchange timed out on THIS rank: every rank must leave the kernel together
         status = -1.0;
-        if (ntile < 0) ntile = 0;
-        if (!ctx->chain_timed_out) {                   // (the launch could not be made at all)
+        if (!timed_out) {                              // (the launch could not be made at all)
             ctx->n_coop_fallbacks++;
         } else if (ctx->panel_coop) {
             ctx->panel_coop = 0;
@@ -3859,12 +3937,13 @@ extern "C" int asb_panel_read_run(asb_ctx* ctx, int64_t k0, int64_t k1, int nsub
         wa.kb[ct] = k0 + (long long)ct * ASB_PANEL_COLS;
         wa.nc[ct] = ct < ntile ? nc[ct] : 0;
     }
+    // (rd_*: what asb_panel_read_commit, the next call on this context, needs to know of this read)
     ctx->rd_k0 = k0;
     ctx->rd_ntile = ntile;
     for (int ct = 0; ct < 8; ++ct) { ctx->rd_nc[ct] = ct < ntile ? nc[ct] : 0; ctx->rd_proven[ct] = ct < ntile ? proven[ct] : 0; }
     if (ntile > 0) {
         int rgrid = 0, cgrid = 0;
-        if ((rc = read_enqueue(ctx, k0, ntile, nc, spec_ntile, spec_nc, true, &rgrid, &cgrid))) return rc;
+        if ((rc = read_enqueue(ctx, k0, ntile, nc, rs.spec_ntile, rs.spec_nc, true, &rgrid, &cgrid))) return rc;
         ctx->rd_rgrid = rgrid;
     }
     hipLaunchKernelGGL(k_read_words, dim3(1), dim3(64), 0, ctx->stream, ctx->tile_res, ntile, wa, status, words_dev);
@@ -3877,59 +3956,33 @@ extern "C" int asb_panel_read_run(asb_ctx* ctx, int64_t k0, int64_t k1, int nsub
 // asb_panel_read_run packed them.  *total = components the read commits (the same number on every rank).
 extern "C" int asb_panel_read_commit(asb_ctx* ctx, const double* words, int64_t* total_out, int* full_out, int* rejected_out) {
     if (!ctx || !ctx->energy || ctx->mode != ASB_DEFLATE_PROJECT || !words || !total_out) return ASB_ERR_ARG;
-    const int ntile = ctx->rd_ntile;
-    const double* words_min = words;
-    double words_local[ASB_MAX_SUB];
+    ReadState rs;
+    rs.ntile = ctx->rd_ntile;
+    for (int ct = 0; ct < ASB_MAX_SUB; ++ct) {
+        rs.kb[ct] = ctx->rd_k0 + 16 * ct;
+        rs.nc[ct] = ctx->rd_nc[ct];
+        rs.proven[ct] = ctx->rd_proven[ct];
+    }
+    int keep[ASB_MAX_SUB] = {0}, local[ASB_MAX_SUB];     // keep[ct]: columns of tile ct that are committed (the min over the ranks)
     {
         long long p = (long long)words[ASB_MAX_SUB + 1];
-        for (int ct = 0; ct < ASB_MAX_SUB; ++ct, p /= 32) words_local[ct] = (double)(p % 32);
+        for (int ct = 0; ct < ASB_MAX_SUB; ++ct, p /= 32) local[ct] = (int)(p % 32);
+    }
+    for (int ct = 0; ct < rs.ntile; ++ct) {
+        const int g = (int)words[ct];
+        if (g < 0 || g > rs.nc[ct]) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_panel_read_commit: bad count %d for tile %d", g, ct);
+        keep[ct] = g;
+        if (g < rs.nc[ct]) break;
     }
     long long cw = (ctx->n_loc + 255) / 256;
     const int cgrid = (int)(cw < ctx->nblk_cap ? cw : ctx->nblk_cap);
-    // the verdict
-    int keep[ASB_MAX_SUB] = {0}, nstand = 0;             // keep[ct]: columns of tile ct that are committed; nstand: tiles that take part
-    for (int ct = 0; ct < ntile; ++ct) {
-        const int g = (int)words_min[ct];
-        if (g < 0 || g > ctx->rd_nc[ct]) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_panel_read_commit: bad count %d for tile %d", g, ct);
-        keep[ct] = g;
-        nstand = ct + 1;
-        if (g < ctx->rd_nc[ct]) break;
-    }
-    // what the local chain did: it adopted the tentative energies of tiles 0 .. l_full - 1 (stood in full HERE, consecutively)
-    int l_full = 0;
-    while (l_full < ntile && (int)words_local[l_full] == ctx->rd_nc[l_full]) {
-        // (a tile "not reached" locally also reads nc: it lies behind a local failure, so the loop has stopped before it)
-        ++l_full;
-    }
-    int g_full = 0;
-    while (g_full < nstand && keep[g_full] == ctx->rd_nc[g_full]) ++g_full;
-    int64_t total = 0;
-    auto commit_cols = [&](int ct, int cols) { commit_head(ctx, ct, ctx->rd_k0 + 16 * ct, cols, cgrid); };
-    if (l_full > g_full) {
-        // this shard ran ahead of the verdict: back to the energies at the start of the read, then the verdict column by column
-        ASB_HIP(ctx, hipMemcpyAsync(ctx->energy, ctx->e_class, (size_t)ctx->n_loc * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-        for (int ct = 0; ct < nstand; ++ct)
-            if (keep[ct] > 0) commit_cols(ct, keep[ct]);
-    } else {
-        // l_full == g_full (the minimum cannot stand where this shard did not): the full tiles are adopted, the partial one --
-        // its energies untouched -- keeps its head
-        ctx->nblk = ctx->rd_rgrid;
-        if (g_full < nstand && keep[g_full] > 0) commit_cols(g_full, keep[g_full]);
-    }
-    ASB_CHECK_LAUNCH(ctx);
-    bool rejected = false;
-    int full = 0;
-    for (int ct = 0; ct < nstand; ++ct) {
-        total += keep[ct];
-        ctx->n_spec_steps += ctx->rd_nc[ct] - ctx->rd_proven[ct];
-        ctx->n_spec_kept += keep[ct] > ctx->rd_proven[ct] ? keep[ct] - ctx->rd_proven[ct] : 0;
-        if (keep[ct] < ctx->rd_nc[ct]) rejected = true; else ++full;
-    }
-    if (total > 0) ctx->k_done = ctx->rd_k0 + total;
-    if (total > ctx->max_read_kept) ctx->max_read_kept = total;
-    *total_out = total;
-    if (full_out) *full_out = full;
-    if (rejected_out) *rejected_out = rejected ? 1 : 0;
+    int rc;
+    if ((rc = read_chain_verdict(ctx, rs, keep, local, ctx->rd_rgrid, cgrid, true))) return rc;
+    if (rs.total > 0) ctx->k_done = ctx->rd_k0 + rs.total;
+    if (rs.total > ctx->max_read_kept) ctx->max_read_kept = rs.total;
+    *total_out = rs.total;
+    if (full_out) *full_out = rs.full;
+    if (rejected_out) *rejected_out = rs.rejected ? 1 : 0;
     return ASB_OK;
 }
 
@@ -4195,15 +4248,17 @@ int asb_project_run(asb_ctx* ctx, int64_t k0, int64_t k1) {
             if ((rc = panel_candidates(ctx, k, stalled))) return rc;
         } else if ((rc = asb_panel_select(ctx, k, forced, 1, nullptr, nullptr, nullptr, nullptr))) return rc;
         if (forced >= 0 && (rc = asb_panel_select(ctx, k, forced, 1, nullptr, nullptr, nullptr, nullptr))) return rc;
-        const int steps = forced >= 0 ? 1 : (int)((k1 - k) < ASB_PANEL_COLS ? (k1 - k) : ASB_PANEL_COLS);
-        int64_t done = 0;
+        PanelRunIn in;
+        in.k0 = k;
+        in.steps = forced >= 0 ? 1 : (int)((k1 - k) < ASB_PANEL_COLS ? (k1 - k) : ASB_PANEL_COLS);
+        in.global_all = forced >= 0 ? 1 : global_all;
         // unproven steps only on the plain path: a stalled panel is repeated with provable steps alone
-        ctx->run_spec_max = (ctx->spec_panels && stalled == 0 && forced < 0 && !global_all) ? ctx->spec_budget : 0;
-        rc = asb_panel_run(ctx, k, steps, forced >= 0 ? 1 : global_all, 0, &done);
-        ctx->run_spec_max = 0;
-        if (rc) return rc;
-        if (done > ctx->run_proven) {          // the tail of the panel is unproven: the pass decides how much of it stands
-            const int64_t proven = ctx->run_proven, tried = done - proven;
+        in.spec_max = (ctx->spec_panels && stalled == 0 && forced < 0 && !global_all) ? ctx->spec_budget : 0;
+        PanelRunOut ran;
+        if ((rc = panel_run(ctx, in, &ran))) return rc;
+        int64_t done = ran.committed;
+        if (done > ran.proven) {               // the tail of the panel is unproven: the pass decides how much of it stands
+            const int64_t proven = ran.proven, tried = done - proven;
             if ((rc = project_pass(ctx, k, (int)done, (int)proven, &done))) return rc;
             const int64_t gain = done - proven;
             ctx->n_spec_steps += tried;

@@ -185,7 +185,9 @@ int asb_panel_project(asb_ctx* ctx, int64_t k0, int ncols);
  * spec_max steps whose winner is not provable in advance (*ran steps in all, the first *proven of them certain; identical
  * on every rank).  asb_panel_project_spec is the pass over X for all of them with the energies left untouched;
  * *first_rejected = first unproven step that one of THIS shard's vertices contradicts (ncols: none).  The caller takes
- * the minimum over the ranks and asb_panel_commit applies the energies of that many columns (0: nothing stood). */
+ * the minimum over the ranks and asb_panel_commit applies the energies of that many columns (0: nothing stood).
+ * asb_panel_commit belongs to the asb_panel_project_spec[_dev] before it: it commits that pass and counts the kept unproven
+ * steps against that call's `proven`; it must not follow any other pass. */
 int asb_panel_run_spec(asb_ctx* ctx, int64_t k0, int steps, int global_all, int assembled, int spec_max, int64_t* ran,
                        int64_t* proven);
 int asb_panel_project_spec(asb_ctx* ctx, int64_t k0, int ncols, int proven, int64_t* first_rejected);

@@ -351,3 +351,71 @@ def test_multirank_read_costs_one_min_allreduce(kind):
             assert any(rej), rej                            # ... and some tile did not stand in full
         assert mins.count(9) == st["panels"] - plain and mins.count(9) == len(ntiles)
         assert mins.count(1) == plain and len(mins) == st["panels"]
+
+
+def test_fused_run_and_forced_multirank_protocol_share_one_verdict():
+    """One rank, two drivers of the same reads of X with several sub-panels: the fused loop inside the library (asb_project_run ->
+    double_panel) and the Python panel driver forced to the multi-rank protocol on a one-rank RCCL group (ASB_FORCE_COLLECTIVES'
+    path: asb_panel_read_run / _commit, every collective issued).  Both end in the same verdict body -- the single rank is the
+    case where the minimum over the ranks equals the local counts -- so they must select the same vertices and agree on every
+    component.  N = 1600 is just above the candidate capacity (1536: not every vertex is a candidate, so the several-sub-panel
+    path is taken), F = 64, K = 48 of the 63 directions uniform noise with rest shape "first" has: more than one read of X in
+    both runs (asserted).  All K components of both runs are compared; tolerance: the 1e-7 of
+    test_multirank_read_in_one_exchange_on_structured_data above."""
+    import contextlib
+    import io
+    import socket
+    import torch
+    import torch.distributed as dist
+    from animsnapbases_amd import Comm, posComponents, posSnapshots
+    N, F, K = 1600, 64, 48
+    verts = np.random.default_rng(41).uniform(-1, 1, size=(F, N, 3))
+    param = _param(K)
+
+    tiles = []          # the forced run: tiles of every asb_panel_read_run (the multi-rank read with several sub-panels)
+
+    def run(comm):
+        with contextlib.redirect_stdout(io.StringIO()):
+            snaps = posSnapshots.from_arrays(verts, None, "first", standarize=True, massWeight=False, comm=comm)
+            if comm is not None:
+                read_run = snaps._engine.panel_read_run
+
+                def counted_read_run(*a):
+                    out = read_run(*a)
+                    tiles.append(out[0])
+                    return out
+                snaps._engine.panel_read_run = counted_read_run
+            comp = posComponents(param, snaps)
+            comp.deflate_mode = "project"
+            comp.compute_components_store_singvalues()
+        return comp.selected_vertices.copy(), comp.comps.copy(), comp.weigs.copy(), snaps._engine.deflate_stats()
+
+    fused = run(None)
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    torch.cuda.set_device(0)
+    dist.init_process_group("nccl", init_method="tcp://127.0.0.1:%d" % port, rank=0, world_size=1, device_id=torch.device("cuda", 0))
+    try:
+        comm = Comm(force_collectives=True)
+        assert comm.multi and comm.world == 1
+        forced = run(comm)
+    finally:
+        dist.destroy_process_group()
+    print("reads of X: fused", fused[3]["panels"] + fused[3]["refreshes"], "forced", forced[3]["panels"] + forced[3]["refreshes"],
+          "| unproven steps kept", fused[3]["unproven_kept"], forced[3]["unproven_kept"],
+          "| most components of one read", fused[3]["max_read_kept"], forced[3]["max_read_kept"], "| tiles of the forced reads", tiles)
+    for st in (fused[3], forced[3]):
+        assert st["panels"] >= 2 and st["residual_switch_at"] < 0, st          # two reads at least, all of them in projection mode
+        # both runs took the path under test: the co-resident kernel never fell back, and some read committed more than one
+        # sub-panel's 16 columns -- on one rank only double_panel's chained verdict does that, on the forced run only
+        # asb_panel_read_run / _commit (called, with several tiles)
+        assert st["coop_launches"] > 0 and st["coop_fallbacks"] == 0 and st["max_read_kept"] > 16, st
+    assert tiles and max(tiles) > 1, tiles
+    assert fused[0].shape == forced[0].shape == (K,)
+    assert forced[0].tolist() == fused[0].tolist()
+    c, w = align_signs(forced[1], forced[2], fused[1])
+    assert c.shape == fused[1].shape and c.shape[0] == K
+    print("components: forced against fused %.2e, weights %.2e" % (relerr(c, fused[1]), relerr(w, fused[2])))
+    assert relerr(c, fused[1]) < 1e-7 and relerr(w, fused[2]) < 1e-7
