@@ -2,26 +2,11 @@
 // (find_rbm_procrustes + transform inside align) of the reference.  gfx950 only.
 //
 // Frames arrive in the reference layout (F, N, 3).  One block per frame: centroid of the frame and of
-// frame 0, the 3x3 cross-covariance M = (to - t1)^T (from - t0), its rotation R = U V^T (the orthogonal polar
-// factor, from the Jacobi eigen-decomposition of M^T M; R *= -1 when det R < 0, as the reference does), then
-// v' = R v + (t1 - R t0).  Arithmetic in f64 (the reference works in f32 on the h5 data and stores f32).
+// frame 0, the 3x3 cross-covariance M = (to - t1)^T (from - t0), its rotation R = U V^T (procrustes_rot of
+// asb_kernels.h: one-sided Jacobi on M itself, R *= -1 when M has full rank and det < 0, as the reference does; the
+// proper rotation where a flat frame leaves M with rank < 3), then v' = R v + (t1 - R t0).  Arithmetic in f64 (the
+// reference works in f32 on the h5 data and stores f32).
 #include "asb_kernels.h"
-
-__device__ inline void eig3_full(double a00, double a01, double a02, double a11, double a12, double a22, double lam[3],
-                                 double V[3][3]) {
-    double v00 = 1, v01 = 0, v02 = 0, v10 = 0, v11 = 1, v12 = 0, v20 = 0, v21 = 0, v22 = 1;
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        const double off = a01 * a01 + a02 * a02 + a12 * a12, dia = a00 * a00 + a11 * a11 + a22 * a22;
-        if (off == 0.0 || off <= 1e-36 * dia) break;
-        ASB_JROT(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21)
-        ASB_JROT(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22)
-        ASB_JROT(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22)
-    }
-    lam[0] = a00; lam[1] = a11; lam[2] = a22;
-    V[0][0] = v00; V[0][1] = v01; V[0][2] = v02;
-    V[1][0] = v10; V[1][1] = v11; V[1][2] = v12;
-    V[2][0] = v20; V[2][1] = v21; V[2][2] = v22;
-}
 
 // T (F, 4, 4) row-major homogeneous matrices; frames (F, N, 3)
 __global__ __launch_bounds__(256) void k_procrustes(const double* __restrict__ frames, long long N, int rigid,
@@ -49,29 +34,8 @@ __global__ __launch_bounds__(256) void k_procrustes(const double* __restrict__ f
     __syncthreads();
     block_sum<9>(m, sh);
     if (threadIdx.x != 0) return;
-    // R = M (M^T M)^(-1/2)
-    double B[6] = {0, 0, 0, 0, 0, 0};   // M^T M (sym): 00 01 02 11 12 22
-    for (int k = 0; k < 3; ++k) {
-        B[0] += m[3 * k] * m[3 * k]; B[1] += m[3 * k] * m[3 * k + 1]; B[2] += m[3 * k] * m[3 * k + 2];
-        B[3] += m[3 * k + 1] * m[3 * k + 1]; B[4] += m[3 * k + 1] * m[3 * k + 2]; B[5] += m[3 * k + 2] * m[3 * k + 2];
-    }
-    double lam[3], V[3][3];
-    eig3_full(B[0], B[1], B[2], B[3], B[4], B[5], lam, V);
-    double S[3][3];     // (M^T M)^(-1/2) = V diag(1/sqrt(lam)) V^T
-    for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) {
-            double acc = 0.0;
-            for (int k = 0; k < 3; ++k) acc += V[a][k] * V[b][k] / sqrt(fmax(lam[k], 1e-300));
-            S[a][b] = acc;
-        }
     double R[3][3];
-    for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) R[a][b] = m[3 * a] * S[0][b] + m[3 * a + 1] * S[1][b] + m[3 * a + 2] * S[2][b];
-    const double det = R[0][0] * (R[1][1] * R[2][2] - R[1][2] * R[2][1]) - R[0][1] * (R[1][0] * R[2][2] - R[1][2] * R[2][0]) +
-                       R[0][2] * (R[1][0] * R[2][1] - R[1][1] * R[2][0]);
-    if (det < 0)
-        for (int a = 0; a < 3; ++a)
-            for (int b = 0; b < 3; ++b) R[a][b] = -R[a][b];          // the reference's `R *= -1` (process.py:226-227)
+    procrustes_rot(m, R);
     double* Tm = T + (long long)blockIdx.x * 16;
     for (int a = 0; a < 3; ++a) {
         for (int b = 0; b < 3; ++b) Tm[4 * a + b] = rigid ? R[a][b] : (a == b ? 1.0 : 0.0);
@@ -110,4 +74,11 @@ extern "C" int asb_align_frames(asb_ctx* ctx, double* frames, int64_t F, int64_t
     if (T_out) ASB_HIP(ctx, hipMemcpyAsync(T_out, T.get(), (size_t)F * 16 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return ASB_OK;
+}
+
+// procrustes_rot on the host: m9 = M row-major -> out9 = R row-major
+extern "C" void asb_test_procrustes_rot(const double* m9, double* out9) {
+    double R[3][3];
+    procrustes_rot(m9, R);
+    for (int i = 0; i < 9; ++i) out9[i] = R[i / 3][i % 3];
 }

@@ -268,6 +268,95 @@ __host__ __device__ inline void eig3_top_fast(double a00, double a01, double a02
     lam = l * sc; u0 = x; u1 = y; u2 = z;
 }
 
+// --------------------------------------------------------------------------------------
+// Rotation of a 3 x 3 cross-covariance M (snapshot ingest, utils/process.py:223-227): R = U V^T of M = U diag(s) V^T,
+// times -1 where det < 0 as the reference does.  One-sided (Hestenes) Jacobi on the columns of M / max|m_ij|: column pairs
+// are rotated until they are orthogonal, A V = U diag(s).  Nothing is squared into M^T M and nothing is divided by s, so a
+// thin or flat point set (s3 << s1, s3 = 0) costs no digits: the two longest columns give u1, u2 (u2 re-orthogonalised
+// against u1), the third direction is always their cross product, and the shortest column only decides its sign.
+//   full rank (|a3| > ASB_PROCRUSTES_RANK_TOL |a1|): d = sign det M, R = u1 v1^T + u2 v2^T + d (u1 x u2)(v1 x v2)^T, R = -R if d < 0
+//   rank 2: d = +1 -- the proper rotation U diag(1, 1, det U det V) V^T, where LAPACK's sign of u3 / v3 is arbitrary
+//   rank 1: u2 = any unit vector orthogonal to u1, then as rank 2;   M = 0: R = I
+// --------------------------------------------------------------------------------------
+#define ASB_PROCRUSTES_RANK_TOL 1.0e-12
+
+// makes the columns ap, aq orthogonal, the same rotation on vp, vq; false: they already are (to 2^-51 |ap| |aq|, or one is zero)
+__host__ __device__ inline bool hestenes_pair(double* ap, double* aq, double* vp, double* vq) {
+    const double al = ap[0] * ap[0] + ap[1] * ap[1] + ap[2] * ap[2], be = aq[0] * aq[0] + aq[1] * aq[1] + aq[2] * aq[2];
+    const double ga = ap[0] * aq[0] + ap[1] * aq[1] + ap[2] * aq[2];
+    if (ga * ga <= 1.9721522630525295e-31 * al * be) return false;
+    const double zeta = (be - al) / (2.0 * ga);
+    const double tt = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(zeta * zeta + 1.0));
+    const double cc = 1.0 / sqrt(tt * tt + 1.0), ss = tt * cc;
+    for (int k = 0; k < 3; ++k) {
+        const double tp = cc * ap[k] - ss * aq[k], tq = ss * ap[k] + cc * aq[k];
+        ap[k] = tp; aq[k] = tq;
+        const double wp = cc * vp[k] - ss * vq[k], wq = ss * vp[k] + cc * vq[k];
+        vp[k] = wp; vq[k] = wq;
+    }
+    return true;
+}
+
+__host__ __device__ inline void cross3(const double* a, const double* b, double* c) {
+    c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// m: M row-major; R: the rotation, row-major
+__host__ __device__ inline void procrustes_rot(const double m[9], double R[3][3]) {
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) R[i][j] = i == j ? 1.0 : 0.0;
+    double sc = 0.0;
+    for (int i = 0; i < 9; ++i) sc = fmax(sc, fabs(m[i]));
+    if (!(sc > 0.0)) return;
+    // columns of M / max|m_ij| (the norms below square the entries, which must neither overflow nor flush to zero) and of V
+    double a0[3] = {m[0] / sc, m[3] / sc, m[6] / sc}, a1[3] = {m[1] / sc, m[4] / sc, m[7] / sc}, a2[3] = {m[2] / sc, m[5] / sc, m[8] / sc};
+    double v0[3] = {1, 0, 0}, v1[3] = {0, 1, 0}, v2[3] = {0, 0, 1};
+    for (int sweep = 0; sweep < 30; ++sweep) {
+        bool rot = hestenes_pair(a0, a1, v0, v1);
+        rot |= hestenes_pair(a0, a2, v0, v2);
+        rot |= hestenes_pair(a1, a2, v1, v2);
+        if (!rot) break;
+    }
+    // longest column first: pairs (a, v) change places together, M = sum a_j v_j^T does not notice
+    double n0 = a0[0] * a0[0] + a0[1] * a0[1] + a0[2] * a0[2], n1 = a1[0] * a1[0] + a1[1] * a1[1] + a1[2] * a1[2],
+           n2 = a2[0] * a2[0] + a2[1] * a2[1] + a2[2] * a2[2];
+#define ASB_PR_SWAP(x, y, vx, vy, nx, ny)                                                          \
+    if (ny > nx) {                                                                                 \
+        for (int k = 0; k < 3; ++k) {                                                              \
+            double t = x[k]; x[k] = y[k]; y[k] = t;                                                \
+            t = vx[k]; vx[k] = vy[k]; vy[k] = t;                                                   \
+        }                                                                                          \
+        const double t = nx; nx = ny; ny = t;                                                      \
+    }
+    ASB_PR_SWAP(a0, a1, v0, v1, n0, n1)
+    ASB_PR_SWAP(a0, a2, v0, v2, n0, n2)
+    ASB_PR_SWAP(a1, a2, v1, v2, n1, n2)
+#undef ASB_PR_SWAP
+    const double thr = ASB_PROCRUSTES_RANK_TOL * ASB_PROCRUSTES_RANK_TOL * n0;
+    double u1[3], u2[3], w[3], x[3];
+    const double i0 = 1.0 / sqrt(n0);
+    for (int k = 0; k < 3; ++k) u1[k] = a0[k] * i0;
+    if (n1 > thr) {
+        const double p = u1[0] * a1[0] + u1[1] * a1[1] + u1[2] * a1[2];
+        for (int k = 0; k < 3; ++k) u2[k] = a1[k] - p * u1[k];
+    } else {
+        // rank 1: the coordinate axis u1 has least of, crossed with u1
+        const double m0 = fabs(u1[0]), m1 = fabs(u1[1]), m2 = fabs(u1[2]);
+        double e[3] = {0, 0, 0};
+        e[(m0 <= m1 && m0 <= m2) ? 0 : (m1 <= m2 ? 1 : 2)] = 1.0;
+        cross3(u1, e, u2);
+    }
+    const double i1 = 1.0 / sqrt(u2[0] * u2[0] + u2[1] * u2[1] + u2[2] * u2[2]);
+    for (int k = 0; k < 3; ++k) u2[k] *= i1;
+    cross3(u1, u2, w);
+    cross3(v0, v1, x);
+    bool mirror = false;
+    if (n2 > thr) mirror = (a2[0] * w[0] + a2[1] * w[1] + a2[2] * w[2]) * (v2[0] * x[0] + v2[1] * x[1] + v2[2] * x[2]) < 0.0;
+    const double sg = mirror ? -1.0 : 1.0;       // the reference's `R *= -1` (process.py:226-227), full rank only
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) R[i][j] = sg * (u1[i] * v0[j] + u2[i] * v1[j]) + w[i] * x[j];
+}
+
 // Reduce the per-block partial records of the last k_stream pass (one block).
 // Result in every thread: (be, bi) winner, bs sum of energies.
 __device__ inline void reduce_partials(const double* pmax, const long long* pidx, const double* psum,

@@ -7,6 +7,13 @@ on the GPU (``asb_align_frames``, csrc/asb_ingest.hip): centroids, 3x3 cross-cov
 from the polar factor, transform -- one block per frame.  File parsing and the connected-component
 clean-up are host work (text / graph code, no tensor arithmetic).
 
+The rotation is the reference's ``U V^T`` of the cross-covariance ``M = U diag(s) V^T``, times -1 where its
+determinant is negative.  One case differs on purpose: a flat frame (a cloth at rest) leaves ``M`` with rank 2,
+and the reference's result then depends on the sign LAPACK happens to give ``u3`` and ``v3`` -- a negative
+``det(U V^T)`` turns its ``R *= -1`` into an in-plane half-turn that misaligns the frame.  The device takes the
+proper rotation ``U diag(1, 1, det U det V) V^T`` there (``s3 <= 1e-12 s1``), which is what the reference
+returns whenever that sign comes out positive.
+
 Containers: the reference writes ``.h5`` (h5py, gzip'd float32 ``verts`` + ``tris``); without h5py the
 same keys go to ``.npz`` (``posSnapshots`` reads both).
 """

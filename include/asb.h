@@ -686,6 +686,9 @@ int asb_test_deflate_state(asb_ctx* ctx, double* energy, double* pmax, int64_t* 
                            double* W, double* R);
 int asb_test_local_best(asb_ctx* ctx, int64_t k, double* rec);
 int asb_test_pick_records(asb_ctx* ctx, int64_t k, const double* recs, int64_t n_rec);
+/* The 3x3 rotation solve of asb_align_frames (procrustes_rot, csrc/asb_kernels.h), run on the HOST: m9 = the cross-covariance M
+ * row-major, out9 = R row-major (tests/test_procrustes_rot_cpu.py). */
+void asb_test_procrustes_rot(const double* m9, double* out9);
 /* tests: the sketch replay on host arrays -- cols (r x 3 n: column i, entry 3 v + d, the coefficient of vertex v's row d on the
  * unit direction i divided by sqrt(wn2[i])), wn2 (r), exact energies E (n) -> scores (n; max over the steps of energy / winner's
  * energy), the replay's winners pred (steps; -1 behind its end), *status = 1 (0: the exchange timed out, scores = energies) */
