@@ -36,6 +36,15 @@ struct StreamCfg {
 struct asb_splocs;
 struct asb_geo;
 
+// world positions of the resident tensor (asb_cproj.hip): x = (T * inv_psf + mean) * invm_v
+struct CpWorld {
+    const double* T;
+    long long ldt;
+    const double* mean;
+    const double* invm;
+    double inv_psf;
+};
+
 struct asb_ctx {
     int dev = 0;
     hipStream_t stream = nullptr;
@@ -313,6 +322,15 @@ struct asb_ctx {
     int *cf_ptr = nullptr, *cf_idx = nullptr;     // asb_cforce_run: the CSR of S^T (n_loc + 1 offsets, columns)
     double* cf_val = nullptr;         // its values
     double* cf_scratch = nullptr;     // (3 * cp_n * p, cw) element-major projections of one chunk of frames
+    // reduced constraint forces S^T V (P^T V)^+ P^T p (asb_rforce.hip)
+    double* rf_M = nullptr;           // (3, rf_mpp, rf_Np): M_d^T = (S^T V_d)^T, vertices contiguous, zero padding
+    int64_t rf_n = 0, rf_Np = 0;      // its vertices; rounded up to the kernel's 32
+    int64_t rf_mp = 0, rf_mpp = 0;    // its basis vectors; rounded up to 4
+    double* rf_H = nullptr;           // (3, rf_r, rf_npt) the solver H_d = (A^T A + la I)^-1 A^T
+    int* rf_pt = nullptr;             // (rf_npt) rows of the sampled elements' stacked projections
+    int64_t rf_r = 0, rf_npt = 0, rf_pt_max = -1;     // basis vectors in use (<= rf_mp; 0: no solver), points, largest row
+    double* rf_coef = nullptr;        // (3, rf_r rounded up to 4, cw) coefficients of one chunk of frames
+    double* fd_part = nullptr;        // asb_force_diff: per-frame records + the reduced row
 
     // ---- profiling of the dominant streaming kernel ----
     bool prof = false;
@@ -378,6 +396,17 @@ int asb_deflate_apply_dev(asb_ctx* ctx, int64_t k, const double* s_dev);      //
 int asb_syrk_tn(asb_ctx* ctx, const double* X, long long ld, long long R, int n, double* out);
 int asb_gemm_tn_big(asb_ctx* ctx, const double* X, long long ldx, const double* Y, long long ldy, long long R, int I, int J, double* out);
 #define ASB_CHECK_LAUNCH(ctx) ASB_HIP(ctx, hipGetLastError())
+// asb_cproj.hip, shared with asb_rforce.hip.  The checks of the arguments asb_cproj_run shares with its siblings (messages start
+// with `who`) and the world of the selected tensor, without the mass factors; n_sel: the frames range(f0, f1, fj) selects
+int asb_cproj_world(asb_ctx* ctx, const char* who, int which, int64_t f0, int64_t f1, int64_t fj, int add_mean, double psf,
+                    double sigma_min, double sigma_max, CpWorld* w, int64_t* n_sel);
+// the first device work of a call, after all of its checks: inv_massL (host, or NULL) uploaded and put into w
+int asb_cproj_invm(asb_ctx* ctx, const double* inv_massL, CpWorld* w);
+// selected frames [c0, c0 + cn) projected ELEMENT-major into S (3 cp_n p rows of cw doubles), for the kind of asb_cproj_setup
+void asb_cproj_em_launch(asb_ctx* ctx, const CpWorld& w, int f0, int fj, int c0, int cn, int cw, double smin, double smax, double* S);
+// a host CSR checked (offsets from 0 and not decreasing, columns < n_cols and strictly ascending in a row) and narrowed to int
+int asb_csr_check32(asb_ctx* ctx, const char* who, int64_t n_rows, const int64_t* indptr, const int64_t* indices, const double* data,
+                    long long n_cols, std::vector<int>& p32, std::vector<int>& c32);
 
 // ASB_DEBUG_PANELS: the panel loop's trace on stderr (changes no result); read once per process
 static inline bool asb_debug_panels() {

@@ -35,14 +35,6 @@ template <> struct CpShape<CP_TET_STRAIN> { static constexpr int NV = 4, P = 3, 
 template <> struct CpShape<CP_TET_DEFGRAD> { static constexpr int NV = 4, P = 3, TW = 9; };
 template <> struct CpShape<CP_BEND> { static constexpr int NV = 1, P = 1, TW = 5; };
 
-struct CpWorld {
-    const double* T;
-    long long ldt;
-    const double* mean;
-    const double* invm;
-    double inv_psf;
-};
-
 __device__ __forceinline__ void cp_pos(const CpWorld& w, long long f, int v, double (&x)[3]) {
     const double im = w.invm ? w.invm[v] : 1.0;
 #pragma unroll
@@ -351,38 +343,53 @@ static void cp_launch(asb_ctx* ctx, const CpWorld& w, int f0, int fj, int n_sel,
                        ctx->cp_table + (size_t)ctx->cp_n * CpShape<KIND>::TW, (long long)ctx->cp_n, f0, fj, n_sel, smin, smax, out);
 }
 
-extern "C" int asb_cproj_run(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean, double psf,
-                             double sigma_min, double sigma_max, double* out_dev) {
-    if (!ctx || !out_dev) return ASB_ERR_ARG;
+int asb_cproj_world(asb_ctx* ctx, const char* who, int which, int64_t f0, int64_t f1, int64_t fj, int add_mean, double psf,
+                    double sigma_min, double sigma_max, CpWorld* w, int64_t* n_sel_out) {
     if (ctx->cp_kind < 0 || !ctx->X || ctx->cp_verts != ctx->n_loc || ctx->v0 != 0 || ctx->n_loc != ctx->N_glob)
-        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cproj_run: no element set-up for the resident tensor (asb_cproj_setup)");
-    CpWorld w;
+        ASB_FAIL(ctx, ASB_ERR_ARG, "%s: no element set-up for the resident tensor (asb_cproj_setup)", who);
     int64_t F;
     if (which == 0) {
-        w.T = ctx->X, w.ldt = ctx->Fp, F = ctx->F;
+        w->T = ctx->X, w->ldt = ctx->Fp, F = ctx->F;
     } else if (which == 1) {
-        if (!ctx->ho_Y) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cproj_run: no held-out animation on the device (asb_heldout_upload)");
-        w.T = ctx->ho_Y, w.ldt = ctx->ho_Fp, F = ctx->ho_F;
+        if (!ctx->ho_Y) ASB_FAIL(ctx, ASB_ERR_ARG, "%s: no held-out animation on the device (asb_heldout_upload)", who);
+        w->T = ctx->ho_Y, w->ldt = ctx->ho_Fp, F = ctx->ho_F;
     } else {
         return ASB_ERR_ARG;
     }
     if (f0 < 0 || f1 > F || f0 >= f1 || fj < 1)
-        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cproj_run: range(%lld, %lld, %lld) is not a selection of the %lld frames", (long long)f0,
-                 (long long)f1, (long long)fj, (long long)F);
-    if (add_mean && !ctx->have_mean) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cproj_run: no mean on the device");
-    if (!(psf > 0.0)) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cproj_run: scale %g", psf);
-    if (!(sigma_min <= sigma_max)) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cproj_run: sigma_min %g > sigma_max %g", sigma_min, sigma_max);
+        ASB_FAIL(ctx, ASB_ERR_ARG, "%s: range(%lld, %lld, %lld) is not a selection of the %lld frames", who, (long long)f0, (long long)f1,
+                 (long long)fj, (long long)F);
+    if (add_mean && !ctx->have_mean) ASB_FAIL(ctx, ASB_ERR_ARG, "%s: no mean on the device", who);
+    if (!(psf > 0.0)) ASB_FAIL(ctx, ASB_ERR_ARG, "%s: scale %g", who, psf);
+    if (!(sigma_min <= sigma_max)) ASB_FAIL(ctx, ASB_ERR_ARG, "%s: sigma_min %g > sigma_max %g", who, sigma_min, sigma_max);
     const int64_t n_sel = (f1 - f0 + fj - 1) / fj;
-    if ((n_sel + 63) / 64 > 65535) ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_cproj_run: %lld frames in one call (at most %d)", (long long)n_sel, 65535 * 64);
+    if ((n_sel + 63) / 64 > 65535) ASB_FAIL(ctx, ASB_ERR_LIMIT, "%s: %lld frames in one call (at most %d)", who, (long long)n_sel, 65535 * 64);
+    w->mean = add_mean ? ctx->mean : nullptr;
+    w->invm = nullptr;
+    w->inv_psf = 1.0 / psf;
+    *n_sel_out = n_sel;
+    return ASB_OK;
+}
+
+int asb_cproj_invm(asb_ctx* ctx, const double* inv_massL, CpWorld* w) {
     ASB_HIP(ctx, hipSetDevice(ctx->dev));
-    int rc;
     if (inv_massL) {
+        int rc;
         if ((rc = asb_alloc(ctx, &ctx->cp_invm, (size_t)ctx->n_loc))) return rc;
         ASB_HIP(ctx, hipMemcpyAsync(ctx->cp_invm, inv_massL, (size_t)ctx->n_loc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        w->invm = ctx->cp_invm;
     }
-    w.mean = add_mean ? ctx->mean : nullptr;
-    w.invm = inv_massL ? ctx->cp_invm : nullptr;
-    w.inv_psf = 1.0 / psf;
+    return ASB_OK;
+}
+
+extern "C" int asb_cproj_run(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean, double psf,
+                             double sigma_min, double sigma_max, double* out_dev) {
+    if (!ctx || !out_dev) return ASB_ERR_ARG;
+    CpWorld w;
+    int64_t n_sel;
+    int rc;
+    if ((rc = asb_cproj_world(ctx, "asb_cproj_run", which, f0, f1, fj, add_mean, psf, sigma_min, sigma_max, &w, &n_sel))) return rc;
+    if ((rc = asb_cproj_invm(ctx, inv_massL, &w))) return rc;
     switch (ctx->cp_kind) {
         case CP_EDGE: cp_launch<CP_EDGE>(ctx, w, (int)f0, (int)fj, (int)n_sel, sigma_min, sigma_max, out_dev); break;
         case CP_TRI: cp_launch<CP_TRI>(ctx, w, (int)f0, (int)fj, (int)n_sel, sigma_min, sigma_max, out_dev); break;
@@ -487,67 +494,69 @@ __global__ __launch_bounds__(64 * CP_WAVES) void k_st_apply(const int* __restric
 }
 
 template <int KIND>
-static void cf_launch(asb_ctx* ctx, const CpWorld& w, int f0, int fj, int c0, int cn, int cw, double smin, double smax) {
+static void cf_launch(asb_ctx* ctx, const CpWorld& w, int f0, int fj, int c0, int cn, int cw, double smin, double smax, double* S) {
     const dim3 grid((unsigned)((ctx->cp_n + CP_EB - 1) / CP_EB), (unsigned)((cn + 63) / 64));
     hipLaunchKernelGGL(k_cproj_em<KIND>, grid, dim3(64 * CP_WAVES), 0, ctx->stream, w, ctx->cp_idx, ctx->cp_table, ctx->cp_sptr,
                        ctx->cp_sidx, ctx->cp_table + (size_t)ctx->cp_n * CpShape<KIND>::TW, (long long)ctx->cp_n, f0, fj, c0, cn, cw, smin,
-                       smax, ctx->cf_scratch);
+                       smax, S);
+}
+
+void asb_cproj_em_launch(asb_ctx* ctx, const CpWorld& w, int f0, int fj, int c0, int cn, int cw, double smin, double smax, double* S) {
+    switch (ctx->cp_kind) {
+        case CP_EDGE: cf_launch<CP_EDGE>(ctx, w, f0, fj, c0, cn, cw, smin, smax, S); break;
+        case CP_TRI: cf_launch<CP_TRI>(ctx, w, f0, fj, c0, cn, cw, smin, smax, S); break;
+        case CP_TET_STRAIN: cf_launch<CP_TET_STRAIN>(ctx, w, f0, fj, c0, cn, cw, smin, smax, S); break;
+        case CP_TET_DEFGRAD: cf_launch<CP_TET_DEFGRAD>(ctx, w, f0, fj, c0, cn, cw, smin, smax, S); break;
+        default: cf_launch<CP_BEND>(ctx, w, f0, fj, c0, cn, cw, smin, smax, S); break;
+    }
+}
+
+int asb_csr_check32(asb_ctx* ctx, const char* who, int64_t n_rows, const int64_t* indptr, const int64_t* indices, const double* data,
+                    long long n_cols, std::vector<int>& p32, std::vector<int>& c32) {
+    if (indptr[0] != 0) ASB_FAIL(ctx, ASB_ERR_ARG, "%s: the row offsets of S^T do not start at 0", who);
+    for (int64_t v = 0; v < n_rows; ++v)
+        if (indptr[v + 1] < indptr[v]) ASB_FAIL(ctx, ASB_ERR_ARG, "%s: row offsets of S^T decrease at row %lld", who, (long long)v);
+    const int64_t nnz = indptr[n_rows];
+    if (nnz > 0x7fffffffLL) ASB_FAIL(ctx, ASB_ERR_LIMIT, "%s: too many entries of S^T for 32-bit indices", who);
+    if (nnz > 0 && (!indices || !data)) return ASB_ERR_ARG;
+    p32.resize((size_t)n_rows + 1);
+    c32.resize((size_t)nnz);
+    for (int64_t v = 0; v <= n_rows; ++v) p32[v] = (int)indptr[v];
+    for (int64_t v = 0; v < n_rows; ++v)
+        for (int64_t t = indptr[v]; t < indptr[v + 1]; ++t) {
+            if (indices[t] < 0 || indices[t] >= n_cols)
+                ASB_FAIL(ctx, ASB_ERR_ARG, "%s: row %lld of S^T names column %lld of %lld", who, (long long)v, (long long)indices[t], n_cols);
+            if (t > indptr[v] && indices[t] <= indices[t - 1])
+                ASB_FAIL(ctx, ASB_ERR_ARG, "%s: the columns of row %lld of S^T are not ascending", who, (long long)v);
+            c32[t] = (int)indices[t];
+        }
+    return ASB_OK;
 }
 
 extern "C" int asb_cforce_run(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean,
                               double psf, double sigma_min, double sigma_max, int64_t n_rows, const int64_t* indptr,
                               const int64_t* indices, const double* data, int accumulate, int64_t chunk_frames, double* out_dev) {
     if (!ctx || !out_dev || !indptr || n_rows < 1) return ASB_ERR_ARG;
-    if (ctx->cp_kind < 0 || !ctx->X || ctx->cp_verts != ctx->n_loc || ctx->v0 != 0 || ctx->n_loc != ctx->N_glob)
-        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: no element set-up for the resident tensor (asb_cproj_setup)");
     CpWorld w;
-    int64_t F;
-    if (which == 0) {
-        w.T = ctx->X, w.ldt = ctx->Fp, F = ctx->F;
-    } else if (which == 1) {
-        if (!ctx->ho_Y) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: no held-out animation on the device (asb_heldout_upload)");
-        w.T = ctx->ho_Y, w.ldt = ctx->ho_Fp, F = ctx->ho_F;
-    } else {
-        return ASB_ERR_ARG;
-    }
-    if (f0 < 0 || f1 > F || f0 >= f1 || fj < 1)
-        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: range(%lld, %lld, %lld) is not a selection of the %lld frames", (long long)f0,
-                 (long long)f1, (long long)fj, (long long)F);
-    if (add_mean && !ctx->have_mean) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: no mean on the device");
-    if (!(psf > 0.0)) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: scale %g", psf);
-    if (!(sigma_min <= sigma_max)) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: sigma_min %g > sigma_max %g", sigma_min, sigma_max);
+    int64_t n_sel;
+    int rc;
+    if ((rc = asb_cproj_world(ctx, "asb_cforce_run", which, f0, f1, fj, add_mean, psf, sigma_min, sigma_max, &w, &n_sel))) return rc;
     if (chunk_frames < 0) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: chunk_frames %lld", (long long)chunk_frames);
-    const int64_t n_sel = (f1 - f0 + fj - 1) / fj;
-    if ((n_sel + 63) / 64 > 65535) ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_cforce_run: %lld frames in one call (at most %d)", (long long)n_sel, 65535 * 64);
     // ---- the CSR of S^T: one row per vertex of the tensor, columns = rows of the stacked projections, ascending in a row
     static const int PK[5] = {1, 2, 3, 3, 1};
     const long long n_cols = (long long)ctx->cp_n * PK[ctx->cp_kind];
     if (n_rows != ctx->n_loc)
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: S^T has %lld rows, the tensor %lld vertices", (long long)n_rows, (long long)ctx->n_loc);
-    if (indptr[0] != 0) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: the row offsets of S^T do not start at 0");
-    for (int64_t v = 0; v < n_rows; ++v)
-        if (indptr[v + 1] < indptr[v]) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: row offsets of S^T decrease at row %lld", (long long)v);
+    std::vector<int> p32, c32;
+    if ((rc = asb_csr_check32(ctx, "asb_cforce_run", n_rows, indptr, indices, data, n_cols, p32, c32))) return rc;
     const int64_t nnz = indptr[n_rows];
-    if (nnz > 0x7fffffffLL) ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_cforce_run: too many entries of S^T for 32-bit indices");
-    if (nnz > 0 && (!indices || !data)) return ASB_ERR_ARG;
-    std::vector<int> p32((size_t)n_rows + 1), c32((size_t)nnz);
-    for (int64_t v = 0; v <= n_rows; ++v) p32[v] = (int)indptr[v];
-    for (int64_t v = 0; v < n_rows; ++v)
-        for (int64_t t = indptr[v]; t < indptr[v + 1]; ++t) {
-            if (indices[t] < 0 || indices[t] >= n_cols)
-                ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: row %lld of S^T names column %lld of %lld", (long long)v, (long long)indices[t], n_cols);
-            if (t > indptr[v] && indices[t] <= indices[t - 1])
-                ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: the columns of row %lld of S^T are not ascending", (long long)v);
-            c32[t] = (int)indices[t];
-        }
     // ---- chunk width: whole 128-byte lines per scratch row, the scratch within CF_SCRATCH_BYTES, whole waves if it can
     long long cw = (long long)(CF_SCRATCH_BYTES / (24ull * (unsigned long long)n_cols));
     cw = cw >= 64 ? cw / 64 * 64 : (cw >= 16 ? cw / 16 * 16 : 16);
     if (chunk_frames > 0 && (chunk_frames + 15) / 16 * 16 < cw) cw = (chunk_frames + 15) / 16 * 16;
     const long long span = (n_sel + 15) / 16 * 16;
     if (cw > span) cw = span;
-    ASB_HIP(ctx, hipSetDevice(ctx->dev));
-    int rc;
+    if ((rc = asb_cproj_invm(ctx, inv_massL, &w))) return rc;
     if ((rc = asb_alloc(ctx, &ctx->cf_ptr, p32.size()))) return rc;
     if ((rc = asb_alloc(ctx, &ctx->cf_idx, c32.size() + 1))) return rc;
     if ((rc = asb_alloc(ctx, &ctx->cf_val, c32.size() + 1))) return rc;
@@ -557,23 +566,10 @@ extern "C" int asb_cforce_run(asb_ctx* ctx, int which, int64_t f0, int64_t f1, i
         ASB_HIP(ctx, hipMemcpyAsync(ctx->cf_idx, c32.data(), c32.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
         ASB_HIP(ctx, hipMemcpyAsync(ctx->cf_val, data, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     }
-    if (inv_massL) {
-        if ((rc = asb_alloc(ctx, &ctx->cp_invm, (size_t)ctx->n_loc))) return rc;
-        ASB_HIP(ctx, hipMemcpyAsync(ctx->cp_invm, inv_massL, (size_t)ctx->n_loc * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    }
-    w.mean = add_mean ? ctx->mean : nullptr;
-    w.invm = inv_massL ? ctx->cp_invm : nullptr;
-    w.inv_psf = 1.0 / psf;
     const unsigned gv = (unsigned)((n_rows + CF_VB - 1) / CF_VB);
     for (long long c0 = 0; c0 < n_sel; c0 += cw) {
         const int cn = (int)(c0 + cw < n_sel ? cw : n_sel - c0);
-        switch (ctx->cp_kind) {
-            case CP_EDGE: cf_launch<CP_EDGE>(ctx, w, (int)f0, (int)fj, (int)c0, cn, (int)cw, sigma_min, sigma_max); break;
-            case CP_TRI: cf_launch<CP_TRI>(ctx, w, (int)f0, (int)fj, (int)c0, cn, (int)cw, sigma_min, sigma_max); break;
-            case CP_TET_STRAIN: cf_launch<CP_TET_STRAIN>(ctx, w, (int)f0, (int)fj, (int)c0, cn, (int)cw, sigma_min, sigma_max); break;
-            case CP_TET_DEFGRAD: cf_launch<CP_TET_DEFGRAD>(ctx, w, (int)f0, (int)fj, (int)c0, cn, (int)cw, sigma_min, sigma_max); break;
-            default: cf_launch<CP_BEND>(ctx, w, (int)f0, (int)fj, (int)c0, cn, (int)cw, sigma_min, sigma_max); break;
-        }
+        asb_cproj_em_launch(ctx, w, (int)f0, (int)fj, (int)c0, cn, (int)cw, sigma_min, sigma_max, ctx->cf_scratch);
         hipLaunchKernelGGL(k_st_apply, dim3(gv, (unsigned)((cn + 63) / 64)), dim3(64 * CP_WAVES), 0, ctx->stream, ctx->cf_ptr, ctx->cf_idx,
                            ctx->cf_val, ctx->cf_scratch, (int)cw, (int)c0, cn, (long long)n_rows, accumulate ? 1 : 0, out_dev);
     }

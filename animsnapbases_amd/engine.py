@@ -537,6 +537,43 @@ class HipEngine(object):
                                          ptr(indices), ptr(data), int(bool(accumulate)), int(chunk_frames),
                                          ctypes.c_void_p(int(out_dev_ptr))))
 
+    # ------------------------------------------------------------------ DEIM-reduced constraint forces
+    def rforce_operator(self, St, V):
+        """M_d = S^T V_d on the device for ``St`` (scipy CSR (N, rows), sorted indices) and ``V`` (rows, mp, 3)."""
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        assert V.ndim == 3 and V.shape[2] == 3
+        indptr = np.ascontiguousarray(St.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(St.indices, dtype=np.int64)
+        data = np.ascontiguousarray(St.data, dtype=np.float64)
+        self._ck(self.lib.asb_rforce_operator(self.h, int(St.shape[0]), ptr(indptr), ptr(indices), ptr(data), int(V.shape[0]),
+                                              int(V.shape[1]), ptr(V)))
+
+    def rforce_solver(self, H, rows):
+        """``H`` (3, r, npt) and the rows of the sampled elements' stacked projections the npt interpolation points keep."""
+        H = np.ascontiguousarray(H, dtype=np.float64)
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        assert H.ndim == 3 and H.shape[0] == 3 and H.shape[2] == rows.shape[0]
+        self._ck(self.lib.asb_rforce_solver(self.h, int(H.shape[1]), int(H.shape[2]), ptr(H), ptr(rows)))
+
+    def rforce_run(self, which, f0, f1, fj, inv_massL, add_mean, psf, sigma_min, sigma_max, accumulate, out_dev_ptr):
+        """The reduced constraint forces of the frames range(f0, f1, fj) into (or, ``accumulate``, onto) the caller's device
+        buffer of (F', N, 3) float64; ``cproj_setup`` holds the sampled elements only."""
+        if inv_massL is not None:
+            inv_massL = np.ascontiguousarray(inv_massL, dtype=np.float64)
+            assert inv_massL.shape == (self.N_glob,)
+        self._ck(self.lib.asb_rforce_run(self.h, int(which), int(f0), int(f1), int(fj), ptr(inv_massL), int(bool(add_mean)),
+                                         float(psf), float(sigma_min), float(sigma_max), int(bool(accumulate)),
+                                         ctypes.c_void_p(int(out_dev_ptr))))
+
+    def force_diff(self, a_dev_ptr, b_dev_ptr, F, N, per_frame=False):
+        """(3,) sum (a - b)^2 per axis, max |a - b|, [sum a_x^2, sum a_y^2, sum a_z^2, max a] and, ``per_frame``, the (F, 2)
+        pairs [sum (a - b)^2, sum a^2] of two device tensors (F, N, 3)."""
+        sums, mx, norms = np.empty(3), np.empty(1), np.empty(4)
+        pf = np.empty((int(F), 2)) if per_frame else None
+        self._ck(self.lib.asb_force_diff(self.h, ctypes.c_void_p(int(a_dev_ptr)), ctypes.c_void_p(int(b_dev_ptr)), int(F), int(N),
+                                         ptr(sums), ptr(mx), ptr(norms), ptr(pf)))
+        return sums, float(mx[0]), norms, pf
+
     # ------------------------------------------------------------------ SPLOCS
     def splocs_begin(self):
         self._ck(self.lib.asb_splocs_begin(self.h))

@@ -12,6 +12,7 @@ import sys
 import numpy as np
 
 from . import projections as _proj
+from . import reduced as _red
 from . import utils as _u
 from .distributed import Comm
 from .engine import HipEngine
@@ -227,6 +228,101 @@ class posSnapshots:
         bend = [q[1].bending_indices for q in plan if q[0] == "verts_bending"]
         self.bending_indices = bend[0] if bend else None
         return out, n_sel
+
+    def _rforce_plan(self, kind, basis, elements, wi, reduction, rest_positions, sigma_min, sigma_max, animation, frame_start,
+                     frame_end, frame_jump):
+        """The checks of ``_cproj_args``, the kind's S^T and a function r -> ``reduced.ReducedOperator`` of the basis."""
+        setup, Y, end = self._cproj_args(kind, elements, rest_positions, sigma_min, sigma_max, animation, frame_start, frame_end,
+                                         frame_jump)
+        if reduction not in _red.REDUCTIONS:
+            raise ValueError("unknown reduction %r: one of %s" % (reduction, ", ".join(sorted(_red.REDUCTIONS))))
+        St = _proj.assembly_ST(setup, self.nVerts, wi)
+        data = _red.load_basis(basis)
+
+        def operator(r):
+            return _red.reduced_operator(data["components"], data["interpol_alphas"], data["Pt"], data["interpol_alpha_ranges"],
+                                         r, setup.p, reduction, n_elements=setup.n_elem, verts_bending=kind == "verts_bending")
+        return setup, Y, end, St, operator
+
+    def _rforce_term(self, setup, op, which, frame_start, end, frame_jump, sigma_min, sigma_max):
+        """One reduced term with the operator of the engine: only the sampled elements are set up and projected."""
+        import torch
+        eng = self._engine
+        eng.cproj_setup(_proj.subset_setup(setup, op.elements))
+        eng.rforce_solver(op.H, op.local_rows)
+        n_sel = len(range(frame_start, end, frame_jump))
+        out = torch.empty((n_sel, self.nVerts, 3), dtype=torch.float64, device="cuda:%d" % eng.device_id)
+        eng.rforce_run(which, frame_start, end, frame_jump, self.invMassL, self._standarize, self.pre_scale_factor, sigma_min,
+                       sigma_max, False, out.data_ptr())
+        return out, n_sel
+
+    def reduced_constraint_forces(self, kind, basis, num_components, elements=None, wi=1.0, reduction="deim_pod",
+                                  rest_positions=None, sigma_min=1.0, sigma_max=1.0, animation="train", frame_start=0,
+                                  frame_end=None, frame_jump=1):
+        """Extra (not in the reference's class): the constraint term the reference's REDUCED simulator puts on the global
+        step's right-hand side, b~[f] = S^T V (P^T V)^+ P^T p(q_f) per coordinate (Simulators.py:157-255, :366-399;
+        ``reduced.reduced_operator``), for the frames range(frame_start, frame_end, frame_jump) of the resident animation.
+        ``get_pi`` is evaluated at the interpolation elements only; S^T V is formed once on the device, sparse times dense.
+
+        ``kind``, ``elements``, ``rest_positions``, ``sigma_min`` / ``sigma_max``, ``animation``: as ``constraint_projections``
+        (``elements``: ALL elements of the kind, the ones the basis was built on); ``wi``: the constraint weight of S^T.
+        ``basis``: a ``constraintsComponents`` with components and interpolation points, the path of the ``.npz`` of its
+        ``store_components_n_interpol_points``, or a dict with the keys components, interpol_alphas, Pt,
+        interpol_alpha_ranges.  ``num_components``: m.  ``reduction``: the simulator's
+        ``constraint_projection_reduction_type`` ("deim_pod", "deim_pod_vectorized": single rows; "deim_pca_blocks",
+        "geom_pca_blocks_withSt": whole blocks of p rows).
+
+        Returns ``(tensor, F')``: a ``torch.float64`` device tensor (F', N, 3) in world space, the layout of
+        ``constraint_forces``.  Leaves ``self.assembly_ST[kind]`` and ``self.bending_indices``.  One rank only."""
+        setup, Y, end, St, operator = self._rforce_plan(kind, basis, elements, wi, reduction, rest_positions, sigma_min, sigma_max,
+                                                        animation, frame_start, frame_end, frame_jump)
+        op = operator(num_components)
+        eng = self._engine
+        if Y is not None:
+            eng.heldout_upload(Y, self.massL, self._standarize, self.pre_scale_factor)
+        eng.rforce_operator(St, op.V)
+        out, n_sel = self._rforce_term(setup, op, 0 if Y is None else 1, frame_start, end, frame_jump, sigma_min, sigma_max)
+        self.assembly_ST = {kind: St}
+        self.bending_indices = setup.bending_indices
+        return out, n_sel
+
+    def reduced_force_errors(self, kind, basis, r_values, elements=None, wi=1.0, reduction="deim_pod", rest_positions=None,
+                             sigma_min=1.0, sigma_max=1.0, animation="train", frame_start=0, frame_end=None, frame_jump=1,
+                             per_frame=False):
+        """Extra (not in the reference): how wrong the forces of the reduced simulation are -- for every r of ``r_values`` the
+        reference's ``frobenius_error``, ``max_pointwise_error`` and ``relative_error_per_component``
+        (constraintsComponents.py:524-556) of ``(b, b~_r)``, b the full term of ``constraint_forces`` for this kind and b~_r
+        ``reduced_constraint_forces`` with r components, as five lists ``fro, max, rel_x, rel_y, rel_z``; with ``per_frame``
+        a sixth value, the (len(r_values), F') array of |b[f] - b~_r[f]| / |b[f]| (Frobenius norms of the frame).  Arguments as
+        ``reduced_constraint_forces``.  The full term is computed once, S^T V once for the largest r (prefixes of its
+        columns serve the others); both tensors stay on the device and are compared there (asb_force_diff)."""
+        setup, Y, end, St, operator = self._rforce_plan(kind, basis, elements, wi, reduction, rest_positions, sigma_min, sigma_max,
+                                                        animation, frame_start, frame_end, frame_jump)
+        r_values = [int(r) for r in r_values]
+        ops = [operator(r) for r in r_values]
+        fro, mx, rel, frames = [], [], [[], [], []], []
+        if not ops:
+            return (fro, mx, rel[0], rel[1], rel[2]) + ((np.zeros((0, 0)),) if per_frame else ())
+        eng = self._engine
+        full, n_sel = self.constraint_forces([dict(kind=kind, elements=elements, wi=wi, rest_positions=rest_positions,
+                                                   sigma_min=sigma_min, sigma_max=sigma_max)], animation=animation,
+                                             frame_start=frame_start, frame_end=end, frame_jump=frame_jump)
+        eng.rforce_operator(St, ops[int(np.argmax(r_values))].V)
+        for op in ops:
+            red, _ = self._rforce_term(setup, op, 0 if Y is None else 1, frame_start, end, frame_jump, sigma_min, sigma_max)
+            sums, m, norms, pf = eng.force_diff(full.data_ptr(), red.data_ptr(), n_sel, self.nVerts, per_frame)
+            with np.errstate(divide='ignore', invalid='ignore'):
+                fro.append(float(np.sqrt(sums.sum())))
+                mx.append(float(m / norms[3]))
+                for d in range(3):
+                    rel[d].append(float(np.sqrt(sums[d]) / np.sqrt(norms[d])))
+                if per_frame:
+                    frames.append(np.sqrt(pf[:, 0]) / np.sqrt(pf[:, 1]))
+        self.assembly_ST = {kind: St}
+        self.bending_indices = setup.bending_indices
+        if per_frame:
+            return fro, mx, rel[0], rel[1], rel[2], np.array(frames).reshape(len(ops), -1)
+        return fro, mx, rel[0], rel[1], rel[2]
 
     # ------------------------------------------------------------------ reference methods
     @log_time("")

@@ -222,6 +222,27 @@ def build_setup(kind, elements, rest_positions):
                            b["star_idx"], bending_indices=b["indices"], parts=b)
 
 
+def subset_setup(setup, sel):
+    """The upload of the elements ``sel`` of ``setup`` alone, in that order (an element may repeat): the rest tables are taken
+    over, not rebuilt, so element ``sel[i]`` projects to the same bits as in the full set-up.  For ``verts_bending`` ``sel``
+    counts the constrained vertices (positions in ``bending_indices``)."""
+    sel = np.asarray(sel, dtype=np.int64).reshape(-1)
+    if sel.shape[0] < 1:
+        raise ValueError("%s: no elements" % setup.kind)
+    if sel.min() < 0 or sel.max() >= setup.n_elem:
+        bad = int(sel.max()) if sel.max() >= setup.n_elem else int(sel.min())
+        raise ValueError("%s: element %d of a set-up with elements 0..%d" % (setup.kind, bad, setup.n_elem - 1))
+    tw, n = setup.table_width, setup.n_elem
+    head = setup.table[:n * tw].reshape(n, tw)[sel]
+    if setup.kind != "verts_bending":
+        return ProjectionSetup(setup.kind, setup.idx[sel], head)
+    ptr, wts = setup.star_ptr, setup.table[n * tw:]
+    edges = np.concatenate([np.arange(ptr[i], ptr[i + 1]) for i in sel]) if sel.size else np.zeros(0, dtype=np.int64)
+    new_ptr = np.concatenate([[0], np.cumsum(ptr[sel + 1] - ptr[sel])])
+    return ProjectionSetup(setup.kind, setup.idx[sel], np.concatenate([head.reshape(-1), wts[edges]]), new_ptr,
+                           setup.star_idx[edges], bending_indices=setup.bending_indices[sel])
+
+
 def assembly_ST(setup, n_verts, wi=1.0):
     """The weighted differential operator S^T of one element kind, (n_verts, setup.rows) CSR with sorted indices: what the
     reference's ``*_assembly_ST`` hold (:1221-1284), restated from the rest tables of ``build_setup``.  Column c belongs to

@@ -625,6 +625,35 @@ int asb_cforce_run(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, 
                    double sigma_min, double sigma_max, int64_t n_rows, const int64_t* indptr, const int64_t* indices,
                    const double* data, int accumulate, int64_t chunk_frames, double* out_dev);
 
+/* ------------------------------- DEIM-reduced constraint forces and their error ---- */
+/* The reduced constraint term of the reference's simulator, b~_d = (S^T V_d) H_d P^T p_d per coordinate d with
+ * H_d = (A^T A + la_d I)^-1 A^T, A = P^T V_d (Simulators.py:157-255 prepare_reduced_group / prepare_reduced_verts_bending,
+ * :366-399 get_group_reduced_term), for frames of the resident position tensor.  One rank: v0 = 0 and n_loc = N_glob.
+ * asb_rforce_operator: S^T as a HOST CSR (n_rows = the tensor's vertices, columns < v_rows strictly ascending in every row,
+ * checked as asb_cforce_run checks it) and the basis V (host, v_rows x mp x 3).  Forms M_d = S^T V_d (three n_rows x mp
+ * matrices) on the device, every entry summed by one thread over the row's ascending columns; no dense S^T is formed.  Kept
+ * until the next call; drops the solver. */
+int asb_rforce_operator(asb_ctx* ctx, int64_t n_rows, const int64_t* indptr, const int64_t* indices, const double* data,
+                        int64_t v_rows, int64_t mp, const double* V);
+/* The solver of the next asb_rforce_run calls: H (host, 3 x r x npt), r <= mp -- the first r columns of the operator are
+ * used -- and per interpolation point the row of the SAMPLED elements' stacked projections it keeps (host, npt; row
+ * i p + l is row l of the i-th element handed to asb_cproj_setup). */
+int asb_rforce_solver(asb_ctx* ctx, int64_t r, int64_t npt, const double* H, const int64_t* rows);
+/* b~ of the frames range(f0, f1, fj) after asb_cproj_setup was called with ONLY the sampled elements: their projections
+ * (the arithmetic of asb_cproj_run, first ten arguments as there), coef_d = H_d p_d[rows] (r x n_sel), b~_d = M_d coef_d by
+ * an f64 MFMA kernel whose contraction is never split.  out_dev: caller-owned DEVICE memory, (n_sel, n_rows, 3) doubles;
+ * accumulate 0: every entry is written, 1: added to what is there.  The cost depends on npt, r, n_rows and n_sel only.
+ * Deterministic: no atomics, every entry a fixed-order sum; repeats, accumulate onto zeros and sub-ranges give the bits of the
+ * matching slices of a full run.  Returns after the stream has drained. */
+int asb_rforce_run(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean, double psf,
+                   double sigma_min, double sigma_max, int accumulate, double* out_dev);
+/* The reference's error metrics (constraintsComponents.py:524-556) of b against a, both DEVICE tensors (F, N, 3): sums_out (3)
+ * sum (a - b)^2 per axis, max_out (1) max |a - b|, norms_out (4) sum a_x^2, sum a_y^2, sum a_z^2 and the SIGNED max a,
+ * per_frame_out (F x 2) per frame [sum (a - b)^2, sum a^2] over its N x 3 entries.  Fixed-order reductions, no atomics; a
+ * NaN propagates through the sums as in asb_recon_sweep.  Any output pointer may be NULL. */
+int asb_force_diff(asb_ctx* ctx, const double* a_dev, const double* b_dev, int64_t F, int64_t N, double* sums_out, double* max_out,
+                   double* norms_out, double* per_frame_out);
+
 /* ------------------------------------------------ SPLOCS refinement ----------- */
 /* posComponents.splocs_glob_optimization, snapbases/posComponents.py:132-189.
  * State after a residual-mode deflation: C = comps, W = weigs, U = 0 (:135-139).  One outer
