@@ -44,6 +44,13 @@ struct CpWorld {
     const double* invm;
     double inv_psf;
 };
+#ifdef __HIPCC__
+__device__ __forceinline__ void cp_pos(const CpWorld& w, long long f, int v, double (&x)[3]) {
+    const double im = w.invm ? w.invm[v] : 1.0;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) x[d] = (w.T[(3LL * v + d) * w.ldt + f] * w.inv_psf + (w.mean ? w.mean[3LL * v + d] : 0.0)) * im;
+}
+#endif
 
 struct asb_ctx {
     int dev = 0;
@@ -331,6 +338,10 @@ struct asb_ctx {
     int64_t rf_r = 0, rf_npt = 0, rf_pt_max = -1;     // basis vectors in use (<= rf_mp; 0: no solver), points, largest row
     double* rf_coef = nullptr;        // (3, rf_r rounded up to 4, cw) coefficients of one chunk of frames
     double* fd_part = nullptr;        // asb_force_diff: per-frame records + the reduced row
+    // global step q = A^-1 rhs (asb_gstep.hip)
+    double* gs_Ainv = nullptr;        // (gs_Np, gs_Np) the explicit inverse of A_N, the padding an identity block
+    int64_t gs_n = 0, gs_Np = 0;      // its vertices (0: no set-up); rounded up to the kernel's 32
+    double* gs_diag = nullptr;        // (n_loc) asb_gstep_inertia: masses / h^2
 
     // ---- profiling of the dominant streaming kernel ----
     bool prof = false;
@@ -400,13 +411,17 @@ int asb_gemm_tn_big(asb_ctx* ctx, const double* X, long long ldx, const double* 
 // with `who`) and the world of the selected tensor, without the mass factors; n_sel: the frames range(f0, f1, fj) selects
 int asb_cproj_world(asb_ctx* ctx, const char* who, int which, int64_t f0, int64_t f1, int64_t fj, int add_mean, double psf,
                     double sigma_min, double sigma_max, CpWorld* w, int64_t* n_sel);
+// its part that needs no element set-up: the tensor of `which`, the frame range, the mean and the scale checked, w filled
+int asb_world_frames(asb_ctx* ctx, const char* who, int which, int64_t f0, int64_t f1, int64_t fj, int add_mean, double psf, CpWorld* w,
+                     int64_t* n_sel);
 // the first device work of a call, after all of its checks: inv_massL (host, or NULL) uploaded and put into w
 int asb_cproj_invm(asb_ctx* ctx, const double* inv_massL, CpWorld* w);
 // selected frames [c0, c0 + cn) projected ELEMENT-major into S (3 cp_n p rows of cw doubles), for the kind of asb_cproj_setup
 void asb_cproj_em_launch(asb_ctx* ctx, const CpWorld& w, int f0, int fj, int c0, int cn, int cw, double smin, double smax, double* S);
-// a host CSR checked (offsets from 0 and not decreasing, columns < n_cols and strictly ascending in a row) and narrowed to int
+// a host CSR checked (offsets from 0 and not decreasing, columns < n_cols and strictly ascending in a row) and narrowed to int;
+// `what` names the matrix in the messages
 int asb_csr_check32(asb_ctx* ctx, const char* who, int64_t n_rows, const int64_t* indptr, const int64_t* indices, const double* data,
-                    long long n_cols, std::vector<int>& p32, std::vector<int>& c32);
+                    long long n_cols, std::vector<int>& p32, std::vector<int>& c32, const char* what = "S^T");
 
 // ASB_DEBUG_PANELS: the panel loop's trace on stderr (changes no result); read once per process
 static inline bool asb_debug_panels() {

@@ -35,12 +35,6 @@ template <> struct CpShape<CP_TET_STRAIN> { static constexpr int NV = 4, P = 3, 
 template <> struct CpShape<CP_TET_DEFGRAD> { static constexpr int NV = 4, P = 3, TW = 9; };
 template <> struct CpShape<CP_BEND> { static constexpr int NV = 1, P = 1, TW = 5; };
 
-__device__ __forceinline__ void cp_pos(const CpWorld& w, long long f, int v, double (&x)[3]) {
-    const double im = w.invm ? w.invm[v] : 1.0;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) x[d] = (w.T[(3LL * v + d) * w.ldt + f] * w.inv_psf + (w.mean ? w.mean[3LL * v + d] : 0.0)) * im;
-}
-
 // one Jacobi rotation of the columns p, q of A (N rows) and of V (N rows): true when it rotated
 template <int N>
 __device__ __forceinline__ bool cp_rotate(double (&A)[N][N], double (&V)[N][N], int p, int q) {
@@ -343,10 +337,9 @@ static void cp_launch(asb_ctx* ctx, const CpWorld& w, int f0, int fj, int n_sel,
                        ctx->cp_table + (size_t)ctx->cp_n * CpShape<KIND>::TW, (long long)ctx->cp_n, f0, fj, n_sel, smin, smax, out);
 }
 
-int asb_cproj_world(asb_ctx* ctx, const char* who, int which, int64_t f0, int64_t f1, int64_t fj, int add_mean, double psf,
-                    double sigma_min, double sigma_max, CpWorld* w, int64_t* n_sel_out) {
-    if (ctx->cp_kind < 0 || !ctx->X || ctx->cp_verts != ctx->n_loc || ctx->v0 != 0 || ctx->n_loc != ctx->N_glob)
-        ASB_FAIL(ctx, ASB_ERR_ARG, "%s: no element set-up for the resident tensor (asb_cproj_setup)", who);
+int asb_world_frames(asb_ctx* ctx, const char* who, int which, int64_t f0, int64_t f1, int64_t fj, int add_mean, double psf, CpWorld* w,
+                     int64_t* n_sel_out) {
+    if (!ctx->X || ctx->v0 != 0 || ctx->n_loc != ctx->N_glob) ASB_FAIL(ctx, ASB_ERR_ARG, "%s: no whole tensor on the device (one rank only)", who);
     int64_t F;
     if (which == 0) {
         w->T = ctx->X, w->ldt = ctx->Fp, F = ctx->F;
@@ -361,13 +354,21 @@ int asb_cproj_world(asb_ctx* ctx, const char* who, int which, int64_t f0, int64_
                  (long long)fj, (long long)F);
     if (add_mean && !ctx->have_mean) ASB_FAIL(ctx, ASB_ERR_ARG, "%s: no mean on the device", who);
     if (!(psf > 0.0)) ASB_FAIL(ctx, ASB_ERR_ARG, "%s: scale %g", who, psf);
-    if (!(sigma_min <= sigma_max)) ASB_FAIL(ctx, ASB_ERR_ARG, "%s: sigma_min %g > sigma_max %g", who, sigma_min, sigma_max);
-    const int64_t n_sel = (f1 - f0 + fj - 1) / fj;
-    if ((n_sel + 63) / 64 > 65535) ASB_FAIL(ctx, ASB_ERR_LIMIT, "%s: %lld frames in one call (at most %d)", who, (long long)n_sel, 65535 * 64);
     w->mean = add_mean ? ctx->mean : nullptr;
     w->invm = nullptr;
     w->inv_psf = 1.0 / psf;
-    *n_sel_out = n_sel;
+    *n_sel_out = (f1 - f0 + fj - 1) / fj;
+    return ASB_OK;
+}
+
+int asb_cproj_world(asb_ctx* ctx, const char* who, int which, int64_t f0, int64_t f1, int64_t fj, int add_mean, double psf,
+                    double sigma_min, double sigma_max, CpWorld* w, int64_t* n_sel_out) {
+    if (ctx->cp_kind < 0 || !ctx->X || ctx->cp_verts != ctx->n_loc || ctx->v0 != 0 || ctx->n_loc != ctx->N_glob)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "%s: no element set-up for the resident tensor (asb_cproj_setup)", who);
+    int rc;
+    if ((rc = asb_world_frames(ctx, who, which, f0, f1, fj, add_mean, psf, w, n_sel_out))) return rc;
+    if (!(sigma_min <= sigma_max)) ASB_FAIL(ctx, ASB_ERR_ARG, "%s: sigma_min %g > sigma_max %g", who, sigma_min, sigma_max);
+    if ((*n_sel_out + 63) / 64 > 65535) ASB_FAIL(ctx, ASB_ERR_LIMIT, "%s: %lld frames in one call (at most %d)", who, (long long)*n_sel_out, 65535 * 64);
     return ASB_OK;
 }
 
@@ -512,12 +513,12 @@ void asb_cproj_em_launch(asb_ctx* ctx, const CpWorld& w, int f0, int fj, int c0,
 }
 
 int asb_csr_check32(asb_ctx* ctx, const char* who, int64_t n_rows, const int64_t* indptr, const int64_t* indices, const double* data,
-                    long long n_cols, std::vector<int>& p32, std::vector<int>& c32) {
-    if (indptr[0] != 0) ASB_FAIL(ctx, ASB_ERR_ARG, "%s: the row offsets of S^T do not start at 0", who);
+                    long long n_cols, std::vector<int>& p32, std::vector<int>& c32, const char* what) {
+    if (indptr[0] != 0) ASB_FAIL(ctx, ASB_ERR_ARG, "%s: the row offsets of %s do not start at 0", who, what);
     for (int64_t v = 0; v < n_rows; ++v)
-        if (indptr[v + 1] < indptr[v]) ASB_FAIL(ctx, ASB_ERR_ARG, "%s: row offsets of S^T decrease at row %lld", who, (long long)v);
+        if (indptr[v + 1] < indptr[v]) ASB_FAIL(ctx, ASB_ERR_ARG, "%s: row offsets of %s decrease at row %lld", who, what, (long long)v);
     const int64_t nnz = indptr[n_rows];
-    if (nnz > 0x7fffffffLL) ASB_FAIL(ctx, ASB_ERR_LIMIT, "%s: too many entries of S^T for 32-bit indices", who);
+    if (nnz > 0x7fffffffLL) ASB_FAIL(ctx, ASB_ERR_LIMIT, "%s: too many entries of %s for 32-bit indices", who, what);
     if (nnz > 0 && (!indices || !data)) return ASB_ERR_ARG;
     p32.resize((size_t)n_rows + 1);
     c32.resize((size_t)nnz);
@@ -525,9 +526,9 @@ int asb_csr_check32(asb_ctx* ctx, const char* who, int64_t n_rows, const int64_t
     for (int64_t v = 0; v < n_rows; ++v)
         for (int64_t t = indptr[v]; t < indptr[v + 1]; ++t) {
             if (indices[t] < 0 || indices[t] >= n_cols)
-                ASB_FAIL(ctx, ASB_ERR_ARG, "%s: row %lld of S^T names column %lld of %lld", who, (long long)v, (long long)indices[t], n_cols);
+                ASB_FAIL(ctx, ASB_ERR_ARG, "%s: row %lld of %s names column %lld of %lld", who, (long long)v, what, (long long)indices[t], n_cols);
             if (t > indptr[v] && indices[t] <= indices[t - 1])
-                ASB_FAIL(ctx, ASB_ERR_ARG, "%s: the columns of row %lld of S^T are not ascending", who, (long long)v);
+                ASB_FAIL(ctx, ASB_ERR_ARG, "%s: the columns of row %lld of %s are not ascending", who, (long long)v, what);
             c32[t] = (int)indices[t];
         }
     return ASB_OK;

@@ -574,6 +574,49 @@ class HipEngine(object):
                                          ptr(sums), ptr(mx), ptr(norms), ptr(pf)))
         return sums, float(mx[0]), norms, pf
 
+    # ------------------------------------------------------------------ global step of projective dynamics
+    def gstep_setup(self, A):
+        """Inverts ``A`` (scipy CSR (N, N), sorted indices, symmetric positive definite) on the device; the inverse stays with
+        the context.  Returns max |A (A^-1 1) - 1|."""
+        indptr = np.ascontiguousarray(A.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(A.indices, dtype=np.int64)
+        data = np.ascontiguousarray(A.data, dtype=np.float64)
+        res = ctypes.c_double()
+        self._gstep = None
+        self._ck(self.lib.asb_gstep_setup(self.h, int(A.shape[0]), ptr(indptr), ptr(indices), ptr(data), ctypes.byref(res)))
+        self._gstep = (indptr.copy(), indices.copy(), data.copy(), res.value)      # (copies: A stays the caller's)
+        return res.value
+
+    def gstep_held(self, A):
+        """The residual of the last ``gstep_setup`` if its matrix was ``A`` entry for entry (the inverse is still on the device),
+        else None."""
+        held = getattr(self, "_gstep", None)
+        if held is None or held[0].shape[0] != A.shape[0] + 1:
+            return None
+        same = all(np.array_equal(h, a) for h, a in zip(held[:3], (A.indptr, A.indices, A.data)))
+        return held[3] if same else None
+
+    def gstep_run(self, rhs_dev_ptr, n_frames, out_dev_ptr):
+        """out = rhs A^-1 per coordinate on two device buffers of (n_frames, N, 3) float64 that do not overlap."""
+        self._ck(self.lib.asb_gstep_run(self.h, ctypes.c_void_p(int(rhs_dev_ptr)), int(n_frames), ctypes.c_void_p(int(out_dev_ptr))))
+
+    def gstep_inertia(self, which, f0, f1, fj, inv_massL, add_mean, psf, diag, mode, acc, rhs_dev_ptr):
+        """rhs += diag * s for the frames range(f0, f1, fj): s = x + acc (``mode`` 0) or 2 x - x_prev + acc (1)."""
+        if inv_massL is not None:
+            inv_massL = np.ascontiguousarray(inv_massL, dtype=np.float64)
+            assert inv_massL.shape == (self.N_glob,)
+        diag = np.ascontiguousarray(diag, dtype=np.float64)
+        acc = np.ascontiguousarray(acc, dtype=np.float64)
+        assert diag.shape == (self.N_glob,) and acc.shape == (3,)
+        self._ck(self.lib.asb_gstep_inertia(self.h, int(which), int(f0), int(f1), int(fj), ptr(inv_massL), int(bool(add_mean)),
+                                            float(psf), ptr(diag), int(mode), ptr(acc), ctypes.c_void_p(int(rhs_dev_ptr))))
+
+    def gstep_inverse(self, n):
+        """Test hook: the (n, n) inverse the context holds."""
+        out = np.empty((int(n), int(n)))
+        self._ck(self.lib.asb_test_gstep_inverse(self.h, ptr(out), int(n)))
+        return out
+
     # ------------------------------------------------------------------ SPLOCS
     def splocs_begin(self):
         self._ck(self.lib.asb_splocs_begin(self.h))

@@ -54,6 +54,8 @@ class posSnapshots:
         self.tet_mesh = tet_mesh_file
         self.bending_indices = None             # constraint_projections("verts_bending"): the constrained vertices
         self.assembly_ST = None                 # constraint_forces / constraint_projections(wi=...): kind -> S^T (CSR)
+        self.global_matrix = None               # global_solve_setup: A = M / dt^2 + sum w S^T S (CSR, N x N)
+        self.global_solve_residual = None       # ... and max |A (A^-1 1) - 1| of the device's inverse
 
         # ---- device side ----
         self._comm = comm if comm is not None else Comm()
@@ -181,20 +183,9 @@ class posSnapshots:
             self.assembly_ST = {kind: St}
         return out, n_sel, setup.rows
 
-    def constraint_forces(self, kinds, animation="train", frame_start=0, frame_end=None, frame_jump=1, chunk_frames=None):
-        """Extra (not in the reference's class): the constraint term of the global step's right-hand side,
-        b[f] = sum_k S_k^T p_k(q_f) (``get_sum_ST_p``, Simulators.py:643-724), for the frames
-        range(frame_start, frame_end, frame_jump) of the resident animation -- on the device, the projections p never formed
-        at full size and never downloaded.
-
-        ``kinds``: a non-empty list of dicts ``{"kind", "elements", "wi": 1.0, "rest_positions": None, "sigma_min": 1.0,
-        "sigma_max": 1.0}`` with the meanings of ``constraint_projections``; a kind may be listed once.  The terms are added
-        in list order.  ``chunk_frames``: frames per pass of the device (rounded up to a multiple of 16; None: as many as a
-        256 MB scratch holds), which bounds the scratch and changes no bit of the result.
-
-        Returns ``(tensor, F')``: a ``torch.float64`` device tensor (F', N, 3) in world space, allocated here through torch
-        and owned by the caller -- the layout ``posSnapshots.from_device`` adopts.  Leaves ``self.assembly_ST`` (kind -> CSR)
-        and ``self.bending_indices``.  One rank only."""
+    def _cforce_plan(self, kinds, animation, frame_start, frame_end, frame_jump, chunk_frames=None):
+        """The checks of ``constraint_forces``, in its order: per kind ``(kind, setup, S^T, sigma_min, sigma_max, wi)``, the
+        held-out animation (None: the training tensor) and the end of the frame range."""
         if not isinstance(kinds, (list, tuple)) or len(kinds) == 0:
             raise ValueError("constraint_forces: kinds must be a non-empty list of dicts, not %r" % (kinds,))
         if chunk_frames is not None and (int(chunk_frames) != chunk_frames or chunk_frames < 1):
@@ -212,14 +203,35 @@ class posSnapshots:
                                              frame_start, frame_end, frame_jump)
             if any(kind == q[0] for q in plan):
                 raise ValueError("constraint_forces: kind %r is listed twice" % (kind,))
-            plan.append((kind, setup, _proj.assembly_ST(setup, self.nVerts, spec.get("wi", 1.0)), smin, smax))
+            plan.append((kind, setup, _proj.assembly_ST(setup, self.nVerts, spec.get("wi", 1.0)), smin, smax, spec.get("wi", 1.0)))
+        return plan, Y, end
+
+    def constraint_forces(self, kinds, animation="train", frame_start=0, frame_end=None, frame_jump=1, chunk_frames=None):
+        """Extra (not in the reference's class): the constraint term of the global step's right-hand side,
+        b[f] = sum_k S_k^T p_k(q_f) (``get_sum_ST_p``, Simulators.py:643-724), for the frames
+        range(frame_start, frame_end, frame_jump) of the resident animation -- on the device, the projections p never formed
+        at full size and never downloaded.
+
+        ``kinds``: a non-empty list of dicts ``{"kind", "elements", "wi": 1.0, "rest_positions": None, "sigma_min": 1.0,
+        "sigma_max": 1.0}`` with the meanings of ``constraint_projections``; a kind may be listed once.  The terms are added
+        in list order.  ``chunk_frames``: frames per pass of the device (rounded up to a multiple of 16; None: as many as a
+        256 MB scratch holds), which bounds the scratch and changes no bit of the result.
+
+        Returns ``(tensor, F')``: a ``torch.float64`` device tensor (F', N, 3) in world space, allocated here through torch
+        and owned by the caller -- the layout ``posSnapshots.from_device`` adopts.  Leaves ``self.assembly_ST`` (kind -> CSR)
+        and ``self.bending_indices``.  One rank only."""
+        plan, Y, end = self._cforce_plan(kinds, animation, frame_start, frame_end, frame_jump, chunk_frames)
+        return self._cforce_run(plan, Y, frame_start, end, frame_jump, chunk_frames)
+
+    def _cforce_run(self, plan, Y, frame_start, end, frame_jump, chunk_frames):
+        """``constraint_forces`` for a plan of ``_cforce_plan``."""
         import torch
         eng = self._engine
         if Y is not None:
             eng.heldout_upload(Y, self.massL, self._standarize, self.pre_scale_factor)
         n_sel = len(range(frame_start, end, frame_jump))
         out = torch.empty((n_sel, self.nVerts, 3), dtype=torch.float64, device="cuda:%d" % eng.device_id)
-        for i, (kind, setup, St, smin, smax) in enumerate(plan):
+        for i, (kind, setup, St, smin, smax, _wi) in enumerate(plan):
             eng.cproj_setup(setup)
             eng.cforce_run(0 if Y is None else 1, frame_start, end, frame_jump, self.invMassL, self._standarize,
                            self.pre_scale_factor, smin, smax, St, i > 0, 0 if chunk_frames is None else int(chunk_frames),
@@ -300,17 +312,27 @@ class posSnapshots:
                                                         animation, frame_start, frame_end, frame_jump)
         r_values = [int(r) for r in r_values]
         ops = [operator(r) for r in r_values]
-        fro, mx, rel, frames = [], [], [[], [], []], []
         if not ops:
-            return (fro, mx, rel[0], rel[1], rel[2]) + ((np.zeros((0, 0)),) if per_frame else ())
+            return self._diff_metrics(None, [], 0, per_frame)
         eng = self._engine
         full, n_sel = self.constraint_forces([dict(kind=kind, elements=elements, wi=wi, rest_positions=rest_positions,
                                                    sigma_min=sigma_min, sigma_max=sigma_max)], animation=animation,
                                              frame_start=frame_start, frame_end=end, frame_jump=frame_jump)
         eng.rforce_operator(St, ops[int(np.argmax(r_values))].V)
-        for op in ops:
-            red, _ = self._rforce_term(setup, op, 0 if Y is None else 1, frame_start, end, frame_jump, sigma_min, sigma_max)
-            sums, m, norms, pf = eng.force_diff(full.data_ptr(), red.data_ptr(), n_sel, self.nVerts, per_frame)
+        which = 0 if Y is None else 1
+        out = self._diff_metrics(full, (self._rforce_term(setup, op, which, frame_start, end, frame_jump, sigma_min, sigma_max)[0]
+                                        for op in ops), n_sel, per_frame)
+        self.assembly_ST = {kind: St}
+        self.bending_indices = setup.bending_indices
+        return out
+
+    def _diff_metrics(self, full, others, n_sel, per_frame):
+        """The reference's three metrics (constraintsComponents.py:524-556) of ``(full, t)`` for every device tensor ``t`` of
+        ``others`` (made one at a time), through ``asb_force_diff``: the lists ``fro, max, rel_x, rel_y, rel_z`` and, with
+        ``per_frame``, the (len(others), F') array of |full[f] - t[f]| / |full[f]|."""
+        fro, mx, rel, frames = [], [], [[], [], []], []
+        for t in others:
+            sums, m, norms, pf = self._engine.force_diff(full.data_ptr(), t.data_ptr(), n_sel, self.nVerts, per_frame)
             with np.errstate(divide='ignore', invalid='ignore'):
                 fro.append(float(np.sqrt(sums.sum())))
                 mx.append(float(m / norms[3]))
@@ -318,11 +340,148 @@ class posSnapshots:
                     rel[d].append(float(np.sqrt(sums[d]) / np.sqrt(norms[d])))
                 if per_frame:
                     frames.append(np.sqrt(pf[:, 0]) / np.sqrt(pf[:, 1]))
+        if per_frame:
+            return fro, mx, rel[0], rel[1], rel[2], np.array(frames).reshape(len(fro), -1) if fro else np.zeros((0, 0))
+        return fro, mx, rel[0], rel[1], rel[2]
+
+    # ------------------------------------------------------------------ extras: the global step of projective dynamics
+    def _gstep_one_rank(self, who):
+        if self._comm.multi:
+            raise NotImplementedError("%s on several ranks: the system matrix couples the vertex shards and no distributed "
+                                      "solve is built" % who)
+
+    def _gstep_masses(self, masses):
+        if masses is None:
+            masses = self.mass
+            if masses is None:
+                raise ValueError("no vertex masses: the snapshots were built without mass weighting, pass masses=")
+        return np.asarray(masses, dtype=np.float64)
+
+    def global_solve_setup(self, kinds, dt, masses=None):
+        """Extra (not in the reference's class): prepares the global step of the reference's projective-dynamics solver,
+        ``prepare_global_matrix`` (Simulators.py:117-145), for this mesh: A = M / dt^2 + sum_i w_i S_i^T S_i is assembled on
+        the host from the rest tables (``projections.global_matrix``: one N x N matrix serves the three coordinates) and
+        inverted once on the device, where A^-1 stays until the next set-up.
+
+        ``kinds``: the list of dicts of ``constraint_forces`` (same checks).  ``dt``: the time step h.  ``masses`` (N,): None
+        takes the vertex masses the snapshots were mass-weighted with.  Leaves ``self.global_matrix`` (CSR) and
+        ``self.global_solve_residual`` = max |A (A^-1 1) - 1| as the device computed it.  Cost: the host assembly and symmetry
+        check, and on the device a dense N x N inversion (N^3 flop, 8 N^2 bytes); a set-up whose matrix equals the one the
+        device already holds keeps that inverse.  N <= 46 000, one rank only."""
+        self._gstep_one_rank("global_solve_setup")
+        plan, _, _ = self._cforce_plan(kinds, "train", 0, None, 1)
+        self._gstep_setup(plan, dt, self._gstep_masses(masses))
+
+    def _gstep_setup(self, plan, dt, masses):
+        A = _proj.global_matrix([(q[1], q[5]) for q in plan], self.nVerts, masses, dt)
+        self.global_matrix, self.global_solve_residual = None, None
+        resid = self._engine.gstep_held(A)
+        if resid is None:
+            resid = self._engine.gstep_setup(A)
+        self.global_matrix, self.global_solve_residual = A, resid
+
+    def global_solve(self, rhs):
+        """Extra: q = A^-1 rhs per coordinate for the matrix of the last ``global_solve_setup``.  ``rhs``: a caller-owned
+        ``torch.float64`` device tensor (F', N, 3), contiguous; returns a new one of the same shape, owned by the caller.  The
+        sum over the vertices is never split: a frame's result does not depend on the frames around it."""
+        self._gstep_one_rank("global_solve")
+        if getattr(self, "global_matrix", None) is None:
+            raise ValueError("global_solve: no system matrix on the device, call global_solve_setup first")
+        import torch
+        if not isinstance(rhs, torch.Tensor) or rhs.dtype != torch.float64 or not rhs.is_cuda:
+            raise ValueError("global_solve: rhs must be a torch.float64 device tensor")
+        if rhs.device.index != self._engine.device_id:
+            raise ValueError("global_solve: rhs lives on %s, the snapshots on device %d" % (rhs.device, self._engine.device_id))
+        if rhs.dim() != 3 or rhs.shape[0] < 1 or tuple(rhs.shape[1:]) != (self.nVerts, 3) or not rhs.is_contiguous():
+            raise ValueError("global_solve: rhs of shape %s: a contiguous (F', %d, 3) expected" % (tuple(rhs.shape), self.nVerts))
+        out = torch.empty_like(rhs)
+        torch.cuda.current_stream(rhs.device).synchronize()         # whatever produced rhs is done before the engine reads it
+        self._engine.gstep_run(rhs.data_ptr(), rhs.shape[0], out.data_ptr())
+        return out
+
+    @staticmethod
+    def _gstep_explicit(dt, velocity, gravity):
+        if velocity not in ("difference", "zero"):
+            raise ValueError("velocity must be 'difference' or 'zero', not %r" % (velocity,))
+        g = np.asarray(gravity, dtype=np.float64)
+        if g.shape != (3,) or not np.isfinite(g).all():
+            raise ValueError("gravity %r: three finite numbers expected" % (gravity,))
+        try:
+            h = float(dt)
+        except (TypeError, ValueError):
+            h = float("nan")
+        if not np.isfinite(h) or h <= 0.0:
+            raise ValueError("the time step dt must be finite and positive, not %r" % (dt,))
+        return 1 if velocity == "difference" else 0, h * h * g
+
+    def _gstep_inertia(self, rhs, masses, dt, mode, acc, which, frame_start, end, frame_jump):
+        """rhs += M / dt^2 s of the selected frames."""
+        self._engine.gstep_inertia(which, frame_start, end, frame_jump, self.invMassL, self._standarize, self.pre_scale_factor,
+                                   masses * (1.0 / (float(dt) * float(dt))), mode, acc, rhs.data_ptr())
+
+    def global_step(self, kinds, dt, masses=None, velocity="difference", gravity=(0.0, 0.0, 0.0), animation="train",
+                    frame_start=0, frame_end=None, frame_jump=1, chunk_frames=None):
+        """Extra: one local/global iteration of the reference's solver started at every selected frame of the resident
+        animation (Simulators.py:494-526 with ``num_iterations`` = 1 and q = x_f):
+        Phi(x_f; s_f) = A^-1 (M / dt^2 s_f + sum_k S_k^T p_k(x_f)), on the device.
+
+        ``kinds``, ``animation``, the frame range and ``chunk_frames``: as ``constraint_forces``; ``dt``, ``masses``: as
+        ``global_solve_setup``, whose work is done here first -- the matrix is assembled on every call, the dense inversion
+        is paid only when the matrix differs from the one the device holds.  ``velocity``: "zero" takes the explicit state
+        s_f = x_f + dt^2 g, "difference"
+        s_f = 2 x_f - x_{f-1} + dt^2 g with f - 1 the ANIMATION's previous frame whatever ``frame_jump`` is (at frame 0:
+        x_0), the velocity the reference carries from step to step (:531).  ``gravity``: the acceleration g.
+
+        Returns ``(tensor, F')``: a ``torch.float64`` device tensor (F', N, 3) in world space, owned by the caller.  Further
+        iterations are the caller's loop: adopt the result with ``from_device`` and step again.  One rank only."""
+        self._gstep_one_rank("global_step")
+        mode, acc = self._gstep_explicit(dt, velocity, gravity)
+        m = self._gstep_masses(masses)
+        plan, Y, end = self._cforce_plan(kinds, animation, frame_start, frame_end, frame_jump, chunk_frames)
+        self._gstep_setup(plan, dt, m)
+        b, n_sel = self._cforce_run(plan, Y, frame_start, end, frame_jump, chunk_frames)
+        self._gstep_inertia(b, m, dt, mode, acc, 0 if Y is None else 1, frame_start, end, frame_jump)
+        return self.global_solve(b), n_sel
+
+    def reduced_global_step_errors(self, kind, basis, r_values, dt, masses=None, velocity="difference", gravity=(0.0, 0.0, 0.0),
+                                   elements=None, wi=1.0, reduction="deim_pod", rest_positions=None, sigma_min=1.0,
+                                   sigma_max=1.0, animation="train", frame_start=0, frame_end=None, frame_jump=1,
+                                   per_frame=False):
+        """Extra: how far the reduced right-hand side moves the vertices -- ``reduced_force_errors`` one line further down the
+        iteration.  Cost beside that method's: the work of ``global_solve_setup`` once, one solve plus one per r.
+        For every r of ``r_values`` the three metrics of ``(q, q~_r)``: q = ``global_step`` of this kind and
+        q~_r the same step with b~_r of ``reduced_constraint_forces`` in place of b (same inertia term, same A^-1).  Arguments
+        as ``reduced_force_errors`` plus ``dt``, ``masses``, ``velocity``, ``gravity`` of ``global_step``; the same five lists
+        ``fro, max, rel_x, rel_y, rel_z`` and, with ``per_frame``, the (len(r_values), F') array |q[f] - q~_r[f]| / |q[f]|.
+        The full step is computed once; every tensor stays on the device."""
+        self._gstep_one_rank("reduced_global_step_errors")
+        mode, acc = self._gstep_explicit(dt, velocity, gravity)
+        m = self._gstep_masses(masses)
+        setup, Y, end, St, operator = self._rforce_plan(kind, basis, elements, wi, reduction, rest_positions, sigma_min, sigma_max,
+                                                        animation, frame_start, frame_end, frame_jump)
+        r_values = [int(r) for r in r_values]
+        ops = [operator(r) for r in r_values]
+        if not ops:
+            return self._diff_metrics(None, [], 0, per_frame)
+        eng, which = self._engine, 0 if Y is None else 1
+        spec = dict(kind=kind, elements=elements, wi=wi, rest_positions=rest_positions, sigma_min=sigma_min, sigma_max=sigma_max)
+        plan, Y, end = self._cforce_plan([spec], animation, frame_start, end, frame_jump)
+        self._gstep_setup(plan, dt, m)
+        b, n_sel = self._cforce_run(plan, Y, frame_start, end, frame_jump, None)
+        self._gstep_inertia(b, m, dt, mode, acc, which, frame_start, end, frame_jump)
+        full = self.global_solve(b)
+        del b
+        eng.rforce_operator(St, ops[int(np.argmax(r_values))].V)
+
+        def steps():
+            for op in ops:
+                red, _ = self._rforce_term(setup, op, which, frame_start, end, frame_jump, sigma_min, sigma_max)
+                self._gstep_inertia(red, m, dt, mode, acc, which, frame_start, end, frame_jump)
+                yield self.global_solve(red)
+        out = self._diff_metrics(full, steps(), n_sel, per_frame)
         self.assembly_ST = {kind: St}
         self.bending_indices = setup.bending_indices
-        if per_frame:
-            return fro, mx, rel[0], rel[1], rel[2], np.array(frames).reshape(len(ops), -1)
-        return fro, mx, rel[0], rel[1], rel[2]
+        return out
 
     # ------------------------------------------------------------------ reference methods
     @log_time("")

@@ -288,6 +288,81 @@ def assembly_ST(setup, n_verts, wi=1.0):
     return St
 
 
+def global_matrix(specs, n_verts, masses, dt):
+    """The system matrix of the global step, A_N = diag(masses) / dt^2 + sum_i w_i S_i^T S_i, (n_verts, n_verts) CSR with sorted
+    indices and duplicates summed.  The reference assembles kron(A_N, I_3) from the triplets of ``get_wi_SiT_AiT_Ai_Si``
+    (Simulators.py:117-145): no entry couples two coordinates and the three diagonal blocks are equal, so one N x N matrix
+    serves all three.  ``specs``: a non-empty list of ``(ProjectionSetup, wi)``, one per element kind; restated per kind from
+    the rest tables of ``build_setup``:
+
+      edge_spring   wi / 2 on (v0, v0) and (v1, v1), -wi / 2 on (v0, v1) and (v1, v0) (:322-333)
+      tris_strain   wi |A0| G^T G on (v1, v2, v3), G = [DmInv | -rowsum(DmInv)] (2 x 3) (:431-455)
+      tets_*        wi |V0| G G^T on (v1 .. v4), G = [DmInv ; -colsum(DmInv)] (4 x 3) (:559-584, :802-827)
+      verts_bending wi_v s s^T, s the constraint's selection row (sum(w) at the vertex, -w_j at every star neighbour, :189-191)
+                    and wi_v = wi * (a third of the incident triangle area, :119)
+
+    The reference drops triplets of |value| <= 1e-12 before summing; here nothing is dropped (the matrix stays linear in wi).
+    Both triangles are averaged, so the result is symmetric to the bit.  Raises ValueError for a ``dt`` that is not finite and
+    positive, ``masses`` of another shape than (n_verts,) or not finite and positive, a ``wi`` that is not finite, an empty
+    list, or an element outside the matrix."""
+    from scipy import sparse
+    if not isinstance(specs, (list, tuple)) or len(specs) == 0:
+        raise ValueError("global_matrix: specs must be a non-empty list of (setup, wi), not %r" % (specs,))
+    try:
+        h = float(dt)
+    except (TypeError, ValueError):
+        raise ValueError("global_matrix: the time step dt must be a positive number, not %r" % (dt,))
+    if not np.isfinite(h) or h <= 0.0:
+        raise ValueError("global_matrix: the time step dt must be finite and positive, not %r" % (dt,))
+    n_verts = int(n_verts)
+    m = np.asarray(masses, dtype=np.float64)
+    if m.shape != (n_verts,):
+        raise ValueError("global_matrix: masses of shape %s: (%d,) expected" % (m.shape, n_verts))
+    if not np.isfinite(m).all() or (m <= 0.0).any():
+        raise ValueError("global_matrix: every vertex mass must be finite and positive")
+    diag = np.arange(n_verts, dtype=np.int64)
+    rows, cols, vals = [diag], [diag], [m * (1.0 / (h * h))]
+    for spec in specs:
+        try:
+            setup, wi = spec
+            wi = float(wi)
+        except (TypeError, ValueError):
+            raise ValueError("global_matrix: every entry of specs is a (setup, wi) pair, not %r" % (spec,))
+        if not isinstance(setup, ProjectionSetup):
+            raise ValueError("global_matrix: every entry of specs is a (setup, wi) pair, not %r" % (spec,))
+        if not np.isfinite(wi):
+            raise ValueError("%s: the constraint weight wi must be finite, not %r" % (setup.kind, wi))
+        kind, idx, q, n = setup.kind, setup.idx, setup.parts, setup.n_elem
+        if idx.max() >= n_verts or (setup.star_idx is not None and setup.star_idx.size and setup.star_idx.max() >= n_verts):
+            raise ValueError("%s: an element names vertex %d, the matrix has %d rows" % (kind, int(idx.max()), n_verts))
+        if kind == "verts_bending":
+            S = assembly_ST(setup, n_verts, 1.0)                    # column i: voronoi_area_i * s_i
+            K = (S @ sparse.diags(wi / q["voronoi_area"]) @ S.T).tocoo()
+            rows.append(K.row.astype(np.int64))
+            cols.append(K.col.astype(np.int64))
+            vals.append(K.data)
+            continue
+        if kind == "edge_spring":
+            K = np.broadcast_to(0.5 * wi * np.array([[1.0, -1.0], [-1.0, 1.0]]), (n, 2, 2))
+        elif kind == "tris_strain":
+            D = q["DmInv"]
+            G = np.concatenate([D, -D.sum(axis=2)[:, :, None]], axis=2)             # (n, 2, 3)
+            K = np.einsum("nja,njb->nab", G, G) * (wi * np.abs(q["A0"]))[:, None, None]
+        else:
+            D = q["DmInv"]
+            G = np.concatenate([D, -D.sum(axis=1)[:, None, :]], axis=1)             # (n, 4, 3)
+            K = np.einsum("nac,nbc->nab", G, G) * (wi * np.abs(q["V0"]))[:, None, None]
+        nv = setup.width
+        rows.append(np.broadcast_to(idx[:, :, None], (n, nv, nv)).reshape(-1))
+        cols.append(np.broadcast_to(idx[:, None, :], (n, nv, nv)).reshape(-1))
+        vals.append(np.ascontiguousarray(K).reshape(-1))
+    A = sparse.coo_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(n_verts, n_verts)).tocsr()
+    A = ((A + A.T) * 0.5).tocsr()
+    A.sum_duplicates()
+    A.sort_indices()
+    return A
+
+
 def project_host(setup, positions, sigma_min=1.0, sigma_max=1.0):
     """NumPy restatement of ``get_pi`` for every element and frame: positions (F, N, 3) -> (F, n p, 3).  For scale and for
     checks on small shapes only; the product path is the device kernel."""

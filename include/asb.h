@@ -654,6 +654,31 @@ int asb_rforce_run(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, 
 int asb_force_diff(asb_ctx* ctx, const double* a_dev, const double* b_dev, int64_t F, int64_t N, double* sums_out, double* max_out,
                    double* norms_out, double* per_frame_out);
 
+/* ------------------------------- global step of projective dynamics ---- */
+/* q = A^-1 rhs for A_N = M / h^2 + sum_i w_i S_i^T S_i (Simulators.py:117-145, :508-526): the reference's 3N x 3N matrix is
+ * kron(A_N, I_3), so one N x N matrix serves the three coordinates.  One rank: v0 = 0 and n_loc = N_glob.
+ * asb_gstep_setup: A_N as a HOST CSR (n = the tensor's vertices rows and columns, columns strictly ascending in every row),
+ * checked before use: positive diagonal, symmetric pattern, values symmetric to 1e-12 of the row's largest entry.  It is
+ * scattered into a dense matrix padded to a multiple of 32 by an identity block and inverted in place on the device (blocked
+ * Gauss-Jordan, f64 MFMA); the inverse belongs to the context until the next set-up or asb_destroy.  n <= 46000 (17 GB),
+ * larger n: ASB_ERR_LIMIT, checked before anything else is read.  resid_out (optional): max |A (A^-1 u) - u| for u = 1, A
+ * applied as the sparse matrix, fixed summation order. */
+int asb_gstep_setup(asb_ctx* ctx, int64_t n, const int64_t* indptr, const int64_t* indices, const double* data, double* resid_out);
+/* out[f, m, d] = sum_n rhs[f, n, d] A^-1[n, m]: both caller-owned DEVICE tensors (n_frames, n, 3), frame-major, neither is
+ * transposed and they must not overlap.  f64 MFMA, the three coordinates share every tile of A^-1; the contraction is never
+ * split, every entry is one accumulator summed over ascending n: no atomics, repeats and frame sub-ranges give identical bits.
+ * Every entry of out is written.  Returns after the stream has drained. */
+int asb_gstep_run(asb_ctx* ctx, const double* rhs_dev, int64_t n_frames, double* out_dev);
+/* rhs[f, n, d] += diag[n] s_f[n, d] for the frames range(f0, f1, fj) of the training (which 0) or held-out (1) tensor, from
+ * the world positions x of asb_cproj_run (arguments two to eight as there; no element set-up is needed).
+ * diag (host, n): masses / h^2; acc3 (host, 3): h^2 g.  mode 0: s_f = x_f + acc; mode 1: s_f = 2 x_f - x_{f-1} + acc, f - 1
+ * the TENSOR's previous frame (at frame 0: x_0), the explicit step of Simulators.py:494-495 with the velocity of :531.
+ * rhs_dev: caller-owned DEVICE memory (n_sel, n, 3), read and written entry by entry.  Returns after the stream has drained. */
+int asb_gstep_inertia(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean, double psf,
+                      const double* diag, int mode, const double* acc3, double* rhs_dev);
+/* test hook: the n x n block of the context's A^-1 (row-major) to the host */
+int asb_test_gstep_inverse(asb_ctx* ctx, double* out_host, int64_t n);
+
 /* ------------------------------------------------ SPLOCS refinement ----------- */
 /* posComponents.splocs_glob_optimization, snapbases/posComponents.py:132-189.
  * State after a residual-mode deflation: C = comps, W = weigs, U = 0 (:135-139).  One outer
