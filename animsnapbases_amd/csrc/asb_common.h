@@ -35,6 +35,7 @@ struct StreamCfg {
 
 struct asb_splocs;
 struct asb_geo;
+struct asb_pds;
 
 // world positions of the resident tensor (asb_cproj.hip): x = (T * inv_psf + mean) * invm_v
 struct CpWorld {
@@ -342,6 +343,7 @@ struct asb_ctx {
     double* gs_Ainv = nullptr;        // (gs_Np, gs_Np) the explicit inverse of A_N, the padding an identity block
     int64_t gs_n = 0, gs_Np = 0;      // its vertices (0: no set-up); rounded up to the kernel's 32
     double* gs_diag = nullptr;        // (n_loc) asb_gstep_inertia: masses / h^2
+    asb_pds* pds = nullptr;           // the solve in progress and its buffers (asb_pdsolve.hip)
 
     // ---- profiling of the dominant streaming kernel ----
     bool prof = false;
@@ -357,6 +359,7 @@ int asb_sketch_predict(asb_ctx* ctx, const double* cols, long long stride, const
 int asb_project_run(asb_ctx* ctx, int64_t k0, int64_t k1);
 void asb_splocs_free(asb_ctx* ctx);
 void asb_geo_free(asb_ctx* ctx);
+void asb_pdsolve_free(asb_ctx* ctx);
 #define ASB_GEO_CACHE_SLABS 64          // x 64 distance fields
 const double* asb_geo_cached_field(asb_ctx* ctx, long long slot, long long* n_out);
 // small dense linear algebra on the device (asb_linalg.hip)
@@ -418,6 +421,28 @@ int asb_world_frames(asb_ctx* ctx, const char* who, int which, int64_t f0, int64
 int asb_cproj_invm(asb_ctx* ctx, const double* inv_massL, CpWorld* w);
 // selected frames [c0, c0 + cn) projected ELEMENT-major into S (3 cp_n p rows of cw doubles), for the kind of asb_cproj_setup
 void asb_cproj_em_launch(asb_ctx* ctx, const CpWorld& w, int f0, int fj, int c0, int cn, int cw, double smin, double smax, double* S);
+// the same for any element set-up on the device: the tables asb_cproj_setup uploads, by pointer (asb_pdsolve.hip keeps several)
+struct CpTables {
+    int kind;
+    long long n;                      // elements
+    const int *idx, *sptr, *sidx;
+    const double* table;              // (n x TW), verts_bending: followed by the star edges' weights
+};
+void asb_cproj_em_launch_t(asb_ctx* ctx, const CpTables& t, const CpWorld& w, int f0, int fj, int c0, int cn, int cw, double smin, double smax,
+                           double* S);
+// rows of the stacked projections of a set-up of `kind` with n_elem elements
+long long asb_cproj_rows(int kind, long long n_elem);
+// the chunk width of asb_cforce_run for projections of n_cols rows, and one chunk's k_st_apply on a device CSR
+long long asb_cforce_chunk_width(long long n_cols, long long chunk_frames, long long n_sel);
+void asb_st_apply_launch(asb_ctx* ctx, const int* ptr, const int* ci, const double* val, const double* S, int cw, int c0, int cn,
+                         long long n_rows, int accumulate, double* out);
+// asb_rforce.hip: the chunk width of asb_rforce_run for sampled projections of n_cols rows; one chunk's k_rforce_coef and
+// k_rforce_gemm with the context's operator and solver, from the element-major projections S (coefficients into ctx->rf_coef)
+long long asb_rforce_chunk_width(asb_ctx* ctx, long long n_cols, long long n_sel);
+void asb_rforce_chunk_launch(asb_ctx* ctx, const double* S, int cw, int c0, int cn, int accumulate, double* out);
+// asb_gstep.hip: k_gs_inertia on device arrays; add: out += diag s, otherwise out = diag s (the value the sum adds)
+void asb_gs_inertia_launch(asb_ctx* ctx, const CpWorld& w, int f0, int fj, int n_sel, long long n, const double* diag_dev, int mode,
+                           const double* acc3, bool add, double* out);
 // a host CSR checked (offsets from 0 and not decreasing, columns < n_cols and strictly ascending in a row) and narrowed to int;
 // `what` names the matrix in the messages
 int asb_csr_check32(asb_ctx* ctx, const char* who, int64_t n_rows, const int64_t* indptr, const int64_t* indices, const double* data,

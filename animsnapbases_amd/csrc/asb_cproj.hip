@@ -495,21 +495,47 @@ __global__ __launch_bounds__(64 * CP_WAVES) void k_st_apply(const int* __restric
 }
 
 template <int KIND>
-static void cf_launch(asb_ctx* ctx, const CpWorld& w, int f0, int fj, int c0, int cn, int cw, double smin, double smax, double* S) {
-    const dim3 grid((unsigned)((ctx->cp_n + CP_EB - 1) / CP_EB), (unsigned)((cn + 63) / 64));
-    hipLaunchKernelGGL(k_cproj_em<KIND>, grid, dim3(64 * CP_WAVES), 0, ctx->stream, w, ctx->cp_idx, ctx->cp_table, ctx->cp_sptr,
-                       ctx->cp_sidx, ctx->cp_table + (size_t)ctx->cp_n * CpShape<KIND>::TW, (long long)ctx->cp_n, f0, fj, c0, cn, cw, smin,
-                       smax, S);
+static void cf_launch(asb_ctx* ctx, const CpTables& t, const CpWorld& w, int f0, int fj, int c0, int cn, int cw, double smin, double smax,
+                      double* S) {
+    const dim3 grid((unsigned)((t.n + CP_EB - 1) / CP_EB), (unsigned)((cn + 63) / 64));
+    hipLaunchKernelGGL(k_cproj_em<KIND>, grid, dim3(64 * CP_WAVES), 0, ctx->stream, w, t.idx, t.table, t.sptr, t.sidx,
+                       t.table + (size_t)t.n * CpShape<KIND>::TW, t.n, f0, fj, c0, cn, cw, smin, smax, S);
+}
+
+void asb_cproj_em_launch_t(asb_ctx* ctx, const CpTables& t, const CpWorld& w, int f0, int fj, int c0, int cn, int cw, double smin, double smax,
+                           double* S) {
+    switch (t.kind) {
+        case CP_EDGE: cf_launch<CP_EDGE>(ctx, t, w, f0, fj, c0, cn, cw, smin, smax, S); break;
+        case CP_TRI: cf_launch<CP_TRI>(ctx, t, w, f0, fj, c0, cn, cw, smin, smax, S); break;
+        case CP_TET_STRAIN: cf_launch<CP_TET_STRAIN>(ctx, t, w, f0, fj, c0, cn, cw, smin, smax, S); break;
+        case CP_TET_DEFGRAD: cf_launch<CP_TET_DEFGRAD>(ctx, t, w, f0, fj, c0, cn, cw, smin, smax, S); break;
+        default: cf_launch<CP_BEND>(ctx, t, w, f0, fj, c0, cn, cw, smin, smax, S); break;
+    }
 }
 
 void asb_cproj_em_launch(asb_ctx* ctx, const CpWorld& w, int f0, int fj, int c0, int cn, int cw, double smin, double smax, double* S) {
-    switch (ctx->cp_kind) {
-        case CP_EDGE: cf_launch<CP_EDGE>(ctx, w, f0, fj, c0, cn, cw, smin, smax, S); break;
-        case CP_TRI: cf_launch<CP_TRI>(ctx, w, f0, fj, c0, cn, cw, smin, smax, S); break;
-        case CP_TET_STRAIN: cf_launch<CP_TET_STRAIN>(ctx, w, f0, fj, c0, cn, cw, smin, smax, S); break;
-        case CP_TET_DEFGRAD: cf_launch<CP_TET_DEFGRAD>(ctx, w, f0, fj, c0, cn, cw, smin, smax, S); break;
-        default: cf_launch<CP_BEND>(ctx, w, f0, fj, c0, cn, cw, smin, smax, S); break;
-    }
+    const CpTables t = {ctx->cp_kind, (long long)ctx->cp_n, ctx->cp_idx, ctx->cp_sptr, ctx->cp_sidx, ctx->cp_table};
+    asb_cproj_em_launch_t(ctx, t, w, f0, fj, c0, cn, cw, smin, smax, S);
+}
+
+long long asb_cproj_rows(int kind, long long n_elem) {
+    static const int PK[5] = {1, 2, 3, 3, 1};
+    return n_elem * PK[kind];
+}
+
+// whole 128-byte lines per scratch row, the scratch within CF_SCRATCH_BYTES, whole waves if it can
+long long asb_cforce_chunk_width(long long n_cols, long long chunk_frames, long long n_sel) {
+    long long cw = (long long)(CF_SCRATCH_BYTES / (24ull * (unsigned long long)n_cols));
+    cw = cw >= 64 ? cw / 64 * 64 : (cw >= 16 ? cw / 16 * 16 : 16);
+    if (chunk_frames > 0 && (chunk_frames + 15) / 16 * 16 < cw) cw = (chunk_frames + 15) / 16 * 16;
+    const long long span = (n_sel + 15) / 16 * 16;
+    return cw > span ? span : cw;
+}
+
+void asb_st_apply_launch(asb_ctx* ctx, const int* ptr, const int* ci, const double* val, const double* S, int cw, int c0, int cn,
+                         long long n_rows, int accumulate, double* out) {
+    hipLaunchKernelGGL(k_st_apply, dim3((unsigned)((n_rows + CF_VB - 1) / CF_VB), (unsigned)((cn + 63) / 64)), dim3(64 * CP_WAVES), 0, ctx->stream,
+                       ptr, ci, val, S, cw, c0, cn, n_rows, accumulate ? 1 : 0, out);
 }
 
 int asb_csr_check32(asb_ctx* ctx, const char* who, int64_t n_rows, const int64_t* indptr, const int64_t* indices, const double* data,
@@ -544,19 +570,13 @@ extern "C" int asb_cforce_run(asb_ctx* ctx, int which, int64_t f0, int64_t f1, i
     if ((rc = asb_cproj_world(ctx, "asb_cforce_run", which, f0, f1, fj, add_mean, psf, sigma_min, sigma_max, &w, &n_sel))) return rc;
     if (chunk_frames < 0) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: chunk_frames %lld", (long long)chunk_frames);
     // ---- the CSR of S^T: one row per vertex of the tensor, columns = rows of the stacked projections, ascending in a row
-    static const int PK[5] = {1, 2, 3, 3, 1};
-    const long long n_cols = (long long)ctx->cp_n * PK[ctx->cp_kind];
+    const long long n_cols = asb_cproj_rows(ctx->cp_kind, ctx->cp_n);
     if (n_rows != ctx->n_loc)
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: S^T has %lld rows, the tensor %lld vertices", (long long)n_rows, (long long)ctx->n_loc);
     std::vector<int> p32, c32;
     if ((rc = asb_csr_check32(ctx, "asb_cforce_run", n_rows, indptr, indices, data, n_cols, p32, c32))) return rc;
     const int64_t nnz = indptr[n_rows];
-    // ---- chunk width: whole 128-byte lines per scratch row, the scratch within CF_SCRATCH_BYTES, whole waves if it can
-    long long cw = (long long)(CF_SCRATCH_BYTES / (24ull * (unsigned long long)n_cols));
-    cw = cw >= 64 ? cw / 64 * 64 : (cw >= 16 ? cw / 16 * 16 : 16);
-    if (chunk_frames > 0 && (chunk_frames + 15) / 16 * 16 < cw) cw = (chunk_frames + 15) / 16 * 16;
-    const long long span = (n_sel + 15) / 16 * 16;
-    if (cw > span) cw = span;
+    const long long cw = asb_cforce_chunk_width(n_cols, chunk_frames, n_sel);
     if ((rc = asb_cproj_invm(ctx, inv_massL, &w))) return rc;
     if ((rc = asb_alloc(ctx, &ctx->cf_ptr, p32.size()))) return rc;
     if ((rc = asb_alloc(ctx, &ctx->cf_idx, c32.size() + 1))) return rc;
@@ -567,12 +587,11 @@ extern "C" int asb_cforce_run(asb_ctx* ctx, int which, int64_t f0, int64_t f1, i
         ASB_HIP(ctx, hipMemcpyAsync(ctx->cf_idx, c32.data(), c32.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
         ASB_HIP(ctx, hipMemcpyAsync(ctx->cf_val, data, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     }
-    const unsigned gv = (unsigned)((n_rows + CF_VB - 1) / CF_VB);
     for (long long c0 = 0; c0 < n_sel; c0 += cw) {
         const int cn = (int)(c0 + cw < n_sel ? cw : n_sel - c0);
         asb_cproj_em_launch(ctx, w, (int)f0, (int)fj, (int)c0, cn, (int)cw, sigma_min, sigma_max, ctx->cf_scratch);
-        hipLaunchKernelGGL(k_st_apply, dim3(gv, (unsigned)((cn + 63) / 64)), dim3(64 * CP_WAVES), 0, ctx->stream, ctx->cf_ptr, ctx->cf_idx,
-                           ctx->cf_val, ctx->cf_scratch, (int)cw, (int)c0, cn, (long long)n_rows, accumulate ? 1 : 0, out_dev);
+        asb_st_apply_launch(ctx, ctx->cf_ptr, ctx->cf_idx, ctx->cf_val, ctx->cf_scratch, (int)cw, (int)c0, cn, (long long)n_rows, accumulate,
+                            out_dev);
     }
     ASB_CHECK_LAUNCH(ctx);
     ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the staging vectors die here; the caller owns out_dev

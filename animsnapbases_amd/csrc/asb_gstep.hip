@@ -18,25 +18,20 @@
 //                      A^-1; loads past N or past F' are zero-filled and never leave the buffers.  Epilogue as k_rforce_gemm:
 //                      LDS rows of 97 doubles (the operand buffers are dead by then and are reused), 96 contiguous doubles per
 //                      frame.  The contraction is never split: entry (f, m, d) is ONE accumulator summed over ascending n,
-//                      whatever tile it falls in, so repeats and frame sub-ranges give identical bits.  No atomics.
+//                      whatever tile it falls in, so repeats and frame sub-ranges give identical bits.  No atomics.  The
+//                      tile's loop and epilogue live in asb_gstep_tile.h, shared with k_pdsolve_gemm (asb_pdsolve.hip).
 //   asb_gstep_inertia  rhs[f, n, d] += diag[n] s_f[n, d], the inertia term M/h^2 s of the selected frames, from the world
 //                      positions of asb_cproj.hip (cp_pos: same reciprocals, training or held-out tensor).  Elementwise; a block
 //                      of GS_VB vertices x 64 frames reads the vertex-major tensor along the frames and stages through LDS to
-//                      write per frame its contiguous run, a read-modify-write of its own entries.
-#include "asb_common.h"
+//                      write per frame its contiguous run, a read-modify-write of its own entries.  k_gs_inertia<false>
+//                      stores the same values instead of adding them (asb_gs_inertia_launch, for asb_pdsolve_begin).
+#include "asb_gstep_tile.h"
 
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-
 #define GS_MAX_N 46000      // the limit of the dense geodesics: Np^2 doubles = 17 GB
-#define GS_TF 64            // frames per block of k_gstep_gemm (16 per wave)
-#define GS_TN 32            // vertices per block
-#define GS_KC 16            // values of n per LDS stage
-#define GS_LDR 49           // LDS row of the rhs stage: 48 doubles + 1 (the 16 frames of an MFMA operand fall into different banks)
-#define GS_LDB 48           // LDS row of the A^-1 stage: 32 doubles + 16 (the four k-rows of an operand fall into different bank halves)
 #define GS_VB 16            // vertices per block of k_gs_inertia
 
 // ---------------------------------------------------------------- set-up
@@ -143,93 +138,16 @@ extern "C" int asb_gstep_setup(asb_ctx* ctx, int64_t n, const int64_t* indptr, c
 }
 
 // ---------------------------------------------------------------- the product
-// grid (Np / GS_TN, frame tiles); rhs and out (F, n, 3) frame-major; Ainv (np x np), only its n x n block is read
+// grid (Np / GS_TN, frame tiles); rhs and out (F, n, 3) frame-major; Ainv (np x np), only its n x n block is read.  The tile's
+// loop and epilogue: asb_gstep_tile.h
 __global__ __launch_bounds__(256) void k_gstep_gemm(const double* __restrict__ rhs, const double* __restrict__ Ainv, int n, int np,
                                                     long long F, double* __restrict__ out) {
-    constexpr int RUN = GS_TN * 3, ROW = RUN + 1;
-    constexpr int R_STAGE = GS_TF * GS_LDR, B_STAGE = GS_KC * GS_LDB;
-    static_assert(2 * R_STAGE >= GS_TF * ROW, "the epilogue reuses the rhs buffers");
-    __shared__ double sm[2 * R_STAGE + 2 * B_STAGE];
-    double* Rs = sm;
-    double* Bs = sm + 2 * R_STAGE;
-    const int tid = threadIdx.x, lane = tid & 63, i = lane & 15, g = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    __shared__ double sm[GS_SM];
     const int m0 = (int)blockIdx.x * GS_TN;
     const long long t0 = (long long)blockIdx.y * GS_TF;
-    const long long row_len = 3LL * n;
-    // this thread's share of a stage: 12 doubles of rhs (frame fr[q], column cr[q] of the 48), 2 of A^-1 (row kb[q], column mb)
-    double rr[12], rb[2];
-    auto fetch = [&](int k0) {
-#pragma unroll
-        for (int q = 0; q < 12; ++q) {
-            const int e = tid + 256 * q, fl = e / 48, c = e % 48;
-            const long long f = t0 + fl, col = 3LL * k0 + c;
-            rr[q] = (f < F && col < row_len) ? rhs[f * row_len + col] : 0.0;
-        }
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int e = tid + 256 * q, k = k0 + e / GS_TN, m = m0 + e % GS_TN;
-            rb[q] = (k < n && m < n) ? Ainv[(long long)k * np + m] : 0.0;
-        }
-    };
-    auto stash = [&](int buf) {
-#pragma unroll
-        for (int q = 0; q < 12; ++q) {
-            const int e = tid + 256 * q;
-            Rs[buf * R_STAGE + (e / 48) * GS_LDR + e % 48] = rr[q];
-        }
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int e = tid + 256 * q;
-            Bs[buf * B_STAGE + (e / GS_TN) * GS_LDB + e % GS_TN] = rb[q];
-        }
-    };
     d4 acc[3][2];
-#pragma unroll
-    for (int d = 0; d < 3; ++d)
-#pragma unroll
-        for (int y = 0; y < 2; ++y) acc[d][y] = d4{0.0, 0.0, 0.0, 0.0};
-    fetch(0);
-    stash(0);
-    __syncthreads();
-    int cur = 0;
-    for (int k0 = 0; k0 < n; k0 += GS_KC) {
-        const bool more = k0 + GS_KC < n;
-        if (more) fetch(k0 + GS_KC);
-        const double* ra = Rs + cur * R_STAGE + (wave * 16 + i) * GS_LDR;
-        const double* bb = Bs + cur * B_STAGE + i;
-#pragma unroll
-        for (int ks = 0; ks < GS_KC / 4; ++ks) {
-            const int k = ks * 4 + g;
-            const double b0 = bb[k * GS_LDB], b1 = bb[k * GS_LDB + 16];
-#pragma unroll
-            for (int d = 0; d < 3; ++d) {
-                const double a = ra[k * 3 + d];
-                acc[d][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b0, acc[d][0], 0, 0, 0);
-                acc[d][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b1, acc[d][1], 0, 0, 0);
-            }
-        }
-        if (more) stash(cur ^ 1);
-        __syncthreads();
-        cur ^= 1;
-    }
-    // every wave is past its last read of the operand buffers (the barrier above): they become the output stage.
-    // accumulator q of lane (i, g): frame g + 4 q of the wave's 16, vertex i of the 16
-    double* stage = sm;
-#pragma unroll
-    for (int d = 0; d < 3; ++d)
-#pragma unroll
-        for (int y = 0; y < 2; ++y)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) stage[(wave * 16 + g + 4 * q) * ROW + (16 * y + i) * 3 + d] = acc[d][y][q];
-    __syncthreads();
-    const int nv = n - m0 < GS_TN ? n - m0 : GS_TN;
-    const int nf = F - t0 < GS_TF ? (int)(F - t0) : GS_TF;
-    const int run = nv * 3;
-    for (int e = tid; e < GS_TF * RUN; e += 256) {
-        const int fl = e / RUN, k = e % RUN;
-        if (fl < nf && k < run) out[(t0 + fl) * row_len + 3LL * m0 + k] = stage[fl * ROW + k];
-    }
+    gs_contract(rhs, Ainv, n, np, F, m0, t0, sm, acc);
+    gs_store_fm(acc, sm, n, F, m0, t0, out);
 }
 
 extern "C" int asb_gstep_run(asb_ctx* ctx, const double* rhs_dev, int64_t n_frames, double* out_dev) {
@@ -251,7 +169,8 @@ extern "C" int asb_gstep_run(asb_ctx* ctx, const double* rhs_dev, int64_t n_fram
 
 // ---------------------------------------------------------------- the inertia term
 // grid (vertex blocks, frame tiles); rhs (n_sel, n_verts, 3).  mode 0: s = x_f + acc; 1: s = 2 x_f - x_{f-1} + acc, f - 1 the
-// tensor's previous frame (x_0 at frame 0)
+// tensor's previous frame (x_0 at frame 0).  ADD: rhs += diag s; otherwise rhs = diag s, the very value the sum adds
+template <bool ADD>
 __global__ __launch_bounds__(256) void k_gs_inertia(CpWorld w, int f0, int fj, int n_sel, long long n_verts, const double* __restrict__ diag,
                                                     int mode, double acc0, double acc1, double acc2, double* __restrict__ rhs) {
     constexpr int RUN = GS_VB * 3, ROW = RUN + 1;
@@ -284,8 +203,21 @@ __global__ __launch_bounds__(256) void k_gs_inertia(CpWorld w, int f0, int fj, i
     const int run = nv * 3;
     for (int e = threadIdx.x; e < 64 * RUN; e += 256) {
         const int fl = e / RUN, k = e % RUN;
-        if (fl < nf && k < run) rhs[((long long)(t0 + fl) * n_verts + v_base) * 3 + k] += stage[fl * ROW + k];
+        if (fl < nf && k < run) {
+            double* o = rhs + ((long long)(t0 + fl) * n_verts + v_base) * 3 + k;
+            if (ADD) *o += stage[fl * ROW + k];
+            else *o = stage[fl * ROW + k];
+        }
     }
+}
+
+void asb_gs_inertia_launch(asb_ctx* ctx, const CpWorld& w, int f0, int fj, int n_sel, long long n, const double* diag_dev, int mode,
+                           const double* acc3, bool add, double* out) {
+    const dim3 grid((unsigned)((n + GS_VB - 1) / GS_VB), (unsigned)((n_sel + 63) / 64));
+    if (add)
+        hipLaunchKernelGGL(k_gs_inertia<true>, grid, dim3(256), 0, ctx->stream, w, f0, fj, n_sel, n, diag_dev, mode, acc3[0], acc3[1], acc3[2], out);
+    else
+        hipLaunchKernelGGL(k_gs_inertia<false>, grid, dim3(256), 0, ctx->stream, w, f0, fj, n_sel, n, diag_dev, mode, acc3[0], acc3[1], acc3[2], out);
 }
 
 extern "C" int asb_gstep_inertia(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean, double psf,
@@ -304,9 +236,7 @@ extern "C" int asb_gstep_inertia(asb_ctx* ctx, int which, int64_t f0, int64_t f1
     if ((rc = asb_cproj_invm(ctx, inv_massL, &w))) return rc;
     if ((rc = asb_alloc(ctx, &ctx->gs_diag, (size_t)n))) return rc;
     ASB_HIP(ctx, hipMemcpyAsync(ctx->gs_diag, diag, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    const dim3 grid((unsigned)((n + GS_VB - 1) / GS_VB), (unsigned)((n_sel + 63) / 64));
-    hipLaunchKernelGGL(k_gs_inertia, grid, dim3(256), 0, ctx->stream, w, (int)f0, (int)fj, (int)n_sel, (long long)n, ctx->gs_diag, mode, acc3[0],
-                       acc3[1], acc3[2], rhs_dev);
+    asb_gs_inertia_launch(ctx, w, (int)f0, (int)fj, (int)n_sel, (long long)n, ctx->gs_diag, mode, acc3, true, rhs_dev);
     ASB_CHECK_LAUNCH(ctx);
     ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the host arrays may go; the caller owns rhs_dev
     return ASB_OK;

@@ -1,0 +1,347 @@
+// The local/global iterations of the reference's projective-dynamics solver (projective_dynamics/Simulators.py:494-526) for a
+// batch of frames of the resident animation: q_0 given, q_{k+1} = A^-1 (sum_i S_i^T p_i(q_k) + M/h^2 s), s fixed.  Every
+// selected frame is its own solve.  Collisions, positional constraints and velocities carried between frames are not modelled.
+//
+// State of a solve over the n_sel frames range(f0, f1, fj), owned by the context and reused by the next solve:
+//   ms  (n_sel, N, 3) frame-major   the inertia term diag[n] s_f[n, d], formed once by k_gs_inertia<false> (asb_gstep.hip): the
+//                                   very values asb_gstep_inertia adds
+//   Q   (3 N, ld) vertex-major      the iterate, row 3 v + d, frames contiguous, ld = n_sel rounded up to 64.  The layout of
+//                                   CpWorld: with T = Q, no mean, no masses and inv_psf = 1, cp_pos returns the stored value
+//                                   and the per-element routines of asb_cproj.hip run on it unchanged.  The padding columns
+//                                   [n_sel, ld) are zeroed once and never read as frames nor written.
+//   b   (n_sel, N, 3) frame-major   the right-hand side of the iteration in flight
+//   slots                           per kind the device tables of an asb_cproj_setup and the CSR of its S^T, registered once:
+//                                   no host-to-device copy happens inside the iteration loop
+//
+// One iteration, in stream order:
+//   per slot, in order, per chunk of frames   k_cproj_em on the iterate's world, then k_st_apply (the first slot overwrites b,
+//                                   the later ones accumulate); the reduced slot: k_cproj_em of the sampled elements,
+//                                   k_rforce_coef, k_rforce_gemm with the context's operator and solver
+//   k_pd_add                        b += ms, elementwise -- the order of asb_gstep_inertia
+//   k_pdsolve_gemm                  the tile of k_gstep_gemm (asb_gstep_tile.h: same loop, same accumulators) with a
+//                                   VERTEX-major epilogue: the 64 frames x 96 rows of a block go through LDS rows of PD_LDQ =
+//                                   65 doubles, row 3 m + d holding its 64 frames.  Writes: lane (i, g) stores frame g + 4 q
+//                                   of vertex i, ds_write_b64 serves 16 lanes (one g) at a time and their addresses differ by
+//                                   3 * 65 * i doubles -- odd, so the 16 land in 16 different bank pairs.  Reads: 64 lanes read 64
+//                                   consecutive doubles of a row and store them as one 512-byte run of Q.  On request the same
+//                                   accumulators are staged a second time, frame-major (gs_store_fm), into the caller's tensor.
+//                                   With the history on, the block first reads the entries of Q it is about to overwrite:
+//                                   wave w sums rows w, w + 4, .. of its 64 frames, the four partials are added in wave order,
+//                                   and k_pd_hist adds the vertex tiles' records of a frame in ascending order.
+// Nothing is split and nothing is atomic: repeats, frame sub-ranges and any chunk width give identical bits.
+#include "asb_gstep_tile.h"
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#define PD_LDQ 65           // LDS row of the vertex-major epilogue: 64 frames + 1
+#define PD_MAX_SLOTS 8
+
+struct PdSlot {
+    int kind = -1, reduced = 0;
+    long long n_elem = 0, n_cols = 0;
+    int *idx = nullptr, *sptr = nullptr, *sidx = nullptr;       // the tables of asb_cproj_setup, taken over from the context
+    double* table = nullptr;
+    int *st_ptr = nullptr, *st_idx = nullptr;                   // the CSR of S^T (not for the reduced kind)
+    double* st_val = nullptr;
+    double smin = 1.0, smax = 1.0;
+};
+
+struct asb_pds {
+    bool begun = false;
+    long long n = 0, n_sel = 0, ld = 0;
+    double *ms = nullptr, *Q = nullptr, *b = nullptr;
+    double *part = nullptr, *hist = nullptr;      // (vertex tiles, n_sel, 2) records of one iteration; (iterations, n_sel, 2)
+    int n_slots = 0;
+    PdSlot slot[PD_MAX_SLOTS];
+};
+
+void asb_pdsolve_free(asb_ctx* ctx) {             // (the buffers went with the context's registered allocations)
+    delete ctx->pds;
+    ctx->pds = nullptr;
+}
+
+// ---------------------------------------------------------------- the start state
+// grid (rows / 4, frame tiles): wave = one row 3 v + d x 64 frames.  start 0: the explicit state s_f (mode as k_gs_inertia),
+// 1: the frame x_f
+__global__ __launch_bounds__(256) void k_pd_init(CpWorld w, int f0, int fj, int n_sel, long long n_verts, int start, int mode, double acc0,
+                                                 double acc1, double acc2, double* __restrict__ Q, long long ld) {
+    const int lane = threadIdx.x & 63;
+    const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int c = (int)blockIdx.y * 64 + lane;
+    if (r >= 3 * n_verts || c >= n_sel) return;
+    const int v = (int)(r / 3), d = (int)(r % 3);
+    const long long f = (long long)f0 + (long long)c * fj;
+    const double acc[3] = {acc0, acc1, acc2};
+    double x[3], xp[3];
+    cp_pos(w, f, v, x);
+    if (start == 0) {
+        if (mode == 1) {
+            cp_pos(w, f > 0 ? f - 1 : 0, v, xp);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) x[k] = 2.0 * x[k] - xp[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) x[k] = x[k] + acc[k];
+    }
+    Q[r * ld + c] = d == 0 ? x[0] : (d == 1 ? x[1] : x[2]);
+}
+
+// grid (row tiles of 64, frame tiles of 64): in (n_sel, rows) frame-major -> Q (rows, ld), a copy
+__global__ __launch_bounds__(256) void k_pd_transpose(const double* __restrict__ in, int n_sel, long long rows, double* __restrict__ Q,
+                                                      long long ld) {
+    __shared__ double tile[64 * 65];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long long r0 = (long long)blockIdx.x * 64;
+    const int t0 = (int)blockIdx.y * 64;
+    for (int fl = wv; fl < 64; fl += 4)
+        if (t0 + fl < n_sel && r0 + lane < rows) tile[fl * 65 + lane] = in[(long long)(t0 + fl) * rows + r0 + lane];
+    __syncthreads();
+    for (int rl = wv; rl < 64; rl += 4)
+        if (r0 + rl < rows && t0 + lane < n_sel) Q[(r0 + rl) * ld + t0 + lane] = tile[lane * 65 + rl];
+}
+
+// b[i] += ms[i]
+__global__ __launch_bounds__(256) void k_pd_add(double* __restrict__ b, const double* __restrict__ ms, long long len) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < len; i += (long long)gridDim.x * 256) b[i] += ms[i];
+}
+
+// ---------------------------------------------------------------- the product, written into the iterate
+// grid (Np / GS_TN, frame tiles); b (F, n, 3) frame-major; Q (3 n, ld); out (F, n, 3) with FM; part (gridDim.x, F, 2) with HIST
+template <bool FM, bool HIST>
+__global__ __launch_bounds__(256) void k_pdsolve_gemm(const double* __restrict__ b, const double* __restrict__ Ainv, int n, int np,
+                                                      long long F, double* __restrict__ Q, long long ld, double* __restrict__ out,
+                                                      double* __restrict__ part) {
+    constexpr int ROWS = GS_TN * 3;
+    static_assert(ROWS * PD_LDQ + 4 * 64 * 2 <= GS_SM, "the vertex-major stage and the history partials reuse the operand buffers");
+    __shared__ double sm[GS_SM];
+    const int m0 = (int)blockIdx.x * GS_TN;
+    const long long t0 = (long long)blockIdx.y * GS_TF;
+    d4 acc[3][2];
+    gs_contract(b, Ainv, n, np, F, m0, t0, sm, acc);
+    const int tid = threadIdx.x, lane = tid & 63, i = lane & 15, g = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+#pragma unroll
+        for (int y = 0; y < 2; ++y)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) sm[((16 * y + i) * 3 + d) * PD_LDQ + wave * 16 + g + 4 * q] = acc[d][y][q];
+    __syncthreads();
+    const int nv = n - m0 < GS_TN ? n - m0 : GS_TN;
+    const int nf = F - t0 < GS_TF ? (int)(F - t0) : GS_TF;
+    const int run = nv * 3;
+    double* qt = Q + 3LL * m0 * ld + t0;          // the tile's corner: row r, frame fl at qt[r * ld + fl]
+    if (HIST) {
+        double d2 = 0.0, n2 = 0.0;
+        if (lane < nf)
+            for (int r = wave; r < run; r += 4) {
+                const double nw = sm[r * PD_LDQ + lane], e = nw - qt[(long long)r * ld + lane];
+                d2 = fma(e, e, d2);
+                n2 = fma(nw, nw, n2);
+            }
+        double* hp = sm + ROWS * PD_LDQ;
+        hp[(wave * 64 + lane) * 2] = d2;
+        hp[(wave * 64 + lane) * 2 + 1] = n2;
+        __syncthreads();                          // every read of the old entries is done before the first write below
+        if (wave == 0 && lane < nf) {
+            double* o = part + ((long long)blockIdx.x * F + t0 + lane) * 2;
+            o[0] = ((hp[lane * 2] + hp[(64 + lane) * 2]) + hp[(128 + lane) * 2]) + hp[(192 + lane) * 2];
+            o[1] = ((hp[lane * 2 + 1] + hp[(64 + lane) * 2 + 1]) + hp[(128 + lane) * 2 + 1]) + hp[(192 + lane) * 2 + 1];
+        }
+    }
+    for (int e = tid; e < ROWS * 64; e += 256) {
+        const int r = e >> 6, fl = e & 63;
+        if (r < run && fl < nf) qt[(long long)r * ld + fl] = sm[r * PD_LDQ + fl];
+    }
+    if (FM) {
+        __syncthreads();                          // the stage is read out: it is staged again, frame-major
+        gs_store_fm(acc, sm, n, F, m0, t0, out);
+    }
+}
+
+// one thread per frame: rec[f] = the vertex tiles' records of frame f added in ascending tile order
+__global__ __launch_bounds__(256) void k_pd_hist(const double* __restrict__ part, int tiles, long long F, double* __restrict__ rec) {
+    const long long f = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (f >= F) return;
+    double d2 = 0.0, n2 = 0.0;
+    for (int t = 0; t < tiles; ++t) {
+        d2 += part[((long long)t * F + f) * 2];
+        n2 += part[((long long)t * F + f) * 2 + 1];
+    }
+    rec[f * 2] = d2;
+    rec[f * 2 + 1] = n2;
+}
+
+// ---------------------------------------------------------------- entry points
+// a buffer of the context and one of a slot change places, with their registered capacities
+template <typename T>
+static void pd_swap(asb_ctx* ctx, T** a, T** b) {
+    auto cap = [&](void* key) {
+        auto it = ctx->alloc_bytes.find(key);
+        const size_t c = it == ctx->alloc_bytes.end() ? 0 : it->second;
+        if (it != ctx->alloc_bytes.end()) ctx->alloc_bytes.erase(it);
+        return c;
+    };
+    const size_t ca = cap((void*)a), cb = cap((void*)b);
+    std::swap(*a, *b);
+    if (*a) ctx->alloc_bytes[(void*)a] = cb;
+    if (*b) ctx->alloc_bytes[(void*)b] = ca;
+}
+
+extern "C" int asb_pdsolve_begin(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean,
+                                 double psf, const double* diag, int mode, const double* acc3, int start, const double* start_dev) {
+    if (!ctx || !diag || !acc3) return ASB_ERR_ARG;
+    if (ctx->pds) ctx->pds->begun = false, ctx->pds->n_slots = 0;
+    if (fj >= 1 && f1 > f0 && ((f1 - f0 + fj - 1) / fj + 63) / 64 > 65535)        // on the count alone, before any tensor is looked at
+        ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_pdsolve_begin: %lld frames in one solve (at most %d)", (long long)((f1 - f0 + fj - 1) / fj), 65535 * 64);
+    if (mode != 0 && mode != 1) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_begin: mode %d (0: s = x, 1: s = 2 x - x_prev)", mode);
+    if (start < 0 || start > 2 || (start == 2 && !start_dev))
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_begin: start %d (0: the explicit state, 1: the frame, 2: a device tensor)", start);
+    CpWorld w;
+    int64_t n_sel;
+    int rc;
+    if ((rc = asb_world_frames(ctx, "asb_pdsolve_begin", which, f0, f1, fj, add_mean, psf, &w, &n_sel))) return rc;
+    const int64_t n = ctx->n_loc;
+    if (ctx->gs_n < 1 || !ctx->gs_Ainv || ctx->gs_n != n)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_begin: no inverse for the %lld vertices of the tensor on the device (asb_gstep_setup)", (long long)n);
+    for (int64_t v = 0; v < n; ++v)
+        if (!std::isfinite(diag[v])) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_begin: diag[%lld] is not finite", (long long)v);
+    if (!std::isfinite(acc3[0]) || !std::isfinite(acc3[1]) || !std::isfinite(acc3[2])) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_begin: acc is not finite");
+    if ((rc = asb_cproj_invm(ctx, inv_massL, &w))) return rc;
+    if (!ctx->pds) ctx->pds = new asb_pds();
+    asb_pds* s = ctx->pds;
+    const long long ld = (n_sel + 63) / 64 * 64;
+    const size_t len = (size_t)n_sel * n * 3;
+    if ((rc = asb_alloc(ctx, &ctx->gs_diag, (size_t)n))) return rc;
+    if ((rc = asb_alloc(ctx, &s->ms, len))) return rc;
+    if ((rc = asb_alloc(ctx, &s->b, len))) return rc;
+    if ((rc = asb_alloc(ctx, &s->Q, (size_t)3 * n * ld))) return rc;
+    ASB_HIP(ctx, hipMemcpyAsync(ctx->gs_diag, diag, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    ASB_HIP(ctx, hipMemsetAsync(s->Q, 0, (size_t)3 * n * ld * sizeof(double), ctx->stream));
+    asb_gs_inertia_launch(ctx, w, (int)f0, (int)fj, (int)n_sel, (long long)n, ctx->gs_diag, mode, acc3, false, s->ms);
+    const unsigned gt = (unsigned)((n_sel + 63) / 64);
+    if (start == 2)
+        hipLaunchKernelGGL(k_pd_transpose, dim3((unsigned)((3 * n + 63) / 64), gt), dim3(256), 0, ctx->stream, start_dev, (int)n_sel,
+                           (long long)(3 * n), s->Q, ld);
+    else
+        hipLaunchKernelGGL(k_pd_init, dim3((unsigned)((3 * n + 3) / 4), gt), dim3(256), 0, ctx->stream, w, (int)f0, (int)fj, (int)n_sel,
+                           (long long)n, start, mode, acc3[0], acc3[1], acc3[2], s->Q, ld);
+    ASB_CHECK_LAUNCH(ctx);
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the host arrays and the caller's start tensor may go
+    s->n = n, s->n_sel = n_sel, s->ld = ld, s->begun = true;
+    return ASB_OK;
+}
+
+extern "C" int asb_pdsolve_slot(asb_ctx* ctx, double sigma_min, double sigma_max, int reduced, int64_t n_rows, const int64_t* indptr,
+                                const int64_t* indices, const double* data) {
+    if (!ctx) return ASB_ERR_ARG;
+    asb_pds* s = ctx->pds;
+    if (!s || !s->begun) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_slot: no solve begun (asb_pdsolve_begin)");
+    if (s->n_slots >= PD_MAX_SLOTS) ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_pdsolve_slot: more than %d kinds", PD_MAX_SLOTS);
+    if (ctx->cp_kind < 0 || ctx->cp_verts != s->n || ctx->n_loc != s->n)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_slot: no element set-up for the resident tensor (asb_cproj_setup)");
+    if (!(sigma_min <= sigma_max)) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_slot: sigma_min %g > sigma_max %g", sigma_min, sigma_max);
+    const long long n_cols = asb_cproj_rows(ctx->cp_kind, ctx->cp_n);
+    PdSlot& p = s->slot[s->n_slots];
+    int rc;
+    if (reduced) {
+        for (int k = 0; k < s->n_slots; ++k)
+            if (s->slot[k].reduced)
+                ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_slot: a second reduced kind (the context holds one operator and one solver)");
+        if (ctx->rf_mp < 1 || ctx->rf_r < 1 || ctx->rf_n != s->n)
+            ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_slot: no operator or solver for the tensor on the device (asb_rforce_operator, asb_rforce_solver)");
+        if (ctx->rf_pt_max >= n_cols)
+            ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_slot: an interpolation point names row %lld, the sampled elements have %lld", (long long)ctx->rf_pt_max, n_cols);
+    } else {
+        if (!indptr) return ASB_ERR_ARG;
+        if (n_rows != s->n) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_slot: S^T has %lld rows, the tensor %lld vertices", (long long)n_rows, s->n);
+        std::vector<int> p32, c32;
+        if ((rc = asb_csr_check32(ctx, "asb_pdsolve_slot", n_rows, indptr, indices, data, n_cols, p32, c32))) return rc;
+        const int64_t nnz = indptr[n_rows];
+        ASB_HIP(ctx, hipSetDevice(ctx->dev));
+        if ((rc = asb_alloc(ctx, &p.st_ptr, p32.size()))) return rc;
+        if ((rc = asb_alloc(ctx, &p.st_idx, c32.size() + 1))) return rc;
+        if ((rc = asb_alloc(ctx, &p.st_val, c32.size() + 1))) return rc;
+        ASB_HIP(ctx, hipMemcpyAsync(p.st_ptr, p32.data(), p32.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        if (nnz > 0) {
+            ASB_HIP(ctx, hipMemcpyAsync(p.st_idx, c32.data(), c32.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+            ASB_HIP(ctx, hipMemcpyAsync(p.st_val, data, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        }
+        ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));      // (the staging vectors die here)
+    }
+    // the tables of asb_cproj_setup pass to the slot (the slot's previous buffers to the context, which has no set-up now)
+    pd_swap(ctx, &ctx->cp_idx, &p.idx);
+    pd_swap(ctx, &ctx->cp_table, &p.table);
+    pd_swap(ctx, &ctx->cp_sptr, &p.sptr);
+    pd_swap(ctx, &ctx->cp_sidx, &p.sidx);
+    p.kind = ctx->cp_kind, p.n_elem = ctx->cp_n, p.n_cols = n_cols, p.reduced = reduced ? 1 : 0;
+    p.smin = sigma_min, p.smax = sigma_max;
+    ctx->cp_kind = -1;
+    ++s->n_slots;
+    return ASB_OK;
+}
+
+extern "C" int asb_pdsolve_iterate(asb_ctx* ctx, int64_t n_iter, int64_t chunk_frames, double* out_dev, double* hist_out) {
+    if (!ctx) return ASB_ERR_ARG;
+    asb_pds* s = ctx->pds;
+    if (!s || !s->begun || s->n_slots < 1) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_iterate: no solve begun or no kind registered (asb_pdsolve_begin, asb_pdsolve_slot)");
+    if (n_iter < 1 || n_iter > (1 << 20)) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_iterate: %lld iterations", (long long)n_iter);
+    if (chunk_frames < 0) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_iterate: chunk_frames %lld", (long long)chunk_frames);
+    if (ctx->gs_n != s->n || !ctx->gs_Ainv || ctx->n_loc != s->n)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_iterate: the inverse or the tensor changed since asb_pdsolve_begin");
+    const long long n_sel = s->n_sel, n = s->n;
+    long long cw[PD_MAX_SLOTS];
+    size_t scratch = 0, coef = 0;
+    for (int k = 0; k < s->n_slots; ++k) {
+        const PdSlot& p = s->slot[k];
+        if (p.reduced) {
+            if (ctx->rf_mp < 1 || ctx->rf_r < 1 || ctx->rf_n != n || ctx->rf_pt_max >= p.n_cols)
+                ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_iterate: the operator or solver changed since asb_pdsolve_slot");
+            cw[k] = asb_rforce_chunk_width(ctx, p.n_cols, n_sel);
+            coef = (size_t)3 * (((size_t)ctx->rf_r + 3) / 4 * 4) * cw[k];
+        } else {
+            cw[k] = asb_cforce_chunk_width(p.n_cols, chunk_frames, n_sel);
+        }
+        scratch = std::max<size_t>(scratch, (size_t)3 * p.n_cols * cw[k]);
+    }
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    const int tiles = (int)(ctx->gs_Np / GS_TN);
+    int rc;
+    if ((rc = asb_alloc(ctx, &ctx->cf_scratch, scratch))) return rc;
+    if (coef && (rc = asb_alloc(ctx, &ctx->rf_coef, coef))) return rc;
+    if (hist_out) {
+        if ((rc = asb_alloc(ctx, &s->part, (size_t)tiles * n_sel * 2))) return rc;
+        if ((rc = asb_alloc(ctx, &s->hist, (size_t)n_iter * n_sel * 2))) return rc;
+    }
+    const CpWorld wq = {s->Q, s->ld, nullptr, nullptr, 1.0};
+    const long long len = n_sel * n * 3;
+    const unsigned g_add = (unsigned)std::min<long long>((len + 255) / 256, 1 << 20);
+    const dim3 grid((unsigned)tiles, (unsigned)((n_sel + GS_TF - 1) / GS_TF));
+    for (int64_t it = 0; it < n_iter; ++it) {
+        for (int k = 0; k < s->n_slots; ++k) {
+            const PdSlot& p = s->slot[k];
+            const CpTables t = {p.kind, p.n_elem, p.idx, p.sptr, p.sidx, p.table};
+            for (long long c0 = 0; c0 < n_sel; c0 += cw[k]) {
+                const int cn = (int)(c0 + cw[k] < n_sel ? cw[k] : n_sel - c0);
+                asb_cproj_em_launch_t(ctx, t, wq, 0, 1, (int)c0, cn, (int)cw[k], p.smin, p.smax, ctx->cf_scratch);
+                if (p.reduced) asb_rforce_chunk_launch(ctx, ctx->cf_scratch, (int)cw[k], (int)c0, cn, k > 0, s->b);
+                else asb_st_apply_launch(ctx, p.st_ptr, p.st_idx, p.st_val, ctx->cf_scratch, (int)cw[k], (int)c0, cn, n, k > 0, s->b);
+            }
+        }
+        hipLaunchKernelGGL(k_pd_add, dim3(g_add), dim3(256), 0, ctx->stream, s->b, s->ms, len);
+        const bool fm = out_dev && it == n_iter - 1;
+        auto kern = fm ? (hist_out ? k_pdsolve_gemm<true, true> : k_pdsolve_gemm<true, false>)
+                       : (hist_out ? k_pdsolve_gemm<false, true> : k_pdsolve_gemm<false, false>);
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, ctx->stream, s->b, ctx->gs_Ainv, (int)n, (int)ctx->gs_Np, n_sel, s->Q, s->ld, out_dev, s->part);
+        if (hist_out)
+            hipLaunchKernelGGL(k_pd_hist, dim3((unsigned)((n_sel + 255) / 256)), dim3(256), 0, ctx->stream, s->part, tiles, n_sel,
+                               s->hist + (size_t)it * n_sel * 2);
+    }
+    ASB_CHECK_LAUNCH(ctx);
+    if (hist_out)
+        ASB_HIP(ctx, hipMemcpyAsync(hist_out, s->hist, (size_t)n_iter * n_sel * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the caller owns out_dev and may read it on any stream
+    return ASB_OK;
+}

@@ -184,6 +184,24 @@ extern "C" int asb_rforce_solver(asb_ctx* ctx, int64_t r, int64_t npt, const dou
     return ASB_OK;
 }
 
+// whole frame tiles of the product, the scratch (projections + coefficients) within RF_SCRATCH_BYTES
+long long asb_rforce_chunk_width(asb_ctx* ctx, long long n_cols, long long n_sel) {
+    const int rpp = ((int)ctx->rf_r + 3) / 4 * 4;
+    long long cw = (long long)(RF_SCRATCH_BYTES / (24ull * (unsigned long long)(n_cols + rpp)));
+    cw = cw >= RF_TF ? cw / RF_TF * RF_TF : RF_TF;
+    const long long span = (n_sel + RF_TF - 1) / RF_TF * RF_TF;
+    return cw > span ? span : cw;
+}
+
+void asb_rforce_chunk_launch(asb_ctx* ctx, const double* S, int cw, int c0, int cn, int accumulate, double* out) {
+    const int r = (int)ctx->rf_r, rpp = (r + 3) / 4 * 4, npt = (int)ctx->rf_npt;
+    hipLaunchKernelGGL(k_rforce_coef, dim3((unsigned)(cw / 64), (unsigned)rpp, 3), dim3(64), 0, ctx->stream, ctx->rf_H, ctx->rf_pt, r, npt, rpp,
+                       S, cw, cn, ctx->rf_coef);
+    hipLaunchKernelGGL(k_rforce_gemm, dim3((unsigned)(ctx->rf_Np / RF_TN), (unsigned)((cn + RF_TF - 1) / RF_TF)), dim3(256), 0, ctx->stream,
+                       ctx->rf_M, (long long)ctx->rf_Np, (int)ctx->rf_mpp, ctx->rf_coef, cw, rpp, c0, cn, (long long)ctx->rf_n, accumulate ? 1 : 0,
+                       out);
+}
+
 extern "C" int asb_rforce_run(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean, double psf,
                               double sigma_min, double sigma_max, int accumulate, double* out_dev) {
     if (!ctx || !out_dev) return ASB_ERR_ARG;
@@ -194,27 +212,18 @@ extern "C" int asb_rforce_run(asb_ctx* ctx, int which, int64_t f0, int64_t f1, i
     if (ctx->rf_mp < 1 || ctx->rf_r < 1) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_rforce_run: no operator or solver on the device (asb_rforce_operator, asb_rforce_solver)");
     if (ctx->rf_n != ctx->n_loc)
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_rforce_run: the operator has %lld rows, the tensor %lld vertices", (long long)ctx->rf_n, (long long)ctx->n_loc);
-    static const int PK[5] = {1, 2, 3, 3, 1};
-    const long long n_cols = (long long)ctx->cp_n * PK[ctx->cp_kind];
+    const long long n_cols = asb_cproj_rows(ctx->cp_kind, ctx->cp_n);
     if (ctx->rf_pt_max >= n_cols)
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_rforce_run: an interpolation point names row %lld, the sampled elements have %lld", (long long)ctx->rf_pt_max, n_cols);
-    const int r = (int)ctx->rf_r, rpp = (r + 3) / 4 * 4, npt = (int)ctx->rf_npt;
-    // ---- chunk width: whole frame tiles of the product, the scratch within RF_SCRATCH_BYTES
-    long long cw = (long long)(RF_SCRATCH_BYTES / (24ull * (unsigned long long)(n_cols + rpp)));
-    cw = cw >= RF_TF ? cw / RF_TF * RF_TF : RF_TF;
-    const long long span = (n_sel + RF_TF - 1) / RF_TF * RF_TF;
-    if (cw > span) cw = span;
+    const int rpp = ((int)ctx->rf_r + 3) / 4 * 4;
+    const long long cw = asb_rforce_chunk_width(ctx, n_cols, n_sel);
     if ((rc = asb_cproj_invm(ctx, inv_massL, &w))) return rc;
     if ((rc = asb_alloc(ctx, &ctx->cf_scratch, (size_t)3 * n_cols * cw))) return rc;
     if ((rc = asb_alloc(ctx, &ctx->rf_coef, (size_t)3 * rpp * cw))) return rc;
-    const unsigned gn = (unsigned)(ctx->rf_Np / RF_TN);
     for (long long c0 = 0; c0 < n_sel; c0 += cw) {
         const int cn = (int)(c0 + cw < n_sel ? cw : n_sel - c0);
         asb_cproj_em_launch(ctx, w, (int)f0, (int)fj, (int)c0, cn, (int)cw, sigma_min, sigma_max, ctx->cf_scratch);
-        hipLaunchKernelGGL(k_rforce_coef, dim3((unsigned)(cw / 64), (unsigned)rpp, 3), dim3(64), 0, ctx->stream, ctx->rf_H, ctx->rf_pt, r, npt,
-                           rpp, ctx->cf_scratch, (int)cw, cn, ctx->rf_coef);
-        hipLaunchKernelGGL(k_rforce_gemm, dim3(gn, (unsigned)((cn + RF_TF - 1) / RF_TF)), dim3(256), 0, ctx->stream, ctx->rf_M, (long long)ctx->rf_Np,
-                           (int)ctx->rf_mpp, ctx->rf_coef, (int)cw, rpp, (int)c0, cn, (long long)ctx->rf_n, accumulate ? 1 : 0, out_dev);
+        asb_rforce_chunk_launch(ctx, ctx->cf_scratch, (int)cw, (int)c0, cn, accumulate, out_dev);
     }
     ASB_CHECK_LAUNCH(ctx);
     ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the caller owns out_dev and may read it on any stream

@@ -617,6 +617,44 @@ class HipEngine(object):
         self._ck(self.lib.asb_test_gstep_inverse(self.h, ptr(out), int(n)))
         return out
 
+    # ------------------------------------------------------------------ solver iterations of projective dynamics
+    def pdsolve_begin(self, which, f0, f1, fj, inv_massL, add_mean, psf, diag, mode, acc, start, start_dev_ptr=None):
+        """Begins a solve over the frames range(f0, f1, fj) after ``gstep_setup``: the inertia term diag * s (``mode``, ``acc`` as
+        ``gstep_inertia``) and the iterate, started at s (``start`` 0), at the frame (1) or at the caller's device buffer of
+        (F', N, 3) float64 (2)."""
+        if inv_massL is not None:
+            inv_massL = np.ascontiguousarray(inv_massL, dtype=np.float64)
+            assert inv_massL.shape == (self.N_glob,)
+        diag = np.ascontiguousarray(diag, dtype=np.float64)
+        acc = np.ascontiguousarray(acc, dtype=np.float64)
+        assert diag.shape == (self.N_glob,) and acc.shape == (3,)
+        self._pd_frames = None
+        self._ck(self.lib.asb_pdsolve_begin(self.h, int(which), int(f0), int(f1), int(fj), ptr(inv_massL), int(bool(add_mean)),
+                                            float(psf), ptr(diag), int(mode), ptr(acc), int(start),
+                                            ctypes.c_void_p(int(start_dev_ptr)) if start_dev_ptr else None))
+        self._pd_frames = len(range(int(f0), int(f1), int(fj)))
+
+    def pdsolve_slot(self, sigma_min, sigma_max, St=None):
+        """The kind of the last ``cproj_setup`` becomes the next term of the solve in progress, with ``St`` (scipy CSR (N, rows),
+        sorted indices); ``St`` None: the reduced term of the sampled elements with the engine's operator and solver."""
+        if St is None:
+            self._ck(self.lib.asb_pdsolve_slot(self.h, float(sigma_min), float(sigma_max), 1, 0, None, None, None))
+            return
+        indptr = np.ascontiguousarray(St.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(St.indices, dtype=np.int64)
+        data = np.ascontiguousarray(St.data, dtype=np.float64)
+        self._ck(self.lib.asb_pdsolve_slot(self.h, float(sigma_min), float(sigma_max), 0, int(St.shape[0]), ptr(indptr), ptr(indices),
+                                           ptr(data)))
+
+    def pdsolve_iterate(self, n_iter, chunk_frames=0, out_dev_ptr=None, history=False):
+        """``n_iter`` iterations of the solve in progress; the last iterate into the caller's device buffer of (F', N, 3) float64
+        if given.  ``history``: returns the (n_iter, F', 2) array [|q_new - q_old|^2, |q_new|^2], else None."""
+        frames = getattr(self, "_pd_frames", None)
+        hist = np.empty((max(int(n_iter), 0), frames, 2)) if history and frames is not None else None
+        self._ck(self.lib.asb_pdsolve_iterate(self.h, int(n_iter), int(chunk_frames),
+                                              ctypes.c_void_p(int(out_dev_ptr)) if out_dev_ptr else None, ptr(hist)))
+        return hist
+
     # ------------------------------------------------------------------ SPLOCS
     def splocs_begin(self):
         self._ck(self.lib.asb_splocs_begin(self.h))

@@ -433,7 +433,8 @@ class posSnapshots:
         x_0), the velocity the reference carries from step to step (:531).  ``gravity``: the acceleration g.
 
         Returns ``(tensor, F')``: a ``torch.float64`` device tensor (F', N, 3) in world space, owned by the caller.  Further
-        iterations are the caller's loop: adopt the result with ``from_device`` and step again.  One rank only."""
+        iterations are ``solve_frames``: they keep s_f fixed while q moves, which re-adopting the result with ``from_device``
+        and stepping again would not.  One rank only."""
         self._gstep_one_rank("global_step")
         mode, acc = self._gstep_explicit(dt, velocity, gravity)
         m = self._gstep_masses(masses)
@@ -482,6 +483,164 @@ class posSnapshots:
         self.assembly_ST = {kind: St}
         self.bending_indices = setup.bending_indices
         return out
+
+    # ------------------------------------------------------------------ extras: the solver's iterations
+    _SOLVE_SCOPE = """Out of scope, as for ``global_step``: collision handling (``resolve_collision`` and the self-collision passes),
+        positional constraints, velocities carried from one solved frame into the next (every selected frame is an independent
+        solve from the animation's own x_f, x_{f-1}), the hyper-reduced operator A^-1 S^T V (a reduced iteration still pays the
+        N^2 product) and several ranks."""
+
+    def _solve_args(self, who, dt, velocity, gravity, num_iterations, start, masses):
+        """The checks of the solve's own arguments, before anything touches the device: (mode, acc, masses, K)."""
+        self._gstep_one_rank(who)
+        mode, acc = self._gstep_explicit(dt, velocity, gravity)
+        try:
+            K = int(num_iterations)
+        except (TypeError, ValueError):
+            K = 0
+        if K != num_iterations or K < 1:
+            raise ValueError("%s: num_iterations %r: a positive number of iterations" % (who, num_iterations))
+        if isinstance(start, str):
+            if start not in ("explicit", "frame"):
+                raise ValueError("%s: start must be 'explicit', 'frame' or a torch.float64 device tensor, not %r" % (who, start))
+        else:
+            import torch
+            if not isinstance(start, torch.Tensor) or start.dtype != torch.float64 or not start.is_cuda:
+                raise ValueError("%s: start must be 'explicit', 'frame' or a torch.float64 device tensor" % who)
+        return mode, acc, self._gstep_masses(masses), K
+
+    def _solve_plan(self, who, kinds, animation, frame_start, frame_end, frame_jump, chunk_frames):
+        """``_cforce_plan`` of the kinds with their reduction keys taken off, and for the one entry that carries a ``basis``
+        its index in the plan and r -> ``reduced.ReducedOperator``."""
+        keys = ("basis", "num_components", "reduction")
+        if not isinstance(kinds, (list, tuple)):
+            raise ValueError("%s: kinds must be a non-empty list of dicts, not %r" % (who, kinds))
+        plain, red = [], None
+        for i, spec in enumerate(kinds):
+            if isinstance(spec, dict) and any(k in spec for k in keys):
+                if "basis" not in spec or "num_components" not in spec:
+                    raise ValueError("%s: a reduced kind carries both 'basis' and 'num_components'" % who)
+                if red is not None:
+                    raise ValueError("%s: a second reduced kind (%r after %r): the engine holds one reduced operator"
+                                     % (who, spec.get("kind"), kinds[red[0]].get("kind")))
+                red = (i, spec)
+                spec = {k: v for k, v in spec.items() if k not in keys}
+            plain.append(spec)
+        plan, Y, end = self._cforce_plan(plain, animation, frame_start, frame_end, frame_jump, chunk_frames)
+        if red is None:
+            return plan, Y, end, None
+        i, spec = red
+        setup, _, _, St, operator = self._rforce_plan(spec["kind"], spec["basis"], spec.get("elements"), spec.get("wi", 1.0),
+                                                      spec.get("reduction", "deim_pod"), spec.get("rest_positions"),
+                                                      spec.get("sigma_min", 1.0), spec.get("sigma_max", 1.0), animation, frame_start,
+                                                      end, frame_jump)
+        return plan, Y, end, (i, setup, St, operator)
+
+    def _solve_start(self, who, start, n_sel):
+        """(start code of the engine, device pointer or None); a tensor is checked as ``global_solve`` checks its rhs."""
+        if isinstance(start, str):
+            return (0 if start == "explicit" else 1), None
+        if start.device.index != self._engine.device_id:
+            raise ValueError("%s: start lives on %s, the snapshots on device %d" % (who, start.device, self._engine.device_id))
+        if start.dim() != 3 or tuple(start.shape) != (n_sel, self.nVerts, 3) or not start.is_contiguous():
+            raise ValueError("%s: start of shape %s: a contiguous (%d, %d, 3) expected" % (who, tuple(start.shape), n_sel, self.nVerts))
+        return 2, start.data_ptr()
+
+    def _solve_run(self, who, plan, red, Y, frame_start, end, frame_jump, chunk_frames, K, start, m, dt, mode, acc, history):
+        """The solve for a plan whose matrix is on the device; ``red``: None or (index in the plan, full set-up, operator of the
+        r in use), the engine's ``rforce_operator`` holding at least its columns."""
+        import torch
+        eng = self._engine
+        n_sel = len(range(frame_start, end, frame_jump))
+        code, ptr = self._solve_start(who, start, n_sel)
+        if code == 2:
+            torch.cuda.current_stream(start.device).synchronize()   # whatever produced start is done before the engine reads it
+        if Y is not None:
+            eng.heldout_upload(Y, self.massL, self._standarize, self.pre_scale_factor)
+        eng.pdsolve_begin(0 if Y is None else 1, frame_start, end, frame_jump, self.invMassL, self._standarize, self.pre_scale_factor,
+                          m * (1.0 / (float(dt) * float(dt))), mode, acc, code, ptr)
+        for i, (_kind, setup, St, smin, smax, _wi) in enumerate(plan):
+            if red is not None and red[0] == i:
+                eng.cproj_setup(_proj.subset_setup(red[1], red[2].elements))
+                eng.rforce_solver(red[2].H, red[2].local_rows)
+                eng.pdsolve_slot(smin, smax, None)
+            else:
+                eng.cproj_setup(setup)
+                eng.pdsolve_slot(smin, smax, St)
+        out = torch.empty((n_sel, self.nVerts, 3), dtype=torch.float64, device="cuda:%d" % eng.device_id)
+        hist = eng.pdsolve_iterate(K, 0 if chunk_frames is None else int(chunk_frames), out.data_ptr(), history)
+        self.assembly_ST = {q[0]: q[2] for q in plan}
+        bend = [q[1].bending_indices for q in plan if q[0] == "verts_bending"]
+        self.bending_indices = bend[0] if bend else None
+        if history:
+            with np.errstate(divide='ignore', invalid='ignore'):
+                return out, n_sel, np.sqrt(hist[:, :, 0]) / np.sqrt(hist[:, :, 1])
+        return out, n_sel
+
+    def solve_frames(self, kinds, dt, num_iterations=10, masses=None, velocity="difference", gravity=(0.0, 0.0, 0.0), start="explicit",
+                     animation="train", frame_start=0, frame_end=None, frame_jump=1, chunk_frames=None, history=False):
+        """Extra: the local/global iterations of the reference's solver (Simulators.py:494-526) for every selected frame of
+        the resident animation, on the device: q_0 given, q_{k+1} = A^-1 (M / dt^2 s_f + sum_i S_i^T p_i(q_k)) for
+        ``num_iterations`` iterations, the explicit state s_f held fixed while q moves.  The iterate stays on the device
+        between iterations in the layout the projection kernels read; the kinds' tables and S^T are uploaded once per solve.
+
+        ``kinds``: the list of dicts of ``constraint_forces``; ONE entry may also carry ``basis``, ``num_components`` and
+        ``reduction`` (default "deim_pod") with the meanings of ``reduced_constraint_forces``: that kind's term is then the
+        reduced one, as the simulator's per-group ``*_reduced`` flags choose.  A is always the full matrix of all listed kinds.
+        ``dt``, ``masses``, ``velocity``, ``gravity``, ``animation``, the frame range and ``chunk_frames``: as ``global_step``.
+        ``start``: "explicit" (q_0 = s_f, the reference's), "frame" (q_0 = x_f; one iteration is then ``global_step`` bit for
+        bit) or a contiguous ``torch.float64`` device tensor (F', N, 3) -- a solve continued from an earlier result equals the
+        longer solve bit for bit.  ``history``: also the (num_iterations, F') array of |q_{k+1} - q_k| / |q_{k+1}| (Frobenius
+        norms of the frame).
+
+        Returns ``(tensor, F')`` (``(tensor, F', steps)`` with ``history``): a ``torch.float64`` device tensor (F', N, 3) in
+        world space, owned by the caller.  Device memory held by the engine beside A^-1: three times the result plus the
+        projections of one chunk.  %s"""
+        who = "solve_frames"
+        mode, acc, m, K = self._solve_args(who, dt, velocity, gravity, num_iterations, start, masses)
+        plan, Y, end, red = self._solve_plan(who, kinds, animation, frame_start, frame_end, frame_jump, chunk_frames)
+        self._solve_start(who, start, len(range(frame_start, end, frame_jump)))
+        if red is not None:
+            op = red[3](int(kinds[red[0]]["num_components"]))
+        self._gstep_setup(plan, dt, m)
+        if red is not None:
+            self._engine.rforce_operator(red[2], op.V)
+            red = (red[0], red[1], op)
+        return self._solve_run(who, plan, red, Y, frame_start, end, frame_jump, chunk_frames, K, start, m, dt, mode, acc, history)
+
+    solve_frames.__doc__ %= _SOLVE_SCOPE
+
+    def reduced_solve_errors(self, kind, basis, r_values, dt, num_iterations=10, masses=None, velocity="difference",
+                             gravity=(0.0, 0.0, 0.0), start="explicit", elements=None, wi=1.0, reduction="deim_pod", rest_positions=None,
+                             sigma_min=1.0, sigma_max=1.0, animation="train", frame_start=0, frame_end=None, frame_jump=1,
+                             per_frame=False):
+        """Extra: how far the DEIM-reduced simulation is from the full one after the solver's iterations -- for every r of
+        ``r_values`` the three metrics of ``(q, q~_r)``, q = ``solve_frames`` of this kind and q~_r the same solve with the kind
+        reduced to r components (same A^-1, same inertia term, same start).  Arguments as ``reduced_global_step_errors`` plus
+        ``num_iterations`` and ``start``; the same five lists ``fro, max, rel_x, rel_y, rel_z`` and, with ``per_frame``, the
+        (len(r_values), F') array |q[f] - q~_r[f]| / |q[f]|.  The full solve runs once, one reduced solve per r (S^T V once, for
+        the largest r); every tensor stays on the device and is compared there.  With ``num_iterations=1, start="frame"`` these
+        are the numbers of ``reduced_global_step_errors``.  %s"""
+        who = "reduced_solve_errors"
+        mode, acc, m, K = self._solve_args(who, dt, velocity, gravity, num_iterations, start, masses)
+        spec = dict(kind=kind, elements=elements, wi=wi, rest_positions=rest_positions, sigma_min=sigma_min, sigma_max=sigma_max)
+        plan, Y, end, red = self._solve_plan(who, [dict(spec, basis=basis, num_components=0, reduction=reduction)], animation,
+                                             frame_start, frame_end, frame_jump, None)
+        r_values = [int(r) for r in r_values]
+        ops = [red[3](r) for r in r_values]
+        if not ops:
+            return self._diff_metrics(None, [], 0, per_frame)
+        self._solve_start(who, start, len(range(frame_start, end, frame_jump)))
+        self._gstep_setup(plan, dt, m)
+        run = lambda rd: self._solve_run(who, plan, rd, Y, frame_start, end, frame_jump, None, K, start, m, dt, mode, acc, False)
+        full, n_sel = run(None)
+        self._engine.rforce_operator(red[2], ops[int(np.argmax(r_values))].V)
+        out = self._diff_metrics(full, (run((red[0], red[1], op))[0] for op in ops), n_sel, per_frame)
+        self.assembly_ST = {kind: red[2]}
+        self.bending_indices = red[1].bending_indices
+        return out
+
+    reduced_solve_errors.__doc__ %= _SOLVE_SCOPE
 
     # ------------------------------------------------------------------ reference methods
     @log_time("")

@@ -679,6 +679,30 @@ int asb_gstep_inertia(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t f
 /* test hook: the n x n block of the context's A^-1 (row-major) to the host */
 int asb_test_gstep_inverse(asb_ctx* ctx, double* out_host, int64_t n);
 
+/* ------------------------------------------------ projective dynamics: the solver's iterations (asb_pdsolve.hip) ----------- */
+/* The local/global loop of Simulators.py:494-526 for the frames range(f0, f1, fj) of the training (which 0) or held-out (1)
+ * tensor, every frame an independent solve: q_{k+1} = A^-1 (sum_i S_i^T p_i(q_k) + M / h^2 s_f) with s_f fixed.  The iterate
+ * stays on the device between iterations, vertex-major (row 3 v + d, the frames contiguous, padded to 64), the layout the
+ * projection kernels read.  No collisions, no positional constraints, no velocities carried from frame to frame.  One rank.
+ * asb_pdsolve_begin: after asb_gstep_setup.  Arguments two to eleven as asb_gstep_inertia; the inertia term diag s_f is
+ * formed once with that entry's arithmetic.  start 0: q_0 = s_f (the reference's), 1: q_0 = x_f, 2: q_0 = start_dev, a DEVICE
+ * tensor (n_sel, n, 3).  More than 65535 * 64 selected frames: ASB_ERR_LIMIT, judged on the count alone before anything
+ * else.  Drops the kinds of the previous solve; its buffers are reused. */
+int asb_pdsolve_begin(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean, double psf,
+                      const double* diag, int mode, const double* acc3, int start, const double* start_dev);
+/* Registers the kind of the preceding asb_cproj_setup as the next term of the right-hand side: its device tables pass to
+ * the solve (the context has no element set-up afterwards) together with the HOST CSR of its S^T (as asb_cforce_run takes
+ * and checks it), uploaded here once.  reduced != 0: the set-up holds the SAMPLED elements and the term is that of
+ * asb_rforce_run with the context's operator and solver (the CSR arguments are ignored); a second reduced kind is refused. */
+int asb_pdsolve_slot(asb_ctx* ctx, double sigma_min, double sigma_max, int reduced, int64_t n_rows, const int64_t* indptr,
+                     const int64_t* indices, const double* data);
+/* n_iter further iterations of the solve in progress.  chunk_frames as asb_cforce_run (no bit depends on it).  out_dev
+ * (optional): caller-owned DEVICE memory (n_sel, n, 3), the iterate after the last of them, frame-major.  hist_out
+ * (optional, host, n_iter x n_sel x 2): per iteration and frame [|q_new - q_old|^2, |q_new|^2] over its n x 3 entries, summed
+ * in a fixed order.  The product is that of asb_gstep_run entry for entry; no atomics; repeats, sub-ranges and any chunk
+ * width give identical bits.  Returns after the stream has drained. */
+int asb_pdsolve_iterate(asb_ctx* ctx, int64_t n_iter, int64_t chunk_frames, double* out_dev, double* hist_out);
+
 /* ------------------------------------------------ SPLOCS refinement ----------- */
 /* posComponents.splocs_glob_optimization, snapbases/posComponents.py:132-189.
  * State after a residual-mode deflation: C = comps, W = weigs, U = 0 (:135-139).  One outer
