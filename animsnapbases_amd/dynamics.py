@@ -1,0 +1,535 @@
+"""``ResidentDynamics`` -- what ``posSnapshots`` offers beyond the reference's class: the pieces of the reference's
+projective-dynamics solver (Simulators.py) evaluated on the device for the frames of the resident animation -- constraint
+projections, constraint forces, their DEIM reduction, the global step and the solver's iterations.
+A public call checks its arguments into the named records below before the engine is touched; the helpers take the records.
+"""
+import collections
+
+import numpy as np
+
+from . import projections as _proj
+from . import reduced as _red
+
+
+class Frames(collections.namedtuple("Frames", "which start end jump Y")):
+    """The frames range(start, end, jump) of the training tensor (``which`` 0) or of the held-out animation ``Y`` (``which`` 1)."""
+    __slots__ = ()
+
+    @property
+    def n_sel(self):
+        return len(range(self.start, self.end, self.jump))
+
+    def args(self, host):
+        """The seven leading arguments of the engine's ``*_run`` calls."""
+        return (self.which, self.start, self.end, self.jump, host.invMassL, host._standarize, host.pre_scale_factor)
+
+    def upload(self, host):
+        """The held-out animation onto the device, transformed like the training tensor."""
+        if self.Y is not None:
+            host._engine.heldout_upload(self.Y, host.massL, host._standarize, host.pre_scale_factor)
+
+
+# One element kind of a call: its rest set-up (projections.ProjectionSetup), S^T (CSR, weighted by wi) and the strain clamp.
+Term = collections.namedtuple("Term", "kind setup St sigma_min sigma_max wi")
+# The explicit state s_f = x_f (+ x_f - x_{f-1}, ``mode`` 1) + ``acc`` = dt^2 g and its inertia term ``diag`` = masses / dt^2.
+Explicit = collections.namedtuple("Explicit", "mode acc diag masses dt")
+# The reduced kind of a solve: its ``index`` in the plan, the full set-up and S^T, ``operator``: r -> reduced.ReducedOperator,
+# and ``op``: the operator in use (None until one is chosen), the engine's ``rforce_operator`` holding at least its columns.
+Reduced = collections.namedtuple("Reduced", "index setup St operator op")
+# One kind with a basis: what ``reduced_constraint_forces`` and the ``reduced_*_errors`` methods check their arguments into.
+ReducedPlan = collections.namedtuple("ReducedPlan", "term frames operator")
+
+
+class ResidentDynamics(object):
+    """Mixin of ``posSnapshots``.  Reads from the host object: ``_engine``, ``_comm``, ``nVerts``, ``frs``, ``verts``, ``tris``,
+    ``test_verts``, ``mass``, ``massL``, ``invMassL``, ``_standarize``, ``pre_scale_factor``, ``mean`` and ``snapTensor``.
+    Leaves: ``assembly_ST``, ``bending_indices``, ``global_matrix``, ``global_solve_residual``."""
+
+    # ------------------------------------------------------------------ the records of a call
+    def _frames(self, animation, frame_start, frame_end, frame_jump):
+        """The checked ``Frames`` of a public call; ``frame_end`` None: the animation's last frame."""
+        if isinstance(animation, str) and animation not in ("train", "test"):
+            raise ValueError("animation must be 'train', 'test' or an (F', N, 3) array, not %r" % (animation,))
+        train = isinstance(animation, str) and animation == "train"
+        Y, F = None, self.frs
+        if not train:
+            Y = self.test_verts if isinstance(animation, str) else animation
+            if Y is None:
+                raise ValueError("no test animation (test_verts is None)")
+            Y = np.asarray(Y, dtype=np.float64)
+            if Y.ndim != 3 or Y.shape[1:] != (self.nVerts, 3) or Y.shape[0] < 1:
+                raise ValueError("held-out animation of shape %s: (F', %d, 3) expected" % (Y.shape, self.nVerts))
+            F = Y.shape[0]
+        frame_end = F if frame_end is None else frame_end
+        if frame_jump < 1 or frame_start < 0 or frame_end > F or frame_start >= frame_end:
+            raise ValueError("empty frame range: range(%r, %r, %r) selects none of the %d frames"
+                             % (frame_start, frame_end, frame_jump, F))
+        return Frames(0 if train else 1, frame_start, frame_end, frame_jump, Y)
+
+    def _setup(self, kind, elements, rest_positions, sigma_min, sigma_max):
+        """The checks of one element kind and its rest set-up."""
+        if kind not in _proj.KINDS:
+            raise ValueError("unknown projection kind %r: one of %s" % (kind, ", ".join(sorted(_proj.KINDS))))
+        if self._comm.multi:
+            raise NotImplementedError("constraint_projections on several ranks: elements straddle the vertex shards and no "
+                                      "halo of positions is built")
+        if not sigma_min <= sigma_max:
+            raise ValueError("sigma_min %r > sigma_max %r" % (sigma_min, sigma_max))
+        if elements is None:
+            if kind != "verts_bending" or self.tris is None:
+                raise ValueError("%s: no elements given%s" % (kind, " and the snapshots have no triangles" if kind == "verts_bending" else ""))
+            elements = self.tris
+        if rest_positions is None:
+            if self.verts is not None:
+                rest_positions = self.verts[0]
+            else:                                   # an adopted device tensor: frame 0 back in world space
+                rest_positions = self.snapTensor[0] / self.pre_scale_factor + (self.mean if self._standarize else 0.0)
+        rest = np.asarray(rest_positions, dtype=np.float64)
+        if rest.shape != (self.nVerts, 3):
+            raise ValueError("rest positions of shape %s: (%d, 3) expected" % (rest.shape, self.nVerts))
+        return _proj.build_setup(kind, elements, rest)
+
+    def _plan(self, kinds, chunk_frames=None):
+        """The checks of ``constraint_forces`` on its kinds, in its order: one ``Term`` per kind."""
+        if not isinstance(kinds, (list, tuple)) or len(kinds) == 0:
+            raise ValueError("constraint_forces: kinds must be a non-empty list of dicts, not %r" % (kinds,))
+        if chunk_frames is not None and (int(chunk_frames) != chunk_frames or chunk_frames < 1):
+            raise ValueError("constraint_forces: chunk_frames %r: a positive number of frames or None" % (chunk_frames,))
+        known = ("kind", "elements", "wi", "rest_positions", "sigma_min", "sigma_max")
+        plan = []
+        for spec in kinds:
+            if not isinstance(spec, dict) or "kind" not in spec:
+                raise ValueError("constraint_forces: every entry of kinds is a dict with a 'kind', not %r" % (spec,))
+            extra = sorted(set(spec) - set(known))
+            if extra:
+                raise ValueError("constraint_forces: unknown key %r (one of %s)" % (extra[0], ", ".join(known)))
+            kind, smin, smax, wi = spec["kind"], spec.get("sigma_min", 1.0), spec.get("sigma_max", 1.0), spec.get("wi", 1.0)
+            setup = self._setup(kind, spec.get("elements"), spec.get("rest_positions"), smin, smax)
+            if any(kind == t.kind for t in plan):
+                raise ValueError("constraint_forces: kind %r is listed twice" % (kind,))
+            plan.append(Term(kind, setup, _proj.assembly_ST(setup, self.nVerts, wi), smin, smax, wi))
+        return plan
+
+    @staticmethod
+    def _operator(term, basis, reduction):
+        """r -> ``reduced.ReducedOperator`` of the basis for the kind of ``term``."""
+        if reduction not in _red.REDUCTIONS:
+            raise ValueError("unknown reduction %r: one of %s" % (reduction, ", ".join(sorted(_red.REDUCTIONS))))
+        data = _red.load_basis(basis)
+        return lambda r: _red.reduced_operator(data["components"], data["interpol_alphas"], data["Pt"], data["interpol_alpha_ranges"],
+                                               r, term.setup.p, reduction, n_elements=term.setup.n_elem,
+                                               verts_bending=term.kind == "verts_bending")
+
+    def _reduced_plan(self, spec, basis, reduction, frames):
+        """The ``ReducedPlan`` of one kind (``spec``: a dict of ``constraint_forces``) with a basis."""
+        term, = self._plan([spec])
+        return ReducedPlan(term, frames, self._operator(term, basis, reduction))
+
+    def _explicit(self, who, dt, velocity, gravity, masses):
+        """The one-rank refusal and the checks of the explicit state's arguments: ``Explicit``."""
+        self._one_rank(who)
+        if velocity not in ("difference", "zero"):
+            raise ValueError("velocity must be 'difference' or 'zero', not %r" % (velocity,))
+        g = np.asarray(gravity, dtype=np.float64)
+        if g.shape != (3,) or not np.isfinite(g).all():
+            raise ValueError("gravity %r: three finite numbers expected" % (gravity,))
+        try:
+            h = float(dt)
+        except (TypeError, ValueError):
+            h = float("nan")
+        if not np.isfinite(h) or h <= 0.0:
+            raise ValueError("the time step dt must be finite and positive, not %r" % (dt,))
+        masses = self._masses(masses)
+        return Explicit(1 if velocity == "difference" else 0, h * h * g, masses * (1.0 / (h * h)), masses, dt)
+
+    def _masses(self, masses):
+        masses = self.mass if masses is None else masses
+        if masses is None:
+            raise ValueError("no vertex masses: the snapshots were built without mass weighting, pass masses=")
+        return np.asarray(masses, dtype=np.float64)
+
+    def _one_rank(self, who):
+        if self._comm.multi:
+            raise NotImplementedError("%s on several ranks: the system matrix couples the vertex shards and no distributed "
+                                      "solve is built" % who)
+
+    # ------------------------------------------------------------------ what every run shares
+    def _alloc(self, frames, rows=None):
+        """The result of a call: a caller-owned device tensor (F', rows, 3), rows = N by default."""
+        import torch
+        return torch.empty((frames.n_sel, self.nVerts if rows is None else rows, 3), dtype=torch.float64,
+                           device="cuda:%d" % self._engine.device_id)
+
+    def _leave(self, terms):
+        self.assembly_ST = {t.kind: t.St for t in terms}
+        self.bending_indices = next((t.setup.bending_indices for t in terms if t.kind == "verts_bending"), None)
+
+    def _cforce_run(self, plan, frames, chunk_frames):
+        """``constraint_forces`` for a plan of ``_plan``."""
+        frames.upload(self)
+        out = self._alloc(frames)
+        for i, t in enumerate(plan):
+            self._engine.cproj_setup(t.setup)
+            self._engine.cforce_run(*frames.args(self), t.sigma_min, t.sigma_max, t.St, i > 0,
+                                    0 if chunk_frames is None else int(chunk_frames), out.data_ptr())
+        self._leave(plan)
+        return out
+
+    def _rforce_term(self, term, op, frames):
+        """One reduced term with the operator of the engine: only the sampled elements are set up and projected."""
+        self._engine.cproj_setup(_proj.subset_setup(term.setup, op.elements))
+        self._engine.rforce_solver(op.H, op.local_rows)
+        out = self._alloc(frames)
+        self._engine.rforce_run(*frames.args(self), term.sigma_min, term.sigma_max, False, out.data_ptr())
+        return out
+
+    def _step(self, b, ex, frames):
+        """A^-1 (b + M / dt^2 s) of the selected frames; the inertia term is added onto ``b``."""
+        self._engine.gstep_inertia(*frames.args(self), ex.diag, ex.mode, ex.acc, b.data_ptr())
+        return self.global_solve(b)
+
+    def _errors(self, plan, r_values, per_frame, full, reduced):
+        """The body of the ``reduced_*_errors`` methods for a ``ReducedPlan``: ``full()`` makes the full device tensor, once;
+        ``reduced(op)`` the one of a ``ReducedOperator``, S^T V of the largest r on the device by then."""
+        r_values = [int(r) for r in r_values]
+        ops = [plan.operator(r) for r in r_values]
+        if not ops:
+            return self._diff_metrics(None, [], 0, per_frame)
+        ref = full()
+        self._engine.rforce_operator(plan.term.St, ops[int(np.argmax(r_values))].V)
+        out = self._diff_metrics(ref, (reduced(op) for op in ops), plan.frames.n_sel, per_frame)
+        self._leave([plan.term])
+        return out
+
+    def _diff_metrics(self, full, others, n_sel, per_frame):
+        """The reference's three metrics (constraintsComponents.py:524-556) of ``(full, t)`` for every device tensor ``t`` of
+        ``others`` (made one at a time), through ``asb_force_diff``: the lists ``fro, max, rel_x, rel_y, rel_z`` and, with
+        ``per_frame``, the (len(others), F') array of |full[f] - t[f]| / |full[f]|."""
+        fro, mx, rel, frames = [], [], [[], [], []], []
+        for t in others:
+            sums, m, norms, pf = self._engine.force_diff(full.data_ptr(), t.data_ptr(), n_sel, self.nVerts, per_frame)
+            with np.errstate(divide='ignore', invalid='ignore'):
+                fro.append(float(np.sqrt(sums.sum())))
+                mx.append(float(m / norms[3]))
+                for d in range(3):
+                    rel[d].append(float(np.sqrt(sums[d]) / np.sqrt(norms[d])))
+                if per_frame:
+                    frames.append(np.sqrt(pf[:, 0]) / np.sqrt(pf[:, 1]))
+        out = (fro, mx, rel[0], rel[1], rel[2])
+        return out + (np.array(frames).reshape(len(fro), -1) if fro else np.zeros((0, 0)),) if per_frame else out
+
+    # ------------------------------------------------------------------ constraint projections and forces of the animation
+    def constraint_projections(self, kind, elements=None, rest_positions=None, sigma_min=1.0, sigma_max=1.0, animation="train",
+                               frame_start=0, frame_end=None, frame_jump=1, wi=None):
+        """Extra (not in the reference's class): the constraint-projection snapshots the reference's projective-dynamics
+        simulator records (Simulators.py:655-724) -- ``get_pi`` of every element for every frame
+        (projective_dynamics/Constraint_projections.py) -- computed on the device from the resident animation in world space
+        (mass weighting, mean row and scale undone), for the frames range(frame_start, frame_end, frame_jump).
+
+        ``kind``: "edge_spring" (elements (E, 2)), "tris_strain" ((T, 3)), "tets_strain" / "tets_deformation_gradient"
+        ((T, 4)) or "verts_bending" (elements: the (M, 3) triangles, None = ``self.tris``; the constrained vertices are left
+        in ``self.bending_indices``).  ``rest_positions`` (N, 3): default frame 0 of the world-space input.  ``sigma_min`` /
+        ``sigma_max``: the clamp of the strain kinds.  ``animation``: "train", "test" (``test_verts``) or an (F', N, 3) array.
+        ``wi``: the constraint weight; when given, the kind's weighted differential operator S^T (``projections.assembly_ST``)
+        is left in ``self.assembly_ST[kind]``.
+
+        Returns ``(tensor, F', rows)``: a ``torch.float64`` device tensor (F', rows, 3), rows = elements x p, allocated here
+        through torch and owned by the caller (what ``nonlinearSnapshots(frames_device=...)`` adopts).  One rank only."""
+        frames = self._frames(animation, frame_start, frame_end, frame_jump)
+        setup = self._setup(kind, elements, rest_positions, sigma_min, sigma_max)
+        St = None if wi is None else _proj.assembly_ST(setup, self.nVerts, wi)
+        frames.upload(self)
+        self._engine.cproj_setup(setup)
+        out = self._alloc(frames, setup.rows)
+        self._engine.cproj_run(*frames.args(self), sigma_min, sigma_max, out.data_ptr())
+        self.bending_indices = setup.bending_indices
+        if St is not None:
+            self.assembly_ST = {kind: St}
+        return out, frames.n_sel, setup.rows
+
+    def constraint_forces(self, kinds, animation="train", frame_start=0, frame_end=None, frame_jump=1, chunk_frames=None):
+        """Extra (not in the reference's class): the constraint term of the global step's right-hand side,
+        b[f] = sum_k S_k^T p_k(q_f) (``get_sum_ST_p``, Simulators.py:643-724), for the frames
+        range(frame_start, frame_end, frame_jump) of the resident animation -- on the device, the projections p never formed
+        at full size and never downloaded.
+
+        ``kinds``: a non-empty list of dicts ``{"kind", "elements", "wi": 1.0, "rest_positions": None, "sigma_min": 1.0,
+        "sigma_max": 1.0}`` with the meanings of ``constraint_projections``; a kind may be listed once.  The terms are added
+        in list order.  ``chunk_frames``: frames per pass of the device (rounded up to a multiple of 16; None: as many as a
+        256 MB scratch holds), which bounds the scratch and changes no bit of the result.
+
+        Returns ``(tensor, F')``: a ``torch.float64`` device tensor (F', N, 3) in world space, allocated here through torch
+        and owned by the caller -- the layout ``posSnapshots.from_device`` adopts.  Leaves ``self.assembly_ST`` (kind -> CSR)
+        and ``self.bending_indices``.  One rank only."""
+        frames = self._frames(animation, frame_start, frame_end, frame_jump)
+        return self._cforce_run(self._plan(kinds, chunk_frames), frames, chunk_frames), frames.n_sel
+
+    def reduced_constraint_forces(self, kind, basis, num_components, elements=None, wi=1.0, reduction="deim_pod",
+                                  rest_positions=None, sigma_min=1.0, sigma_max=1.0, animation="train", frame_start=0,
+                                  frame_end=None, frame_jump=1):
+        """Extra (not in the reference's class): the constraint term the reference's REDUCED simulator puts on the global
+        step's right-hand side, b~[f] = S^T V (P^T V)^+ P^T p(q_f) per coordinate (Simulators.py:157-255, :366-399;
+        ``reduced.reduced_operator``), for the frames range(frame_start, frame_end, frame_jump) of the resident animation.
+        ``get_pi`` is evaluated at the interpolation elements only; S^T V is formed once on the device, sparse times dense.
+
+        ``kind``, ``elements``, ``rest_positions``, ``sigma_min`` / ``sigma_max``, ``animation``: as ``constraint_projections``
+        (``elements``: ALL elements of the kind, the ones the basis was built on); ``wi``: the constraint weight of S^T.
+        ``basis``: a ``constraintsComponents`` with components and interpolation points, the path of the ``.npz`` of its
+        ``store_components_n_interpol_points``, or a dict with the keys components, interpol_alphas, Pt,
+        interpol_alpha_ranges.  ``num_components``: m.  ``reduction``: the simulator's
+        ``constraint_projection_reduction_type`` ("deim_pod", "deim_pod_vectorized": single rows; "deim_pca_blocks",
+        "geom_pca_blocks_withSt": whole blocks of p rows).
+
+        Returns ``(tensor, F')``: a ``torch.float64`` device tensor (F', N, 3) in world space, the layout of
+        ``constraint_forces``.  Leaves ``self.assembly_ST[kind]`` and ``self.bending_indices``.  One rank only."""
+        spec = dict(kind=kind, elements=elements, wi=wi, rest_positions=rest_positions, sigma_min=sigma_min, sigma_max=sigma_max)
+        plan = self._reduced_plan(spec, basis, reduction, self._frames(animation, frame_start, frame_end, frame_jump))
+        op = plan.operator(num_components)
+        plan.frames.upload(self)
+        self._engine.rforce_operator(plan.term.St, op.V)
+        out = self._rforce_term(plan.term, op, plan.frames)
+        self._leave([plan.term])
+        return out, plan.frames.n_sel
+
+    def reduced_force_errors(self, kind, basis, r_values, elements=None, wi=1.0, reduction="deim_pod", rest_positions=None,
+                             sigma_min=1.0, sigma_max=1.0, animation="train", frame_start=0, frame_end=None, frame_jump=1,
+                             per_frame=False):
+        """Extra (not in the reference): how wrong the forces of the reduced simulation are -- for every r of ``r_values`` the
+        reference's ``frobenius_error``, ``max_pointwise_error`` and ``relative_error_per_component``
+        (constraintsComponents.py:524-556) of ``(b, b~_r)``, b the full term of ``constraint_forces`` for this kind and b~_r
+        ``reduced_constraint_forces`` with r components, as five lists ``fro, max, rel_x, rel_y, rel_z``; with ``per_frame``
+        a sixth value, the (len(r_values), F') array of |b[f] - b~_r[f]| / |b[f]| (Frobenius norms of the frame).  Arguments as
+        ``reduced_constraint_forces``.  The full term is computed once, S^T V once for the largest r (prefixes of its
+        columns serve the others); both tensors stay on the device and are compared there (asb_force_diff)."""
+        spec = dict(kind=kind, elements=elements, wi=wi, rest_positions=rest_positions, sigma_min=sigma_min, sigma_max=sigma_max)
+        plan = self._reduced_plan(spec, basis, reduction, self._frames(animation, frame_start, frame_end, frame_jump))
+        return self._errors(plan, r_values, per_frame, lambda: self._cforce_run([plan.term], plan.frames, None),
+                            lambda op: self._rforce_term(plan.term, op, plan.frames))
+
+    # ------------------------------------------------------------------ the global step of projective dynamics
+    def global_solve_setup(self, kinds, dt, masses=None):
+        """Extra (not in the reference's class): prepares the global step of the reference's projective-dynamics solver,
+        ``prepare_global_matrix`` (Simulators.py:117-145), for this mesh: A = M / dt^2 + sum_i w_i S_i^T S_i is assembled on
+        the host from the rest tables (``projections.global_matrix``: one N x N matrix serves the three coordinates) and
+        inverted once on the device, where A^-1 stays until the next set-up.
+
+        ``kinds``: the list of dicts of ``constraint_forces`` (same checks).  ``dt``: the time step h.  ``masses`` (N,): None
+        takes the vertex masses the snapshots were mass-weighted with.  Leaves ``self.global_matrix`` (CSR) and
+        ``self.global_solve_residual`` = max |A (A^-1 1) - 1| as the device computed it.  Cost: the host assembly and symmetry
+        check, and on the device a dense N x N inversion (N^3 flop, 8 N^2 bytes); a set-up whose matrix equals the one the
+        device already holds keeps that inverse.  N <= 46 000, one rank only."""
+        self._one_rank("global_solve_setup")
+        self._matrix(self._plan(kinds), self._masses(masses), dt)
+
+    def _matrix(self, plan, masses, dt):
+        """A of the plan, inverted on the device unless the device holds that very matrix."""
+        A = _proj.global_matrix([(t.setup, t.wi) for t in plan], self.nVerts, masses, dt)
+        self.global_matrix, self.global_solve_residual = None, None
+        resid = self._engine.gstep_held(A)
+        if resid is None:
+            resid = self._engine.gstep_setup(A)
+        self.global_matrix, self.global_solve_residual = A, resid
+
+    def global_solve(self, rhs):
+        """Extra: q = A^-1 rhs per coordinate for the matrix of the last ``global_solve_setup``.  ``rhs``: a caller-owned
+        ``torch.float64`` device tensor (F', N, 3), contiguous; returns a new one of the same shape, owned by the caller.  The
+        sum over the vertices is never split: a frame's result does not depend on the frames around it."""
+        self._one_rank("global_solve")
+        if getattr(self, "global_matrix", None) is None:
+            raise ValueError("global_solve: no system matrix on the device, call global_solve_setup first")
+        import torch
+        if not isinstance(rhs, torch.Tensor) or rhs.dtype != torch.float64 or not rhs.is_cuda:
+            raise ValueError("global_solve: rhs must be a torch.float64 device tensor")
+        if rhs.device.index != self._engine.device_id:
+            raise ValueError("global_solve: rhs lives on %s, the snapshots on device %d" % (rhs.device, self._engine.device_id))
+        if rhs.dim() != 3 or rhs.shape[0] < 1 or tuple(rhs.shape[1:]) != (self.nVerts, 3) or not rhs.is_contiguous():
+            raise ValueError("global_solve: rhs of shape %s: a contiguous (F', %d, 3) expected" % (tuple(rhs.shape), self.nVerts))
+        out = torch.empty_like(rhs)
+        torch.cuda.current_stream(rhs.device).synchronize()         # whatever produced rhs is done before the engine reads it
+        self._engine.gstep_run(rhs.data_ptr(), rhs.shape[0], out.data_ptr())
+        return out
+
+    def global_step(self, kinds, dt, masses=None, velocity="difference", gravity=(0.0, 0.0, 0.0), animation="train",
+                    frame_start=0, frame_end=None, frame_jump=1, chunk_frames=None):
+        """Extra: one local/global iteration of the reference's solver started at every selected frame of the resident
+        animation (Simulators.py:494-526 with ``num_iterations`` = 1 and q = x_f):
+        Phi(x_f; s_f) = A^-1 (M / dt^2 s_f + sum_k S_k^T p_k(x_f)), on the device.
+
+        ``kinds``, ``animation``, the frame range and ``chunk_frames``: as ``constraint_forces``; ``dt``, ``masses``: as
+        ``global_solve_setup``, whose work is done here first -- the matrix is assembled on every call, the dense inversion
+        is paid only when the matrix differs from the one the device holds.  ``velocity``: "zero" takes the explicit state
+        s_f = x_f + dt^2 g, "difference"
+        s_f = 2 x_f - x_{f-1} + dt^2 g with f - 1 the ANIMATION's previous frame whatever ``frame_jump`` is (at frame 0:
+        x_0), the velocity the reference carries from step to step (:531).  ``gravity``: the acceleration g.
+
+        Returns ``(tensor, F')``: a ``torch.float64`` device tensor (F', N, 3) in world space, owned by the caller.  Further
+        iterations are ``solve_frames``: they keep s_f fixed while q moves, which re-adopting the result with ``from_device``
+        and stepping again would not.  One rank only."""
+        ex = self._explicit("global_step", dt, velocity, gravity, masses)
+        frames = self._frames(animation, frame_start, frame_end, frame_jump)
+        plan = self._plan(kinds, chunk_frames)
+        self._matrix(plan, ex.masses, ex.dt)
+        return self._step(self._cforce_run(plan, frames, chunk_frames), ex, frames), frames.n_sel
+
+    def reduced_global_step_errors(self, kind, basis, r_values, dt, masses=None, velocity="difference", gravity=(0.0, 0.0, 0.0),
+                                   elements=None, wi=1.0, reduction="deim_pod", rest_positions=None, sigma_min=1.0,
+                                   sigma_max=1.0, animation="train", frame_start=0, frame_end=None, frame_jump=1,
+                                   per_frame=False):
+        """Extra: how far the reduced right-hand side moves the vertices -- ``reduced_force_errors`` one line further down the
+        iteration.  Cost beside that method's: the work of ``global_solve_setup`` once, one solve plus one per r.
+        For every r of ``r_values`` the three metrics of ``(q, q~_r)``: q = ``global_step`` of this kind and
+        q~_r the same step with b~_r of ``reduced_constraint_forces`` in place of b (same inertia term, same A^-1).  Arguments
+        as ``reduced_force_errors`` plus ``dt``, ``masses``, ``velocity``, ``gravity`` of ``global_step``; the same five lists
+        ``fro, max, rel_x, rel_y, rel_z`` and, with ``per_frame``, the (len(r_values), F') array |q[f] - q~_r[f]| / |q[f]|.
+        The full step is computed once; every tensor stays on the device."""
+        ex = self._explicit("reduced_global_step_errors", dt, velocity, gravity, masses)
+        spec = dict(kind=kind, elements=elements, wi=wi, rest_positions=rest_positions, sigma_min=sigma_min, sigma_max=sigma_max)
+        plan = self._reduced_plan(spec, basis, reduction, self._frames(animation, frame_start, frame_end, frame_jump))
+
+        def full():
+            self._matrix([plan.term], ex.masses, ex.dt)
+            return self._step(self._cforce_run([plan.term], plan.frames, None), ex, plan.frames)
+        return self._errors(plan, r_values, per_frame, full,
+                            lambda op: self._step(self._rforce_term(plan.term, op, plan.frames), ex, plan.frames))
+
+    # ------------------------------------------------------------------ the solver's iterations
+    _SOLVE_SCOPE = """Out of scope, as for ``global_step``: collision handling (``resolve_collision`` and the self-collision passes),
+        positional constraints, velocities carried from one solved frame into the next (every selected frame is an independent
+        solve from the animation's own x_f, x_{f-1}), the hyper-reduced operator A^-1 S^T V (a reduced iteration still pays the
+        N^2 product) and several ranks."""
+
+    def _solve_args(self, who, dt, velocity, gravity, num_iterations, start, masses):
+        """The checks of the solve's own arguments, before anything touches the device: (``Explicit``, K)."""
+        ex = self._explicit(who, dt, velocity, gravity, masses)
+        try:
+            K = int(num_iterations)
+        except (TypeError, ValueError):
+            K = 0
+        if K != num_iterations or K < 1:
+            raise ValueError("%s: num_iterations %r: a positive number of iterations" % (who, num_iterations))
+        if isinstance(start, str):
+            if start not in ("explicit", "frame"):
+                raise ValueError("%s: start must be 'explicit', 'frame' or a torch.float64 device tensor, not %r" % (who, start))
+        else:
+            import torch
+            if not isinstance(start, torch.Tensor) or start.dtype != torch.float64 or not start.is_cuda:
+                raise ValueError("%s: start must be 'explicit', 'frame' or a torch.float64 device tensor" % who)
+        return ex, K
+
+    def _solve_plan(self, who, kinds, chunk_frames):
+        """``_plan`` of the kinds with their reduction keys taken off, and for the one entry that carries a ``basis`` its
+        ``Reduced`` (no operator chosen yet), else None."""
+        keys = ("basis", "num_components", "reduction")
+        if not isinstance(kinds, (list, tuple)):
+            raise ValueError("%s: kinds must be a non-empty list of dicts, not %r" % (who, kinds))
+        plain, red = [], None
+        for i, spec in enumerate(kinds):
+            if isinstance(spec, dict) and any(k in spec for k in keys):
+                if "basis" not in spec or "num_components" not in spec:
+                    raise ValueError("%s: a reduced kind carries both 'basis' and 'num_components'" % who)
+                if red is not None:
+                    raise ValueError("%s: a second reduced kind (%r after %r): the engine holds one reduced operator"
+                                     % (who, spec.get("kind"), kinds[red].get("kind")))
+                red = i
+                spec = {k: v for k, v in spec.items() if k not in keys}
+            plain.append(spec)
+        plan = self._plan(plain, chunk_frames)
+        if red is None:
+            return plan, None
+        t = plan[red]
+        return plan, Reduced(red, t.setup, t.St, self._operator(t, kinds[red]["basis"], kinds[red].get("reduction", "deim_pod")), None)
+
+    def _solve_start(self, who, start, n_sel):
+        """(start code of the engine, the caller's tensor or None); a tensor is checked as ``global_solve`` checks its rhs."""
+        if isinstance(start, str):
+            return (0 if start == "explicit" else 1), None
+        if start.device.index != self._engine.device_id:
+            raise ValueError("%s: start lives on %s, the snapshots on device %d" % (who, start.device, self._engine.device_id))
+        if start.dim() != 3 or tuple(start.shape) != (n_sel, self.nVerts, 3) or not start.is_contiguous():
+            raise ValueError("%s: start of shape %s: a contiguous (%d, %d, 3) expected" % (who, tuple(start.shape), n_sel, self.nVerts))
+        return 2, start
+
+    def _solve_run(self, plan, red, frames, ex, begin, K, chunk_frames, history):
+        """The solve (matrix on the device); ``red``: None or the ``Reduced`` with its ``op``; ``begin``: what ``_solve_start`` gave."""
+        eng = self._engine
+        code, start = begin
+        if code == 2:
+            import torch
+            torch.cuda.current_stream(start.device).synchronize()   # whatever produced start is done before the engine reads it
+        frames.upload(self)
+        eng.pdsolve_begin(*frames.args(self), ex.diag, ex.mode, ex.acc, code, None if start is None else start.data_ptr())
+        for i, t in enumerate(plan):
+            if red is not None and red.index == i:
+                eng.cproj_setup(_proj.subset_setup(red.setup, red.op.elements))
+                eng.rforce_solver(red.op.H, red.op.local_rows)
+                eng.pdsolve_slot(t.sigma_min, t.sigma_max, None)
+            else:
+                eng.cproj_setup(t.setup)
+                eng.pdsolve_slot(t.sigma_min, t.sigma_max, t.St)
+        out = self._alloc(frames)
+        hist = eng.pdsolve_iterate(K, 0 if chunk_frames is None else int(chunk_frames), out.data_ptr(), history)
+        self._leave(plan)
+        if history:
+            with np.errstate(divide='ignore', invalid='ignore'):
+                return out, frames.n_sel, np.sqrt(hist[:, :, 0]) / np.sqrt(hist[:, :, 1])
+        return out, frames.n_sel
+
+    def solve_frames(self, kinds, dt, num_iterations=10, masses=None, velocity="difference", gravity=(0.0, 0.0, 0.0), start="explicit",
+                     animation="train", frame_start=0, frame_end=None, frame_jump=1, chunk_frames=None, history=False):
+        """Extra: the local/global iterations of the reference's solver (Simulators.py:494-526) for every selected frame of
+        the resident animation, on the device: q_0 given, q_{k+1} = A^-1 (M / dt^2 s_f + sum_i S_i^T p_i(q_k)) for
+        ``num_iterations`` iterations, the explicit state s_f held fixed while q moves.  The iterate stays on the device
+        between iterations in the layout the projection kernels read; the kinds' tables and S^T are uploaded once per solve.
+
+        ``kinds``: the list of dicts of ``constraint_forces``; ONE entry may also carry ``basis``, ``num_components`` and
+        ``reduction`` (default "deim_pod") with the meanings of ``reduced_constraint_forces``: that kind's term is then the
+        reduced one, as the simulator's per-group ``*_reduced`` flags choose.  A is always the full matrix of all listed kinds.
+        ``dt``, ``masses``, ``velocity``, ``gravity``, ``animation``, the frame range and ``chunk_frames``: as ``global_step``.
+        ``start``: "explicit" (q_0 = s_f, the reference's), "frame" (q_0 = x_f; one iteration is then ``global_step`` bit for
+        bit) or a contiguous ``torch.float64`` device tensor (F', N, 3) -- a solve continued from an earlier result equals the
+        longer solve bit for bit.  ``history``: also the (num_iterations, F') array of |q_{k+1} - q_k| / |q_{k+1}| (Frobenius
+        norms of the frame).
+
+        Returns ``(tensor, F')`` (``(tensor, F', steps)`` with ``history``): a ``torch.float64`` device tensor (F', N, 3) in
+        world space, owned by the caller.  Device memory held by the engine beside A^-1: three times the result plus the
+        projections of one chunk.  %s"""
+        who = "solve_frames"
+        ex, K = self._solve_args(who, dt, velocity, gravity, num_iterations, start, masses)
+        frames = self._frames(animation, frame_start, frame_end, frame_jump)
+        plan, red = self._solve_plan(who, kinds, chunk_frames)
+        begin = self._solve_start(who, start, frames.n_sel)
+        if red is not None:
+            red = red._replace(op=red.operator(int(kinds[red.index]["num_components"])))
+        self._matrix(plan, ex.masses, ex.dt)
+        if red is not None:
+            self._engine.rforce_operator(red.St, red.op.V)
+        return self._solve_run(plan, red, frames, ex, begin, K, chunk_frames, history)
+
+    solve_frames.__doc__ %= _SOLVE_SCOPE
+
+    def reduced_solve_errors(self, kind, basis, r_values, dt, num_iterations=10, masses=None, velocity="difference",
+                             gravity=(0.0, 0.0, 0.0), start="explicit", elements=None, wi=1.0, reduction="deim_pod", rest_positions=None,
+                             sigma_min=1.0, sigma_max=1.0, animation="train", frame_start=0, frame_end=None, frame_jump=1,
+                             per_frame=False):
+        """Extra: how far the DEIM-reduced simulation is from the full one after the solver's iterations -- for every r of
+        ``r_values`` the three metrics of ``(q, q~_r)``, q = ``solve_frames`` of this kind and q~_r the same solve with the kind
+        reduced to r components (same A^-1, same inertia term, same start).  Arguments as ``reduced_global_step_errors`` plus
+        ``num_iterations`` and ``start``; the same five lists ``fro, max, rel_x, rel_y, rel_z`` and, with ``per_frame``, the
+        (len(r_values), F') array |q[f] - q~_r[f]| / |q[f]|.  The full solve runs once, one reduced solve per r (S^T V once, for
+        the largest r); every tensor stays on the device and is compared there.  With ``num_iterations=1, start="frame"`` these
+        are the numbers of ``reduced_global_step_errors``.  %s"""
+        who = "reduced_solve_errors"
+        ex, K = self._solve_args(who, dt, velocity, gravity, num_iterations, start, masses)
+        spec = dict(kind=kind, elements=elements, wi=wi, rest_positions=rest_positions, sigma_min=sigma_min, sigma_max=sigma_max)
+        frames = self._frames(animation, frame_start, frame_end, frame_jump)
+        terms, red = self._solve_plan(who, [dict(spec, basis=basis, num_components=0, reduction=reduction)], None)
+        begin = self._solve_start(who, start, frames.n_sel)
+        run = lambda rd: self._solve_run(terms, rd, frames, ex, begin, K, None, False)[0]
+
+        def full():
+            self._matrix(terms, ex.masses, ex.dt)
+            return run(None)
+        return self._errors(ReducedPlan(terms[0], frames, red.operator), r_values, per_frame, full,
+                            lambda op: run(red._replace(op=op)))
+
+    reduced_solve_errors.__doc__ %= _SOLVE_SCOPE

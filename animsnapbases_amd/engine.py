@@ -85,6 +85,23 @@ class HipEngine(object):
         if rc != 0:
             raise RuntimeError("libasb_hip: status %d: %s" % (rc, self.lib.asb_last_error(self.h).decode()))
 
+    @staticmethod
+    def _vec(x, shape):
+        """``x`` as a contiguous float64 array of that shape.  (``ptr`` is a bare address: the caller keeps the result in a
+        local for the length of the C call.)"""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        assert x.shape == shape
+        return x
+
+    def _invm(self, inv_massL):
+        return None if inv_massL is None else self._vec(inv_massL, (self.N_glob,))
+
+    @staticmethod
+    def _csr(M):
+        """(rows, indptr, indices, data) of a scipy CSR matrix as the C ABI reads them."""
+        return (int(M.shape[0]), np.ascontiguousarray(M.indptr, dtype=np.int64), np.ascontiguousarray(M.indices, dtype=np.int64),
+                np.ascontiguousarray(M.data, dtype=np.float64))
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.asb_destroy(self.h)      # (synchronises the copy stream; a caller-owned pinned buffer is not freed there)
@@ -497,9 +514,7 @@ class HipEngine(object):
             out["frame_err"] = np.empty((n_sel, n))
             if normals:
                 out["angle"] = np.empty((n_sel, n))
-        if inv_massL is not None:
-            inv_massL = np.ascontiguousarray(inv_massL, dtype=np.float64)
-            assert inv_massL.shape == (self.N_glob,)
+        inv_massL = self._invm(inv_massL)
         self._ck(self.lib.asb_onmesh_run(self.h, int(which), int(r), int(f0), int(f1), int(fj), int(bool(normals)),
                                          ptr(inv_massL), int(bool(add_mean)), float(psf), float(denom),
                                          ptr(out["accum_norm"]), ptr(out["mesh_num"]), ptr(out["mesh_den"]),
@@ -516,9 +531,7 @@ class HipEngine(object):
     def cproj_run(self, which, f0, f1, fj, inv_massL, add_mean, psf, sigma_min, sigma_max, out_dev_ptr):
         """The projections of the frames range(f0, f1, fj) of the training (which 0) or held-out (1) tensor into the caller's
         device buffer of (F', rows, 3) float64."""
-        if inv_massL is not None:
-            inv_massL = np.ascontiguousarray(inv_massL, dtype=np.float64)
-            assert inv_massL.shape == (self.N_glob,)
+        inv_massL = self._invm(inv_massL)
         self._ck(self.lib.asb_cproj_run(self.h, int(which), int(f0), int(f1), int(fj), ptr(inv_massL), int(bool(add_mean)),
                                         float(psf), float(sigma_min), float(sigma_max), ctypes.c_void_p(int(out_dev_ptr))))
 
@@ -526,14 +539,10 @@ class HipEngine(object):
         """The constraint forces S^T p of the same frames for the kind of the last ``cproj_setup`` into (or, ``accumulate``,
         onto) the caller's device buffer of (F', N, 3) float64.  ``St``: scipy CSR (N, rows) with sorted indices;
         ``chunk_frames``: frames per pass, 0 = automatic."""
-        if inv_massL is not None:
-            inv_massL = np.ascontiguousarray(inv_massL, dtype=np.float64)
-            assert inv_massL.shape == (self.N_glob,)
-        indptr = np.ascontiguousarray(St.indptr, dtype=np.int64)
-        indices = np.ascontiguousarray(St.indices, dtype=np.int64)
-        data = np.ascontiguousarray(St.data, dtype=np.float64)
+        inv_massL = self._invm(inv_massL)
+        n, indptr, indices, data = self._csr(St)
         self._ck(self.lib.asb_cforce_run(self.h, int(which), int(f0), int(f1), int(fj), ptr(inv_massL), int(bool(add_mean)),
-                                         float(psf), float(sigma_min), float(sigma_max), int(St.shape[0]), ptr(indptr),
+                                         float(psf), float(sigma_min), float(sigma_max), n, ptr(indptr),
                                          ptr(indices), ptr(data), int(bool(accumulate)), int(chunk_frames),
                                          ctypes.c_void_p(int(out_dev_ptr))))
 
@@ -542,10 +551,8 @@ class HipEngine(object):
         """M_d = S^T V_d on the device for ``St`` (scipy CSR (N, rows), sorted indices) and ``V`` (rows, mp, 3)."""
         V = np.ascontiguousarray(V, dtype=np.float64)
         assert V.ndim == 3 and V.shape[2] == 3
-        indptr = np.ascontiguousarray(St.indptr, dtype=np.int64)
-        indices = np.ascontiguousarray(St.indices, dtype=np.int64)
-        data = np.ascontiguousarray(St.data, dtype=np.float64)
-        self._ck(self.lib.asb_rforce_operator(self.h, int(St.shape[0]), ptr(indptr), ptr(indices), ptr(data), int(V.shape[0]),
+        n, indptr, indices, data = self._csr(St)
+        self._ck(self.lib.asb_rforce_operator(self.h, n, ptr(indptr), ptr(indices), ptr(data), int(V.shape[0]),
                                               int(V.shape[1]), ptr(V)))
 
     def rforce_solver(self, H, rows):
@@ -558,9 +565,7 @@ class HipEngine(object):
     def rforce_run(self, which, f0, f1, fj, inv_massL, add_mean, psf, sigma_min, sigma_max, accumulate, out_dev_ptr):
         """The reduced constraint forces of the frames range(f0, f1, fj) into (or, ``accumulate``, onto) the caller's device
         buffer of (F', N, 3) float64; ``cproj_setup`` holds the sampled elements only."""
-        if inv_massL is not None:
-            inv_massL = np.ascontiguousarray(inv_massL, dtype=np.float64)
-            assert inv_massL.shape == (self.N_glob,)
+        inv_massL = self._invm(inv_massL)
         self._ck(self.lib.asb_rforce_run(self.h, int(which), int(f0), int(f1), int(fj), ptr(inv_massL), int(bool(add_mean)),
                                          float(psf), float(sigma_min), float(sigma_max), int(bool(accumulate)),
                                          ctypes.c_void_p(int(out_dev_ptr))))
@@ -578,12 +583,10 @@ class HipEngine(object):
     def gstep_setup(self, A):
         """Inverts ``A`` (scipy CSR (N, N), sorted indices, symmetric positive definite) on the device; the inverse stays with
         the context.  Returns max |A (A^-1 1) - 1|."""
-        indptr = np.ascontiguousarray(A.indptr, dtype=np.int64)
-        indices = np.ascontiguousarray(A.indices, dtype=np.int64)
-        data = np.ascontiguousarray(A.data, dtype=np.float64)
+        n, indptr, indices, data = self._csr(A)
         res = ctypes.c_double()
         self._gstep = None
-        self._ck(self.lib.asb_gstep_setup(self.h, int(A.shape[0]), ptr(indptr), ptr(indices), ptr(data), ctypes.byref(res)))
+        self._ck(self.lib.asb_gstep_setup(self.h, n, ptr(indptr), ptr(indices), ptr(data), ctypes.byref(res)))
         self._gstep = (indptr.copy(), indices.copy(), data.copy(), res.value)      # (copies: A stays the caller's)
         return res.value
 
@@ -602,12 +605,8 @@ class HipEngine(object):
 
     def gstep_inertia(self, which, f0, f1, fj, inv_massL, add_mean, psf, diag, mode, acc, rhs_dev_ptr):
         """rhs += diag * s for the frames range(f0, f1, fj): s = x + acc (``mode`` 0) or 2 x - x_prev + acc (1)."""
-        if inv_massL is not None:
-            inv_massL = np.ascontiguousarray(inv_massL, dtype=np.float64)
-            assert inv_massL.shape == (self.N_glob,)
-        diag = np.ascontiguousarray(diag, dtype=np.float64)
-        acc = np.ascontiguousarray(acc, dtype=np.float64)
-        assert diag.shape == (self.N_glob,) and acc.shape == (3,)
+        inv_massL = self._invm(inv_massL)
+        diag, acc = self._vec(diag, (self.N_glob,)), self._vec(acc, (3,))
         self._ck(self.lib.asb_gstep_inertia(self.h, int(which), int(f0), int(f1), int(fj), ptr(inv_massL), int(bool(add_mean)),
                                             float(psf), ptr(diag), int(mode), ptr(acc), ctypes.c_void_p(int(rhs_dev_ptr))))
 
@@ -622,12 +621,8 @@ class HipEngine(object):
         """Begins a solve over the frames range(f0, f1, fj) after ``gstep_setup``: the inertia term diag * s (``mode``, ``acc`` as
         ``gstep_inertia``) and the iterate, started at s (``start`` 0), at the frame (1) or at the caller's device buffer of
         (F', N, 3) float64 (2)."""
-        if inv_massL is not None:
-            inv_massL = np.ascontiguousarray(inv_massL, dtype=np.float64)
-            assert inv_massL.shape == (self.N_glob,)
-        diag = np.ascontiguousarray(diag, dtype=np.float64)
-        acc = np.ascontiguousarray(acc, dtype=np.float64)
-        assert diag.shape == (self.N_glob,) and acc.shape == (3,)
+        inv_massL = self._invm(inv_massL)
+        diag, acc = self._vec(diag, (self.N_glob,)), self._vec(acc, (3,))
         self._pd_frames = None
         self._ck(self.lib.asb_pdsolve_begin(self.h, int(which), int(f0), int(f1), int(fj), ptr(inv_massL), int(bool(add_mean)),
                                             float(psf), ptr(diag), int(mode), ptr(acc), int(start),
@@ -640,10 +635,8 @@ class HipEngine(object):
         if St is None:
             self._ck(self.lib.asb_pdsolve_slot(self.h, float(sigma_min), float(sigma_max), 1, 0, None, None, None))
             return
-        indptr = np.ascontiguousarray(St.indptr, dtype=np.int64)
-        indices = np.ascontiguousarray(St.indices, dtype=np.int64)
-        data = np.ascontiguousarray(St.data, dtype=np.float64)
-        self._ck(self.lib.asb_pdsolve_slot(self.h, float(sigma_min), float(sigma_max), 0, int(St.shape[0]), ptr(indptr), ptr(indices),
+        n, indptr, indices, data = self._csr(St)
+        self._ck(self.lib.asb_pdsolve_slot(self.h, float(sigma_min), float(sigma_max), 0, n, ptr(indptr), ptr(indices),
                                            ptr(data)))
 
     def pdsolve_iterate(self, n_iter, chunk_frames=0, out_dev_ptr=None, history=False):
@@ -1087,10 +1080,8 @@ class HipEngine(object):
         """The sparse differential operator S^T (scipy sparse, |V| x e p) as CSR on the device."""
         St = St.tocsr()
         St.sort_indices()
-        indptr = np.ascontiguousarray(St.indptr, dtype=np.int64)
-        indices = np.ascontiguousarray(St.indices, dtype=np.int64)
-        data = np.ascontiguousarray(St.data, dtype=np.float64)
-        self._ck(self.lib.asb_st_upload(self.h, int(St.shape[0]), int(St.shape[1]), int(data.shape[0]), ptr(indptr),
+        n, indptr, indices, data = self._csr(St)
+        self._ck(self.lib.asb_st_upload(self.h, n, int(St.shape[1]), int(data.shape[0]), ptr(indptr),
                                         ptr(indices), ptr(data)))
 
     def st_residual_argmax(self):

@@ -55,10 +55,10 @@ def main():
     eng = snaps._engine
     # the parts alone
     snaps.global_solve_setup([spec], dt, masses)
-    plan, _, end = snaps._cforce_plan([spec], "train", 0, None, 1)
-    b, _ = snaps._cforce_run(plan, None, 0, end, 1, None)
+    term, = snaps._plan([spec])
+    b = snaps._cforce_run([term], snaps._frames("train", 0, None, 1), None)
     out = torch.empty_like(b)
-    setup, St, smin, smax = plan[0][1], plan[0][2], plan[0][3], plan[0][4]
+    setup, St, smin, smax = term.setup, term.St, term.sigma_min, term.sigma_max
     eng.cproj_setup(setup)
     cforce_ms = best_of_3(torch, lambda: eng.cforce_run(0, 0, F, 1, None, False, 1.0, smin, smax, St, False, 0, b.data_ptr()))
     eng.gstep_run(b.data_ptr(), F, out.data_ptr())
