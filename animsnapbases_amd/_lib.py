@@ -180,6 +180,8 @@ PROTOTYPES = {
                                   ctypes.c_void_p]),
     "asb_pdsolve_slot": (c_int, [ctypes.c_void_p, c_dbl, c_dbl, c_int, c_i64, c_dp, c_dp, c_dp]),
     "asb_pdsolve_iterate": (c_int, [ctypes.c_void_p, c_i64, c_i64, ctypes.c_void_p, c_dp]),
+    "asb_hyper_operator": (c_int, [ctypes.c_void_p]),
+    "asb_hyper_iterate": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_i64, ctypes.c_void_p]),
     "asb_splocs_begin": (c_int, [ctypes.c_void_p]),
     "asb_splocs_gram": (c_int, [ctypes.c_void_p, c_dp, c_dp, ctypes.POINTER(c_dbl)]),
     "asb_splocs_weights": (c_int, [ctypes.c_void_p, c_dp, c_dp, c_dp, c_dp]),

@@ -344,6 +344,10 @@ struct asb_ctx {
     int64_t gs_n = 0, gs_Np = 0;      // its vertices (0: no set-up); rounded up to the kernel's 32
     double* gs_diag = nullptr;        // (n_loc) asb_gstep_inertia: masses / h^2
     asb_pds* pds = nullptr;           // the solve in progress and its buffers (asb_pdsolve.hip)
+    // hyper-reduced iterations (asb_pdsolve.hip): G_d^T = (A^-1 M_d)^T in rf_M's layout, (3, rf_mpp, rf_Np)
+    double* hy_G = nullptr;
+    int hy_ok = 0;                    // hy_G belongs to the current gs_Ainv and rf_M (asb_gstep_setup / asb_rforce_operator clear it)
+    int64_t cp_vmax = -1;             // largest vertex the last asb_cproj_setup names (elements and star edges)
 
     // ---- profiling of the dominant streaming kernel ----
     bool prof = false;
@@ -440,6 +444,8 @@ void asb_st_apply_launch(asb_ctx* ctx, const int* ptr, const int* ci, const doub
 // k_rforce_gemm with the context's operator and solver, from the element-major projections S (coefficients into ctx->rf_coef)
 long long asb_rforce_chunk_width(asb_ctx* ctx, long long n_cols, long long n_sel);
 void asb_rforce_chunk_launch(asb_ctx* ctx, const double* S, int cw, int c0, int cn, int accumulate, double* out);
+// its first half alone: k_rforce_coef of one chunk into ctx->rf_coef ((3, rf_r rounded up to 4, cw), zero past row rf_r and frame cn)
+void asb_rforce_coef_launch(asb_ctx* ctx, const double* S, int cw, int cn);
 // asb_gstep.hip: k_gs_inertia on device arrays; add: out += diag s, otherwise out = diag s (the value the sum adds)
 void asb_gs_inertia_launch(asb_ctx* ctx, const CpWorld& w, int f0, int fj, int n_sel, long long n, const double* diag_dev, int mode,
                            const double* acc3, bool add, double* out);

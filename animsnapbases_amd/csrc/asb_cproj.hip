@@ -289,11 +289,13 @@ extern "C" int asb_cproj_setup(asb_ctx* ctx, int kind, int64_t n_elem, const int
     const long long n_loc = ctx->n_loc;
     if (n_loc > 0x7fffffffLL || n_elem > 0x7fffffffLL / 16) ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_cproj_setup: too large for 32-bit indices");
     ctx->cp_kind = -1;
+    int64_t vmax = -1;
     std::vector<int> i32((size_t)n_elem * nv), p32, s32;
     for (int64_t i = 0; i < n_elem * nv; ++i) {
         if (idx[i] < 0 || idx[i] >= n_loc)
             ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cproj_setup: element %lld names vertex %lld of %lld", (long long)(i / nv), (long long)idx[i], n_loc);
         i32[i] = (int)idx[i];
+        if (idx[i] > vmax) vmax = idx[i];
     }
     int64_t nnz = 0;
     if (kind == CP_BEND) {
@@ -310,6 +312,7 @@ extern "C" int asb_cproj_setup(asb_ctx* ctx, int kind, int64_t n_elem, const int
             if (star_idx[i] < 0 || star_idx[i] >= n_loc)
                 ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cproj_setup: star edge %lld names vertex %lld of %lld", (long long)i, (long long)star_idx[i], n_loc);
             s32[i] = (int)star_idx[i];
+            if (star_idx[i] > vmax) vmax = star_idx[i];
         }
     }
     ASB_HIP(ctx, hipSetDevice(ctx->dev));
@@ -327,6 +330,7 @@ extern "C" int asb_cproj_setup(asb_ctx* ctx, int kind, int64_t n_elem, const int
     ctx->cp_kind = kind;
     ctx->cp_n = n_elem;
     ctx->cp_verts = n_loc;
+    ctx->cp_vmax = vmax;
     return ASB_OK;
 }
 

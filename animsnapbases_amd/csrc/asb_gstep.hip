@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void k_gs_resid(const int* __restrict__ ptr, c
 
 extern "C" int asb_gstep_setup(asb_ctx* ctx, int64_t n, const int64_t* indptr, const int64_t* indices, const double* data, double* resid_out) {
     if (!ctx || !indptr || n < 1) return ASB_ERR_ARG;
-    ctx->gs_n = 0;
+    ctx->gs_n = 0, ctx->hy_ok = 0;
     if (n > GS_MAX_N)
         ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_gstep_setup: %lld vertices are too many for an explicit inverse (at most %d)", (long long)n, GS_MAX_N);
     if (!ctx->X || ctx->v0 != 0 || ctx->n_loc != ctx->N_glob)

@@ -46,6 +46,7 @@ struct PdSlot {
     int *st_ptr = nullptr, *st_idx = nullptr;                   // the CSR of S^T (not for the reduced kind)
     double* st_val = nullptr;
     double smin = 1.0, smax = 1.0;
+    long long vmax = -1;                                        // the largest vertex its tables name
 };
 
 struct asb_pds {
@@ -53,6 +54,9 @@ struct asb_pds {
     long long n = 0, n_sel = 0, ld = 0;
     double *ms = nullptr, *Q = nullptr, *b = nullptr;
     double *part = nullptr, *hist = nullptr;      // (vertex tiles, n_sel, 2) records of one iteration; (iterations, n_sel, 2)
+    // asb_hyper_iterate: c = A^-1 ms (3 N, ld) vertex-major like Q; the touched rows of Q and c (3 N_t, ld) and the touched
+    // columns of G^T (3, mpp, N_t rounded up to 32, zero padding)
+    double *c = nullptr, *Qc = nullptr, *cc = nullptr, *Gc = nullptr;
     int n_slots = 0;
     PdSlot slot[PD_MAX_SLOTS];
 };
@@ -277,7 +281,7 @@ extern "C" int asb_pdsolve_slot(asb_ctx* ctx, double sigma_min, double sigma_max
     pd_swap(ctx, &ctx->cp_sptr, &p.sptr);
     pd_swap(ctx, &ctx->cp_sidx, &p.sidx);
     p.kind = ctx->cp_kind, p.n_elem = ctx->cp_n, p.n_cols = n_cols, p.reduced = reduced ? 1 : 0;
-    p.smin = sigma_min, p.smax = sigma_max;
+    p.smin = sigma_min, p.smax = sigma_max, p.vmax = ctx->cp_vmax;
     ctx->cp_kind = -1;
     ++s->n_slots;
     return ASB_OK;
@@ -342,6 +346,241 @@ extern "C" int asb_pdsolve_iterate(asb_ctx* ctx, int64_t n_iter, int64_t chunk_f
     ASB_CHECK_LAUNCH(ctx);
     if (hist_out)
         ASB_HIP(ctx, hipMemcpyAsync(hist_out, s->hist, (size_t)n_iter * n_sel * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the caller owns out_dev and may read it on any stream
+    return ASB_OK;
+}
+
+// ================================================================ hyper-reduced iterations
+// When the solve's only kind is reduced, an iteration is affine in the coefficients: per coordinate d
+//   q_{k+1} = c + G_d coef_d(q_k),   c = A^-1 ms (once per solve),   G_d = A^-1 M_d (N x mp, once per matrix and basis),
+// and coef(q_k) reads q_k at the vertices of the sampled elements only -- the TOUCHED vertices.  Iterations 1 .. K-1 therefore
+// run on the touched rows of c, G and q (compact buffers of N_t vertices, the element tables renumbered by the host); only
+// the last iteration expands to all N rows.  No N^2 product is left in the loop.
+//
+//   asb_hyper_operator    k_hy_operator: Gt_d[j][m] = sum_n A^-1[n][m] M_d[n][j], one thread per (m, 8 values of j), n ascending,
+//                         one FMA accumulator per entry, never split.  Stored like rf_M, (3, mpp, Np), zero padding.  Marked
+//                         valid; asb_gstep_setup and asb_rforce_operator clear the mark, and a stale G is refused.
+//   asb_hyper_iterate     c by ONE launch of k_pdsolve_gemm<false, false> on ms (gs_contract, vertex-major epilogue) into a buffer
+//                         shaped like Q.  touched given: k_hy_gather_rows copies the touched rows of Q and c, k_hy_gather_cols
+//                         the touched columns of Gt.  Then per iteration and chunk of frames three launches: k_cproj_em on the
+//                         (compact) iterate, k_rforce_coef, k_hyper_apply.  No host-to-device copy, no synchronisation in the loop.
+//   k_hyper_apply         Q'[3 v + d][f] = fl(c[3 v + d][f] + acc), acc = sum_j G_d[v][j] coef_d[j][f] from 0 over j = 0 .. rpp
+//                         in order: v_mfma_f64_16x16x4_f64 with A = G (vertices x j) and B = coef (j x frames), the roles of
+//                         k_rforce_gemm swapped, so that an accumulator row is a vertex and its 16 lanes run along 16 contiguous
+//                         frames.  A block of 4 waves owns 32 vertices x 64 frames x 3 coordinates (wave w: frames 16 w ..).
+//                         The vertex-major store is DIRECT, no LDS: a store instruction of a wave writes four 128-byte runs (16
+//                         frames of rows g, g + 4, ..), each a whole aligned cache line of Q -- staging could only widen the
+//                         runs to 512 bytes at the price of a barrier and 24 KB of LDS.  c is read with the same addresses.
+//                         FM (the last iteration): the same values fl(c + acc) are also staged frame-major in LDS, rows of 97
+//                         doubles (the 16 lanes of a ds_write_b64 pass sit 97 doubles apart: odd, 16 different bank pairs),
+//                         and written per frame as its contiguous run of 96 doubles, as gs_store_fm does.
+//                         Tail predicates: vertices >= nv, frames >= cn of the chunk; the padding columns of Q are never
+//                         written.  An entry's value does not depend on the tile, chunk or row set it falls in: "touched" and
+//                         "all" give the same bits.  No atomics.
+#define HY_TF 64
+#define HY_TN 32
+#define HY_JB 8
+
+// grid (blocks of 256 over n, mp / HY_JB, 3)
+__global__ __launch_bounds__(256) void k_hy_operator(const double* __restrict__ Ainv, int n, int np, const double* __restrict__ Mt,
+                                                     long long Np, int mp, int mpp, double* __restrict__ Gt) {
+    const int m = (int)blockIdx.x * 256 + threadIdx.x;
+    const int j0 = (int)blockIdx.y * HY_JB, d = blockIdx.z;
+    if (m >= n) return;
+    const double* row = Mt + ((long long)d * mpp + j0) * Np;
+    double a[HY_JB];
+#pragma unroll
+    for (int q = 0; q < HY_JB; ++q) a[q] = 0.0;
+    for (int k = 0; k < n; ++k) {                 // ascending n, one accumulator per entry
+        const double x = Ainv[(long long)k * np + m];
+#pragma unroll
+        for (int q = 0; q < HY_JB; ++q)
+            if (j0 + q < mp) a[q] = fma(x, row[q * Np + k], a[q]);
+    }
+#pragma unroll
+    for (int q = 0; q < HY_JB; ++q)
+        if (j0 + q < mp) Gt[((long long)d * mpp + j0 + q) * Np + m] = a[q];
+}
+
+// grid (3 nt, ld / 64), one wave: row 3 tv[t] + d of src (ld doubles, the padding included) -> row 3 t + d of dst
+__global__ __launch_bounds__(64) void k_hy_gather_rows(const double* __restrict__ src, const int* __restrict__ tv, long long ld,
+                                                       double* __restrict__ dst) {
+    const long long r = blockIdx.x, col = (long long)blockIdx.y * 64 + threadIdx.x;
+    dst[r * ld + col] = src[(3LL * tv[r / 3] + r % 3) * ld + col];
+}
+
+// grid (rows, blocks of 64 over ntp), one wave: column tv[t] of src (rows x Np) -> column t of dst (rows x ntp), 0 for t >= nt
+__global__ __launch_bounds__(64) void k_hy_gather_cols(const double* __restrict__ src, long long Np, const int* __restrict__ tv, int nt, int ntp,
+                                                       double* __restrict__ dst) {
+    const long long r = blockIdx.x;
+    const int t = (int)blockIdx.y * 64 + threadIdx.x;
+    if (t < ntp) dst[r * ntp + t] = t < nt ? src[r * Np + tv[t]] : 0.0;
+}
+
+// grid (ldg / HY_TN covering nv, frame tiles of the chunk).  Gt (3, mpp, ldg), ldg a multiple of HY_TN, zero past nv; coef (3, rpp,
+// cw), cw a multiple of HY_TF, zero past row r and frame cn; c, Q (3 nv, ld); out (n_sel, nv, 3) with FM
+template <bool FM>
+__global__ __launch_bounds__(256) void k_hyper_apply(const double* __restrict__ Gt, long long ldg, int mpp, const double* __restrict__ coef,
+                                                     int cw, int rpp, const double* __restrict__ c, double* __restrict__ Q, long long ld,
+                                                     int c0, int cn, int nv, double* __restrict__ out) {
+    constexpr int RUN = HY_TN * 3, ROW = RUN + 1;
+    __shared__ double stage[FM ? HY_TF * ROW : 1];
+    const int lane = threadIdx.x & 63, i = lane & 15, g = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int v0 = (int)blockIdx.x * HY_TN;
+    const int t0 = (int)blockIdx.y * HY_TF;
+    d4 acc[3][2];
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+#pragma unroll
+        for (int y = 0; y < 2; ++y) acc[d][y] = d4{0.0, 0.0, 0.0, 0.0};
+    const double* pa = Gt + v0 + i;                       // A: vertex i of 16, k = g
+    const double* pb = coef + t0 + wave * 16 + i;         // B: k = g, frame i of the wave's 16
+    for (int k0 = 0; k0 < rpp; k0 += 4) {
+        const int k = k0 + g;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            const double* a = pa + ((long long)d * mpp + k) * ldg;
+            const double b = pb[((long long)d * rpp + k) * cw];
+            acc[d][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[0], b, acc[d][0], 0, 0, 0);
+            acc[d][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[16], b, acc[d][1], 0, 0, 0);
+        }
+    }
+    // accumulator q of lane (i, g): vertex g + 4 q of the 16, frame i of the wave's 16
+    const int fl = wave * 16 + i;
+    const bool fok = t0 + fl < cn;
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+#pragma unroll
+        for (int y = 0; y < 2; ++y)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int vl = 16 * y + g + 4 * q;
+                double val = 0.0;
+                if (fok && v0 + vl < nv) {
+                    const long long at = (3LL * (v0 + vl) + d) * ld + c0 + t0 + fl;
+                    val = c[at] + acc[d][y][q];
+                    Q[at] = val;
+                }
+                if (FM) stage[fl * ROW + vl * 3 + d] = val;
+            }
+    if (FM) {
+        __syncthreads();
+        const int nvt = nv - v0 < HY_TN ? nv - v0 : HY_TN;
+        const int nf = cn - t0 < HY_TF ? cn - t0 : HY_TF;
+        const int run = nvt * 3;
+        for (int e = threadIdx.x; e < HY_TF * RUN; e += 256) {
+            const int f = e / RUN, k = e % RUN;
+            if (f < nf && k < run) out[((long long)(c0 + t0 + f) * nv + v0) * 3 + k] = stage[f * ROW + k];
+        }
+    }
+}
+
+extern "C" int asb_hyper_operator(asb_ctx* ctx) {
+    if (!ctx) return ASB_ERR_ARG;
+    ctx->hy_ok = 0;
+    if (ctx->gs_n < 1 || !ctx->gs_Ainv) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_operator: no inverse on the device (asb_gstep_setup)");
+    if (ctx->rf_mp < 1 || !ctx->rf_M) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_operator: no operator S^T V on the device (asb_rforce_operator)");
+    if (ctx->rf_n != ctx->gs_n || ctx->gs_n != ctx->n_loc)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_operator: the inverse has %lld rows, S^T V %lld, the tensor %lld vertices", (long long)ctx->gs_n,
+                 (long long)ctx->rf_n, (long long)ctx->n_loc);
+    const long long jb = (ctx->rf_mp + HY_JB - 1) / HY_JB;
+    if (jb > 65535) ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_hyper_operator: %lld basis vectors (at most %d)", (long long)ctx->rf_mp, 65535 * HY_JB);
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    const size_t len = (size_t)3 * ctx->rf_mpp * ctx->rf_Np;
+    int rc;
+    if ((rc = asb_alloc(ctx, &ctx->hy_G, len))) return rc;
+    ASB_HIP(ctx, hipMemsetAsync(ctx->hy_G, 0, len * sizeof(double), ctx->stream));
+    hipLaunchKernelGGL(k_hy_operator, dim3((unsigned)((ctx->gs_n + 255) / 256), (unsigned)jb, 3), dim3(256), 0, ctx->stream, ctx->gs_Ainv,
+                       (int)ctx->gs_n, (int)ctx->gs_Np, ctx->rf_M, (long long)ctx->rf_Np, (int)ctx->rf_mp, (int)ctx->rf_mpp, ctx->hy_G);
+    ASB_CHECK_LAUNCH(ctx);
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->hy_ok = 1;
+    return ASB_OK;
+}
+
+extern "C" int asb_hyper_iterate(asb_ctx* ctx, int64_t n_iter, int64_t n_touched, const int64_t* touched, int64_t chunk_frames,
+                                 double* out_dev) {
+    if (!ctx) return ASB_ERR_ARG;
+    asb_pds* s = ctx->pds;
+    if (!s || !s->begun || s->n_slots < 1) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: no solve begun or no kind registered (asb_pdsolve_begin, asb_pdsolve_slot)");
+    if (s->n_slots != 1 || !s->slot[0].reduced)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: %d kinds, %s: every kind must be reduced, which today means exactly one kind", s->n_slots,
+                 s->slot[0].reduced ? "one of them reduced" : "the first not reduced");
+    if (n_iter < 1 || n_iter > (1 << 20)) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: %lld iterations", (long long)n_iter);
+    if (chunk_frames < 0) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: chunk_frames %lld", (long long)chunk_frames);
+    if (ctx->gs_n != s->n || !ctx->gs_Ainv || ctx->n_loc != s->n)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: the inverse or the tensor changed since asb_pdsolve_begin");
+    const PdSlot& p = s->slot[0];
+    if (ctx->rf_mp < 1 || ctx->rf_r < 1 || ctx->rf_n != s->n || ctx->rf_pt_max >= p.n_cols)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: the operator or solver changed since asb_pdsolve_slot");
+    if (!ctx->hy_ok || !ctx->hy_G)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: no operator A^-1 S^T V for the inverse and the basis on the device (asb_hyper_operator "
+                                   "after asb_gstep_setup and asb_rforce_operator): a stale one is refused");
+    const long long n = s->n, n_sel = s->n_sel, ld = s->ld;
+    const bool compact = touched != nullptr;
+    const long long nt = compact ? n_touched : n;
+    if (compact) {
+        if (nt < 1 || nt > n) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: %lld touched vertices of %lld", (long long)nt, n);
+        for (long long t = 0; t < nt; ++t)
+            if (touched[t] < 0 || touched[t] >= n || (t > 0 && touched[t] <= touched[t - 1]))
+                ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: touched[%lld] = %lld: ascending vertices of 0..%lld", t, (long long)touched[t], n - 1);
+    }
+    if (p.vmax >= nt)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: the element set-up names vertex %lld, the iterate has %lld rows", p.vmax, nt);
+    const int r = (int)ctx->rf_r, rpp = (r + 3) / 4 * 4, mpp = (int)ctx->rf_mpp;
+    long long cw = asb_rforce_chunk_width(ctx, p.n_cols, n_sel);
+    if (chunk_frames > 0) cw = std::min<long long>(cw, (chunk_frames + HY_TF - 1) / HY_TF * HY_TF);
+    const long long ntp = (nt + HY_TN - 1) / HY_TN * HY_TN;
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    int rc;
+    if ((rc = asb_alloc(ctx, &ctx->cf_scratch, (size_t)3 * p.n_cols * cw))) return rc;
+    if ((rc = asb_alloc(ctx, &ctx->rf_coef, (size_t)3 * rpp * cw))) return rc;
+    if ((rc = asb_alloc(ctx, &s->c, (size_t)3 * n * ld))) return rc;
+    ASB_HIP(ctx, hipMemsetAsync(s->c, 0, (size_t)3 * n * ld * sizeof(double), ctx->stream));
+    hipLaunchKernelGGL((k_pdsolve_gemm<false, false>), dim3((unsigned)(ctx->gs_Np / GS_TN), (unsigned)((n_sel + GS_TF - 1) / GS_TF)), dim3(256), 0,
+                       ctx->stream, s->ms, ctx->gs_Ainv, (int)n, (int)ctx->gs_Np, n_sel, s->c, ld, nullptr, nullptr);
+    asb_tmp<int> tv;
+    double *Qi = s->Q, *ci = s->c, *Gi = ctx->hy_G;     // what iterations 1 .. K-1 run on
+    long long ldg = ctx->rf_Np;
+    if (compact) {
+        std::vector<int> t32((size_t)nt);
+        for (long long t = 0; t < nt; ++t) t32[t] = (int)touched[t];
+        if ((rc = tv.alloc(ctx, (size_t)nt))) return rc;
+        if ((rc = asb_alloc(ctx, &s->Qc, (size_t)3 * nt * ld))) return rc;
+        if ((rc = asb_alloc(ctx, &s->cc, (size_t)3 * nt * ld))) return rc;
+        if ((rc = asb_alloc(ctx, &s->Gc, (size_t)3 * mpp * ntp))) return rc;
+        ASB_HIP(ctx, hipMemcpyAsync(tv.get(), t32.data(), (size_t)nt * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        const dim3 gr((unsigned)(3 * nt), (unsigned)(ld / 64));
+        hipLaunchKernelGGL(k_hy_gather_rows, gr, dim3(64), 0, ctx->stream, s->Q, tv.get(), ld, s->Qc);
+        hipLaunchKernelGGL(k_hy_gather_rows, gr, dim3(64), 0, ctx->stream, s->c, tv.get(), ld, s->cc);
+        hipLaunchKernelGGL(k_hy_gather_cols, dim3((unsigned)(3 * mpp), (unsigned)((ntp + 63) / 64)), dim3(64), 0, ctx->stream, ctx->hy_G,
+                           (long long)ctx->rf_Np, tv.get(), (int)nt, (int)ntp, s->Gc);
+        ASB_CHECK_LAUNCH(ctx);
+        ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));      // (the staging vector dies here, before the loop)
+        Qi = s->Qc, ci = s->cc, Gi = s->Gc, ldg = ntp;
+    }
+    const CpTables tb = {p.kind, p.n_elem, p.idx, p.sptr, p.sidx, p.table};
+    const CpWorld wq = {Qi, ld, nullptr, nullptr, 1.0};
+    for (int64_t it = 0; it < n_iter; ++it) {
+        const bool last = it == n_iter - 1;
+        for (long long c0 = 0; c0 < n_sel; c0 += cw) {
+            const int cn = (int)(c0 + cw < n_sel ? cw : n_sel - c0);
+            asb_cproj_em_launch_t(ctx, tb, wq, 0, 1, (int)c0, cn, (int)cw, p.smin, p.smax, ctx->cf_scratch);
+            asb_rforce_coef_launch(ctx, ctx->cf_scratch, (int)cw, cn);
+            const unsigned gy = (unsigned)((cn + HY_TF - 1) / HY_TF);
+            if (!last)
+                hipLaunchKernelGGL((k_hyper_apply<false>), dim3((unsigned)(ntp / HY_TN), gy), dim3(256), 0, ctx->stream, Gi, ldg, mpp, ctx->rf_coef,
+                                   (int)cw, rpp, ci, Qi, ld, (int)c0, cn, (int)nt, nullptr);
+            else if (out_dev)
+                hipLaunchKernelGGL((k_hyper_apply<true>), dim3((unsigned)(ctx->rf_Np / HY_TN), gy), dim3(256), 0, ctx->stream, ctx->hy_G,
+                                   (long long)ctx->rf_Np, mpp, ctx->rf_coef, (int)cw, rpp, s->c, s->Q, ld, (int)c0, cn, (int)n, out_dev);
+            else
+                hipLaunchKernelGGL((k_hyper_apply<false>), dim3((unsigned)(ctx->rf_Np / HY_TN), gy), dim3(256), 0, ctx->stream, ctx->hy_G,
+                                   (long long)ctx->rf_Np, mpp, ctx->rf_coef, (int)cw, rpp, s->c, s->Q, ld, (int)c0, cn, (int)n, nullptr);
+        }
+    }
+    ASB_CHECK_LAUNCH(ctx);
     ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the caller owns out_dev and may read it on any stream
     return ASB_OK;
 }

@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void k_rforce_gemm(const double* __restrict__ 
 extern "C" int asb_rforce_operator(asb_ctx* ctx, int64_t n_rows, const int64_t* indptr, const int64_t* indices, const double* data,
                                    int64_t v_rows, int64_t mp, const double* V) {
     if (!ctx || !indptr || !V || n_rows < 1) return ASB_ERR_ARG;
-    ctx->rf_mp = 0, ctx->rf_r = 0;
+    ctx->rf_mp = 0, ctx->rf_r = 0, ctx->hy_ok = 0;
     if (!ctx->X || ctx->v0 != 0 || ctx->n_loc != ctx->N_glob)
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_rforce_operator: no whole tensor on the device (one rank only)");
     if (n_rows != ctx->n_loc)
@@ -193,10 +193,15 @@ long long asb_rforce_chunk_width(asb_ctx* ctx, long long n_cols, long long n_sel
     return cw > span ? span : cw;
 }
 
-void asb_rforce_chunk_launch(asb_ctx* ctx, const double* S, int cw, int c0, int cn, int accumulate, double* out) {
+void asb_rforce_coef_launch(asb_ctx* ctx, const double* S, int cw, int cn) {
     const int r = (int)ctx->rf_r, rpp = (r + 3) / 4 * 4, npt = (int)ctx->rf_npt;
     hipLaunchKernelGGL(k_rforce_coef, dim3((unsigned)(cw / 64), (unsigned)rpp, 3), dim3(64), 0, ctx->stream, ctx->rf_H, ctx->rf_pt, r, npt, rpp,
                        S, cw, cn, ctx->rf_coef);
+}
+
+void asb_rforce_chunk_launch(asb_ctx* ctx, const double* S, int cw, int c0, int cn, int accumulate, double* out) {
+    const int rpp = ((int)ctx->rf_r + 3) / 4 * 4;
+    asb_rforce_coef_launch(ctx, S, cw, cn);
     hipLaunchKernelGGL(k_rforce_gemm, dim3((unsigned)(ctx->rf_Np / RF_TN), (unsigned)((cn + RF_TF - 1) / RF_TF)), dim3(256), 0, ctx->stream,
                        ctx->rf_M, (long long)ctx->rf_Np, (int)ctx->rf_mpp, ctx->rf_coef, cw, rpp, c0, cn, (long long)ctx->rf_n, accumulate ? 1 : 0,
                        out);

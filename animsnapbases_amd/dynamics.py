@@ -188,15 +188,18 @@ class ResidentDynamics(object):
         self._engine.gstep_inertia(*frames.args(self), ex.diag, ex.mode, ex.acc, b.data_ptr())
         return self.global_solve(b)
 
-    def _errors(self, plan, r_values, per_frame, full, reduced):
+    def _errors(self, plan, r_values, per_frame, full, reduced, hyper=None):
         """The body of the ``reduced_*_errors`` methods for a ``ReducedPlan``: ``full()`` makes the full device tensor, once;
-        ``reduced(op)`` the one of a ``ReducedOperator``, S^T V of the largest r on the device by then."""
+        ``reduced(op)`` the one of a ``ReducedOperator``, S^T V of the largest r on the device by then -- and with ``hyper``
+        A^-1 S^T V of that r, formed once behind it."""
         r_values = [int(r) for r in r_values]
         ops = [plan.operator(r) for r in r_values]
         if not ops:
             return self._diff_metrics(None, [], 0, per_frame)
         ref = full()
         self._engine.rforce_operator(plan.term.St, ops[int(np.argmax(r_values))].V)
+        if hyper is not None:
+            self._engine.hyper_operator()
         out = self._diff_metrics(ref, (reduced(op) for op in ops), plan.frames.n_sel, per_frame)
         self._leave([plan.term])
         return out
@@ -395,8 +398,20 @@ class ResidentDynamics(object):
     # ------------------------------------------------------------------ the solver's iterations
     _SOLVE_SCOPE = """Out of scope, as for ``global_step``: collision handling (``resolve_collision`` and the self-collision passes),
         positional constraints, velocities carried from one solved frame into the next (every selected frame is an independent
-        solve from the animation's own x_f, x_{f-1}), the hyper-reduced operator A^-1 S^T V (a reduced iteration still pays the
-        N^2 product) and several ranks."""
+        solve from the animation's own x_f, x_{f-1}) and several ranks.
+
+        ``hyper`` (None, "touched" or "all"): the hyper-reduced operator A^-1 S^T V, as the reference's reduced simulator holds
+        its ``projecting_mat`` (Simulators.py:157-220).  With EVERY listed kind reduced the iteration is affine in the
+        coefficients, q_{k+1} = c + G coef(q_k) per coordinate with c = A^-1 M / dt^2 s_f (once per solve) and
+        G = A^-1 S^T V (N x m, once per call), and coef reads q_k only at the vertices of the sampled elements: no N^2
+        product is left in an iteration.  "touched": all but the last iteration run on those vertices' rows only, the last on
+        all N; "all": every iteration on all N rows (for checks, and for continuing with ``start=``); both give the same
+        bits.  None: the path without the operator, unchanged.  Refused with ``hyper`` (ValueError, before the device is
+        touched): a kind without ``basis`` / ``num_components`` -- every kind must be reduced, and since the engine holds one
+        reduced operator that means exactly one kind --, ``history=True`` (step norms over all rows would need the whole
+        iterate in every iteration) and an unknown value.  Out of scope for ``hyper``: several reduced kinds in one solve,
+        the history, a reduction of the positions themselves (a basis U of q), velocities carried between frames, several
+        ranks."""
 
     def _solve_args(self, who, dt, velocity, gravity, num_iterations, start, masses):
         """The checks of the solve's own arguments, before anything touches the device: (``Explicit``, K)."""
@@ -449,8 +464,24 @@ class ResidentDynamics(object):
             raise ValueError("%s: start of shape %s: a contiguous (%d, %d, 3) expected" % (who, tuple(start.shape), n_sel, self.nVerts))
         return 2, start
 
-    def _solve_run(self, plan, red, frames, ex, begin, K, chunk_frames, history):
-        """The solve (matrix on the device); ``red``: None or the ``Reduced`` with its ``op``; ``begin``: what ``_solve_start`` gave."""
+    @staticmethod
+    def _hyper_check(who, hyper, kinds, history):
+        """The refusals of ``hyper``, before anything touches the device."""
+        if hyper is None:
+            return
+        if hyper not in ("touched", "all"):
+            raise ValueError("%s: hyper must be None, 'touched' or 'all', not %r" % (who, hyper))
+        if history:
+            raise ValueError("%s: history=True with hyper=%r: the step norms run over all rows and would force the full iterate "
+                             "in every iteration" % (who, hyper))
+        if not isinstance(kinds, (list, tuple)) or len(kinds) != 1 or not isinstance(kinds[0], dict) \
+                or "basis" not in kinds[0] or "num_components" not in kinds[0]:
+            raise ValueError("%s: hyper=%r needs every kind reduced ('basis' and 'num_components'), and the engine holds one reduced "
+                             "operator: exactly one kind, a reduced one" % (who, hyper))
+
+    def _solve_run(self, plan, red, frames, ex, begin, K, chunk_frames, history, hyper=None):
+        """The solve (matrix on the device); ``red``: None or the ``Reduced`` with its ``op``; ``begin``: what ``_solve_start`` gave.
+        ``hyper``: the one kind is ``red`` and A^-1 S^T V is on the device."""
         eng = self._engine
         code, start = begin
         if code == 2:
@@ -458,6 +489,16 @@ class ResidentDynamics(object):
             torch.cuda.current_stream(start.device).synchronize()   # whatever produced start is done before the engine reads it
         frames.upload(self)
         eng.pdsolve_begin(*frames.args(self), ex.diag, ex.mode, ex.acc, code, None if start is None else start.data_ptr())
+        if hyper is not None:
+            t, = plan
+            touched, compact = _proj.touched_setup(_proj.subset_setup(red.setup, red.op.elements), self.nVerts if hyper == "all" else None)
+            eng.cproj_setup(compact)
+            eng.rforce_solver(red.op.H, red.op.local_rows)
+            eng.pdsolve_slot(t.sigma_min, t.sigma_max, None)
+            out = self._alloc(frames)
+            eng.hyper_iterate(K, None if hyper == "all" else touched, 0 if chunk_frames is None else int(chunk_frames), out.data_ptr())
+            self._leave(plan)
+            return out, frames.n_sel
         for i, t in enumerate(plan):
             if red is not None and red.index == i:
                 eng.cproj_setup(_proj.subset_setup(red.setup, red.op.elements))
@@ -475,7 +516,7 @@ class ResidentDynamics(object):
         return out, frames.n_sel
 
     def solve_frames(self, kinds, dt, num_iterations=10, masses=None, velocity="difference", gravity=(0.0, 0.0, 0.0), start="explicit",
-                     animation="train", frame_start=0, frame_end=None, frame_jump=1, chunk_frames=None, history=False):
+                     animation="train", frame_start=0, frame_end=None, frame_jump=1, chunk_frames=None, history=False, hyper=None):
         """Extra: the local/global iterations of the reference's solver (Simulators.py:494-526) for every selected frame of
         the resident animation, on the device: q_0 given, q_{k+1} = A^-1 (M / dt^2 s_f + sum_i S_i^T p_i(q_k)) for
         ``num_iterations`` iterations, the explicit state s_f held fixed while q moves.  The iterate stays on the device
@@ -494,6 +535,7 @@ class ResidentDynamics(object):
         world space, owned by the caller.  Device memory held by the engine beside A^-1: three times the result plus the
         projections of one chunk.  %s"""
         who = "solve_frames"
+        self._hyper_check(who, hyper, kinds, history)
         ex, K = self._solve_args(who, dt, velocity, gravity, num_iterations, start, masses)
         frames = self._frames(animation, frame_start, frame_end, frame_jump)
         plan, red = self._solve_plan(who, kinds, chunk_frames)
@@ -503,33 +545,38 @@ class ResidentDynamics(object):
         self._matrix(plan, ex.masses, ex.dt)
         if red is not None:
             self._engine.rforce_operator(red.St, red.op.V)
-        return self._solve_run(plan, red, frames, ex, begin, K, chunk_frames, history)
+        if hyper is not None:
+            self._engine.hyper_operator()
+        return self._solve_run(plan, red, frames, ex, begin, K, chunk_frames, history, hyper)
 
     solve_frames.__doc__ %= _SOLVE_SCOPE
 
     def reduced_solve_errors(self, kind, basis, r_values, dt, num_iterations=10, masses=None, velocity="difference",
                              gravity=(0.0, 0.0, 0.0), start="explicit", elements=None, wi=1.0, reduction="deim_pod", rest_positions=None,
                              sigma_min=1.0, sigma_max=1.0, animation="train", frame_start=0, frame_end=None, frame_jump=1,
-                             per_frame=False):
+                             per_frame=False, hyper=None):
         """Extra: how far the DEIM-reduced simulation is from the full one after the solver's iterations -- for every r of
         ``r_values`` the three metrics of ``(q, q~_r)``, q = ``solve_frames`` of this kind and q~_r the same solve with the kind
         reduced to r components (same A^-1, same inertia term, same start).  Arguments as ``reduced_global_step_errors`` plus
         ``num_iterations`` and ``start``; the same five lists ``fro, max, rel_x, rel_y, rel_z`` and, with ``per_frame``, the
         (len(r_values), F') array |q[f] - q~_r[f]| / |q[f]|.  The full solve runs once, one reduced solve per r (S^T V once, for
         the largest r); every tensor stays on the device and is compared there.  With ``num_iterations=1, start="frame"`` these
-        are the numbers of ``reduced_global_step_errors``.  %s"""
+        are the numbers of ``reduced_global_step_errors``.  With ``hyper`` the full solve still runs once as before, the per-r
+        reduced solves go through the hyper-reduced path, and A^-1 S^T V is formed once, for the largest r (prefixes of its
+        columns serve the others, as those of S^T V do).  %s"""
         who = "reduced_solve_errors"
+        self._hyper_check(who, hyper, [dict(basis=basis, num_components=0)], False)
         ex, K = self._solve_args(who, dt, velocity, gravity, num_iterations, start, masses)
         spec = dict(kind=kind, elements=elements, wi=wi, rest_positions=rest_positions, sigma_min=sigma_min, sigma_max=sigma_max)
         frames = self._frames(animation, frame_start, frame_end, frame_jump)
         terms, red = self._solve_plan(who, [dict(spec, basis=basis, num_components=0, reduction=reduction)], None)
         begin = self._solve_start(who, start, frames.n_sel)
-        run = lambda rd: self._solve_run(terms, rd, frames, ex, begin, K, None, False)[0]
+        run = lambda rd: self._solve_run(terms, rd, frames, ex, begin, K, None, False, None if rd is None else hyper)[0]
 
         def full():
             self._matrix(terms, ex.masses, ex.dt)
             return run(None)
         return self._errors(ReducedPlan(terms[0], frames, red.operator), r_values, per_frame, full,
-                            lambda op: run(red._replace(op=op)))
+                            lambda op: run(red._replace(op=op)), hyper)
 
     reduced_solve_errors.__doc__ %= _SOLVE_SCOPE

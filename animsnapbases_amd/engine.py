@@ -648,6 +648,21 @@ class HipEngine(object):
                                               ctypes.c_void_p(int(out_dev_ptr)) if out_dev_ptr else None, ptr(hist)))
         return hist
 
+    def hyper_operator(self):
+        """G_d = A^-1 (S^T V_d) on the device from the inverse of ``gstep_setup`` and the operator of ``rforce_operator``; either
+        call afterwards invalidates it."""
+        self._ck(self.lib.asb_hyper_operator(self.h))
+
+    def hyper_iterate(self, n_iter, touched=None, chunk_frames=0, out_dev_ptr=None):
+        """``n_iter`` hyper-reduced iterations of the solve in progress, whose one slot is the reduced kind.  ``touched``: the
+        ascending vertices the slot's set-up is renumbered into (all but the last iteration run on those rows), or None: the
+        set-up names the mesh's vertices and every iteration runs on all rows."""
+        if touched is not None:
+            touched = np.ascontiguousarray(touched, dtype=np.int64)
+            assert touched.ndim == 1
+        self._ck(self.lib.asb_hyper_iterate(self.h, int(n_iter), 0 if touched is None else int(touched.shape[0]), ptr(touched),
+                                            int(chunk_frames), ctypes.c_void_p(int(out_dev_ptr)) if out_dev_ptr else None))
+
     # ------------------------------------------------------------------ SPLOCS
     def splocs_begin(self):
         self._ck(self.lib.asb_splocs_begin(self.h))

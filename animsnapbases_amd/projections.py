@@ -234,13 +234,41 @@ def subset_setup(setup, sel):
         raise ValueError("%s: element %d of a set-up with elements 0..%d" % (setup.kind, bad, setup.n_elem - 1))
     tw, n = setup.table_width, setup.n_elem
     head = setup.table[:n * tw].reshape(n, tw)[sel]
+    q = setup.parts
     if setup.kind != "verts_bending":
-        return ProjectionSetup(setup.kind, setup.idx[sel], head)
+        return ProjectionSetup(setup.kind, setup.idx[sel], head, parts={k: v[sel] for k, v in q.items()})
     ptr, wts = setup.star_ptr, setup.table[n * tw:]
     edges = np.concatenate([np.arange(ptr[i], ptr[i + 1]) for i in sel]) if sel.size else np.zeros(0, dtype=np.int64)
     new_ptr = np.concatenate([[0], np.cumsum(ptr[sel + 1] - ptr[sel])])
+    per_edge = dict(star_ptr=new_ptr, star_idx=setup.star_idx[edges], weights=wts[edges])
+    parts = {k: per_edge[k] if k in per_edge else v[sel] for k, v in q.items()}
     return ProjectionSetup(setup.kind, setup.idx[sel], np.concatenate([head.reshape(-1), wts[edges]]), new_ptr,
-                           setup.star_idx[edges], bending_indices=setup.bending_indices[sel])
+                           setup.star_idx[edges], bending_indices=setup.bending_indices[sel], parts=parts)
+
+
+def touched_setup(setup, n_verts=None):
+    """``(touched, compact)`` for the hyper-reduced iterations: ``touched`` the sorted unique vertices the elements of
+    ``setup`` read (their corners; for ``verts_bending`` the constrained vertices and their star neighbours), ``compact`` the
+    same set-up with every vertex index replaced by its position in ``touched`` -- so that the elements project the rows
+    ``q[:, touched]`` of an iterate exactly as ``setup`` projects ``q``.  The tables are taken over, not rebuilt: the same bits.
+    ``bending_indices`` keeps naming the mesh's vertices.  ``n_verts`` given: ``touched`` is ``arange(n_verts)`` and the
+    renumbering is the identity (every row of the iterate is kept)."""
+    star = setup.star_idx if setup.star_idx is not None else np.zeros(0, dtype=np.int64)
+    if n_verts is None:
+        touched = np.unique(np.concatenate([setup.idx.reshape(-1), star]))
+    else:
+        touched = np.arange(int(n_verts), dtype=np.int64)
+        if setup.idx.max() >= n_verts or (star.size and star.max() >= n_verts):
+            raise ValueError("%s: an element names vertex %d of %d" % (setup.kind, int(max(setup.idx.max(), star.max() if star.size else 0)), n_verts))
+    pos = lambda a: np.searchsorted(touched, a).astype(np.int64)
+    parts = dict(setup.parts)
+    if setup.kind == "verts_bending":
+        for k in ("indices", "star_idx"):
+            if k in parts:
+                parts[k] = pos(parts[k])
+    compact = ProjectionSetup(setup.kind, pos(setup.idx), setup.table, setup.star_ptr,
+                              None if setup.star_idx is None else pos(setup.star_idx), bending_indices=setup.bending_indices, parts=parts)
+    return touched, compact
 
 
 def assembly_ST(setup, n_verts, wi=1.0):

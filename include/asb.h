@@ -702,6 +702,21 @@ int asb_pdsolve_slot(asb_ctx* ctx, double sigma_min, double sigma_max, int reduc
  * in a fixed order.  The product is that of asb_gstep_run entry for entry; no atomics; repeats, sub-ranges and any chunk
  * width give identical bits.  Returns after the stream has drained. */
 int asb_pdsolve_iterate(asb_ctx* ctx, int64_t n_iter, int64_t chunk_frames, double* out_dev, double* hist_out);
+/* Hyper-reduced iterations: with every kind reduced (one operator per context: exactly ONE reduced kind) an iteration is
+ * q_{k+1} = c + G_d coef_d(q_k) per coordinate, c = A^-1 ms, G_d = A^-1 (S^T V_d), and coef reads q_k only at the vertices of
+ * the sampled elements (the touched vertices): no N^2 product is left in the loop.
+ * asb_hyper_operator: after asb_gstep_setup and asb_rforce_operator.  Forms G_d^T in the layout of the operator S^T V, every
+ * entry one accumulator over ascending n, and keeps it with the context.  A later asb_gstep_setup or asb_rforce_operator
+ * invalidates it: asb_hyper_iterate then refuses (ASB_ERR_ARG) instead of using a stale operator.
+ * asb_hyper_iterate: in place of asb_pdsolve_iterate, after asb_pdsolve_begin and ONE asb_pdsolve_slot with reduced != 0 (any
+ * other set of slots is refused).  touched (host, n_touched, strictly ascending vertices) != NULL: the element set-up of the
+ * slot is numbered in 0 .. n_touched - 1 (position in touched); iterations 1 .. n_iter - 1 run on those rows only, the last
+ * on all n rows.  touched NULL: the set-up is numbered in the mesh's vertices and every iteration runs on all rows.  The two
+ * give identical bits, as do repeats, sub-ranges and any chunk_frames (> 0: at most that many frames, rounded up to 64, per
+ * pass).  out_dev (optional): caller-owned DEVICE memory (n_sel, n, 3), the iterate after the last iteration.  The whole
+ * iterate is left in the solve's state.  No atomics.  Returns after the stream has drained. */
+int asb_hyper_operator(asb_ctx* ctx);
+int asb_hyper_iterate(asb_ctx* ctx, int64_t n_iter, int64_t n_touched, const int64_t* touched, int64_t chunk_frames, double* out_dev);
 
 /* ------------------------------------------------ SPLOCS refinement ----------- */
 /* posComponents.splocs_glob_optimization, snapbases/posComponents.py:132-189.
