@@ -17,6 +17,7 @@ c_int = ctypes.c_int
 c_dbl = ctypes.c_double
 
 ASB_OK = 0
+ERR_ARG = -1            # ASB_ERR_ARG
 ERR_LIMIT = -4          # ASB_ERR_LIMIT
 DEFLATE_RESIDUAL, DEFLATE_PROJECT = 0, 1
 
@@ -182,6 +183,10 @@ PROTOTYPES = {
     "asb_pdsolve_iterate": (c_int, [ctypes.c_void_p, c_i64, c_i64, ctypes.c_void_p, c_dp]),
     "asb_hyper_operator": (c_int, [ctypes.c_void_p]),
     "asb_hyper_iterate": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_i64, ctypes.c_void_p]),
+    "asb_pdsolve_carry": (c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "asb_pdsolve_advance": (c_int, [ctypes.c_void_p]),
+    "asb_pdsolve_positions": (c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "asb_test_pdsolve_state": (c_int, [ctypes.c_void_p, c_int, c_dp, c_i64, c_i64]),
     "asb_splocs_begin": (c_int, [ctypes.c_void_p]),
     "asb_splocs_gram": (c_int, [ctypes.c_void_p, c_dp, c_dp, ctypes.POINTER(c_dbl)]),
     "asb_splocs_weights": (c_int, [ctypes.c_void_p, c_dp, c_dp, c_dp, c_dp]),

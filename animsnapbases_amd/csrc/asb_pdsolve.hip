@@ -1,6 +1,7 @@
 // The local/global iterations of the reference's projective-dynamics solver (projective_dynamics/Simulators.py:494-526) for a
 // batch of frames of the resident animation: q_0 given, q_{k+1} = A^-1 (sum_i S_i^T p_i(q_k) + M/h^2 s), s fixed.  Every
-// selected frame is its own solve.  Collisions, positional constraints and velocities carried between frames are not modelled.
+// selected frame is its own solve.  Collisions and positional constraints are not modelled.  The end of the reference's step
+// (:531-532: velocities = (q - positions) / dt, positions = q) is asb_pdsolve_advance below: a roll-out is iterate, advance, iterate ...
 //
 // State of a solve over the n_sel frames range(f0, f1, fj), owned by the context and reused by the next solve:
 //   ms  (n_sel, N, 3) frame-major   the inertia term diag[n] s_f[n, d], formed once by k_gs_inertia<false> (asb_gstep.hip): the
@@ -10,6 +11,9 @@
 //                                   and the per-element routines of asb_cproj.hip run on it unchanged.  The padding columns
 //                                   [n_sel, ld) are zeroed once and never read as frames nor written.
 //   b   (n_sel, N, 3) frame-major   the right-hand side of the iteration in flight
+//   P   (3 N, ld) vertex-major      only after asb_pdsolve_carry: the positions at the START of the current time step (the
+//                                   reference's model.positions), laid out and padded like Q; with it the solve's own device
+//                                   copy of diag, which ctx->gs_diag is not (asb_gstep_inertia rewrites that one)
 //   slots                           per kind the device tables of an asb_cproj_setup and the CSR of its S^T, registered once:
 //                                   no host-to-device copy happens inside the iteration loop
 //
@@ -57,6 +61,13 @@ struct asb_pds {
     // asb_hyper_iterate: c = A^-1 ms (3 N, ld) vertex-major like Q; the touched rows of Q and c (3 N_t, ld) and the touched
     // columns of G^T (3, mpp, N_t rounded up to 32, zero padding)
     double *c = nullptr, *Qc = nullptr, *cc = nullptr, *Gc = nullptr;
+    // the time step: what asb_pdsolve_begin was given (for asb_pdsolve_carry) and what asb_pdsolve_carry made
+    bool carry = false;
+    CpWorld w = {};
+    int f0 = 0, fj = 1;
+    double acc[3] = {0.0, 0.0, 0.0};
+    std::vector<double> diag_host;
+    double *P = nullptr, *diag = nullptr;
     int n_slots = 0;
     PdSlot slot[PD_MAX_SLOTS];
 };
@@ -197,7 +208,7 @@ static void pd_swap(asb_ctx* ctx, T** a, T** b) {
 extern "C" int asb_pdsolve_begin(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean,
                                  double psf, const double* diag, int mode, const double* acc3, int start, const double* start_dev) {
     if (!ctx || !diag || !acc3) return ASB_ERR_ARG;
-    if (ctx->pds) ctx->pds->begun = false, ctx->pds->n_slots = 0;
+    if (ctx->pds) ctx->pds->begun = false, ctx->pds->n_slots = 0, ctx->pds->carry = false;
     if (fj >= 1 && f1 > f0 && ((f1 - f0 + fj - 1) / fj + 63) / 64 > 65535)        // on the count alone, before any tensor is looked at
         ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_pdsolve_begin: %lld frames in one solve (at most %d)", (long long)((f1 - f0 + fj - 1) / fj), 65535 * 64);
     if (mode != 0 && mode != 1) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_begin: mode %d (0: s = x, 1: s = 2 x - x_prev)", mode);
@@ -235,6 +246,9 @@ extern "C" int asb_pdsolve_begin(asb_ctx* ctx, int which, int64_t f0, int64_t f1
     ASB_CHECK_LAUNCH(ctx);
     ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the host arrays and the caller's start tensor may go
     s->n = n, s->n_sel = n_sel, s->ld = ld, s->begun = true;
+    s->w = w, s->f0 = (int)f0, s->fj = (int)fj;
+    s->acc[0] = acc3[0], s->acc[1] = acc3[1], s->acc[2] = acc3[2];
+    s->diag_host.assign(diag, diag + n);
     return ASB_OK;
 }
 
@@ -347,6 +361,125 @@ extern "C" int asb_pdsolve_iterate(asb_ctx* ctx, int64_t n_iter, int64_t chunk_f
     if (hist_out)
         ASB_HIP(ctx, hipMemcpyAsync(hist_out, s->hist, (size_t)n_iter * n_sel * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the caller owns out_dev and may read it on any stream
+    return ASB_OK;
+}
+
+// ================================================================ the end of a time step
+// Simulators.py:531-532 and the next :495 in one pass over the state: per entry (row r = 3 v + d, frame f)
+//   s = fl(fl(2 Q - P) + acc[d]),   P <- Q,   Q <- s,   ms[f][v][d] <- fl(diag[v] s)
+// the operation order of k_gs_inertia<false> and k_pd_init(start 0, mode 1): an advance from (Q, P) = (x_f, x_{f-1}) leaves the
+// bits asb_pdsolve_begin(mode 1, start 0) leaves.  Q and P are vertex-major, ms is frame-major: a block owns 64 rows x 64
+// frames, wave w takes rows w, w + 4, ..  Its 64 lanes run along the frames: Q and P are read and written as 512-byte runs.
+// diag s goes through an LDS tile of 64 x PD_LDQ doubles, entry (frame fl, row rl) at fl * 65 + rl: the 64 lanes of a write sit
+// 65 doubles apart (odd: every bank pair once per 16 lanes), the 64 lanes of a read are consecutive, and ms is written as
+// runs of up to 64 doubles along r.  Tail predicates: rows >= 3 N, frames >= n_sel; the padding columns of Q and P are never
+// written and stay zero.  Two tensors read, three written, no atomics.
+// grid (row tiles of 64, frame tiles of 64)
+__global__ __launch_bounds__(256) void k_pd_advance(double* __restrict__ Q, double* __restrict__ P, const double* __restrict__ diag, int n_sel,
+                                                    long long rows, long long ld, double acc0, double acc1, double acc2,
+                                                    double* __restrict__ ms) {
+    __shared__ double tile[64 * PD_LDQ];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long long r0 = (long long)blockIdx.x * 64;
+    const int t0 = (int)blockIdx.y * 64;
+    for (int rl = wv; rl < 64; rl += 4) {
+        const long long r = r0 + rl;
+        if (r < rows && t0 + lane < n_sel) {
+            const long long at = r * ld + t0 + lane;
+            const int d = (int)(r % 3);
+            const double q = Q[at];
+            const double x = 2.0 * q - P[at];
+            const double s = x + (d == 0 ? acc0 : (d == 1 ? acc1 : acc2));
+            P[at] = q;
+            Q[at] = s;
+            tile[lane * PD_LDQ + rl] = diag[r / 3] * s;
+        }
+    }
+    __syncthreads();
+    for (int fl = wv; fl < 64; fl += 4)
+        if (t0 + fl < n_sel && r0 + lane < rows) ms[(long long)(t0 + fl) * rows + r0 + lane] = tile[fl * PD_LDQ + lane];
+}
+
+// grid (row tiles of 64, frame tiles of 64): P (rows, ld) vertex-major -> out (n_sel, rows) frame-major, k_pd_transpose reversed
+__global__ __launch_bounds__(256) void k_pd_untranspose(const double* __restrict__ P, int n_sel, long long rows, long long ld,
+                                                        double* __restrict__ out) {
+    __shared__ double tile[64 * PD_LDQ];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long long r0 = (long long)blockIdx.x * 64;
+    const int t0 = (int)blockIdx.y * 64;
+    for (int rl = wv; rl < 64; rl += 4)
+        if (r0 + rl < rows && t0 + lane < n_sel) tile[lane * PD_LDQ + rl] = P[(r0 + rl) * ld + t0 + lane];
+    __syncthreads();
+    for (int fl = wv; fl < 64; fl += 4)
+        if (t0 + fl < n_sel && r0 + lane < rows) out[(long long)(t0 + fl) * rows + r0 + lane] = tile[fl * PD_LDQ + lane];
+}
+
+extern "C" int asb_pdsolve_carry(asb_ctx* ctx, const double* pos_dev) {
+    if (!ctx) return ASB_ERR_ARG;
+    asb_pds* s = ctx->pds;
+    if (!s || !s->begun) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_carry: no solve begun (asb_pdsolve_begin)");
+    s->carry = false;
+    if (ctx->n_loc != s->n || (!pos_dev && s->w.T != ctx->X && s->w.T != ctx->ho_Y))
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_carry: the tensor changed since asb_pdsolve_begin");
+    const long long n = s->n, n_sel = s->n_sel, ld = s->ld;
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    int rc;
+    if ((rc = asb_alloc(ctx, &s->P, (size_t)3 * n * ld))) return rc;
+    if ((rc = asb_alloc(ctx, &s->diag, (size_t)n))) return rc;
+    ASB_HIP(ctx, hipMemcpyAsync(s->diag, s->diag_host.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    ASB_HIP(ctx, hipMemsetAsync(s->P, 0, (size_t)3 * n * ld * sizeof(double), ctx->stream));      // the padding columns, once per carry
+    const unsigned gt = (unsigned)((n_sel + 63) / 64);
+    if (pos_dev)
+        hipLaunchKernelGGL(k_pd_transpose, dim3((unsigned)((3 * n + 63) / 64), gt), dim3(256), 0, ctx->stream, pos_dev, (int)n_sel,
+                           (long long)(3 * n), s->P, ld);
+    else
+        hipLaunchKernelGGL(k_pd_init, dim3((unsigned)((3 * n + 3) / 4), gt), dim3(256), 0, ctx->stream, s->w, s->f0, s->fj, (int)n_sel,
+                           (long long)n, 1, 0, 0.0, 0.0, 0.0, s->P, ld);
+    ASB_CHECK_LAUNCH(ctx);
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the caller's tensor may go
+    s->carry = true;
+    return ASB_OK;
+}
+
+extern "C" int asb_pdsolve_advance(asb_ctx* ctx) {
+    if (!ctx) return ASB_ERR_ARG;
+    asb_pds* s = ctx->pds;
+    if (!s || !s->begun) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_advance: no solve begun (asb_pdsolve_begin)");
+    if (!s->carry || !s->P || !s->diag)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_advance: the solve carries no previous positions (asb_pdsolve_carry after asb_pdsolve_begin)");
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    const dim3 grid((unsigned)((3 * s->n + 63) / 64), (unsigned)((s->n_sel + 63) / 64));
+    hipLaunchKernelGGL(k_pd_advance, grid, dim3(256), 0, ctx->stream, s->Q, s->P, s->diag, (int)s->n_sel, 3 * s->n, s->ld, s->acc[0], s->acc[1],
+                       s->acc[2], s->ms);
+    ASB_CHECK_LAUNCH(ctx);
+    return ASB_OK;
+}
+
+extern "C" int asb_pdsolve_positions(asb_ctx* ctx, double* out_dev) {
+    if (!ctx || !out_dev) return ASB_ERR_ARG;
+    asb_pds* s = ctx->pds;
+    if (!s || !s->begun) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_positions: no solve begun (asb_pdsolve_begin)");
+    if (!s->carry || !s->P)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_positions: the solve carries no previous positions (asb_pdsolve_carry after asb_pdsolve_begin)");
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    const dim3 grid((unsigned)((3 * s->n + 63) / 64), (unsigned)((s->n_sel + 63) / 64));
+    hipLaunchKernelGGL(k_pd_untranspose, grid, dim3(256), 0, ctx->stream, s->P, (int)s->n_sel, 3 * s->n, s->ld, out_dev);
+    ASB_CHECK_LAUNCH(ctx);
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the caller owns out_dev and may read it on any stream
+    return ASB_OK;
+}
+
+// test hook: the iterate Q (which 0) or the carried positions P (1) as they lie on the device, (3 n, ld) with the padding
+extern "C" int asb_test_pdsolve_state(asb_ctx* ctx, int which, double* out_host, int64_t rows, int64_t ld) {
+    if (!ctx || !out_host) return ASB_ERR_ARG;
+    asb_pds* s = ctx->pds;
+    if (!s || !s->begun || (which != 0 && which != 1) || (which == 1 && (!s->carry || !s->P)))
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_pdsolve_state: no such state (0: the iterate of a begun solve, 1: the positions of a carry)");
+    if (rows != 3 * s->n || ld != s->ld)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_pdsolve_state: the state is (%lld, %lld), not (%lld, %lld)", 3 * s->n, s->ld, (long long)rows, (long long)ld);
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    ASB_HIP(ctx, hipMemcpyAsync(out_host, which ? s->P : s->Q, (size_t)rows * ld * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return ASB_OK;
 }
 

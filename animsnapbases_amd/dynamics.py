@@ -1,6 +1,7 @@
 """``ResidentDynamics`` -- what ``posSnapshots`` offers beyond the reference's class: the pieces of the reference's
 projective-dynamics solver (Simulators.py) evaluated on the device for the frames of the resident animation -- constraint
-projections, constraint forces, their DEIM reduction, the global step and the solver's iterations.
+projections, constraint forces, their DEIM reduction, the global step, the solver's iterations and its time steps (DESIGN.md
+3.10-3.16).
 A public call checks its arguments into the named records below before the engine is touched; the helpers take the records.
 """
 import collections
@@ -397,8 +398,8 @@ class ResidentDynamics(object):
 
     # ------------------------------------------------------------------ the solver's iterations
     _SOLVE_SCOPE = """Out of scope, as for ``global_step``: collision handling (``resolve_collision`` and the self-collision passes),
-        positional constraints, velocities carried from one solved frame into the next (every selected frame is an independent
-        solve from the animation's own x_f, x_{f-1}) and several ranks.
+        positional constraints and several ranks.  Every selected frame is an independent solve; further time steps from its
+        result, the velocity carried along, are ``simulate_frames``.
 
         ``hyper`` (None, "touched" or "all"): the hyper-reduced operator A^-1 S^T V, as the reference's reduced simulator holds
         its ``projecting_mat`` (Simulators.py:157-220).  With EVERY listed kind reduced the iteration is affine in the
@@ -410,8 +411,8 @@ class ResidentDynamics(object):
         touched): a kind without ``basis`` / ``num_components`` -- every kind must be reduced, and since the engine holds one
         reduced operator that means exactly one kind --, ``history=True`` (step norms over all rows would need the whole
         iterate in every iteration) and an unknown value.  Out of scope for ``hyper``: several reduced kinds in one solve,
-        the history, a reduction of the positions themselves (a basis U of q), velocities carried between frames, several
-        ranks."""
+        the history, a reduction of the positions themselves (a basis U of q), several ranks.  Not part of a solve, with or
+        without ``hyper``: velocities carried between frames or steps -- that is ``simulate_frames``, which takes ``hyper`` too."""
 
     def _solve_args(self, who, dt, velocity, gravity, num_iterations, start, masses):
         """The checks of the solve's own arguments, before anything touches the device: (``Explicit``, K)."""
@@ -479,6 +480,27 @@ class ResidentDynamics(object):
             raise ValueError("%s: hyper=%r needs every kind reduced ('basis' and 'num_components'), and the engine holds one reduced "
                              "operator: exactly one kind, a reduced one" % (who, hyper))
 
+    def _solve_slots(self, plan, red, hyper):
+        """The kinds of the plan registered with the solve in progress, in order; with ``hyper`` the one reduced kind on its
+        touched vertices, which are returned."""
+        eng = self._engine
+        if hyper is not None:
+            t, = plan
+            touched, compact = _proj.touched_setup(_proj.subset_setup(red.setup, red.op.elements), self.nVerts if hyper == "all" else None)
+            eng.cproj_setup(compact)
+            eng.rforce_solver(red.op.H, red.op.local_rows)
+            eng.pdsolve_slot(t.sigma_min, t.sigma_max, None)
+            return touched
+        for i, t in enumerate(plan):
+            if red is not None and red.index == i:
+                eng.cproj_setup(_proj.subset_setup(red.setup, red.op.elements))
+                eng.rforce_solver(red.op.H, red.op.local_rows)
+                eng.pdsolve_slot(t.sigma_min, t.sigma_max, None)
+            else:
+                eng.cproj_setup(t.setup)
+                eng.pdsolve_slot(t.sigma_min, t.sigma_max, t.St)
+        return None
+
     def _solve_run(self, plan, red, frames, ex, begin, K, chunk_frames, history, hyper=None):
         """The solve (matrix on the device); ``red``: None or the ``Reduced`` with its ``op``; ``begin``: what ``_solve_start`` gave.
         ``hyper``: the one kind is ``red`` and A^-1 S^T V is on the device."""
@@ -490,23 +512,12 @@ class ResidentDynamics(object):
         frames.upload(self)
         eng.pdsolve_begin(*frames.args(self), ex.diag, ex.mode, ex.acc, code, None if start is None else start.data_ptr())
         if hyper is not None:
-            t, = plan
-            touched, compact = _proj.touched_setup(_proj.subset_setup(red.setup, red.op.elements), self.nVerts if hyper == "all" else None)
-            eng.cproj_setup(compact)
-            eng.rforce_solver(red.op.H, red.op.local_rows)
-            eng.pdsolve_slot(t.sigma_min, t.sigma_max, None)
+            touched = self._solve_slots(plan, red, hyper)
             out = self._alloc(frames)
             eng.hyper_iterate(K, None if hyper == "all" else touched, 0 if chunk_frames is None else int(chunk_frames), out.data_ptr())
             self._leave(plan)
             return out, frames.n_sel
-        for i, t in enumerate(plan):
-            if red is not None and red.index == i:
-                eng.cproj_setup(_proj.subset_setup(red.setup, red.op.elements))
-                eng.rforce_solver(red.op.H, red.op.local_rows)
-                eng.pdsolve_slot(t.sigma_min, t.sigma_max, None)
-            else:
-                eng.cproj_setup(t.setup)
-                eng.pdsolve_slot(t.sigma_min, t.sigma_max, t.St)
+        self._solve_slots(plan, red, None)
         out = self._alloc(frames)
         hist = eng.pdsolve_iterate(K, 0 if chunk_frames is None else int(chunk_frames), out.data_ptr(), history)
         self._leave(plan)
@@ -580,3 +591,152 @@ class ResidentDynamics(object):
                             lambda op: run(red._replace(op=op)), hyper)
 
     reduced_solve_errors.__doc__ %= _SOLVE_SCOPE
+
+    # ------------------------------------------------------------------ time steps: the velocity carried from step to step
+    @staticmethod
+    def _rollout_args(who, num_steps, record_every, state):
+        """The checks of the roll-out's own arguments, before anything touches the device: (T, r or None)."""
+        def count(x):
+            try:
+                n = int(x)
+            except (TypeError, ValueError):
+                return 0
+            return n if n == x and not isinstance(x, bool) and n >= 1 else 0
+        T = count(num_steps)
+        if T < 1:
+            raise ValueError("%s: num_steps %r: a positive number of time steps" % (who, num_steps))
+        every = None if record_every is None else count(record_every)
+        if every == 0:
+            raise ValueError("%s: record_every %r: a positive number of time steps or None" % (who, record_every))
+        if state is not None:
+            import torch
+            if not isinstance(state, (list, tuple)) or len(state) != 2 or not all(
+                    isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.is_cuda for t in state):
+                raise ValueError("%s: state must be a pair (q, q_prev) of torch.float64 device tensors" % who)
+        return T, every
+
+    def _rollout_state(self, who, state, n_sel):
+        """The tensors of ``state`` checked as ``global_solve`` checks its rhs."""
+        for t in state or ():
+            if t.device.index != self._engine.device_id:
+                raise ValueError("%s: state lives on %s, the snapshots on device %d" % (who, t.device, self._engine.device_id))
+            if t.dim() != 3 or tuple(t.shape) != (n_sel, self.nVerts, 3) or not t.is_contiguous():
+                raise ValueError("%s: state of shape %s: contiguous (%d, %d, 3) tensors expected" % (who, tuple(t.shape), n_sel, self.nVerts))
+
+    def _rollout_run(self, plan, red, frames, ex, state, K, T, chunk_frames, every, hyper=None):
+        """The roll-out (matrix on the device; ``red``, ``hyper`` as ``_solve_run``): ``(q, q_prev, records or None, steps)``."""
+        import torch
+        eng = self._engine
+        if state is not None:
+            torch.cuda.current_stream(state[0].device).synchronize()    # whatever produced the state is done before the engine reads it
+        frames.upload(self)
+        if state is None:
+            eng.pdsolve_begin(*frames.args(self), ex.diag, ex.mode, ex.acc, 0, None)
+            eng.pdsolve_carry(None)
+        else:                                       # the pair becomes (iterate, carried positions); the advance makes s_1 of them
+            eng.pdsolve_begin(*frames.args(self), ex.diag, ex.mode, ex.acc, 2, state[0].data_ptr())
+            eng.pdsolve_carry(state[1].data_ptr())
+            eng.pdsolve_advance()
+        touched = self._solve_slots(plan, red, hyper)
+        steps = [] if every is None else list(range(every, T + 1, every))
+        records = None
+        if every is not None:
+            records = torch.empty((len(steps), frames.n_sel, self.nVerts, 3), dtype=torch.float64, device="cuda:%d" % eng.device_id)
+        q = records[-1] if steps and steps[-1] == T else self._alloc(frames)
+        cf = 0 if chunk_frames is None else int(chunk_frames)
+        for t in range(1, T + 1):
+            if t > 1:
+                eng.pdsolve_advance()
+            out = q if t == T else (records[t // every - 1] if every is not None and t % every == 0 else None)
+            ptr = None if out is None else out.data_ptr()
+            if hyper is not None:
+                eng.hyper_iterate(K, None if hyper == "all" else touched, cf, ptr)
+            else:
+                eng.pdsolve_iterate(K, cf, ptr, False)
+        q_prev = self._alloc(frames)
+        eng.pdsolve_positions(q_prev.data_ptr())
+        self._leave(plan)
+        return q, q_prev, records, steps
+
+    def simulate_frames(self, kinds, dt, num_steps, num_iterations=10, masses=None, velocity="difference", gravity=(0.0, 0.0, 0.0),
+                        state=None, animation="train", frame_start=0, frame_end=None, frame_jump=1, chunk_frames=None,
+                        record_every=None, hyper=None):
+        """Extra: ``num_steps`` time steps of the reference's solver (Simulators.py ``step()``, :494-532) from every selected
+        frame of the resident animation, on the device.  Every selected frame is an independent initial condition: positions
+        x_f, velocity (x_f - x_{f-1}) / dt (``velocity`` "difference", f - 1 as in ``global_step``) or 0 ("zero").  A step is
+        ``num_iterations`` local/global iterations from q_0 = s_t, then (:531-532) p_{t+1} = q and the next explicit state
+        s_{t+1} = 2 q - p_t + dt^2 g -- the velocity (q - p_t) / dt carried into the next step.  Step 1 is
+        ``solve_frames(start="explicit")`` bit for bit.  The state never leaves the device: the carry is one kernel on the
+        iterate, the previous positions and the inertia term; the matrix, S^T V and A^-1 S^T V are formed once per call.
+
+        ``kinds`` (one entry may be reduced), ``dt``, ``num_iterations``, ``masses``, ``gravity``, ``animation``, the frame range,
+        ``chunk_frames`` and ``hyper``: as ``solve_frames``, with its refusals.  ``state``: a pair ``(q, q_prev)`` of contiguous
+        ``torch.float64`` device tensors (F', N, 3), the positions now and one step earlier: the roll-out continues from them
+        (``velocity`` is then ignored and the animation only selects F'), and T1 steps continued by T2 equal T1 + T2 steps bit
+        for bit.  ``record_every`` = r: also the positions after the steps r, 2 r, .. <= ``num_steps``.
+
+        Returns ``(q, q_prev, F')``: the positions after the last step and one step earlier (for ``num_steps`` = 1: x_f, or
+        ``state[0]``), two ``torch.float64`` device tensors (F', N, 3) owned by the caller -- the pair ``state=`` takes.  With
+        ``record_every`` a fourth value ``(records, steps)``: a caller-owned (R, F', N, 3) device tensor, each record written
+        by the last iteration of its step straight into its slice, and the list of those step numbers; when the last step is
+        recorded, ``q`` is the view ``records[-1]``.  Device memory held by the engine beside that of ``solve_frames``: one more
+        tensor of the iterate's size.  Out of scope: collisions, positional constraints, forces other than constant gravity,
+        several reduced kinds, the history of step norms, several ranks."""
+        who = "simulate_frames"
+        self._hyper_check(who, hyper, kinds, False)
+        ex, K = self._solve_args(who, dt, velocity, gravity, num_iterations, "explicit", masses)
+        T, every = self._rollout_args(who, num_steps, record_every, state)
+        frames = self._frames(animation, frame_start, frame_end, frame_jump)
+        plan, red = self._solve_plan(who, kinds, chunk_frames)
+        self._rollout_state(who, state, frames.n_sel)
+        if red is not None:
+            red = red._replace(op=red.operator(int(kinds[red.index]["num_components"])))
+        self._matrix(plan, ex.masses, ex.dt)
+        if red is not None:
+            self._engine.rforce_operator(red.St, red.op.V)
+        if hyper is not None:
+            self._engine.hyper_operator()
+        q, q_prev, records, steps = self._rollout_run(plan, red, frames, ex, state, K, T, chunk_frames, every, hyper)
+        return (q, q_prev, frames.n_sel) + (() if every is None else ((records, steps),))
+
+    def reduced_rollout_errors(self, kind, basis, r_values, dt, num_steps, num_iterations=10, masses=None, velocity="difference",
+                               gravity=(0.0, 0.0, 0.0), elements=None, wi=1.0, reduction="deim_pod", rest_positions=None,
+                               sigma_min=1.0, sigma_max=1.0, animation="train", frame_start=0, frame_end=None, frame_jump=1,
+                               record_every=1, hyper=None):
+        """Extra: how far the DEIM-reduced SIMULATION drifts from the full one along a trajectory -- ``reduced_solve_errors``
+        carried through ``num_steps`` time steps of ``simulate_frames``.  For every r of ``r_values`` and every recorded step
+        (``record_every`` = r0: the steps r0, 2 r0, .. <= ``num_steps``) the three metrics of ``(q_t, q~_{r,t})``: both roll-outs
+        start at the same frames with the same velocity, the same A^-1 and the same masses, and from step 2 on each follows
+        its own trajectory.  Arguments as ``reduced_solve_errors`` plus ``num_steps`` and ``record_every``; the start is the
+        explicit state and there is no per-frame output.  The full roll-out runs once with its records, one reduced roll-out
+        per r (S^T V and, with ``hyper``, A^-1 S^T V once, for the largest r); every record stays on the device and is compared
+        there, slice by slice.
+
+        Returns ``(fro, max, rel_x, rel_y, rel_z, steps)``: five (len(r_values), R) arrays and the list of the R recorded
+        steps.  With ``num_steps=1, record_every=1`` the numbers are those of ``reduced_solve_errors``."""
+        who = "reduced_rollout_errors"
+        self._hyper_check(who, hyper, [dict(basis=basis, num_components=0)], False)
+        ex, K = self._solve_args(who, dt, velocity, gravity, num_iterations, "explicit", masses)
+        T, every = self._rollout_args(who, num_steps, record_every, None)
+        if every is None:
+            raise ValueError("%s: record_every %r: a positive number of time steps" % (who, record_every))
+        spec = dict(kind=kind, elements=elements, wi=wi, rest_positions=rest_positions, sigma_min=sigma_min, sigma_max=sigma_max)
+        frames = self._frames(animation, frame_start, frame_end, frame_jump)
+        terms, red = self._solve_plan(who, [dict(spec, basis=basis, num_components=0, reduction=reduction)], None)
+        r_values = [int(r) for r in r_values]
+        ops = [red.operator(r) for r in r_values]
+        steps = list(range(every, T + 1, every))
+        out = np.zeros((5, len(ops), len(steps)))
+        if not ops:
+            return tuple(out) + (steps,)
+        run = lambda rd: self._rollout_run(terms, rd, frames, ex, None, K, T, None, every, None if rd is None else hyper)[2]
+        self._matrix(terms, ex.masses, ex.dt)
+        full = run(None)
+        self._engine.rforce_operator(terms[0].St, ops[int(np.argmax(r_values))].V)
+        if hyper is not None:
+            self._engine.hyper_operator()
+        for i, op in enumerate(ops):
+            rec = run(red._replace(op=op))
+            for j in range(len(steps)):
+                out[:, i, j] = [m[0] for m in self._diff_metrics(full[j], [rec[j]], frames.n_sel, False)]
+        return tuple(out) + (steps,)

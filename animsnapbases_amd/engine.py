@@ -663,6 +663,28 @@ class HipEngine(object):
         self._ck(self.lib.asb_hyper_iterate(self.h, int(n_iter), 0 if touched is None else int(touched.shape[0]), ptr(touched),
                                             int(chunk_frames), ctypes.c_void_p(int(out_dev_ptr)) if out_dev_ptr else None))
 
+    # ------------------------------------------------------------------ time steps on the solve's state
+    def pdsolve_carry(self, pos_dev_ptr=None):
+        """The solve in progress gets the positions at the start of its time step: the begun frames x_f, or the caller's
+        device buffer of (F', N, 3) float64."""
+        self._ck(self.lib.asb_pdsolve_carry(self.h, ctypes.c_void_p(int(pos_dev_ptr)) if pos_dev_ptr else None))
+
+    def pdsolve_advance(self):
+        """The end of a time step: with q the iterate and p the carried positions, s = 2 q - p + acc becomes the iterate and
+        the explicit state of the inertia term, q the carried positions.  In stream order; does not wait."""
+        self._ck(self.lib.asb_pdsolve_advance(self.h))
+
+    def pdsolve_positions(self, out_dev_ptr):
+        """The carried positions into the caller's device buffer of (F', N, 3) float64."""
+        self._ck(self.lib.asb_pdsolve_positions(self.h, ctypes.c_void_p(int(out_dev_ptr))))
+
+    def pdsolve_state(self, which):
+        """Test hook: the iterate (``which`` 0) or the carried positions (1) as stored, (3 N, F' rounded up to 64)."""
+        ld = (self._pd_frames + 63) // 64 * 64
+        out = np.empty((3 * self.N_glob, ld))
+        self._ck(self.lib.asb_test_pdsolve_state(self.h, int(which), ptr(out), out.shape[0], ld))
+        return out
+
     # ------------------------------------------------------------------ SPLOCS
     def splocs_begin(self):
         self._ck(self.lib.asb_splocs_begin(self.h))

@@ -683,7 +683,8 @@ int asb_test_gstep_inverse(asb_ctx* ctx, double* out_host, int64_t n);
 /* The local/global loop of Simulators.py:494-526 for the frames range(f0, f1, fj) of the training (which 0) or held-out (1)
  * tensor, every frame an independent solve: q_{k+1} = A^-1 (sum_i S_i^T p_i(q_k) + M / h^2 s_f) with s_f fixed.  The iterate
  * stays on the device between iterations, vertex-major (row 3 v + d, the frames contiguous, padded to 64), the layout the
- * projection kernels read.  No collisions, no positional constraints, no velocities carried from frame to frame.  One rank.
+ * projection kernels read.  No collisions, no positional constraints.  One rank.  The end of a time step (:531-532) is
+ * asb_pdsolve_advance below.
  * asb_pdsolve_begin: after asb_gstep_setup.  Arguments two to eleven as asb_gstep_inertia; the inertia term diag s_f is
  * formed once with that entry's arithmetic.  start 0: q_0 = s_f (the reference's), 1: q_0 = x_f, 2: q_0 = start_dev, a DEVICE
  * tensor (n_sel, n, 3).  More than 65535 * 64 selected frames: ASB_ERR_LIMIT, judged on the count alone before anything
@@ -717,6 +718,25 @@ int asb_pdsolve_iterate(asb_ctx* ctx, int64_t n_iter, int64_t chunk_frames, doub
  * iterate is left in the solve's state.  No atomics.  Returns after the stream has drained. */
 int asb_hyper_operator(asb_ctx* ctx);
 int asb_hyper_iterate(asb_ctx* ctx, int64_t n_iter, int64_t n_touched, const int64_t* touched, int64_t chunk_frames, double* out_dev);
+
+/* ------------------------------------------------ projective dynamics: time steps on the solve's state ----------- */
+/* The last two lines of the reference's step (Simulators.py:531-532, :741-742: velocities = (q - positions) / dt, positions = q)
+ * and the explicit state of the next step (:495), as one device operation on the state of the solve in progress.
+ * asb_pdsolve_carry: after asb_pdsolve_begin.  Gives the solve P, the positions at the START of the current time step, laid
+ * out like the iterate.  pos_dev NULL: P = x_f of the begun frames in world space (directly after asb_pdsolve_begin: the
+ * tensor it read must still be the one on the device); otherwise a caller-owned DEVICE tensor (n_sel, n, 3).  The solve
+ * keeps its own device copy of the diag that asb_pdsolve_begin was given, so a later asb_gstep_inertia does not disturb
+ * it.  A new asb_pdsolve_begin drops the carry.  Returns after the stream has drained.
+ * asb_pdsolve_advance: after asb_pdsolve_carry (ASB_ERR_ARG otherwise, nothing launched).  With q the iterate, per entry
+ * s = fl(fl(2 q - P) + acc[d]); then P = q, the iterate = s and the inertia term = fl(diag s): the arithmetic of
+ * asb_pdsolve_begin(mode 1, start 0), so an advance from (x_f, x_{f-1}) leaves its bits.  One pass, no atomics, no host
+ * copy; in stream order, the call does not wait.  A time step is asb_pdsolve_iterate or asb_hyper_iterate, then this.
+ * asb_pdsolve_positions: P, frame-major, into caller-owned DEVICE memory (n_sel, n, 3).  Returns after the stream has drained. */
+int asb_pdsolve_carry(asb_ctx* ctx, const double* pos_dev);
+int asb_pdsolve_advance(asb_ctx* ctx);
+int asb_pdsolve_positions(asb_ctx* ctx, double* out_dev);
+/* test hook: the iterate (which 0) or P (1) as stored, (rows = 3 n, ld = n_sel rounded up to 64) with its padding, to the host */
+int asb_test_pdsolve_state(asb_ctx* ctx, int which, double* out_host, int64_t rows, int64_t ld);
 
 /* ------------------------------------------------ SPLOCS refinement ----------- */
 /* posComponents.splocs_glob_optimization, snapbases/posComponents.py:132-189.
