@@ -36,6 +36,7 @@ struct StreamCfg {
 struct asb_splocs;
 struct asb_geo;
 struct asb_pds;
+struct asb_gsl;
 
 // world positions of the resident tensor (asb_cproj.hip): x = (T * inv_psf + mean) * invm_v
 struct CpWorld {
@@ -348,6 +349,9 @@ struct asb_ctx {
     double* hy_G = nullptr;
     int hy_ok = 0;                    // hy_G belongs to the current gs_Ainv and rf_M (asb_gstep_setup / asb_rforce_operator clear it)
     int64_t cp_vmax = -1;             // largest vertex the last asb_cproj_setup names (elements and star edges)
+    // the global step's second solver (asb_gslab.hip): the block-tridiagonal slab factor of A_N.  The context holds EITHER
+    // gs_Ainv (gs_n > 0) or the factor (asb_gslab_n(ctx) > 0): each set-up releases the other
+    asb_gsl* gsl = nullptr;
 
     // ---- profiling of the dominant streaming kernel ----
     bool prof = false;
@@ -364,6 +368,7 @@ int asb_project_run(asb_ctx* ctx, int64_t k0, int64_t k1);
 void asb_splocs_free(asb_ctx* ctx);
 void asb_geo_free(asb_ctx* ctx);
 void asb_pdsolve_free(asb_ctx* ctx);
+void asb_gslab_free(asb_ctx* ctx);
 #define ASB_GEO_CACHE_SLABS 64          // x 64 distance fields
 const double* asb_geo_cached_field(asb_ctx* ctx, long long slot, long long* n_out);
 // small dense linear algebra on the device (asb_linalg.hip)
@@ -449,6 +454,24 @@ void asb_rforce_coef_launch(asb_ctx* ctx, const double* S, int cw, int cn);
 // asb_gstep.hip: k_gs_inertia on device arrays; add: out += diag s, otherwise out = diag s (the value the sum adds)
 void asb_gs_inertia_launch(asb_ctx* ctx, const CpWorld& w, int f0, int fj, int n_sel, long long n, const double* diag_dev, int mode,
                            const double* acc3, bool add, double* out);
+// asb_gstep.hip: the checks of a system matrix that asb_gstep_setup and asb_gslab_setup share, messages starting with `who`:
+// the tensor on the device has n vertices (one rank), asb_csr_check32, finite values, a positive diagonal, a symmetric pattern
+// and values symmetric to 1e-12 of the row's largest
+int asb_gs_check_matrix(asb_ctx* ctx, const char* who, int64_t n, const int64_t* indptr, const int64_t* indices, const double* data,
+                        std::vector<int>& p32, std::vector<int>& c32);
+// asb_gslab.hip.  asb_gslab_n: the vertices of the slab factor the context holds (0: none); asb_gslab_release: the factor
+// and its work matrices are freed (asb_gstep_setup calls it: the context holds one solver)
+long long asb_gslab_n(const asb_ctx* ctx);
+void asb_gslab_release(asb_ctx* ctx);
+// A^-1 applied through the factor, all in stream order, nothing synchronised.  solve_fm: rhs (F, n, 3) frame-major -> Qv (3 n, ld)
+// vertex-major, ld = F rounded up to 64 (columns [F, ld) of Qv are written as zero); Qv NULL: a buffer of the factor.  out
+// (optional): the same values frame-major (F, n, 3)
+int asb_gslab_solve_fm(asb_ctx* ctx, const double* rhs, long long F, double* Qv, double* out);
+// Gt (rows, Np) with the n vertices contiguous in a row (the layout of rf_M) -> Ot, same layout: Ot[r] = A^-1 Gt[r]; the
+// entries of Ot past vertex n are left as they are
+int asb_gslab_solve_rows(asb_ctx* ctx, const double* Gt, long long rows, long long Np, double* Ot);
+// asb_pdsolve.hip: k_pd_untranspose, P (rows, ld) vertex-major -> out (n_sel, rows) frame-major
+void asb_pd_untranspose_launch(asb_ctx* ctx, const double* P, int n_sel, long long rows, long long ld, double* out);
 // a host CSR checked (offsets from 0 and not decreasing, columns < n_cols and strictly ascending in a row) and narrowed to int;
 // `what` names the matrix in the messages
 int asb_csr_check32(asb_ctx* ctx, const char* who, int64_t n_rows, const int64_t* indptr, const int64_t* indices, const double* data,

@@ -25,6 +25,8 @@
 //                      of GS_VB vertices x 64 frames reads the vertex-major tensor along the frames and stages through LDS to
 //                      write per frame its contiguous run, a read-modify-write of its own entries.  k_gs_inertia<false>
 //                      stores the same values instead of adding them (asb_gs_inertia_launch, for asb_pdsolve_begin).
+// The context holds this inverse OR the block-tridiagonal slab factor of asb_gslab.hip (each set-up releases the other): with the
+// factor held asb_gstep_run goes through its sweep and asb_test_gstep_inverse is refused; with the inverse held nothing changed.
 #include "asb_gstep_tile.h"
 
 #include <algorithm>
@@ -68,29 +70,23 @@ __global__ __launch_bounds__(256) void k_gs_resid(const int* __restrict__ ptr, c
     res[i] = fabs(a - 1.0);
 }
 
-extern "C" int asb_gstep_setup(asb_ctx* ctx, int64_t n, const int64_t* indptr, const int64_t* indices, const double* data, double* resid_out) {
-    if (!ctx || !indptr || n < 1) return ASB_ERR_ARG;
-    ctx->gs_n = 0, ctx->hy_ok = 0;
-    if (n > GS_MAX_N)
-        ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_gstep_setup: %lld vertices are too many for an explicit inverse (at most %d)", (long long)n, GS_MAX_N);
-    if (!ctx->X || ctx->v0 != 0 || ctx->n_loc != ctx->N_glob)
-        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_gstep_setup: no whole tensor on the device (one rank only)");
+int asb_gs_check_matrix(asb_ctx* ctx, const char* who, int64_t n, const int64_t* indptr, const int64_t* indices, const double* data,
+                        std::vector<int>& p32, std::vector<int>& c32) {
+    if (!ctx->X || ctx->v0 != 0 || ctx->n_loc != ctx->N_glob) ASB_FAIL(ctx, ASB_ERR_ARG, "%s: no whole tensor on the device (one rank only)", who);
     if (n != ctx->n_loc)
-        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_gstep_setup: the matrix has %lld rows, the tensor %lld vertices", (long long)n, (long long)ctx->n_loc);
-    std::vector<int> p32, c32;
+        ASB_FAIL(ctx, ASB_ERR_ARG, "%s: the matrix has %lld rows, the tensor %lld vertices", who, (long long)n, (long long)ctx->n_loc);
     int rc;
-    if ((rc = asb_csr_check32(ctx, "asb_gstep_setup", n, indptr, indices, data, n, p32, c32, "the system matrix"))) return rc;
-    const int64_t nnz = indptr[n];
+    if ((rc = asb_csr_check32(ctx, who, n, indptr, indices, data, n, p32, c32, "the system matrix"))) return rc;
     // ---- finite values, positive diagonal, symmetric pattern, symmetric values to 1e-12 of the row's largest entry
     std::vector<double> rmax((size_t)n, 0.0);
     for (int64_t i = 0; i < n; ++i) {
         double dg = 0.0;
         for (int64_t t = indptr[i]; t < indptr[i + 1]; ++t) {
-            if (!std::isfinite(data[t])) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_gstep_setup: row %lld holds a value that is not finite", (long long)i);
+            if (!std::isfinite(data[t])) ASB_FAIL(ctx, ASB_ERR_ARG, "%s: row %lld holds a value that is not finite", who, (long long)i);
             if (indices[t] == i) dg = data[t];
             if (std::fabs(data[t]) > rmax[i]) rmax[i] = std::fabs(data[t]);
         }
-        if (!(dg > 0.0)) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_gstep_setup: the diagonal of row %lld is %g (must be positive)", (long long)i, dg);
+        if (!(dg > 0.0)) ASB_FAIL(ctx, ASB_ERR_ARG, "%s: the diagonal of row %lld is %g (must be positive)", who, (long long)i, dg);
     }
     for (int64_t i = 0; i < n; ++i)
         for (int64_t t = indptr[i]; t < indptr[i + 1]; ++t) {
@@ -100,12 +96,25 @@ extern "C" int asb_gstep_setup(asb_ctx* ctx, int64_t n, const int64_t* indptr, c
             const int* hi = c32.data() + indptr[j + 1];
             const int* at = std::lower_bound(lo, hi, (int)i);
             if (at == hi || *at != (int)i)
-                ASB_FAIL(ctx, ASB_ERR_ARG, "asb_gstep_setup: entry (%lld, %lld) has no mirror: the pattern is not symmetric", (long long)i, (long long)j);
+                ASB_FAIL(ctx, ASB_ERR_ARG, "%s: entry (%lld, %lld) has no mirror: the pattern is not symmetric", who, (long long)i, (long long)j);
             const double other = data[at - c32.data()];
             if (std::fabs(data[t] - other) > 1e-12 * rmax[i])
-                ASB_FAIL(ctx, ASB_ERR_ARG, "asb_gstep_setup: entries (%lld, %lld) = %.17g and its mirror %.17g differ: not symmetric", (long long)i,
+                ASB_FAIL(ctx, ASB_ERR_ARG, "%s: entries (%lld, %lld) = %.17g and its mirror %.17g differ: not symmetric", who, (long long)i,
                          (long long)j, data[t], other);
         }
+    return ASB_OK;
+}
+
+extern "C" int asb_gstep_setup(asb_ctx* ctx, int64_t n, const int64_t* indptr, const int64_t* indices, const double* data, double* resid_out) {
+    if (!ctx || !indptr || n < 1) return ASB_ERR_ARG;
+    ctx->gs_n = 0, ctx->hy_ok = 0;
+    asb_gslab_release(ctx);                                   // the context holds one solver
+    if (n > GS_MAX_N)
+        ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_gstep_setup: %lld vertices are too many for an explicit inverse (at most %d)", (long long)n, GS_MAX_N);
+    std::vector<int> p32, c32;
+    int rc;
+    if ((rc = asb_gs_check_matrix(ctx, "asb_gstep_setup", n, indptr, indices, data, p32, c32))) return rc;
+    const int64_t nnz = indptr[n];
     const int ni = (int)n, np = (ni + GS_TN - 1) / GS_TN * GS_TN;
     ASB_HIP(ctx, hipSetDevice(ctx->dev));
     asb_tmp<int> dptr, dci;
@@ -152,13 +161,20 @@ __global__ __launch_bounds__(256) void k_gstep_gemm(const double* __restrict__ r
 
 extern "C" int asb_gstep_run(asb_ctx* ctx, const double* rhs_dev, int64_t n_frames, double* out_dev) {
     if (!ctx || !rhs_dev || !out_dev) return ASB_ERR_ARG;
-    if (ctx->gs_n < 1 || !ctx->gs_Ainv) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_gstep_run: no inverse on the device (asb_gstep_setup)");
+    const long long n_slab = asb_gslab_n(ctx);
+    if (n_slab < 1 && (ctx->gs_n < 1 || !ctx->gs_Ainv)) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_gstep_run: no inverse on the device (asb_gstep_setup)");
     if (n_frames < 1 || (n_frames + GS_TF - 1) / GS_TF > 65535)
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_gstep_run: %lld frames in one call (1 .. %d)", (long long)n_frames, 65535 * GS_TF);
-    const long long len = (long long)n_frames * ctx->gs_n * 3;
+    const long long len = (long long)n_frames * (n_slab > 0 ? n_slab : ctx->gs_n) * 3;
     if (rhs_dev < out_dev + len && out_dev < rhs_dev + len)
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_gstep_run: the right-hand side and the output overlap (the product is not done in place)");
     ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    if (n_slab > 0) {                                         // the slab factor: in -> sweep -> rows -> k_pd_untranspose
+        int rc;
+        if ((rc = asb_gslab_solve_fm(ctx, rhs_dev, n_frames, nullptr, out_dev))) return rc;
+        ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return ASB_OK;
+    }
     const dim3 grid((unsigned)(ctx->gs_Np / GS_TN), (unsigned)((n_frames + GS_TF - 1) / GS_TF));
     hipLaunchKernelGGL(k_gstep_gemm, grid, dim3(256), 0, ctx->stream, rhs_dev, ctx->gs_Ainv, (int)ctx->gs_n, (int)ctx->gs_Np,
                        (long long)n_frames, out_dev);
@@ -245,6 +261,7 @@ extern "C" int asb_gstep_inertia(asb_ctx* ctx, int which, int64_t f0, int64_t f1
 // test hook: the n x n block of the context's A^-1, row-major, to the host
 extern "C" int asb_test_gstep_inverse(asb_ctx* ctx, double* out_host, int64_t n) {
     if (!ctx || !out_host) return ASB_ERR_ARG;
+    if (asb_gslab_n(ctx) > 0) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_gstep_inverse: the context holds the slab factor, no explicit inverse");
     if (ctx->gs_n < 1 || n != ctx->gs_n) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_gstep_inverse: the inverse has %lld rows, not %lld", (long long)ctx->gs_n, (long long)n);
     ASB_HIP(ctx, hipSetDevice(ctx->dev));
     ASB_HIP(ctx, hipMemcpy2DAsync(out_host, (size_t)n * sizeof(double), ctx->gs_Ainv, (size_t)ctx->gs_Np * sizeof(double), (size_t)n * sizeof(double),

@@ -33,6 +33,8 @@
 //                                   wave w sums rows w, w + 4, .. of its 64 frames, the four partials are added in wave order,
 //                                   and k_pd_hist adds the vertex tiles' records of a frame in ascending order.
 // Nothing is split and nothing is atomic: repeats, frame sub-ranges and any chunk width give identical bits.
+// With the slab factor of asb_gslab.hip held instead of the inverse, the product of an iteration, c of a hyper-reduced solve and
+// the operator A^-1 S^T V go through that unit's sweep (asb_gslab_solve_fm / _rows); the history is then refused.
 #include "asb_gstep_tile.h"
 
 #include <algorithm>
@@ -189,6 +191,12 @@ __global__ __launch_bounds__(256) void k_pd_hist(const double* __restrict__ part
     rec[f * 2 + 1] = n2;
 }
 
+// the vertices of the solver the context holds, the explicit inverse or the slab factor (asb_gslab.hip); 0: none
+static long long pd_solver_n(const asb_ctx* ctx) {
+    const long long m = asb_gslab_n(ctx);
+    return m > 0 ? m : (ctx->gs_Ainv ? ctx->gs_n : 0);
+}
+
 // ---------------------------------------------------------------- entry points
 // a buffer of the context and one of a slot change places, with their registered capacities
 template <typename T>
@@ -219,7 +227,7 @@ extern "C" int asb_pdsolve_begin(asb_ctx* ctx, int which, int64_t f0, int64_t f1
     int rc;
     if ((rc = asb_world_frames(ctx, "asb_pdsolve_begin", which, f0, f1, fj, add_mean, psf, &w, &n_sel))) return rc;
     const int64_t n = ctx->n_loc;
-    if (ctx->gs_n < 1 || !ctx->gs_Ainv || ctx->gs_n != n)
+    if (pd_solver_n(ctx) != n)
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_begin: no inverse for the %lld vertices of the tensor on the device (asb_gstep_setup)", (long long)n);
     for (int64_t v = 0; v < n; ++v)
         if (!std::isfinite(diag[v])) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_begin: diag[%lld] is not finite", (long long)v);
@@ -307,8 +315,11 @@ extern "C" int asb_pdsolve_iterate(asb_ctx* ctx, int64_t n_iter, int64_t chunk_f
     if (!s || !s->begun || s->n_slots < 1) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_iterate: no solve begun or no kind registered (asb_pdsolve_begin, asb_pdsolve_slot)");
     if (n_iter < 1 || n_iter > (1 << 20)) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_iterate: %lld iterations", (long long)n_iter);
     if (chunk_frames < 0) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_iterate: chunk_frames %lld", (long long)chunk_frames);
-    if (ctx->gs_n != s->n || !ctx->gs_Ainv || ctx->n_loc != s->n)
+    if (pd_solver_n(ctx) != s->n || ctx->n_loc != s->n)
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_iterate: the inverse or the tensor changed since asb_pdsolve_begin");
+    const bool slab = asb_gslab_n(ctx) > 0;
+    if (slab && hist_out)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_iterate: the history of step norms is not built for the slab factor (asb_gslab_setup)");
     const long long n_sel = s->n_sel, n = s->n;
     long long cw[PD_MAX_SLOTS];
     size_t scratch = 0, coef = 0;
@@ -325,7 +336,7 @@ extern "C" int asb_pdsolve_iterate(asb_ctx* ctx, int64_t n_iter, int64_t chunk_f
         scratch = std::max<size_t>(scratch, (size_t)3 * p.n_cols * cw[k]);
     }
     ASB_HIP(ctx, hipSetDevice(ctx->dev));
-    const int tiles = (int)(ctx->gs_Np / GS_TN);
+    const int tiles = slab ? 0 : (int)(ctx->gs_Np / GS_TN);
     int rc;
     if ((rc = asb_alloc(ctx, &ctx->cf_scratch, scratch))) return rc;
     if (coef && (rc = asb_alloc(ctx, &ctx->rf_coef, coef))) return rc;
@@ -350,6 +361,10 @@ extern "C" int asb_pdsolve_iterate(asb_ctx* ctx, int64_t n_iter, int64_t chunk_f
         }
         hipLaunchKernelGGL(k_pd_add, dim3(g_add), dim3(256), 0, ctx->stream, s->b, s->ms, len);
         const bool fm = out_dev && it == n_iter - 1;
+        if (slab) {                                 // in -> sweep -> rows into the iterate (-> k_pd_untranspose)
+            if ((rc = asb_gslab_solve_fm(ctx, s->b, n_sel, s->Q, fm ? out_dev : nullptr))) return rc;
+            continue;
+        }
         auto kern = fm ? (hist_out ? k_pdsolve_gemm<true, true> : k_pdsolve_gemm<true, false>)
                        : (hist_out ? k_pdsolve_gemm<false, true> : k_pdsolve_gemm<false, false>);
         hipLaunchKernelGGL(kern, grid, dim3(256), 0, ctx->stream, s->b, ctx->gs_Ainv, (int)n, (int)ctx->gs_Np, n_sel, s->Q, s->ld, out_dev, s->part);
@@ -412,6 +427,11 @@ __global__ __launch_bounds__(256) void k_pd_untranspose(const double* __restrict
     __syncthreads();
     for (int fl = wv; fl < 64; fl += 4)
         if (t0 + fl < n_sel && r0 + lane < rows) out[(long long)(t0 + fl) * rows + r0 + lane] = tile[fl * PD_LDQ + lane];
+}
+
+void asb_pd_untranspose_launch(asb_ctx* ctx, const double* P, int n_sel, long long rows, long long ld, double* out) {
+    hipLaunchKernelGGL(k_pd_untranspose, dim3((unsigned)((rows + 63) / 64), (unsigned)((n_sel + 63) / 64)), dim3(256), 0, ctx->stream, P, n_sel, rows,
+                       ld, out);
 }
 
 extern "C" int asb_pdsolve_carry(asb_ctx* ctx, const double* pos_dev) {
@@ -612,10 +632,11 @@ __global__ __launch_bounds__(256) void k_hyper_apply(const double* __restrict__ 
 extern "C" int asb_hyper_operator(asb_ctx* ctx) {
     if (!ctx) return ASB_ERR_ARG;
     ctx->hy_ok = 0;
-    if (ctx->gs_n < 1 || !ctx->gs_Ainv) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_operator: no inverse on the device (asb_gstep_setup)");
+    const long long ns = pd_solver_n(ctx);
+    if (ns < 1) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_operator: no inverse on the device (asb_gstep_setup)");
     if (ctx->rf_mp < 1 || !ctx->rf_M) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_operator: no operator S^T V on the device (asb_rforce_operator)");
-    if (ctx->rf_n != ctx->gs_n || ctx->gs_n != ctx->n_loc)
-        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_operator: the inverse has %lld rows, S^T V %lld, the tensor %lld vertices", (long long)ctx->gs_n,
+    if (ctx->rf_n != ns || ns != ctx->n_loc)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_operator: the inverse has %lld rows, S^T V %lld, the tensor %lld vertices", ns,
                  (long long)ctx->rf_n, (long long)ctx->n_loc);
     const long long jb = (ctx->rf_mp + HY_JB - 1) / HY_JB;
     if (jb > 65535) ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_hyper_operator: %lld basis vectors (at most %d)", (long long)ctx->rf_mp, 65535 * HY_JB);
@@ -624,6 +645,12 @@ extern "C" int asb_hyper_operator(asb_ctx* ctx) {
     int rc;
     if ((rc = asb_alloc(ctx, &ctx->hy_G, len))) return rc;
     ASB_HIP(ctx, hipMemsetAsync(ctx->hy_G, 0, len * sizeof(double), ctx->stream));
+    if (asb_gslab_n(ctx) > 0) {                     // the slab factor: the 3 mpp rows of rf_M are the columns of one sweep
+        if ((rc = asb_gslab_solve_rows(ctx, ctx->rf_M, 3 * ctx->rf_mpp, ctx->rf_Np, ctx->hy_G))) return rc;
+        ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->hy_ok = 1;
+        return ASB_OK;
+    }
     hipLaunchKernelGGL(k_hy_operator, dim3((unsigned)((ctx->gs_n + 255) / 256), (unsigned)jb, 3), dim3(256), 0, ctx->stream, ctx->gs_Ainv,
                        (int)ctx->gs_n, (int)ctx->gs_Np, ctx->rf_M, (long long)ctx->rf_Np, (int)ctx->rf_mp, (int)ctx->rf_mpp, ctx->hy_G);
     ASB_CHECK_LAUNCH(ctx);
@@ -642,7 +669,7 @@ extern "C" int asb_hyper_iterate(asb_ctx* ctx, int64_t n_iter, int64_t n_touched
                  s->slot[0].reduced ? "one of them reduced" : "the first not reduced");
     if (n_iter < 1 || n_iter > (1 << 20)) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: %lld iterations", (long long)n_iter);
     if (chunk_frames < 0) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: chunk_frames %lld", (long long)chunk_frames);
-    if (ctx->gs_n != s->n || !ctx->gs_Ainv || ctx->n_loc != s->n)
+    if (pd_solver_n(ctx) != s->n || ctx->n_loc != s->n)
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: the inverse or the tensor changed since asb_pdsolve_begin");
     const PdSlot& p = s->slot[0];
     if (ctx->rf_mp < 1 || ctx->rf_r < 1 || ctx->rf_n != s->n || ctx->rf_pt_max >= p.n_cols)
@@ -671,8 +698,12 @@ extern "C" int asb_hyper_iterate(asb_ctx* ctx, int64_t n_iter, int64_t n_touched
     if ((rc = asb_alloc(ctx, &ctx->rf_coef, (size_t)3 * rpp * cw))) return rc;
     if ((rc = asb_alloc(ctx, &s->c, (size_t)3 * n * ld))) return rc;
     ASB_HIP(ctx, hipMemsetAsync(s->c, 0, (size_t)3 * n * ld * sizeof(double), ctx->stream));
-    hipLaunchKernelGGL((k_pdsolve_gemm<false, false>), dim3((unsigned)(ctx->gs_Np / GS_TN), (unsigned)((n_sel + GS_TF - 1) / GS_TF)), dim3(256), 0,
-                       ctx->stream, s->ms, ctx->gs_Ainv, (int)n, (int)ctx->gs_Np, n_sel, s->c, ld, nullptr, nullptr);
+    if (asb_gslab_n(ctx) > 0) {                     // c through the slab factor: in -> sweep -> rows
+        if ((rc = asb_gslab_solve_fm(ctx, s->ms, n_sel, s->c, nullptr))) return rc;
+    } else {
+        hipLaunchKernelGGL((k_pdsolve_gemm<false, false>), dim3((unsigned)(ctx->gs_Np / GS_TN), (unsigned)((n_sel + GS_TF - 1) / GS_TF)), dim3(256), 0,
+                           ctx->stream, s->ms, ctx->gs_Ainv, (int)n, (int)ctx->gs_Np, n_sel, s->c, ld, nullptr, nullptr);
+    }
     asb_tmp<int> tv;
     double *Qi = s->Q, *ci = s->c, *Gi = ctx->hy_G;     // what iterations 1 .. K-1 run on
     long long ldg = ctx->rf_Np;

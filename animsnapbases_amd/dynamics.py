@@ -1,7 +1,7 @@
 """``ResidentDynamics`` -- what ``posSnapshots`` offers beyond the reference's class: the pieces of the reference's
 projective-dynamics solver (Simulators.py) evaluated on the device for the frames of the resident animation -- constraint
-projections, constraint forces, their DEIM reduction, the global step, the solver's iterations and its time steps (DESIGN.md
-3.10-3.16).
+projections, constraint forces, their DEIM reduction, the global step, the solver's iterations and its time steps, with the choice of the global step's solver (DESIGN.md
+3.10-3.17).
 A public call checks its arguments into the named records below before the engine is touched; the helpers take the records.
 """
 import collections
@@ -44,7 +44,8 @@ ReducedPlan = collections.namedtuple("ReducedPlan", "term frames operator")
 class ResidentDynamics(object):
     """Mixin of ``posSnapshots``.  Reads from the host object: ``_engine``, ``_comm``, ``nVerts``, ``frs``, ``verts``, ``tris``,
     ``test_verts``, ``mass``, ``massL``, ``invMassL``, ``_standarize``, ``pre_scale_factor``, ``mean`` and ``snapTensor``.
-    Leaves: ``assembly_ST``, ``bending_indices``, ``global_matrix``, ``global_solve_residual``."""
+    Leaves: ``assembly_ST``, ``bending_indices``, ``global_matrix``, ``global_solve_residual`` and, under the slab solver
+    (``set_global_solver``), ``global_solve_slabs`` = (slabs, vertices of the largest)."""
 
     # ------------------------------------------------------------------ the records of a call
     def _frames(self, animation, frame_start, frame_end, frame_jump):
@@ -321,14 +322,58 @@ class ResidentDynamics(object):
         takes the vertex masses the snapshots were mass-weighted with.  Leaves ``self.global_matrix`` (CSR) and
         ``self.global_solve_residual`` = max |A (A^-1 1) - 1| as the device computed it.  Cost: the host assembly and symmetry
         check, and on the device a dense N x N inversion (N^3 flop, 8 N^2 bytes); a set-up whose matrix equals the one the
-        device already holds keeps that inverse.  N <= 46 000, one rank only."""
+        device already holds keeps that inverse.  N <= 46 000, one rank only.  Under ``set_global_solver("slab")`` the matrix is
+        factorised over breadth-first slabs instead (no limit on N but memory) and ``self.global_solve_slabs`` is left too."""
         self._one_rank("global_solve_setup")
         self._matrix(self._plan(kinds), self._masses(masses), dt)
 
+    def set_global_solver(self, kind="inverse", slab_target=None):
+        """Extra: how every later call of this object applies A^-1 -- ``global_solve``, ``global_step``, ``solve_frames``,
+        ``simulate_frames`` and the four ``reduced_*_errors`` sweeps that solve.
+
+        ``kind`` "inverse" (the default): the explicit dense inverse of ``global_solve_setup``, N <= 46 000.  "slab": A is
+        ordered by breadth-first level sets of its own graph grouped into slabs of at least ``slab_target`` vertices
+        (``projections.slab_plan``), factorised block-tridiagonally on the device and applied by a forward and a backward
+        sweep over the slabs (csrc/asb_gslab.hip): no limit on N but memory -- the factor holds the sum of the
+        squared slab sizes in doubles, a solve one work matrix of N x 3 F' more.  ``slab_target``: None takes
+        ``projections.SLAB_TARGET`` (256); only with "slab".  Results of the two solvers agree to rounding (64 eps kappa(A)
+        max |q| each), not to the bit; under either, repeats, frame sub-ranges and chunk widths give identical bits.
+        Out of scope under "slab": ``history=True`` of ``solve_frames`` (ValueError).  The arguments are checked before the
+        device is touched; the device's solver is replaced by the next call that needs the matrix."""
+        if kind not in ("inverse", "slab"):
+            raise ValueError("set_global_solver: kind must be 'inverse' or 'slab', not %r" % (kind,))
+        if slab_target is not None:
+            if kind != "slab":
+                raise ValueError("set_global_solver: slab_target is for kind='slab' only")
+            try:
+                t = int(slab_target)
+            except (TypeError, ValueError):
+                t = 0
+            if t != slab_target or isinstance(slab_target, bool) or t < 1:
+                raise ValueError("set_global_solver: slab_target %r: a positive number of vertices per slab or None" % (slab_target,))
+            slab_target = t
+        self._global_solver = (kind, slab_target)
+
+    def _slab_solver(self):
+        """None under the explicit inverse, else the slab target in force."""
+        kind, target = getattr(self, "_global_solver", ("inverse", None))
+        return None if kind == "inverse" else (_proj.SLAB_TARGET if target is None else target)
+
     def _matrix(self, plan, masses, dt):
-        """A of the plan, inverted on the device unless the device holds that very matrix."""
+        """A of the plan, inverted (or, under the slab solver, factorised) on the device unless the device holds that very
+        matrix."""
         A = _proj.global_matrix([(t.setup, t.wi) for t in plan], self.nVerts, masses, dt)
         self.global_matrix, self.global_solve_residual = None, None
+        target = self._slab_solver()
+        if target is not None:
+            self.global_solve_slabs = None
+            sp = _proj.slab_plan(A, target)
+            held = self._engine.gslab_held(A, sp)
+            if held is None:
+                held = self._engine.gslab_setup(A, sp)
+            self.global_matrix, self.global_solve_residual = A, held[0]
+            self.global_solve_slabs = (len(sp.slab_ptr) - 1, int(np.diff(sp.slab_ptr).max()))
+            return
         resid = self._engine.gstep_held(A)
         if resid is None:
             resid = self._engine.gstep_setup(A)
@@ -540,13 +585,16 @@ class ResidentDynamics(object):
         ``start``: "explicit" (q_0 = s_f, the reference's), "frame" (q_0 = x_f; one iteration is then ``global_step`` bit for
         bit) or a contiguous ``torch.float64`` device tensor (F', N, 3) -- a solve continued from an earlier result equals the
         longer solve bit for bit.  ``history``: also the (num_iterations, F') array of |q_{k+1} - q_k| / |q_{k+1}| (Frobenius
-        norms of the frame).
+        norms of the frame); refused under ``set_global_solver("slab")``.
 
         Returns ``(tensor, F')`` (``(tensor, F', steps)`` with ``history``): a ``torch.float64`` device tensor (F', N, 3) in
         world space, owned by the caller.  Device memory held by the engine beside A^-1: three times the result plus the
         projections of one chunk.  %s"""
         who = "solve_frames"
         self._hyper_check(who, hyper, kinds, history)
+        if history and self._slab_solver() is not None:
+            raise ValueError("%s: history=True under set_global_solver('slab'): the step norms are formed by the explicit inverse's "
+                             "product kernel and are out of scope for the slab solver" % who)
         ex, K = self._solve_args(who, dt, velocity, gravity, num_iterations, start, masses)
         frames = self._frames(animation, frame_start, frame_end, frame_jump)
         plan, red = self._solve_plan(who, kinds, chunk_frames)

@@ -585,7 +585,7 @@ class HipEngine(object):
         the context.  Returns max |A (A^-1 1) - 1|."""
         n, indptr, indices, data = self._csr(A)
         res = ctypes.c_double()
-        self._gstep = None
+        self._gstep = self._gslab = None            # (the context holds one solver: the set-up releases a slab factor)
         self._ck(self.lib.asb_gstep_setup(self.h, n, ptr(indptr), ptr(indices), ptr(data), ctypes.byref(res)))
         self._gstep = (indptr.copy(), indices.copy(), data.copy(), res.value)      # (copies: A stays the caller's)
         return res.value
@@ -614,6 +614,51 @@ class HipEngine(object):
         """Test hook: the (n, n) inverse the context holds."""
         out = np.empty((int(n), int(n)))
         self._ck(self.lib.asb_test_gstep_inverse(self.h, ptr(out), int(n)))
+        return out
+
+    def gslab_setup(self, A, plan):
+        """Factorises ``A`` (as ``gstep_setup`` takes it) block-tridiagonally over the slabs of ``plan``
+        (``projections.slab_plan``) on the device; the factor replaces the explicit inverse in the context and every later
+        ``gstep_run``, ``pdsolve_*`` and ``hyper_*`` call goes through it.  Returns (max |A (A^-1 1) - 1|, (slabs, largest
+        padded slab))."""
+        n, indptr, indices, data = self._csr(A)
+        order = np.ascontiguousarray(plan.order, dtype=np.int64)
+        sptr = np.ascontiguousarray(plan.slab_ptr, dtype=np.int64)
+        res = ctypes.c_double()
+        self._gstep = self._gslab = None
+        self._ck(self.lib.asb_gslab_setup(self.h, n, ptr(indptr), ptr(indices), ptr(data), int(sptr.shape[0]) - 1, ptr(sptr),
+                                          ptr(order), ctypes.byref(res)))
+        info = self.gslab_info()
+        self._gslab = (indptr.copy(), indices.copy(), data.copy(), order.copy(), sptr.copy(), res.value, (int(info[0]), int(info[1])))
+        return res.value, self._gslab[6]
+
+    def gslab_held(self, A, plan):
+        """(residual, (slabs, largest padded slab)) of the last ``gslab_setup`` if its matrix and plan were these entry for
+        entry (the factor is still on the device), else None."""
+        held = getattr(self, "_gslab", None)
+        if held is None or held[0].shape[0] != A.shape[0] + 1:
+            return None
+        same = all(np.array_equal(h, a) for h, a in zip(held[:5], (A.indptr, A.indices, A.data, plan.order, plan.slab_ptr)))
+        return (held[5], held[6]) if same else None
+
+    def gslab_info(self):
+        """(slabs, largest padded slab, padded rows of the work matrix, doubles of the factor) of the factor on the device."""
+        out = np.zeros(4, dtype=np.int64)
+        self._ck(self.lib.asb_gslab_info(self.h, ptr(out)))
+        return out
+
+    def gslab_gemm_time(self, sp, w):
+        """Timing hook: (ms of the sweep's product kernel, ms of asb_gemm_nn) on one (sp x sp)(sp x w) product, best of three."""
+        out = np.zeros(2)
+        self._ck(self.lib.asb_test_gslab_gemm_time(self.h, int(sp), int(w), ptr(out)))
+        return float(out[0]), float(out[1])
+
+    def gslab_solve(self, rhs):
+        """Test hook: A^-1 ``rhs`` for a host array (N, w) through the device's sweep."""
+        rhs = np.ascontiguousarray(rhs, dtype=np.float64)
+        assert rhs.ndim == 2 and rhs.shape[0] == self.N_glob and rhs.shape[1] >= 1
+        out = np.empty_like(rhs)
+        self._ck(self.lib.asb_test_gslab_solve(self.h, ptr(rhs), int(rhs.shape[1]), ptr(out)))
         return out
 
     # ------------------------------------------------------------------ solver iterations of projective dynamics

@@ -676,8 +676,34 @@ int asb_gstep_run(asb_ctx* ctx, const double* rhs_dev, int64_t n_frames, double*
  * rhs_dev: caller-owned DEVICE memory (n_sel, n, 3), read and written entry by entry.  Returns after the stream has drained. */
 int asb_gstep_inertia(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean, double psf,
                       const double* diag, int mode, const double* acc3, double* rhs_dev);
-/* test hook: the n x n block of the context's A^-1 (row-major) to the host */
+/* test hook: the n x n block of the context's A^-1 (row-major) to the host; refused (ASB_ERR_ARG) under the slab factor */
 int asb_test_gstep_inverse(asb_ctx* ctx, double* out_host, int64_t n);
+
+/* ------------------------------- global step: the block-tridiagonal slab factor (asb_gslab.hip) ---- */
+/* The second solver of the global step, for any n that fits the memory.  The context holds EITHER the explicit inverse of
+ * asb_gstep_setup OR this factor: each set-up releases the other and invalidates the operator of asb_hyper_operator.  With the
+ * factor held, asb_gstep_run, asb_pdsolve_begin / _iterate, asb_hyper_operator and asb_hyper_iterate apply A^-1 through it;
+ * asb_pdsolve_iterate with a history and asb_test_gstep_inverse are refused (ASB_ERR_ARG).
+ * asb_gslab_setup: A_N as the HOST CSR of asb_gstep_setup, with that entry's checks, plus a slab plan (projections.slab_plan):
+ * order (n) = permuted index -> vertex, a permutation; slab_ptr (nslab + 1) = slab boundaries in the permuted numbering,
+ * ascending from 0 to n; no entry of A may couple slabs more than one apart.  Each violation is ASB_ERR_ARG; the counts are
+ * judged before anything behind a pointer is read.  ASB_ERR_LIMIT: padded rows past 32-bit indices, or a slab of more than
+ * 8192 vertices.  S_0 = A_00, S_k = A_kk - C_k S_{k-1}^-1 C_k^T (C_k = A_{k,k-1}) are formed and inverted on the device (the dense
+ * layer's GEMM and SPD inverse); only the S_k^-1 are kept, padded to multiples of 16: sum sp_k^2 doubles.  A Schur complement
+ * that is not positive definite: ASB_ERR_NUMERIC, no solver is left.  resid_out (optional): max |A (A^-1 u) - u| for u = 1
+ * through the sweep and the sparse A.
+ * The sweep: forward u_k = S_k^-1 (b_k - C_k u_{k-1}), backward x_k = u_k - S_k^-1 (C_{k+1}^T x_{k+1}), all columns at once, one
+ * sparse and one f64-MFMA product per slab and direction in stream order.  No contraction is split between blocks and
+ * nothing is atomic: an entry does not depend on the columns around it, on chunk_frames or on a repeat. */
+int asb_gslab_setup(asb_ctx* ctx, int64_t n, const int64_t* indptr, const int64_t* indices, const double* data, int64_t nslab,
+                    const int64_t* slab_ptr, const int64_t* order, double* resid_out);
+/* counts_out (4): slabs, largest padded slab, padded rows of the work matrix, doubles held by the factor */
+int asb_gslab_info(asb_ctx* ctx, int64_t* counts_out);
+/* test hook: out_host (n, w) = A^-1 rhs_host (n, w) through the sweep; any w >= 1, host arrays (they may be the same) */
+int asb_test_gslab_solve(asb_ctx* ctx, const double* rhs_host, int64_t w, double* out_host);
+/* timing hook: ms_out (2) = best of three of the sweep's product kernel and of asb_gemm_nn on the same (sp x sp) (sp x w) product
+ * of zero-filled device buffers; sp a multiple of 16 (<= 8192), w of 64 */
+int asb_test_gslab_gemm_time(asb_ctx* ctx, int64_t sp, int64_t w, double* ms_out);
 
 /* ------------------------------------------------ projective dynamics: the solver's iterations (asb_pdsolve.hip) ----------- */
 /* The local/global loop of Simulators.py:494-526 for the frames range(f0, f1, fj) of the training (which 0) or held-out (1)
