@@ -171,6 +171,7 @@ PROTOTYPES = {
                                c_int, c_i64, ctypes.c_void_p]),
     "asb_rforce_operator": (c_int, [ctypes.c_void_p, c_i64, c_dp, c_dp, c_dp, c_i64, c_i64, c_dp]),
     "asb_rforce_solver": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp]),
+    "asb_rforce_bank": (c_int, [ctypes.c_void_p, c_int]),
     "asb_rforce_run": (c_int, [ctypes.c_void_p, c_int, c_i64, c_i64, c_i64, c_dp, c_int, c_dbl, c_dbl, c_dbl, c_int, ctypes.c_void_p]),
     "asb_force_diff": (c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp]),
     "asb_gstep_setup": (c_int, [ctypes.c_void_p, c_i64, c_dp, c_dp, c_dp, ctypes.POINTER(c_dbl)]),

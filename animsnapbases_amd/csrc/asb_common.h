@@ -348,6 +348,18 @@ struct asb_ctx {
     // hyper-reduced iterations (asb_pdsolve.hip): G_d^T = (A^-1 M_d)^T in rf_M's layout, (3, rf_mpp, rf_Np)
     double* hy_G = nullptr;
     int hy_ok = 0;                    // hy_G belongs to the current gs_Ainv and rf_M (asb_gstep_setup / asb_rforce_operator clear it)
+    double* hy_Gc = nullptr;          // asb_hyper_iterate: the touched columns of hy_G, (3, rf_mpp, N_t rounded up to 32, zero padding)
+    // The banks of asb_rforce_bank: rf_* and hy_* above are the CURRENT bank rf_cur; the others rest in rf_bank (the entry of
+    // the current one holds nothing).  asb_rf_select swaps the fields with their registered capacities, so every launcher
+    // keeps reading ctx->rf_*; asb_rf_view reads any bank without a swap.
+    struct RfBank {
+        double *M = nullptr, *H = nullptr, *coef = nullptr, *G = nullptr, *Gc = nullptr;
+        int* pt = nullptr;
+        int64_t n = 0, Np = 0, mp = 0, mpp = 0, r = 0, npt = 0, pt_max = -1;
+        int ok = 0;
+    };
+    RfBank rf_bank[ASB_RFORCE_BANKS];
+    int rf_cur = 0;
     int64_t cp_vmax = -1;             // largest vertex the last asb_cproj_setup names (elements and star edges)
     // the global step's second solver (asb_gslab.hip): the block-tridiagonal slab factor of A_N.  The context holds EITHER
     // gs_Ainv (gs_n > 0) or the factor (asb_gslab_n(ctx) > 0): each set-up releases the other
@@ -451,6 +463,23 @@ long long asb_rforce_chunk_width(asb_ctx* ctx, long long n_cols, long long n_sel
 void asb_rforce_chunk_launch(asb_ctx* ctx, const double* S, int cw, int c0, int cn, int accumulate, double* out);
 // its first half alone: k_rforce_coef of one chunk into ctx->rf_coef ((3, rf_r rounded up to 4, cw), zero past row rf_r and frame cn)
 void asb_rforce_coef_launch(asb_ctx* ctx, const double* S, int cw, int cn);
+// The banks (asb_rforce_bank).  RfView: what the kernels need of one bank, by value.  asb_rf_select makes `bank` the current one
+// (host work only: pointers and their registered capacities change places); asb_rf_view reads a bank wherever it rests;
+// asb_rf_invalidate_all clears the A^-1 S^T V mark of every bank (a new system matrix); the _v launchers are
+// asb_rforce_chunk_width / _coef_launch / _chunk_launch for a view.
+struct RfView {
+    const double *M, *H, *G;
+    double *coef, *Gc;
+    const int* pt;
+    long long n, Np, mp, mpp, r, npt, pt_max;
+    int ok;
+};
+void asb_rf_select(asb_ctx* ctx, int bank);
+RfView asb_rf_view(const asb_ctx* ctx, int bank);
+void asb_rf_invalidate_all(asb_ctx* ctx);
+long long asb_rforce_chunk_width_r(long long r, long long n_cols, long long n_sel);
+void asb_rforce_coef_launch_v(asb_ctx* ctx, const RfView& v, const double* S, int cw, int cn);
+void asb_rforce_chunk_launch_v(asb_ctx* ctx, const RfView& v, const double* S, int cw, int c0, int cn, int accumulate, double* out);
 // asb_gstep.hip: k_gs_inertia on device arrays; add: out += diag s, otherwise out = diag s (the value the sum adds)
 void asb_gs_inertia_launch(asb_ctx* ctx, const CpWorld& w, int f0, int fj, int n_sel, long long n, const double* diag_dev, int mode,
                            const double* acc3, bool add, double* out);
@@ -510,6 +539,21 @@ static inline int asb_alloc(asb_ctx* ctx, T** p, size_t count) {
     ASB_HIP(ctx, hipMalloc((void**)p, want));
     ctx->alloc_bytes[(void*)p] = want;
     return ASB_OK;
+}
+
+// two context-owned buffers change places, with their registered capacities (both owners live inside the context or its solve)
+template <typename T>
+static inline void asb_swap_buf(asb_ctx* ctx, T** a, T** b) {
+    auto cap = [&](void* key) {
+        auto it = ctx->alloc_bytes.find(key);
+        const size_t c = it == ctx->alloc_bytes.end() ? 0 : it->second;
+        if (it != ctx->alloc_bytes.end()) ctx->alloc_bytes.erase(it);
+        return c;
+    };
+    const size_t ca = cap((void*)a), cb = cap((void*)b);
+    std::swap(*a, *b);
+    if (*a) ctx->alloc_bytes[(void*)a] = cb;
+    if (*b) ctx->alloc_bytes[(void*)b] = ca;
 }
 
 // A device buffer that lives inside one call: freed when it goes out of scope (hipFree waits for the device, so work still in

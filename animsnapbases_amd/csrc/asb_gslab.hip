@@ -294,7 +294,8 @@ extern "C" int asb_gslab_setup(asb_ctx* ctx, int64_t n, const int64_t* indptr, c
     if (!ctx || !indptr || !slab_ptr || !order || n < 1 || nslab < 1) return ASB_ERR_ARG;
     ASB_HIP(ctx, hipSetDevice(ctx->dev));
     // the context holds one solver: the explicit inverse goes, and an earlier factor
-    ctx->gs_n = 0, ctx->hy_ok = 0;
+    ctx->gs_n = 0;
+    asb_rf_invalidate_all(ctx);
     (void)asb_alloc(ctx, &ctx->gs_Ainv, 0);
     asb_gslab_release(ctx);
     if (nslab > n) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_gslab_setup: %lld slabs for %lld vertices", (long long)nslab, (long long)n);

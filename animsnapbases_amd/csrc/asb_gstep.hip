@@ -107,7 +107,8 @@ int asb_gs_check_matrix(asb_ctx* ctx, const char* who, int64_t n, const int64_t*
 
 extern "C" int asb_gstep_setup(asb_ctx* ctx, int64_t n, const int64_t* indptr, const int64_t* indices, const double* data, double* resid_out) {
     if (!ctx || !indptr || n < 1) return ASB_ERR_ARG;
-    ctx->gs_n = 0, ctx->hy_ok = 0;
+    ctx->gs_n = 0;
+    asb_rf_invalidate_all(ctx);
     asb_gslab_release(ctx);                                   // the context holds one solver
     if (n > GS_MAX_N)
         ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_gstep_setup: %lld vertices are too many for an explicit inverse (at most %d)", (long long)n, GS_MAX_N);

@@ -19,8 +19,9 @@
 //
 // One iteration, in stream order:
 //   per slot, in order, per chunk of frames   k_cproj_em on the iterate's world, then k_st_apply (the first slot overwrites b,
-//                                   the later ones accumulate); the reduced slot: k_cproj_em of the sampled elements,
-//                                   k_rforce_coef, k_rforce_gemm with the context's operator and solver
+//                                   the later ones accumulate); a reduced slot: k_cproj_em of the sampled elements,
+//                                   k_rforce_coef, k_rforce_gemm with the operator and solver of the slot's BANK
+//                                   (asb_rforce_bank: the one current when the slot was registered; one reduced slot per bank)
 //   k_pd_add                        b += ms, elementwise -- the order of asb_gstep_inertia
 //   k_pdsolve_gemm                  the tile of k_gstep_gemm (asb_gstep_tile.h: same loop, same accumulators) with a
 //                                   VERTEX-major epilogue: the 64 frames x 96 rows of a block go through LDS rows of PD_LDQ =
@@ -53,6 +54,7 @@ struct PdSlot {
     double* st_val = nullptr;
     double smin = 1.0, smax = 1.0;
     long long vmax = -1;                                        // the largest vertex its tables name
+    int bank = 0;                                               // reduced: the bank of its operator and solver
 };
 
 struct asb_pds {
@@ -60,9 +62,9 @@ struct asb_pds {
     long long n = 0, n_sel = 0, ld = 0;
     double *ms = nullptr, *Q = nullptr, *b = nullptr;
     double *part = nullptr, *hist = nullptr;      // (vertex tiles, n_sel, 2) records of one iteration; (iterations, n_sel, 2)
-    // asb_hyper_iterate: c = A^-1 ms (3 N, ld) vertex-major like Q; the touched rows of Q and c (3 N_t, ld) and the touched
-    // columns of G^T (3, mpp, N_t rounded up to 32, zero padding)
-    double *c = nullptr, *Qc = nullptr, *cc = nullptr, *Gc = nullptr;
+    // asb_hyper_iterate: c = A^-1 ms (3 N, ld) vertex-major like Q; the touched rows of Q and c (3 N_t, ld).  (The touched
+    // columns of G^T belong to the banks: ctx->hy_Gc.)
+    double *c = nullptr, *Qc = nullptr, *cc = nullptr;
     // the time step: what asb_pdsolve_begin was given (for asb_pdsolve_carry) and what asb_pdsolve_carry made
     bool carry = false;
     CpWorld w = {};
@@ -198,21 +200,6 @@ static long long pd_solver_n(const asb_ctx* ctx) {
 }
 
 // ---------------------------------------------------------------- entry points
-// a buffer of the context and one of a slot change places, with their registered capacities
-template <typename T>
-static void pd_swap(asb_ctx* ctx, T** a, T** b) {
-    auto cap = [&](void* key) {
-        auto it = ctx->alloc_bytes.find(key);
-        const size_t c = it == ctx->alloc_bytes.end() ? 0 : it->second;
-        if (it != ctx->alloc_bytes.end()) ctx->alloc_bytes.erase(it);
-        return c;
-    };
-    const size_t ca = cap((void*)a), cb = cap((void*)b);
-    std::swap(*a, *b);
-    if (*a) ctx->alloc_bytes[(void*)a] = cb;
-    if (*b) ctx->alloc_bytes[(void*)b] = ca;
-}
-
 extern "C" int asb_pdsolve_begin(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean,
                                  double psf, const double* diag, int mode, const double* acc3, int start, const double* start_dev) {
     if (!ctx || !diag || !acc3) return ASB_ERR_ARG;
@@ -274,7 +261,7 @@ extern "C" int asb_pdsolve_slot(asb_ctx* ctx, double sigma_min, double sigma_max
     int rc;
     if (reduced) {
         for (int k = 0; k < s->n_slots; ++k)
-            if (s->slot[k].reduced)
+            if (s->slot[k].reduced && s->slot[k].bank == ctx->rf_cur)       // (another bank: asb_rforce_bank before the operator)
                 ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_slot: a second reduced kind (the context holds one operator and one solver)");
         if (ctx->rf_mp < 1 || ctx->rf_r < 1 || ctx->rf_n != s->n)
             ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_slot: no operator or solver for the tensor on the device (asb_rforce_operator, asb_rforce_solver)");
@@ -298,15 +285,32 @@ extern "C" int asb_pdsolve_slot(asb_ctx* ctx, double sigma_min, double sigma_max
         ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));      // (the staging vectors die here)
     }
     // the tables of asb_cproj_setup pass to the slot (the slot's previous buffers to the context, which has no set-up now)
-    pd_swap(ctx, &ctx->cp_idx, &p.idx);
-    pd_swap(ctx, &ctx->cp_table, &p.table);
-    pd_swap(ctx, &ctx->cp_sptr, &p.sptr);
-    pd_swap(ctx, &ctx->cp_sidx, &p.sidx);
+    asb_swap_buf(ctx, &ctx->cp_idx, &p.idx);
+    asb_swap_buf(ctx, &ctx->cp_table, &p.table);
+    asb_swap_buf(ctx, &ctx->cp_sptr, &p.sptr);
+    asb_swap_buf(ctx, &ctx->cp_sidx, &p.sidx);
     p.kind = ctx->cp_kind, p.n_elem = ctx->cp_n, p.n_cols = n_cols, p.reduced = reduced ? 1 : 0;
-    p.smin = sigma_min, p.smax = sigma_max, p.vmax = ctx->cp_vmax;
+    p.smin = sigma_min, p.smax = sigma_max, p.vmax = ctx->cp_vmax, p.bank = ctx->rf_cur;
     ctx->cp_kind = -1;
     ++s->n_slots;
     return ASB_OK;
+}
+
+// the per-bank buffers of the reduced slots, sized here: coef[k] doubles of coefficients and (optional) gc[k] doubles of
+// gathered columns, each allocated with its bank selected, the bank of the call restored; rv: the slots' views, taken afterwards
+static int pd_bank_alloc(asb_ctx* ctx, const asb_pds* s, const size_t* coef, const size_t* gc, RfView* rv) {
+    const int cur = ctx->rf_cur;
+    int rc = ASB_OK;
+    for (int k = 0; k < s->n_slots && rc == ASB_OK; ++k) {
+        if (!s->slot[k].reduced) continue;
+        asb_rf_select(ctx, s->slot[k].bank);
+        rc = asb_alloc(ctx, &ctx->rf_coef, coef[k]);
+        if (rc == ASB_OK && gc) rc = asb_alloc(ctx, &ctx->hy_Gc, gc[k]);
+    }
+    asb_rf_select(ctx, cur);
+    for (int k = 0; k < s->n_slots; ++k)
+        if (s->slot[k].reduced) rv[k] = asb_rf_view(ctx, s->slot[k].bank);
+    return rc;
 }
 
 extern "C" int asb_pdsolve_iterate(asb_ctx* ctx, int64_t n_iter, int64_t chunk_frames, double* out_dev, double* hist_out) {
@@ -322,14 +326,16 @@ extern "C" int asb_pdsolve_iterate(asb_ctx* ctx, int64_t n_iter, int64_t chunk_f
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_iterate: the history of step norms is not built for the slab factor (asb_gslab_setup)");
     const long long n_sel = s->n_sel, n = s->n;
     long long cw[PD_MAX_SLOTS];
-    size_t scratch = 0, coef = 0;
+    size_t scratch = 0, coef[PD_MAX_SLOTS] = {};
+    RfView rv[PD_MAX_SLOTS] = {};
     for (int k = 0; k < s->n_slots; ++k) {
         const PdSlot& p = s->slot[k];
         if (p.reduced) {
-            if (ctx->rf_mp < 1 || ctx->rf_r < 1 || ctx->rf_n != n || ctx->rf_pt_max >= p.n_cols)
+            rv[k] = asb_rf_view(ctx, p.bank);
+            if (rv[k].mp < 1 || rv[k].r < 1 || rv[k].n != n || rv[k].pt_max >= p.n_cols)
                 ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_iterate: the operator or solver changed since asb_pdsolve_slot");
-            cw[k] = asb_rforce_chunk_width(ctx, p.n_cols, n_sel);
-            coef = (size_t)3 * (((size_t)ctx->rf_r + 3) / 4 * 4) * cw[k];
+            cw[k] = asb_rforce_chunk_width_r(rv[k].r, p.n_cols, n_sel);
+            coef[k] = (size_t)3 * (((size_t)rv[k].r + 3) / 4 * 4) * cw[k];
         } else {
             cw[k] = asb_cforce_chunk_width(p.n_cols, chunk_frames, n_sel);
         }
@@ -339,7 +345,7 @@ extern "C" int asb_pdsolve_iterate(asb_ctx* ctx, int64_t n_iter, int64_t chunk_f
     const int tiles = slab ? 0 : (int)(ctx->gs_Np / GS_TN);
     int rc;
     if ((rc = asb_alloc(ctx, &ctx->cf_scratch, scratch))) return rc;
-    if (coef && (rc = asb_alloc(ctx, &ctx->rf_coef, coef))) return rc;
+    if ((rc = pd_bank_alloc(ctx, s, coef, nullptr, rv))) return rc;
     if (hist_out) {
         if ((rc = asb_alloc(ctx, &s->part, (size_t)tiles * n_sel * 2))) return rc;
         if ((rc = asb_alloc(ctx, &s->hist, (size_t)n_iter * n_sel * 2))) return rc;
@@ -355,7 +361,7 @@ extern "C" int asb_pdsolve_iterate(asb_ctx* ctx, int64_t n_iter, int64_t chunk_f
             for (long long c0 = 0; c0 < n_sel; c0 += cw[k]) {
                 const int cn = (int)(c0 + cw[k] < n_sel ? cw[k] : n_sel - c0);
                 asb_cproj_em_launch_t(ctx, t, wq, 0, 1, (int)c0, cn, (int)cw[k], p.smin, p.smax, ctx->cf_scratch);
-                if (p.reduced) asb_rforce_chunk_launch(ctx, ctx->cf_scratch, (int)cw[k], (int)c0, cn, k > 0, s->b);
+                if (p.reduced) asb_rforce_chunk_launch_v(ctx, rv[k], ctx->cf_scratch, (int)cw[k], (int)c0, cn, k > 0, s->b);
                 else asb_st_apply_launch(ctx, p.st_ptr, p.st_idx, p.st_val, ctx->cf_scratch, (int)cw[k], (int)c0, cn, n, k > 0, s->b);
             }
         }
@@ -504,21 +510,27 @@ extern "C" int asb_test_pdsolve_state(asb_ctx* ctx, int which, double* out_host,
 }
 
 // ================================================================ hyper-reduced iterations
-// When the solve's only kind is reduced, an iteration is affine in the coefficients: per coordinate d
-//   q_{k+1} = c + G_d coef_d(q_k),   c = A^-1 ms (once per solve),   G_d = A^-1 M_d (N x mp, once per matrix and basis),
-// and coef(q_k) reads q_k at the vertices of the sampled elements only -- the TOUCHED vertices.  Iterations 1 .. K-1 therefore
+// When every kind of the solve is reduced (each on its own bank of asb_rforce_bank), an iteration is affine in the coefficients:
+// per coordinate d
+//   q_{k+1} = c + sum_s G_{s,d} coef_{s,d}(q_k),   c = A^-1 ms (once per solve),   G_{s,d} = A^-1 M_{s,d} (N x mp_s, once per matrix and basis),
+// and coef(q_k) reads q_k at the vertices of the sampled elements only -- the TOUCHED vertices, the union over the kinds.  Iterations 1 .. K-1 therefore
 // run on the touched rows of c, G and q (compact buffers of N_t vertices, the element tables renumbered by the host); only
 // the last iteration expands to all N rows.  No N^2 product is left in the loop.
 //
 //   asb_hyper_operator    k_hy_operator: Gt_d[j][m] = sum_n A^-1[n][m] M_d[n][j], one thread per (m, 8 values of j), n ascending,
 //                         one FMA accumulator per entry, never split.  Stored like rf_M, (3, mpp, Np), zero padding.  Marked
-//                         valid; asb_gstep_setup and asb_rforce_operator clear the mark, and a stale G is refused.
+//                         valid; asb_gstep_setup / asb_gslab_setup clear the mark of every bank, asb_rforce_operator that of
+//                         its own, and a stale G is refused.
 //   asb_hyper_iterate     c by ONE launch of k_pdsolve_gemm<false, false> on ms (gs_contract, vertex-major epilogue) into a buffer
 //                         shaped like Q.  touched given: k_hy_gather_rows copies the touched rows of Q and c, k_hy_gather_cols
-//                         the touched columns of Gt.  Then per iteration and chunk of frames three launches: k_cproj_em on the
-//                         (compact) iterate, k_rforce_coef, k_hyper_apply.  No host-to-device copy, no synchronisation in the loop.
-//   k_hyper_apply         Q'[3 v + d][f] = fl(c[3 v + d][f] + acc), acc = sum_j G_d[v][j] coef_d[j][f] from 0 over j = 0 .. rpp
-//                         in order: v_mfma_f64_16x16x4_f64 with A = G (vertices x j) and B = coef (j x frames), the roles of
+//                         the touched columns of every bank's Gt.  Then per iteration and chunk of frames 2 S + 1 launches for S
+//                         kinds: per kind k_cproj_em on the (compact) iterate and k_rforce_coef into its bank's coefficients --
+//                         ALL of them from the old iterate -- and then ONE k_hyper_apply, which alone writes the iterate (a
+//                         Jacobi update over the kinds, as the reference's; kind-by-kind applies would be Gauss-Seidel).  No
+//                         host-to-device copy, no synchronisation in the loop.
+//   k_hyper_apply         Q'[3 v + d][f] = fl(c[3 v + d][f] + acc), acc from 0 over the segments (kinds) in slot order and inside
+//                         a segment over j = 0 .. rpp in order, acc += G_d[v][j] coef_d[j][f]; the segments come as a by-value
+//                         table {Gt, coef, mpp, rpp} x 8 with a count (200 bytes of kernel arguments, read by scalar loads): v_mfma_f64_16x16x4_f64 with A = G (vertices x j) and B = coef (j x frames), the roles of
 //                         k_rforce_gemm swapped, so that an accumulator row is a vertex and its 16 lanes run along 16 contiguous
 //                         frames.  A block of 4 waves owns 32 vertices x 64 frames x 3 coordinates (wave w: frames 16 w ..).
 //                         The vertex-major store is DIRECT, no LDS: a store instruction of a wave writes four 128-byte runs (16
@@ -570,12 +582,23 @@ __global__ __launch_bounds__(64) void k_hy_gather_cols(const double* __restrict_
     if (t < ntp) dst[r * ntp + t] = t < nt ? src[r * Np + tv[t]] : 0.0;
 }
 
-// grid (ldg / HY_TN covering nv, frame tiles of the chunk).  Gt (3, mpp, ldg), ldg a multiple of HY_TN, zero past nv; coef (3, rpp,
-// cw), cw a multiple of HY_TF, zero past row r and frame cn; c, Q (3 nv, ld); out (n_sel, nv, 3) with FM
+// One term of the affine form: Gt (3, mpp, ldg) of a bank, zero past nv; coef (3, rpp, cw) of that bank, zero past row r and frame cn
+#define HY_MAX_SEG PD_MAX_SLOTS
+struct HySeg {
+    const double *Gt, *coef;
+    int mpp, rpp;
+};
+struct HySegs {
+    HySeg s[HY_MAX_SEG];
+    int n;
+};
+
+// grid (ldg / HY_TN covering nv, frame tiles of the chunk).  ldg (shared by the segments) a multiple of HY_TN; cw (shared) a
+// multiple of HY_TF; c, Q (3 nv, ld); out (n_sel, nv, 3) with FM.  The segments run in slot order, j ascending inside each, as ONE
+// chain of MFMAs per accumulator from 0; then Q' = fl(c + acc).  One segment: the instruction order of the single-kind kernel.
 template <bool FM>
-__global__ __launch_bounds__(256) void k_hyper_apply(const double* __restrict__ Gt, long long ldg, int mpp, const double* __restrict__ coef,
-                                                     int cw, int rpp, const double* __restrict__ c, double* __restrict__ Q, long long ld,
-                                                     int c0, int cn, int nv, double* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_hyper_apply(const HySegs segs, long long ldg, int cw, const double* __restrict__ c,
+                                                     double* __restrict__ Q, long long ld, int c0, int cn, int nv, double* __restrict__ out) {
     constexpr int RUN = HY_TN * 3, ROW = RUN + 1;
     __shared__ double stage[FM ? HY_TF * ROW : 1];
     const int lane = threadIdx.x & 63, i = lane & 15, g = lane >> 4;
@@ -587,16 +610,19 @@ __global__ __launch_bounds__(256) void k_hyper_apply(const double* __restrict__ 
     for (int d = 0; d < 3; ++d)
 #pragma unroll
         for (int y = 0; y < 2; ++y) acc[d][y] = d4{0.0, 0.0, 0.0, 0.0};
-    const double* pa = Gt + v0 + i;                       // A: vertex i of 16, k = g
-    const double* pb = coef + t0 + wave * 16 + i;         // B: k = g, frame i of the wave's 16
-    for (int k0 = 0; k0 < rpp; k0 += 4) {
-        const int k = k0 + g;
+    for (int sg = 0; sg < segs.n; ++sg) {
+        const int mpp = segs.s[sg].mpp, rpp = segs.s[sg].rpp;
+        const double* pa = segs.s[sg].Gt + v0 + i;                    // A: vertex i of 16, k = g
+        const double* pb = segs.s[sg].coef + t0 + wave * 16 + i;      // B: k = g, frame i of the wave's 16
+        for (int k0 = 0; k0 < rpp; k0 += 4) {
+            const int k = k0 + g;
 #pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            const double* a = pa + ((long long)d * mpp + k) * ldg;
-            const double b = pb[((long long)d * rpp + k) * cw];
-            acc[d][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[0], b, acc[d][0], 0, 0, 0);
-            acc[d][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[16], b, acc[d][1], 0, 0, 0);
+            for (int d = 0; d < 3; ++d) {
+                const double* a = pa + ((long long)d * mpp + k) * ldg;
+                const double b = pb[((long long)d * rpp + k) * cw];
+                acc[d][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[0], b, acc[d][0], 0, 0, 0);
+                acc[d][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[16], b, acc[d][1], 0, 0, 0);
+            }
         }
     }
     // accumulator q of lane (i, g): vertex g + 4 q of the 16, frame i of the wave's 16
@@ -664,19 +690,24 @@ extern "C" int asb_hyper_iterate(asb_ctx* ctx, int64_t n_iter, int64_t n_touched
     if (!ctx) return ASB_ERR_ARG;
     asb_pds* s = ctx->pds;
     if (!s || !s->begun || s->n_slots < 1) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: no solve begun or no kind registered (asb_pdsolve_begin, asb_pdsolve_slot)");
-    if (s->n_slots != 1 || !s->slot[0].reduced)
-        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: %d kinds, %s: every kind must be reduced, which today means exactly one kind", s->n_slots,
-                 s->slot[0].reduced ? "one of them reduced" : "the first not reduced");
+    for (int k = 0; k < s->n_slots; ++k)
+        if (!s->slot[k].reduced)
+            ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: %d kinds, kind %d not reduced: every kind must be reduced, each on a bank of its own "
+                                       "(asb_rforce_bank)", s->n_slots, k);
     if (n_iter < 1 || n_iter > (1 << 20)) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: %lld iterations", (long long)n_iter);
     if (chunk_frames < 0) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: chunk_frames %lld", (long long)chunk_frames);
     if (pd_solver_n(ctx) != s->n || ctx->n_loc != s->n)
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: the inverse or the tensor changed since asb_pdsolve_begin");
-    const PdSlot& p = s->slot[0];
-    if (ctx->rf_mp < 1 || ctx->rf_r < 1 || ctx->rf_n != s->n || ctx->rf_pt_max >= p.n_cols)
-        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: the operator or solver changed since asb_pdsolve_slot");
-    if (!ctx->hy_ok || !ctx->hy_G)
-        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: no operator A^-1 S^T V for the inverse and the basis on the device (asb_hyper_operator "
-                                   "after asb_gstep_setup and asb_rforce_operator): a stale one is refused");
+    const int ns = s->n_slots;
+    RfView rv[PD_MAX_SLOTS] = {};
+    for (int k = 0; k < ns; ++k) {
+        rv[k] = asb_rf_view(ctx, s->slot[k].bank);
+        if (rv[k].mp < 1 || rv[k].r < 1 || rv[k].n != s->n || rv[k].pt_max >= s->slot[k].n_cols)
+            ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: the operator or solver changed since asb_pdsolve_slot");
+        if (!rv[k].ok || !rv[k].G)
+            ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: no operator A^-1 S^T V for the inverse and the basis on the device (asb_hyper_operator "
+                                       "after asb_gstep_setup and asb_rforce_operator): a stale one is refused");
+    }
     const long long n = s->n, n_sel = s->n_sel, ld = s->ld;
     const bool compact = touched != nullptr;
     const long long nt = compact ? n_touched : n;
@@ -686,16 +717,28 @@ extern "C" int asb_hyper_iterate(asb_ctx* ctx, int64_t n_iter, int64_t n_touched
             if (touched[t] < 0 || touched[t] >= n || (t > 0 && touched[t] <= touched[t - 1]))
                 ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: touched[%lld] = %lld: ascending vertices of 0..%lld", t, (long long)touched[t], n - 1);
     }
-    if (p.vmax >= nt)
-        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: the element set-up names vertex %lld, the iterate has %lld rows", p.vmax, nt);
-    const int r = (int)ctx->rf_r, rpp = (r + 3) / 4 * 4, mpp = (int)ctx->rf_mpp;
-    long long cw = asb_rforce_chunk_width(ctx, p.n_cols, n_sel);
+    for (int k = 0; k < ns; ++k)
+        if (s->slot[k].vmax >= nt)
+            ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: the element set-up names vertex %lld, the iterate has %lld rows", s->slot[k].vmax, nt);
+    // one chunk width for all slots: the smallest of the banks'
+    long long cw = 0, cols_max = 0;
+    for (int k = 0; k < ns; ++k) {
+        const long long w = asb_rforce_chunk_width_r(rv[k].r, s->slot[k].n_cols, n_sel);
+        cw = k == 0 ? w : std::min(cw, w);
+        cols_max = std::max(cols_max, s->slot[k].n_cols);
+    }
     if (chunk_frames > 0) cw = std::min<long long>(cw, (chunk_frames + HY_TF - 1) / HY_TF * HY_TF);
     const long long ntp = (nt + HY_TN - 1) / HY_TN * HY_TN;
+    const long long Np = rv[0].Np;                  // (every bank's operator has the n vertices of the solve: one padding)
     ASB_HIP(ctx, hipSetDevice(ctx->dev));
     int rc;
-    if ((rc = asb_alloc(ctx, &ctx->cf_scratch, (size_t)3 * p.n_cols * cw))) return rc;
-    if ((rc = asb_alloc(ctx, &ctx->rf_coef, (size_t)3 * rpp * cw))) return rc;
+    size_t coef[PD_MAX_SLOTS] = {}, gc[PD_MAX_SLOTS] = {};
+    for (int k = 0; k < ns; ++k) {
+        coef[k] = (size_t)3 * (((size_t)rv[k].r + 3) / 4 * 4) * cw;
+        gc[k] = (size_t)3 * rv[k].mpp * ntp;
+    }
+    if ((rc = asb_alloc(ctx, &ctx->cf_scratch, (size_t)3 * cols_max * cw))) return rc;
+    if ((rc = pd_bank_alloc(ctx, s, coef, compact ? gc : nullptr, rv))) return rc;
     if ((rc = asb_alloc(ctx, &s->c, (size_t)3 * n * ld))) return rc;
     ASB_HIP(ctx, hipMemsetAsync(s->c, 0, (size_t)3 * n * ld * sizeof(double), ctx->stream));
     if (asb_gslab_n(ctx) > 0) {                     // c through the slab factor: in -> sweep -> rows
@@ -705,43 +748,57 @@ extern "C" int asb_hyper_iterate(asb_ctx* ctx, int64_t n_iter, int64_t n_touched
                            ctx->stream, s->ms, ctx->gs_Ainv, (int)n, (int)ctx->gs_Np, n_sel, s->c, ld, nullptr, nullptr);
     }
     asb_tmp<int> tv;
-    double *Qi = s->Q, *ci = s->c, *Gi = ctx->hy_G;     // what iterations 1 .. K-1 run on
-    long long ldg = ctx->rf_Np;
+    double *Qi = s->Q, *ci = s->c;                  // what iterations 1 .. K-1 run on
+    HySegs full = {}, part = {};                    // the segments of the last iteration (all rows) and of the others
+    full.n = part.n = ns;
+    for (int k = 0; k < ns; ++k) {
+        const int rpp = ((int)rv[k].r + 3) / 4 * 4;
+        full.s[k] = HySeg{rv[k].G, rv[k].coef, (int)rv[k].mpp, rpp};
+        part.s[k] = full.s[k];
+    }
+    long long ldg = Np;
     if (compact) {
         std::vector<int> t32((size_t)nt);
         for (long long t = 0; t < nt; ++t) t32[t] = (int)touched[t];
         if ((rc = tv.alloc(ctx, (size_t)nt))) return rc;
         if ((rc = asb_alloc(ctx, &s->Qc, (size_t)3 * nt * ld))) return rc;
         if ((rc = asb_alloc(ctx, &s->cc, (size_t)3 * nt * ld))) return rc;
-        if ((rc = asb_alloc(ctx, &s->Gc, (size_t)3 * mpp * ntp))) return rc;
         ASB_HIP(ctx, hipMemcpyAsync(tv.get(), t32.data(), (size_t)nt * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
         const dim3 gr((unsigned)(3 * nt), (unsigned)(ld / 64));
         hipLaunchKernelGGL(k_hy_gather_rows, gr, dim3(64), 0, ctx->stream, s->Q, tv.get(), ld, s->Qc);
         hipLaunchKernelGGL(k_hy_gather_rows, gr, dim3(64), 0, ctx->stream, s->c, tv.get(), ld, s->cc);
-        hipLaunchKernelGGL(k_hy_gather_cols, dim3((unsigned)(3 * mpp), (unsigned)((ntp + 63) / 64)), dim3(64), 0, ctx->stream, ctx->hy_G,
-                           (long long)ctx->rf_Np, tv.get(), (int)nt, (int)ntp, s->Gc);
+        for (int k = 0; k < ns; ++k) {              // the columns of G^T per bank
+            hipLaunchKernelGGL(k_hy_gather_cols, dim3((unsigned)(3 * rv[k].mpp), (unsigned)((ntp + 63) / 64)), dim3(64), 0, ctx->stream, rv[k].G, Np,
+                               tv.get(), (int)nt, (int)ntp, rv[k].Gc);
+            part.s[k].Gt = rv[k].Gc;
+        }
         ASB_CHECK_LAUNCH(ctx);
         ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));      // (the staging vector dies here, before the loop)
-        Qi = s->Qc, ci = s->cc, Gi = s->Gc, ldg = ntp;
+        Qi = s->Qc, ci = s->cc, ldg = ntp;
     }
-    const CpTables tb = {p.kind, p.n_elem, p.idx, p.sptr, p.sidx, p.table};
     const CpWorld wq = {Qi, ld, nullptr, nullptr, 1.0};
     for (int64_t it = 0; it < n_iter; ++it) {
         const bool last = it == n_iter - 1;
         for (long long c0 = 0; c0 < n_sel; c0 += cw) {
             const int cn = (int)(c0 + cw < n_sel ? cw : n_sel - c0);
-            asb_cproj_em_launch_t(ctx, tb, wq, 0, 1, (int)c0, cn, (int)cw, p.smin, p.smax, ctx->cf_scratch);
-            asb_rforce_coef_launch(ctx, ctx->cf_scratch, (int)cw, cn);
+            // ALL coefficients from the old iterate first (the element-major scratch is reused in stream order), then one
+            // launch writes the new iterate: applying kind by kind would make the Jacobi update a Gauss-Seidel one
+            for (int k = 0; k < ns; ++k) {
+                const PdSlot& p = s->slot[k];
+                const CpTables tb = {p.kind, p.n_elem, p.idx, p.sptr, p.sidx, p.table};
+                asb_cproj_em_launch_t(ctx, tb, wq, 0, 1, (int)c0, cn, (int)cw, p.smin, p.smax, ctx->cf_scratch);
+                asb_rforce_coef_launch_v(ctx, rv[k], ctx->cf_scratch, (int)cw, cn);
+            }
             const unsigned gy = (unsigned)((cn + HY_TF - 1) / HY_TF);
             if (!last)
-                hipLaunchKernelGGL((k_hyper_apply<false>), dim3((unsigned)(ntp / HY_TN), gy), dim3(256), 0, ctx->stream, Gi, ldg, mpp, ctx->rf_coef,
-                                   (int)cw, rpp, ci, Qi, ld, (int)c0, cn, (int)nt, nullptr);
+                hipLaunchKernelGGL((k_hyper_apply<false>), dim3((unsigned)(ntp / HY_TN), gy), dim3(256), 0, ctx->stream, part, ldg, (int)cw, ci, Qi, ld,
+                                   (int)c0, cn, (int)nt, nullptr);
             else if (out_dev)
-                hipLaunchKernelGGL((k_hyper_apply<true>), dim3((unsigned)(ctx->rf_Np / HY_TN), gy), dim3(256), 0, ctx->stream, ctx->hy_G,
-                                   (long long)ctx->rf_Np, mpp, ctx->rf_coef, (int)cw, rpp, s->c, s->Q, ld, (int)c0, cn, (int)n, out_dev);
+                hipLaunchKernelGGL((k_hyper_apply<true>), dim3((unsigned)(Np / HY_TN), gy), dim3(256), 0, ctx->stream, full, Np, (int)cw, s->c, s->Q, ld,
+                                   (int)c0, cn, (int)n, out_dev);
             else
-                hipLaunchKernelGGL((k_hyper_apply<false>), dim3((unsigned)(ctx->rf_Np / HY_TN), gy), dim3(256), 0, ctx->stream, ctx->hy_G,
-                                   (long long)ctx->rf_Np, mpp, ctx->rf_coef, (int)cw, rpp, s->c, s->Q, ld, (int)c0, cn, (int)n, nullptr);
+                hipLaunchKernelGGL((k_hyper_apply<false>), dim3((unsigned)(Np / HY_TN), gy), dim3(256), 0, ctx->stream, full, Np, (int)cw, s->c, s->Q, ld,
+                                   (int)c0, cn, (int)n, nullptr);
         }
     }
     ASB_CHECK_LAUNCH(ctx);

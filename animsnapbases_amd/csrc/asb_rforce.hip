@@ -184,27 +184,78 @@ extern "C" int asb_rforce_solver(asb_ctx* ctx, int64_t r, int64_t npt, const dou
     return ASB_OK;
 }
 
+// ---------------------------------------------------------------- the banks
+// Held per bank: S^T V (rf_M), H and its rows (rf_H, rf_pt), the coefficients of one chunk (rf_coef), A^-1 S^T V with its mark
+// (hy_G, hy_ok) and its touched columns (hy_Gc).  The current bank lives in the context's rf_* / hy_* fields, which every
+// launcher reads; the others rest in ctx->rf_bank, whose entry for the current bank is empty.
+static void rf_exchange(asb_ctx* ctx, asb_ctx::RfBank& b) {
+    asb_swap_buf(ctx, &ctx->rf_M, &b.M);
+    asb_swap_buf(ctx, &ctx->rf_H, &b.H);
+    asb_swap_buf(ctx, &ctx->rf_pt, &b.pt);
+    asb_swap_buf(ctx, &ctx->rf_coef, &b.coef);
+    asb_swap_buf(ctx, &ctx->hy_G, &b.G);
+    asb_swap_buf(ctx, &ctx->hy_Gc, &b.Gc);
+    std::swap(ctx->rf_n, b.n), std::swap(ctx->rf_Np, b.Np), std::swap(ctx->rf_mp, b.mp), std::swap(ctx->rf_mpp, b.mpp);
+    std::swap(ctx->rf_r, b.r), std::swap(ctx->rf_npt, b.npt), std::swap(ctx->rf_pt_max, b.pt_max), std::swap(ctx->hy_ok, b.ok);
+}
+
+void asb_rf_select(asb_ctx* ctx, int bank) {
+    if (bank == ctx->rf_cur) return;
+    rf_exchange(ctx, ctx->rf_bank[ctx->rf_cur]);          // the current set goes to rest; the context holds an empty one
+    rf_exchange(ctx, ctx->rf_bank[bank]);
+    ctx->rf_cur = bank;
+}
+
+RfView asb_rf_view(const asb_ctx* ctx, int bank) {
+    if (bank == ctx->rf_cur)
+        return RfView{ctx->rf_M, ctx->rf_H, ctx->hy_G, ctx->rf_coef, ctx->hy_Gc, ctx->rf_pt, (long long)ctx->rf_n, (long long)ctx->rf_Np,
+                      (long long)ctx->rf_mp, (long long)ctx->rf_mpp, (long long)ctx->rf_r, (long long)ctx->rf_npt, (long long)ctx->rf_pt_max,
+                      ctx->hy_ok};
+    const asb_ctx::RfBank& b = ctx->rf_bank[bank];
+    return RfView{b.M, b.H, b.G, b.coef, b.Gc, b.pt, (long long)b.n, (long long)b.Np, (long long)b.mp, (long long)b.mpp, (long long)b.r,
+                  (long long)b.npt, (long long)b.pt_max, b.ok};
+}
+
+void asb_rf_invalidate_all(asb_ctx* ctx) {
+    ctx->hy_ok = 0;
+    for (int k = 0; k < ASB_RFORCE_BANKS; ++k) ctx->rf_bank[k].ok = 0;
+}
+
+extern "C" int asb_rforce_bank(asb_ctx* ctx, int bank) {
+    if (!ctx) return ASB_ERR_ARG;
+    if (bank < 0 || bank >= ASB_RFORCE_BANKS) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_rforce_bank: bank %d of 0..%d", bank, ASB_RFORCE_BANKS - 1);
+    asb_rf_select(ctx, bank);
+    return ASB_OK;
+}
+
 // whole frame tiles of the product, the scratch (projections + coefficients) within RF_SCRATCH_BYTES
-long long asb_rforce_chunk_width(asb_ctx* ctx, long long n_cols, long long n_sel) {
-    const int rpp = ((int)ctx->rf_r + 3) / 4 * 4;
+long long asb_rforce_chunk_width(asb_ctx* ctx, long long n_cols, long long n_sel) { return asb_rforce_chunk_width_r(ctx->rf_r, n_cols, n_sel); }
+
+long long asb_rforce_chunk_width_r(long long r, long long n_cols, long long n_sel) {
+    const int rpp = ((int)r + 3) / 4 * 4;
     long long cw = (long long)(RF_SCRATCH_BYTES / (24ull * (unsigned long long)(n_cols + rpp)));
     cw = cw >= RF_TF ? cw / RF_TF * RF_TF : RF_TF;
     const long long span = (n_sel + RF_TF - 1) / RF_TF * RF_TF;
     return cw > span ? span : cw;
 }
 
-void asb_rforce_coef_launch(asb_ctx* ctx, const double* S, int cw, int cn) {
-    const int r = (int)ctx->rf_r, rpp = (r + 3) / 4 * 4, npt = (int)ctx->rf_npt;
-    hipLaunchKernelGGL(k_rforce_coef, dim3((unsigned)(cw / 64), (unsigned)rpp, 3), dim3(64), 0, ctx->stream, ctx->rf_H, ctx->rf_pt, r, npt, rpp,
-                       S, cw, cn, ctx->rf_coef);
+void asb_rforce_coef_launch_v(asb_ctx* ctx, const RfView& v, const double* S, int cw, int cn) {
+    const int r = (int)v.r, rpp = (r + 3) / 4 * 4, npt = (int)v.npt;
+    hipLaunchKernelGGL(k_rforce_coef, dim3((unsigned)(cw / 64), (unsigned)rpp, 3), dim3(64), 0, ctx->stream, v.H, v.pt, r, npt, rpp, S, cw, cn,
+                       v.coef);
 }
 
+void asb_rforce_chunk_launch_v(asb_ctx* ctx, const RfView& v, const double* S, int cw, int c0, int cn, int accumulate, double* out) {
+    const int rpp = ((int)v.r + 3) / 4 * 4;
+    asb_rforce_coef_launch_v(ctx, v, S, cw, cn);
+    hipLaunchKernelGGL(k_rforce_gemm, dim3((unsigned)(v.Np / RF_TN), (unsigned)((cn + RF_TF - 1) / RF_TF)), dim3(256), 0, ctx->stream, v.M, v.Np,
+                       (int)v.mpp, v.coef, cw, rpp, c0, cn, v.n, accumulate ? 1 : 0, out);
+}
+
+void asb_rforce_coef_launch(asb_ctx* ctx, const double* S, int cw, int cn) { asb_rforce_coef_launch_v(ctx, asb_rf_view(ctx, ctx->rf_cur), S, cw, cn); }
+
 void asb_rforce_chunk_launch(asb_ctx* ctx, const double* S, int cw, int c0, int cn, int accumulate, double* out) {
-    const int rpp = ((int)ctx->rf_r + 3) / 4 * 4;
-    asb_rforce_coef_launch(ctx, S, cw, cn);
-    hipLaunchKernelGGL(k_rforce_gemm, dim3((unsigned)(ctx->rf_Np / RF_TN), (unsigned)((cn + RF_TF - 1) / RF_TF)), dim3(256), 0, ctx->stream,
-                       ctx->rf_M, (long long)ctx->rf_Np, (int)ctx->rf_mpp, ctx->rf_coef, cw, rpp, c0, cn, (long long)ctx->rf_n, accumulate ? 1 : 0,
-                       out);
+    asb_rforce_chunk_launch_v(ctx, asb_rf_view(ctx, ctx->rf_cur), S, cw, c0, cn, accumulate, out);
 }
 
 extern "C" int asb_rforce_run(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean, double psf,

@@ -1,7 +1,7 @@
 """``ResidentDynamics`` -- what ``posSnapshots`` offers beyond the reference's class: the pieces of the reference's
 projective-dynamics solver (Simulators.py) evaluated on the device for the frames of the resident animation -- constraint
-projections, constraint forces, their DEIM reduction, the global step, the solver's iterations and its time steps, with the choice of the global step's solver (DESIGN.md
-3.10-3.17).
+projections, constraint forces, their DEIM reduction, the global step, the solver's iterations and its time steps, with the choice of the global step's solver and
+of how many kinds a solve may reduce.
 A public call checks its arguments into the named records below before the engine is touched; the helpers take the records.
 """
 import collections
@@ -34,8 +34,9 @@ class Frames(collections.namedtuple("Frames", "which start end jump Y")):
 Term = collections.namedtuple("Term", "kind setup St sigma_min sigma_max wi")
 # The explicit state s_f = x_f (+ x_f - x_{f-1}, ``mode`` 1) + ``acc`` = dt^2 g and its inertia term ``diag`` = masses / dt^2.
 Explicit = collections.namedtuple("Explicit", "mode acc diag masses dt")
-# The reduced kind of a solve: its ``index`` in the plan, the full set-up and S^T, ``operator``: r -> reduced.ReducedOperator,
+# A reduced kind of a solve: its ``index`` in the plan, the full set-up and S^T, ``operator``: r -> reduced.ReducedOperator,
 # and ``op``: the operator in use (None until one is chosen), the engine's ``rforce_operator`` holding at least its columns.
+# A solve carries a tuple of them, in list order; with more than one (``set_reduced_kinds``) the i-th lives on the engine's bank i.
 Reduced = collections.namedtuple("Reduced", "index setup St operator op")
 # One kind with a basis: what ``reduced_constraint_forces`` and the ``reduced_*_errors`` methods check their arguments into.
 ReducedPlan = collections.namedtuple("ReducedPlan", "term frames operator")
@@ -305,7 +306,8 @@ class ResidentDynamics(object):
         ``reduced_constraint_forces`` with r components, as five lists ``fro, max, rel_x, rel_y, rel_z``; with ``per_frame``
         a sixth value, the (len(r_values), F') array of |b[f] - b~_r[f]| / |b[f]| (Frobenius norms of the frame).  Arguments as
         ``reduced_constraint_forces``.  The full term is computed once, S^T V once for the largest r (prefixes of its
-        columns serve the others); both tensors stay on the device and are compared there (asb_force_diff)."""
+        columns serve the others); both tensors stay on the device and are compared there (asb_force_diff).  The sweep keeps
+        its one kind whatever ``set_reduced_kinds`` allows: multi-kind sweeps are out of scope."""
         spec = dict(kind=kind, elements=elements, wi=wi, rest_positions=rest_positions, sigma_min=sigma_min, sigma_max=sigma_max)
         plan = self._reduced_plan(spec, basis, reduction, self._frames(animation, frame_start, frame_end, frame_jump))
         return self._errors(plan, r_values, per_frame, lambda: self._cforce_run([plan.term], plan.frames, None),
@@ -430,7 +432,8 @@ class ResidentDynamics(object):
         q~_r the same step with b~_r of ``reduced_constraint_forces`` in place of b (same inertia term, same A^-1).  Arguments
         as ``reduced_force_errors`` plus ``dt``, ``masses``, ``velocity``, ``gravity`` of ``global_step``; the same five lists
         ``fro, max, rel_x, rel_y, rel_z`` and, with ``per_frame``, the (len(r_values), F') array |q[f] - q~_r[f]| / |q[f]|.
-        The full step is computed once; every tensor stays on the device."""
+        The full step is computed once; every tensor stays on the device.  The sweep keeps its one kind whatever
+        ``set_reduced_kinds`` allows: multi-kind sweeps are out of scope."""
         ex = self._explicit("reduced_global_step_errors", dt, velocity, gravity, masses)
         spec = dict(kind=kind, elements=elements, wi=wi, rest_positions=rest_positions, sigma_min=sigma_min, sigma_max=sigma_max)
         plan = self._reduced_plan(spec, basis, reduction, self._frames(animation, frame_start, frame_end, frame_jump))
@@ -453,9 +456,13 @@ class ResidentDynamics(object):
         product is left in an iteration.  "touched": all but the last iteration run on those vertices' rows only, the last on
         all N; "all": every iteration on all N rows (for checks, and for continuing with ``start=``); both give the same
         bits.  None: the path without the operator, unchanged.  Refused with ``hyper`` (ValueError, before the device is
-        touched): a kind without ``basis`` / ``num_components`` -- every kind must be reduced, and since the engine holds one
-        reduced operator that means exactly one kind --, ``history=True`` (step norms over all rows would need the whole
-        iterate in every iteration) and an unknown value.  Out of scope for ``hyper``: several reduced kinds in one solve,
+        touched): a kind without ``basis`` / ``num_components`` -- every kind must be reduced, which without
+        ``set_reduced_kinds`` means exactly one kind --, ``history=True`` (step norms over all rows would need the whole
+        iterate in every iteration) and an unknown value.  Under ``set_reduced_kinds(L)``, L > 1, up to L kinds may be
+        reduced, each on an engine bank of its own; ``hyper`` then takes all of them (a list with a plain kind is refused):
+        q_{k+1} = c + sum_k G_k coef_k(q_k), every coef_k from the OLD iterate -- the Jacobi update of the reference, whose
+        groups' terms are summed before its one solve --, "touched" running on the union of the kinds' touched vertices
+        (DESIGN.md 3.18).  Out of scope for ``hyper`` unless ``set_reduced_kinds`` raises the limit: several reduced kinds in one solve; always:
         the history, a reduction of the positions themselves (a basis U of q), several ranks.  Not part of a solve, with or
         without ``hyper``: velocities carried between frames or steps -- that is ``simulate_frames``, which takes ``hyper`` too."""
 
@@ -477,28 +484,67 @@ class ResidentDynamics(object):
                 raise ValueError("%s: start must be 'explicit', 'frame' or a torch.float64 device tensor" % who)
         return ex, K
 
+    def set_reduced_kinds(self, limit=1):
+        """Extra: how many entries of ``kinds`` may carry ``basis`` / ``num_components`` / ``reduction`` in every later
+        ``solve_frames`` and ``simulate_frames`` of this object -- the reference's reduced simulator keeps one projecting
+        matrix, one set of interpolation points and one solver per constraint group (Simulators.py:49-87, :157-220) and adds
+        the reduced terms of every group whose ``*_reduced`` flag is set (:415-478, :506-526).
+
+        ``limit``: an integer 1..8 (the engine's banks).  1, the default: one reduced kind, every call, message
+        and result as without this method.  L > 1: up to L reduced kinds in one solve, the i-th on the engine's bank i;
+        ``hyper`` then needs EVERY listed kind reduced and runs all of them in one affine iteration on the union of their touched
+        vertices.  A call with one reduced kind is the same whatever the limit.  The four ``reduced_*_errors`` sweeps keep
+        their one kind.  The device buffers of a bank that a call has used stay with the engine afterwards (per bank S^T V and
+        A^-1 S^T V, 24 N m bytes each), also when the limit goes back to 1.  Checked before the device is touched."""
+        if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or not 1 <= limit <= 8:
+            raise ValueError("set_reduced_kinds: limit %r: an integer 1..8" % (limit,))
+        self._reduced_limit = int(limit)
+
     def _solve_plan(self, who, kinds, chunk_frames):
-        """``_plan`` of the kinds with their reduction keys taken off, and for the one entry that carries a ``basis`` its
-        ``Reduced`` (no operator chosen yet), else None."""
+        """``_plan`` of the kinds with their reduction keys taken off, and the tuple of ``Reduced`` (no operator chosen yet) of
+        the entries that carry a ``basis``, in list order: at most ``set_reduced_kinds`` allows."""
         keys = ("basis", "num_components", "reduction")
+        limit = getattr(self, "_reduced_limit", 1)
         if not isinstance(kinds, (list, tuple)):
             raise ValueError("%s: kinds must be a non-empty list of dicts, not %r" % (who, kinds))
-        plain, red = [], None
+        plain, red = [], []
         for i, spec in enumerate(kinds):
             if isinstance(spec, dict) and any(k in spec for k in keys):
                 if "basis" not in spec or "num_components" not in spec:
                     raise ValueError("%s: a reduced kind carries both 'basis' and 'num_components'" % who)
-                if red is not None:
+                if len(red) >= limit and limit == 1:
                     raise ValueError("%s: a second reduced kind (%r after %r): the engine holds one reduced operator"
-                                     % (who, spec.get("kind"), kinds[red].get("kind")))
-                red = i
+                                     % (who, spec.get("kind"), kinds[red[0]].get("kind")))
+                if len(red) >= limit:
+                    raise ValueError("%s: more than %d reduced kinds (%r): set_reduced_kinds(%d) is in force"
+                                     % (who, limit, spec.get("kind"), limit))
+                red.append(i)
                 spec = {k: v for k, v in spec.items() if k not in keys}
             plain.append(spec)
         plan = self._plan(plain, chunk_frames)
-        if red is None:
-            return plan, None
-        t = plan[red]
-        return plan, Reduced(red, t.setup, t.St, self._operator(t, kinds[red]["basis"], kinds[red].get("reduction", "deim_pod")), None)
+        return plan, tuple(Reduced(i, plan[i].setup, plan[i].St,
+                                   self._operator(plan[i], kinds[i]["basis"], kinds[i].get("reduction", "deim_pod")), None) for i in red)
+
+    @staticmethod
+    def _chosen(reds, kinds):
+        """The ``Reduced`` of a call with the operators of their ``num_components``."""
+        return tuple(r._replace(op=r.operator(int(kinds[r.index]["num_components"]))) for r in reds)
+
+    def _with_operators(self, reds, hyper, run):
+        """``run()`` behind the operators of the call: per reduced kind S^T V and, with ``hyper``, A^-1 S^T V on the device,
+        once; several kinds take the engine's banks 0, 1, .. in order, and bank 0 is current again on every way out."""
+        eng, multi = self._engine, len(reds) > 1
+        try:
+            for b, r in enumerate(reds):
+                if multi:
+                    eng.rforce_bank(b)
+                eng.rforce_operator(r.St, r.op.V)
+                if hyper is not None:
+                    eng.hyper_operator()
+            return run()
+        finally:
+            if multi:
+                eng.rforce_bank(0)
 
     def _solve_start(self, who, start, n_sel):
         """(start code of the engine, the caller's tensor or None); a tensor is checked as ``global_solve`` checks its rhs."""
@@ -510,8 +556,7 @@ class ResidentDynamics(object):
             raise ValueError("%s: start of shape %s: a contiguous (%d, %d, 3) expected" % (who, tuple(start.shape), n_sel, self.nVerts))
         return 2, start
 
-    @staticmethod
-    def _hyper_check(who, hyper, kinds, history):
+    def _hyper_check(self, who, hyper, kinds, history):
         """The refusals of ``hyper``, before anything touches the device."""
         if hyper is None:
             return
@@ -520,35 +565,49 @@ class ResidentDynamics(object):
         if history:
             raise ValueError("%s: history=True with hyper=%r: the step norms run over all rows and would force the full iterate "
                              "in every iteration" % (who, hyper))
-        if not isinstance(kinds, (list, tuple)) or len(kinds) != 1 or not isinstance(kinds[0], dict) \
-                or "basis" not in kinds[0] or "num_components" not in kinds[0]:
+        limit = getattr(self, "_reduced_limit", 1)
+        every = isinstance(kinds, (list, tuple)) and len(kinds) >= 1 and all(
+            isinstance(k, dict) and "basis" in k and "num_components" in k for k in kinds)
+        if limit == 1 and (not every or len(kinds) != 1):
             raise ValueError("%s: hyper=%r needs every kind reduced ('basis' and 'num_components'), and the engine holds one reduced "
                              "operator: exactly one kind, a reduced one" % (who, hyper))
+        if not every:
+            raise ValueError("%s: hyper=%r needs every kind reduced ('basis' and 'num_components'): up to %d of them under "
+                             "set_reduced_kinds(%d), none left plain" % (who, hyper, limit, limit))
 
-    def _solve_slots(self, plan, red, hyper):
-        """The kinds of the plan registered with the solve in progress, in order; with ``hyper`` the one reduced kind on its
-        touched vertices, which are returned."""
-        eng = self._engine
-        if hyper is not None:
-            t, = plan
-            touched, compact = _proj.touched_setup(_proj.subset_setup(red.setup, red.op.elements), self.nVerts if hyper == "all" else None)
-            eng.cproj_setup(compact)
-            eng.rforce_solver(red.op.H, red.op.local_rows)
-            eng.pdsolve_slot(t.sigma_min, t.sigma_max, None)
-            return touched
+    def _solve_slots(self, plan, reds, hyper):
+        """The kinds of the plan registered with the solve in progress, in order; a reduced kind as its sampled elements, with
+        its solver, on its bank when there are several.  With ``hyper`` every kind is reduced and numbered in the union of
+        their touched vertices, which is returned."""
+        eng, multi = self._engine, len(reds) > 1
+        red = {r.index: (b, r) for b, r in enumerate(reds)}
+        sub = {i: _proj.subset_setup(r.setup, r.op.elements) for i, (b, r) in red.items()}
+        touched = None
+        if hyper == "all":
+            touched = np.arange(self.nVerts, dtype=np.int64)
+            sub = {i: _proj.touched_setup(u, self.nVerts)[1] for i, u in sub.items()}
+        elif hyper is not None and not multi:           # one kind: its own touched set, found once
+            (i, u), = sub.items()
+            touched, u = _proj.touched_setup(u)
+            sub = {i: u}
+        elif hyper is not None:
+            touched = _proj.touched_union([sub[i] for i in sorted(sub)])
+            sub = {i: _proj.touched_setup(u, into=touched)[1] for i, u in sub.items()}
         for i, t in enumerate(plan):
-            if red is not None and red.index == i:
-                eng.cproj_setup(_proj.subset_setup(red.setup, red.op.elements))
-                eng.rforce_solver(red.op.H, red.op.local_rows)
+            if i in red:
+                if multi:
+                    eng.rforce_bank(red[i][0])
+                eng.cproj_setup(sub[i])
+                eng.rforce_solver(red[i][1].op.H, red[i][1].op.local_rows)
                 eng.pdsolve_slot(t.sigma_min, t.sigma_max, None)
             else:
                 eng.cproj_setup(t.setup)
                 eng.pdsolve_slot(t.sigma_min, t.sigma_max, t.St)
-        return None
+        return touched
 
-    def _solve_run(self, plan, red, frames, ex, begin, K, chunk_frames, history, hyper=None):
-        """The solve (matrix on the device); ``red``: None or the ``Reduced`` with its ``op``; ``begin``: what ``_solve_start`` gave.
-        ``hyper``: the one kind is ``red`` and A^-1 S^T V is on the device."""
+    def _solve_run(self, plan, reds, frames, ex, begin, K, chunk_frames, history, hyper=None):
+        """The solve (matrix on the device); ``reds``: the ``Reduced`` of the plan with their ``op``; ``begin``: what
+        ``_solve_start`` gave.  ``hyper``: every kind is in ``reds`` and their A^-1 S^T V are on the device."""
         eng = self._engine
         code, start = begin
         if code == 2:
@@ -557,12 +616,12 @@ class ResidentDynamics(object):
         frames.upload(self)
         eng.pdsolve_begin(*frames.args(self), ex.diag, ex.mode, ex.acc, code, None if start is None else start.data_ptr())
         if hyper is not None:
-            touched = self._solve_slots(plan, red, hyper)
+            touched = self._solve_slots(plan, reds, hyper)
             out = self._alloc(frames)
             eng.hyper_iterate(K, None if hyper == "all" else touched, 0 if chunk_frames is None else int(chunk_frames), out.data_ptr())
             self._leave(plan)
             return out, frames.n_sel
-        self._solve_slots(plan, red, None)
+        self._solve_slots(plan, reds, None)
         out = self._alloc(frames)
         hist = eng.pdsolve_iterate(K, 0 if chunk_frames is None else int(chunk_frames), out.data_ptr(), history)
         self._leave(plan)
@@ -578,9 +637,10 @@ class ResidentDynamics(object):
         ``num_iterations`` iterations, the explicit state s_f held fixed while q moves.  The iterate stays on the device
         between iterations in the layout the projection kernels read; the kinds' tables and S^T are uploaded once per solve.
 
-        ``kinds``: the list of dicts of ``constraint_forces``; ONE entry may also carry ``basis``, ``num_components`` and
-        ``reduction`` (default "deim_pod") with the meanings of ``reduced_constraint_forces``: that kind's term is then the
-        reduced one, as the simulator's per-group ``*_reduced`` flags choose.  A is always the full matrix of all listed kinds.
+        ``kinds``: the list of dicts of ``constraint_forces``; ONE entry -- up to L entries after ``set_reduced_kinds(L)`` --
+        may also carry ``basis``, ``num_components`` and ``reduction`` (default "deim_pod") with the meanings of
+        ``reduced_constraint_forces``: that kind's term is then the reduced one, as the simulator's per-group ``*_reduced``
+        flags choose; the terms are added in list order.  A is always the full matrix of all listed kinds.
         ``dt``, ``masses``, ``velocity``, ``gravity``, ``animation``, the frame range and ``chunk_frames``: as ``global_step``.
         ``start``: "explicit" (q_0 = s_f, the reference's), "frame" (q_0 = x_f; one iteration is then ``global_step`` bit for
         bit) or a contiguous ``torch.float64`` device tensor (F', N, 3) -- a solve continued from an earlier result equals the
@@ -597,16 +657,11 @@ class ResidentDynamics(object):
                              "product kernel and are out of scope for the slab solver" % who)
         ex, K = self._solve_args(who, dt, velocity, gravity, num_iterations, start, masses)
         frames = self._frames(animation, frame_start, frame_end, frame_jump)
-        plan, red = self._solve_plan(who, kinds, chunk_frames)
+        plan, reds = self._solve_plan(who, kinds, chunk_frames)
         begin = self._solve_start(who, start, frames.n_sel)
-        if red is not None:
-            red = red._replace(op=red.operator(int(kinds[red.index]["num_components"])))
+        reds = self._chosen(reds, kinds)
         self._matrix(plan, ex.masses, ex.dt)
-        if red is not None:
-            self._engine.rforce_operator(red.St, red.op.V)
-        if hyper is not None:
-            self._engine.hyper_operator()
-        return self._solve_run(plan, red, frames, ex, begin, K, chunk_frames, history, hyper)
+        return self._with_operators(reds, hyper, lambda: self._solve_run(plan, reds, frames, ex, begin, K, chunk_frames, history, hyper))
 
     solve_frames.__doc__ %= _SOLVE_SCOPE
 
@@ -622,15 +677,16 @@ class ResidentDynamics(object):
         the largest r); every tensor stays on the device and is compared there.  With ``num_iterations=1, start="frame"`` these
         are the numbers of ``reduced_global_step_errors``.  With ``hyper`` the full solve still runs once as before, the per-r
         reduced solves go through the hyper-reduced path, and A^-1 S^T V is formed once, for the largest r (prefixes of its
-        columns serve the others, as those of S^T V do).  %s"""
+        columns serve the others, as those of S^T V do).  The sweep keeps its one kind whatever ``set_reduced_kinds``
+        allows: multi-kind sweeps are out of scope.  %s"""
         who = "reduced_solve_errors"
         self._hyper_check(who, hyper, [dict(basis=basis, num_components=0)], False)
         ex, K = self._solve_args(who, dt, velocity, gravity, num_iterations, start, masses)
         spec = dict(kind=kind, elements=elements, wi=wi, rest_positions=rest_positions, sigma_min=sigma_min, sigma_max=sigma_max)
         frames = self._frames(animation, frame_start, frame_end, frame_jump)
-        terms, red = self._solve_plan(who, [dict(spec, basis=basis, num_components=0, reduction=reduction)], None)
+        terms, (red,) = self._solve_plan(who, [dict(spec, basis=basis, num_components=0, reduction=reduction)], None)
         begin = self._solve_start(who, start, frames.n_sel)
-        run = lambda rd: self._solve_run(terms, rd, frames, ex, begin, K, None, False, None if rd is None else hyper)[0]
+        run = lambda rd: self._solve_run(terms, () if rd is None else (rd,), frames, ex, begin, K, None, False, None if rd is None else hyper)[0]
 
         def full():
             self._matrix(terms, ex.masses, ex.dt)
@@ -671,8 +727,8 @@ class ResidentDynamics(object):
             if t.dim() != 3 or tuple(t.shape) != (n_sel, self.nVerts, 3) or not t.is_contiguous():
                 raise ValueError("%s: state of shape %s: contiguous (%d, %d, 3) tensors expected" % (who, tuple(t.shape), n_sel, self.nVerts))
 
-    def _rollout_run(self, plan, red, frames, ex, state, K, T, chunk_frames, every, hyper=None):
-        """The roll-out (matrix on the device; ``red``, ``hyper`` as ``_solve_run``): ``(q, q_prev, records or None, steps)``."""
+    def _rollout_run(self, plan, reds, frames, ex, state, K, T, chunk_frames, every, hyper=None):
+        """The roll-out (matrix on the device; ``reds``, ``hyper`` as ``_solve_run``): ``(q, q_prev, records or None, steps)``."""
         import torch
         eng = self._engine
         if state is not None:
@@ -685,7 +741,7 @@ class ResidentDynamics(object):
             eng.pdsolve_begin(*frames.args(self), ex.diag, ex.mode, ex.acc, 2, state[0].data_ptr())
             eng.pdsolve_carry(state[1].data_ptr())
             eng.pdsolve_advance()
-        touched = self._solve_slots(plan, red, hyper)
+        touched = self._solve_slots(plan, reds, hyper)
         steps = [] if every is None else list(range(every, T + 1, every))
         records = None
         if every is not None:
@@ -717,7 +773,8 @@ class ResidentDynamics(object):
         ``solve_frames(start="explicit")`` bit for bit.  The state never leaves the device: the carry is one kernel on the
         iterate, the previous positions and the inertia term; the matrix, S^T V and A^-1 S^T V are formed once per call.
 
-        ``kinds`` (one entry may be reduced), ``dt``, ``num_iterations``, ``masses``, ``gravity``, ``animation``, the frame range,
+        ``kinds`` (one entry may be reduced; up to L after ``set_reduced_kinds(L)``, the banks and the union of the touched
+        vertices set up once and carried through every step), ``dt``, ``num_iterations``, ``masses``, ``gravity``, ``animation``, the frame range,
         ``chunk_frames`` and ``hyper``: as ``solve_frames``, with its refusals.  ``state``: a pair ``(q, q_prev)`` of contiguous
         ``torch.float64`` device tensors (F', N, 3), the positions now and one step earlier: the roll-out continues from them
         (``velocity`` is then ignored and the animation only selects F'), and T1 steps continued by T2 equal T1 + T2 steps bit
@@ -729,22 +786,18 @@ class ResidentDynamics(object):
         by the last iteration of its step straight into its slice, and the list of those step numbers; when the last step is
         recorded, ``q`` is the view ``records[-1]``.  Device memory held by the engine beside that of ``solve_frames``: one more
         tensor of the iterate's size.  Out of scope: collisions, positional constraints, forces other than constant gravity,
-        several reduced kinds, the history of step norms, several ranks."""
+        more reduced kinds than ``set_reduced_kinds`` allows (1 unless set), the history of step norms, several ranks."""
         who = "simulate_frames"
         self._hyper_check(who, hyper, kinds, False)
         ex, K = self._solve_args(who, dt, velocity, gravity, num_iterations, "explicit", masses)
         T, every = self._rollout_args(who, num_steps, record_every, state)
         frames = self._frames(animation, frame_start, frame_end, frame_jump)
-        plan, red = self._solve_plan(who, kinds, chunk_frames)
+        plan, reds = self._solve_plan(who, kinds, chunk_frames)
         self._rollout_state(who, state, frames.n_sel)
-        if red is not None:
-            red = red._replace(op=red.operator(int(kinds[red.index]["num_components"])))
+        reds = self._chosen(reds, kinds)
         self._matrix(plan, ex.masses, ex.dt)
-        if red is not None:
-            self._engine.rforce_operator(red.St, red.op.V)
-        if hyper is not None:
-            self._engine.hyper_operator()
-        q, q_prev, records, steps = self._rollout_run(plan, red, frames, ex, state, K, T, chunk_frames, every, hyper)
+        q, q_prev, records, steps = self._with_operators(
+            reds, hyper, lambda: self._rollout_run(plan, reds, frames, ex, state, K, T, chunk_frames, every, hyper))
         return (q, q_prev, frames.n_sel) + (() if every is None else ((records, steps),))
 
     def reduced_rollout_errors(self, kind, basis, r_values, dt, num_steps, num_iterations=10, masses=None, velocity="difference",
@@ -761,7 +814,8 @@ class ResidentDynamics(object):
         there, slice by slice.
 
         Returns ``(fro, max, rel_x, rel_y, rel_z, steps)``: five (len(r_values), R) arrays and the list of the R recorded
-        steps.  With ``num_steps=1, record_every=1`` the numbers are those of ``reduced_solve_errors``."""
+        steps.  With ``num_steps=1, record_every=1`` the numbers are those of ``reduced_solve_errors``.  The sweep keeps its
+        one kind whatever ``set_reduced_kinds`` allows: multi-kind sweeps are out of scope."""
         who = "reduced_rollout_errors"
         self._hyper_check(who, hyper, [dict(basis=basis, num_components=0)], False)
         ex, K = self._solve_args(who, dt, velocity, gravity, num_iterations, "explicit", masses)
@@ -770,14 +824,14 @@ class ResidentDynamics(object):
             raise ValueError("%s: record_every %r: a positive number of time steps" % (who, record_every))
         spec = dict(kind=kind, elements=elements, wi=wi, rest_positions=rest_positions, sigma_min=sigma_min, sigma_max=sigma_max)
         frames = self._frames(animation, frame_start, frame_end, frame_jump)
-        terms, red = self._solve_plan(who, [dict(spec, basis=basis, num_components=0, reduction=reduction)], None)
+        terms, (red,) = self._solve_plan(who, [dict(spec, basis=basis, num_components=0, reduction=reduction)], None)
         r_values = [int(r) for r in r_values]
         ops = [red.operator(r) for r in r_values]
         steps = list(range(every, T + 1, every))
         out = np.zeros((5, len(ops), len(steps)))
         if not ops:
             return tuple(out) + (steps,)
-        run = lambda rd: self._rollout_run(terms, rd, frames, ex, None, K, T, None, every, None if rd is None else hyper)[2]
+        run = lambda rd: self._rollout_run(terms, () if rd is None else (rd,), frames, ex, None, K, T, None, every, None if rd is None else hyper)[2]
         self._matrix(terms, ex.masses, ex.dt)
         full = run(None)
         self._engine.rforce_operator(terms[0].St, ops[int(np.argmax(r_values))].V)

@@ -562,6 +562,11 @@ class HipEngine(object):
         assert H.ndim == 3 and H.shape[0] == 3 and H.shape[2] == rows.shape[0]
         self._ck(self.lib.asb_rforce_solver(self.h, int(H.shape[1]), int(H.shape[2]), ptr(H), ptr(rows)))
 
+    def rforce_bank(self, bank):
+        """Selects which of the context's 8 banks ``rforce_operator``, ``rforce_solver``, ``rforce_run`` and ``hyper_operator``
+        address from now on and a reduced ``pdsolve_slot`` binds; bank 0 is current in a new engine."""
+        self._ck(self.lib.asb_rforce_bank(self.h, int(bank)))
+
     def rforce_run(self, which, f0, f1, fj, inv_massL, add_mean, psf, sigma_min, sigma_max, accumulate, out_dev_ptr):
         """The reduced constraint forces of the frames range(f0, f1, fj) into (or, ``accumulate``, onto) the caller's device
         buffer of (F', N, 3) float64; ``cproj_setup`` holds the sampled elements only."""
@@ -699,9 +704,10 @@ class HipEngine(object):
         self._ck(self.lib.asb_hyper_operator(self.h))
 
     def hyper_iterate(self, n_iter, touched=None, chunk_frames=0, out_dev_ptr=None):
-        """``n_iter`` hyper-reduced iterations of the solve in progress, whose one slot is the reduced kind.  ``touched``: the
-        ascending vertices the slot's set-up is renumbered into (all but the last iteration run on those rows), or None: the
-        set-up names the mesh's vertices and every iteration runs on all rows."""
+        """``n_iter`` hyper-reduced iterations of the solve in progress, whose slots are all reduced kinds, each on its own bank
+        (``rforce_bank``).  ``touched``: the ascending vertices every slot's set-up is renumbered into -- the union over the kinds
+        (all but the last iteration run on those rows) --, or None: the set-ups name the mesh's vertices and every iteration runs
+        on all rows."""
         if touched is not None:
             touched = np.ascontiguousarray(touched, dtype=np.int64)
             assert touched.ndim == 1

@@ -248,15 +248,27 @@ def subset_setup(setup, sel):
                            setup.star_idx[edges], bending_indices=setup.bending_indices[sel], parts=parts)
 
 
-def touched_setup(setup, n_verts=None):
+def touched_setup(setup, n_verts=None, into=None):
     """``(touched, compact)`` for the hyper-reduced iterations: ``touched`` the sorted unique vertices the elements of
     ``setup`` read (their corners; for ``verts_bending`` the constrained vertices and their star neighbours), ``compact`` the
     same set-up with every vertex index replaced by its position in ``touched`` -- so that the elements project the rows
     ``q[:, touched]`` of an iterate exactly as ``setup`` projects ``q``.  The tables are taken over, not rebuilt: the same bits.
     ``bending_indices`` keeps naming the mesh's vertices.  ``n_verts`` given: ``touched`` is ``arange(n_verts)`` and the
-    renumbering is the identity (every row of the iterate is kept)."""
+    renumbering is the identity (every row of the iterate is kept).  ``into`` given (not with ``n_verts``): a strictly ascending
+    vertex list that holds every vertex the elements read -- the union of several kinds' touched sets, ``touched_union`` --;
+    ``touched`` is that list and the set-up is numbered in it, so that several kinds share the rows ``q[:, into]``."""
     star = setup.star_idx if setup.star_idx is not None else np.zeros(0, dtype=np.int64)
-    if n_verts is None:
+    if into is not None:
+        if n_verts is not None:
+            raise ValueError("%s: either n_verts or into" % setup.kind)
+        touched = np.asarray(into, dtype=np.int64).reshape(-1)
+        own = np.unique(np.concatenate([setup.idx.reshape(-1), star]))
+        if touched.size < 1 or (np.diff(touched) <= 0).any():
+            raise ValueError("%s: into must be a strictly ascending vertex list" % setup.kind)
+        at = np.minimum(np.searchsorted(touched, own), touched.size - 1)
+        if (touched[at] != own).any():
+            raise ValueError("%s: an element names vertex %d, which the given list lacks" % (setup.kind, int(own[touched[at] != own][0])))
+    elif n_verts is None:
         touched = np.unique(np.concatenate([setup.idx.reshape(-1), star]))
     else:
         touched = np.arange(int(n_verts), dtype=np.int64)
@@ -271,6 +283,12 @@ def touched_setup(setup, n_verts=None):
     compact = ProjectionSetup(setup.kind, pos(setup.idx), setup.table, setup.star_ptr,
                               None if setup.star_idx is None else pos(setup.star_idx), bending_indices=setup.bending_indices, parts=parts)
     return touched, compact
+
+
+def touched_union(setups):
+    """The sorted unique vertices the elements of all ``setups`` read: the one list ``touched_setup(setup, into=...)`` numbers
+    every kind of a multi-kind hyper-reduced solve in."""
+    return np.unique(np.concatenate([touched_setup(s)[0] for s in setups]))
 
 
 def assembly_ST(setup, n_verts, wi=1.0):

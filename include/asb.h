@@ -647,6 +647,16 @@ int asb_rforce_solver(asb_ctx* ctx, int64_t r, int64_t npt, const double* H, con
  * matching slices of a full run.  Returns after the stream has drained. */
 int asb_rforce_run(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean, double psf,
                    double sigma_min, double sigma_max, int accumulate, double* out_dev);
+/* Banks: the context holds ASB_RFORCE_BANKS independent sets of what the calls above and asb_hyper_operator make -- per bank the
+ * operator S^T V (3 mpp Np doubles), the solver H (3 r npt doubles) with its rows (npt ints), the coefficient scratch of one
+ * chunk of frames (3 rpp cw doubles), A^-1 S^T V with its valid mark (3 mpp Np doubles) and its touched columns Gt_c (3 mpp N_t
+ * doubles); a bank that was never addressed holds nothing.  A bank that was addressed KEEPS its buffers, whichever bank is
+ * current, until a later call that addresses it sizes them anew or asb_destroy frees them: nothing releases the banks that a
+ * solve no longer uses.  asb_rforce_bank selects the set that asb_rforce_operator,
+ * asb_rforce_solver, asb_rforce_run and asb_hyper_operator address from now on, and that a reduced asb_pdsolve_slot binds.  Bank
+ * 0 is current in a new context.  bank outside 0 .. ASB_RFORCE_BANKS - 1: ASB_ERR_ARG, nothing changed.  Host work only. */
+#define ASB_RFORCE_BANKS 8
+int asb_rforce_bank(asb_ctx* ctx, int bank);
 /* The reference's error metrics (constraintsComponents.py:524-556) of b against a, both DEVICE tensors (F, N, 3): sums_out (3)
  * sum (a - b)^2 per axis, max_out (1) max |a - b|, norms_out (4) sum a_x^2, sum a_y^2, sum a_z^2 and the SIGNED max a,
  * per_frame_out (F x 2) per frame [sum (a - b)^2, sum a^2] over its N x 3 entries.  Fixed-order reductions, no atomics; a
@@ -720,7 +730,9 @@ int asb_pdsolve_begin(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t f
 /* Registers the kind of the preceding asb_cproj_setup as the next term of the right-hand side: its device tables pass to
  * the solve (the context has no element set-up afterwards) together with the HOST CSR of its S^T (as asb_cforce_run takes
  * and checks it), uploaded here once.  reduced != 0: the set-up holds the SAMPLED elements and the term is that of
- * asb_rforce_run with the context's operator and solver (the CSR arguments are ignored); a second reduced kind is refused. */
+ * asb_rforce_run with the operator and solver of the bank that is current now (asb_rforce_bank; the CSR arguments are
+ * ignored): the slot records that bank.  A second reduced kind on a bank this solve has already bound is refused; reduced
+ * kinds on different banks are accepted, up to the 8 slots of a solve. */
 int asb_pdsolve_slot(asb_ctx* ctx, double sigma_min, double sigma_max, int reduced, int64_t n_rows, const int64_t* indptr,
                      const int64_t* indices, const double* data);
 /* n_iter further iterations of the solve in progress.  chunk_frames as asb_cforce_run (no bit depends on it).  out_dev
@@ -729,18 +741,22 @@ int asb_pdsolve_slot(asb_ctx* ctx, double sigma_min, double sigma_max, int reduc
  * in a fixed order.  The product is that of asb_gstep_run entry for entry; no atomics; repeats, sub-ranges and any chunk
  * width give identical bits.  Returns after the stream has drained. */
 int asb_pdsolve_iterate(asb_ctx* ctx, int64_t n_iter, int64_t chunk_frames, double* out_dev, double* hist_out);
-/* Hyper-reduced iterations: with every kind reduced (one operator per context: exactly ONE reduced kind) an iteration is
- * q_{k+1} = c + G_d coef_d(q_k) per coordinate, c = A^-1 ms, G_d = A^-1 (S^T V_d), and coef reads q_k only at the vertices of
- * the sampled elements (the touched vertices): no N^2 product is left in the loop.
- * asb_hyper_operator: after asb_gstep_setup and asb_rforce_operator.  Forms G_d^T in the layout of the operator S^T V, every
- * entry one accumulator over ascending n, and keeps it with the context.  A later asb_gstep_setup or asb_rforce_operator
- * invalidates it: asb_hyper_iterate then refuses (ASB_ERR_ARG) instead of using a stale operator.
- * asb_hyper_iterate: in place of asb_pdsolve_iterate, after asb_pdsolve_begin and ONE asb_pdsolve_slot with reduced != 0 (any
- * other set of slots is refused).  touched (host, n_touched, strictly ascending vertices) != NULL: the element set-up of the
- * slot is numbered in 0 .. n_touched - 1 (position in touched); iterations 1 .. n_iter - 1 run on those rows only, the last
- * on all n rows.  touched NULL: the set-up is numbered in the mesh's vertices and every iteration runs on all rows.  The two
- * give identical bits, as do repeats, sub-ranges and any chunk_frames (> 0: at most that many frames, rounded up to 64, per
- * pass).  out_dev (optional): caller-owned DEVICE memory (n_sel, n, 3), the iterate after the last iteration.  The whole
+/* Hyper-reduced iterations: with every kind reduced (one operator per bank: one reduced kind per bank of asb_rforce_bank) an
+ * iteration is q_{k+1} = c + sum_k G_{k,d} coef_{k,d}(q_k) per coordinate, c = A^-1 ms, G_{k,d} = A^-1 (S_k^T V_{k,d}), and coef
+ * reads q_k only at the vertices of the sampled elements (the touched vertices): no N^2 product is left in the loop.
+ * asb_hyper_operator: after asb_gstep_setup and asb_rforce_operator.  Forms G_d^T of the current bank in the layout of the
+ * operator S^T V, every entry one accumulator over ascending n, and keeps it with the bank.  A later asb_gstep_setup or
+ * asb_gslab_setup invalidates the G of ALL banks, a later asb_rforce_operator that of its own bank only: asb_hyper_iterate
+ * then refuses (ASB_ERR_ARG) instead of using a stale operator.
+ * asb_hyper_iterate: in place of asb_pdsolve_iterate, after asb_pdsolve_begin and one or more asb_pdsolve_slot, ALL with
+ * reduced != 0 (a slot that is not reduced is refused), each bank with a solver and a valid G.  touched (host, n_touched,
+ * strictly ascending vertices) != NULL: ONE list, the union over the kinds; the element set-up of every slot is numbered in
+ * 0 .. n_touched - 1 (position in touched); iterations 1 .. n_iter - 1 run on those rows only, the last on all n rows.
+ * touched NULL: the set-ups are numbered in the mesh's vertices and every iteration runs on all rows.  The two give
+ * identical bits, as do repeats, sub-ranges and any chunk_frames (> 0: at most that many frames, rounded up to 64, per
+ * pass; one width serves all slots, the smallest of the banks').  Within an iteration and chunk the coefficients of ALL slots
+ * are formed from the old iterate before one launch writes the new one: a Jacobi update over the kinds, as the reference's.
+ * out_dev (optional): caller-owned DEVICE memory (n_sel, n, 3), the iterate after the last iteration.  The whole
  * iterate is left in the solve's state.  No atomics.  Returns after the stream has drained. */
 int asb_hyper_operator(asb_ctx* ctx);
 int asb_hyper_iterate(asb_ctx* ctx, int64_t n_iter, int64_t n_touched, const int64_t* touched, int64_t chunk_frames, double* out_dev);
