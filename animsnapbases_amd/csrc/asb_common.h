@@ -54,6 +54,17 @@ __device__ __forceinline__ void cp_pos(const CpWorld& w, long long f, int v, dou
 }
 #endif
 
+// One element set-up on the device: what asb_cproj_setup uploads.  The context holds one (ctx->cp: the kind of the next
+// asb_cproj_run / asb_cforce_run / asb_rforce_run) and every slot of a solve holds one (asb_pdsolve.hip), taken over from the
+// context by asb_cp_move.
+struct CpSetup {
+    int kind = -1;                    // element kind (-1: no set-up)
+    int64_t n = 0, verts = 0;         // its elements; the vertices its indices were checked against
+    int64_t vmax = -1;                // largest vertex it names (elements and star edges)
+    int *idx = nullptr, *sptr = nullptr, *sidx = nullptr;    // indices (n x width); verts_bending: star CSR
+    double* table = nullptr;          // per-element tables (n x TW), verts_bending: followed by the star edges' weights
+};
+
 struct asb_ctx {
     int dev = 0;
     hipStream_t stream = nullptr;
@@ -323,44 +334,36 @@ struct asb_ctx {
     double* om_scratch = nullptr;     // (3*n_loc, cw) reconstruction of one chunk of frames
     double *om_fe = nullptr, *om_ang = nullptr;   // (frames, n_loc) maps, only when asked for
     // constraint projections of the resident positions (asb_cproj.hip)
-    int cp_kind = -1;                 // element kind of the last asb_cproj_setup (-1: none)
-    int64_t cp_n = 0, cp_verts = 0;   // its elements; the vertices its indices were checked against
-    int *cp_idx = nullptr, *cp_sptr = nullptr, *cp_sidx = nullptr;    // indices (cp_n x width); verts_bending: star CSR
-    double* cp_table = nullptr;       // per-element tables (+ the star edges' weights)
+    CpSetup cp;                       // the last asb_cproj_setup (kind -1: none, or a solve's slot took it over)
     double* cp_invm = nullptr;        // (n_loc) 1 / massL
     int *cf_ptr = nullptr, *cf_idx = nullptr;     // asb_cforce_run: the CSR of S^T (n_loc + 1 offsets, columns)
     double* cf_val = nullptr;         // its values
-    double* cf_scratch = nullptr;     // (3 * cp_n * p, cw) element-major projections of one chunk of frames
-    // reduced constraint forces S^T V (P^T V)^+ P^T p (asb_rforce.hip)
-    double* rf_M = nullptr;           // (3, rf_mpp, rf_Np): M_d^T = (S^T V_d)^T, vertices contiguous, zero padding
-    int64_t rf_n = 0, rf_Np = 0;      // its vertices; rounded up to the kernel's 32
-    int64_t rf_mp = 0, rf_mpp = 0;    // its basis vectors; rounded up to 4
-    double* rf_H = nullptr;           // (3, rf_r, rf_npt) the solver H_d = (A^T A + la I)^-1 A^T
-    int* rf_pt = nullptr;             // (rf_npt) rows of the sampled elements' stacked projections
-    int64_t rf_r = 0, rf_npt = 0, rf_pt_max = -1;     // basis vectors in use (<= rf_mp; 0: no solver), points, largest row
-    double* rf_coef = nullptr;        // (3, rf_r rounded up to 4, cw) coefficients of one chunk of frames
+    double* cf_scratch = nullptr;     // (3 * cp.n * p, cw) element-major projections of one chunk of frames
+    // reduced constraint forces S^T V (P^T V)^+ P^T p (asb_rforce.hip) and hyper-reduced iterations (asb_pdsolve.hip): the banks of
+    // asb_rforce_bank.  rf_bank is the ONLY home of a bank's buffers and numbers, whichever bank is current: a selection sets
+    // rf_cur and moves nothing, so a buffer's asb_alloc key (the address of its member here) never changes.  The entry points
+    // that address "the current bank" take rf_bank[rf_cur] (asb_rf_cur), a slot of a solve takes rf_bank[slot.bank].
+    struct RfBank {
+        double* M = nullptr;              // (3, mpp, Np): M_d^T = (S^T V_d)^T, vertices contiguous, zero padding
+        int64_t n = 0, Np = 0;            // its vertices; rounded up to the kernel's 32
+        int64_t mp = 0, mpp = 0;          // its basis vectors (0: no operator); rounded up to 4
+        double* H = nullptr;              // (3, r, npt) the solver H_d = (A^T A + la I)^-1 A^T
+        int* pt = nullptr;                // (npt) rows of the sampled elements' stacked projections
+        int64_t r = 0, npt = 0, pt_max = -1;      // basis vectors in use (<= mp; 0: no solver), points, largest row
+        double* coef = nullptr;           // (3, r rounded up to 4, cw) coefficients of one chunk of frames
+        double* G = nullptr;              // G_d^T = (A^-1 M_d)^T in M's layout, (3, mpp, Np) (asb_hyper_operator)
+        int ok = 0;                       // G belongs to the current solver and M (a new system matrix clears it in every
+                                          // bank, asb_rforce_operator in its own)
+        double* Gc = nullptr;             // asb_hyper_iterate: the touched columns of G, (3, mpp, N_t rounded up to 32, zero padding)
+    };
+    RfBank rf_bank[ASB_RFORCE_BANKS];
+    int rf_cur = 0;
     double* fd_part = nullptr;        // asb_force_diff: per-frame records + the reduced row
     // global step q = A^-1 rhs (asb_gstep.hip)
     double* gs_Ainv = nullptr;        // (gs_Np, gs_Np) the explicit inverse of A_N, the padding an identity block
     int64_t gs_n = 0, gs_Np = 0;      // its vertices (0: no set-up); rounded up to the kernel's 32
     double* gs_diag = nullptr;        // (n_loc) asb_gstep_inertia: masses / h^2
     asb_pds* pds = nullptr;           // the solve in progress and its buffers (asb_pdsolve.hip)
-    // hyper-reduced iterations (asb_pdsolve.hip): G_d^T = (A^-1 M_d)^T in rf_M's layout, (3, rf_mpp, rf_Np)
-    double* hy_G = nullptr;
-    int hy_ok = 0;                    // hy_G belongs to the current gs_Ainv and rf_M (asb_gstep_setup / asb_rforce_operator clear it)
-    double* hy_Gc = nullptr;          // asb_hyper_iterate: the touched columns of hy_G, (3, rf_mpp, N_t rounded up to 32, zero padding)
-    // The banks of asb_rforce_bank: rf_* and hy_* above are the CURRENT bank rf_cur; the others rest in rf_bank (the entry of
-    // the current one holds nothing).  asb_rf_select swaps the fields with their registered capacities, so every launcher
-    // keeps reading ctx->rf_*; asb_rf_view reads any bank without a swap.
-    struct RfBank {
-        double *M = nullptr, *H = nullptr, *coef = nullptr, *G = nullptr, *Gc = nullptr;
-        int* pt = nullptr;
-        int64_t n = 0, Np = 0, mp = 0, mpp = 0, r = 0, npt = 0, pt_max = -1;
-        int ok = 0;
-    };
-    RfBank rf_bank[ASB_RFORCE_BANKS];
-    int rf_cur = 0;
-    int64_t cp_vmax = -1;             // largest vertex the last asb_cproj_setup names (elements and star edges)
     // the global step's second solver (asb_gslab.hip): the block-tridiagonal slab factor of A_N.  The context holds EITHER
     // gs_Ainv (gs_n > 0) or the factor (asb_gslab_n(ctx) > 0): each set-up releases the other
     asb_gsl* gsl = nullptr;
@@ -440,46 +443,27 @@ int asb_world_frames(asb_ctx* ctx, const char* who, int which, int64_t f0, int64
                      int64_t* n_sel);
 // the first device work of a call, after all of its checks: inv_massL (host, or NULL) uploaded and put into w
 int asb_cproj_invm(asb_ctx* ctx, const double* inv_massL, CpWorld* w);
-// selected frames [c0, c0 + cn) projected ELEMENT-major into S (3 cp_n p rows of cw doubles), for the kind of asb_cproj_setup
-void asb_cproj_em_launch(asb_ctx* ctx, const CpWorld& w, int f0, int fj, int c0, int cn, int cw, double smin, double smax, double* S);
-// the same for any element set-up on the device: the tables asb_cproj_setup uploads, by pointer (asb_pdsolve.hip keeps several)
-struct CpTables {
-    int kind;
-    long long n;                      // elements
-    const int *idx, *sptr, *sidx;
-    const double* table;              // (n x TW), verts_bending: followed by the star edges' weights
-};
-void asb_cproj_em_launch_t(asb_ctx* ctx, const CpTables& t, const CpWorld& w, int f0, int fj, int c0, int cn, int cw, double smin, double smax,
-                           double* S);
+// selected frames [c0, c0 + cn) projected ELEMENT-major into S (3 cp.n p rows of cw doubles) for the element set-up cp: the
+// context's (ctx->cp) or a slot's
+void asb_cproj_em_launch(asb_ctx* ctx, const CpSetup& cp, const CpWorld& w, int f0, int fj, int c0, int cn, int cw, double smin, double smax,
+                         double* S);
 // rows of the stacked projections of a set-up of `kind` with n_elem elements
 long long asb_cproj_rows(int kind, long long n_elem);
 // the chunk width of asb_cforce_run for projections of n_cols rows, and one chunk's k_st_apply on a device CSR
 long long asb_cforce_chunk_width(long long n_cols, long long chunk_frames, long long n_sel);
 void asb_st_apply_launch(asb_ctx* ctx, const int* ptr, const int* ci, const double* val, const double* S, int cw, int c0, int cn,
                          long long n_rows, int accumulate, double* out);
-// asb_rforce.hip: the chunk width of asb_rforce_run for sampled projections of n_cols rows; one chunk's k_rforce_coef and
-// k_rforce_gemm with the context's operator and solver, from the element-major projections S (coefficients into ctx->rf_coef)
-long long asb_rforce_chunk_width(asb_ctx* ctx, long long n_cols, long long n_sel);
-void asb_rforce_chunk_launch(asb_ctx* ctx, const double* S, int cw, int c0, int cn, int accumulate, double* out);
-// its first half alone: k_rforce_coef of one chunk into ctx->rf_coef ((3, rf_r rounded up to 4, cw), zero past row rf_r and frame cn)
-void asb_rforce_coef_launch(asb_ctx* ctx, const double* S, int cw, int cn);
-// The banks (asb_rforce_bank).  RfView: what the kernels need of one bank, by value.  asb_rf_select makes `bank` the current one
-// (host work only: pointers and their registered capacities change places); asb_rf_view reads a bank wherever it rests;
-// asb_rf_invalidate_all clears the A^-1 S^T V mark of every bank (a new system matrix); the _v launchers are
-// asb_rforce_chunk_width / _coef_launch / _chunk_launch for a view.
-struct RfView {
-    const double *M, *H, *G;
-    double *coef, *Gc;
-    const int* pt;
-    long long n, Np, mp, mpp, r, npt, pt_max;
-    int ok;
-};
-void asb_rf_select(asb_ctx* ctx, int bank);
-RfView asb_rf_view(const asb_ctx* ctx, int bank);
+// asb_rforce.hip, the banks of asb_rforce_bank (asb_ctx::rf_bank).  asb_rf_cur: the bank the entry points address now;
+// asb_rf_invalidate_all clears the A^-1 S^T V mark of every bank (a new system matrix)
+static inline asb_ctx::RfBank& asb_rf_cur(asb_ctx* ctx) { return ctx->rf_bank[ctx->rf_cur]; }
 void asb_rf_invalidate_all(asb_ctx* ctx);
-long long asb_rforce_chunk_width_r(long long r, long long n_cols, long long n_sel);
-void asb_rforce_coef_launch_v(asb_ctx* ctx, const RfView& v, const double* S, int cw, int cn);
-void asb_rforce_chunk_launch_v(asb_ctx* ctx, const RfView& v, const double* S, int cw, int c0, int cn, int accumulate, double* out);
+// the chunk width of asb_rforce_run for a solver of r basis vectors and sampled projections of n_cols rows; one chunk's
+// k_rforce_coef and k_rforce_gemm with the operator and solver of `bank`, from the element-major projections S (coefficients
+// into bank.coef, which the caller has sized)
+long long asb_rforce_chunk_width(long long r, long long n_cols, long long n_sel);
+void asb_rforce_chunk_launch(asb_ctx* ctx, const asb_ctx::RfBank& bank, const double* S, int cw, int c0, int cn, int accumulate, double* out);
+// its first half alone: k_rforce_coef of one chunk into bank.coef ((3, r rounded up to 4, cw), zero past row r and frame cn)
+void asb_rforce_coef_launch(asb_ctx* ctx, const asb_ctx::RfBank& bank, const double* S, int cw, int cn);
 // asb_gstep.hip: k_gs_inertia on device arrays; add: out += diag s, otherwise out = diag s (the value the sum adds)
 void asb_gs_inertia_launch(asb_ctx* ctx, const CpWorld& w, int f0, int fj, int n_sel, long long n, const double* diag_dev, int mode,
                            const double* acc3, bool add, double* out);
@@ -496,7 +480,7 @@ void asb_gslab_release(asb_ctx* ctx);
 // vertex-major, ld = F rounded up to 64 (columns [F, ld) of Qv are written as zero); Qv NULL: a buffer of the factor.  out
 // (optional): the same values frame-major (F, n, 3)
 int asb_gslab_solve_fm(asb_ctx* ctx, const double* rhs, long long F, double* Qv, double* out);
-// Gt (rows, Np) with the n vertices contiguous in a row (the layout of rf_M) -> Ot, same layout: Ot[r] = A^-1 Gt[r]; the
+// Gt (rows, Np) with the n vertices contiguous in a row (the layout of RfBank::M) -> Ot, same layout: Ot[r] = A^-1 Gt[r]; the
 // entries of Ot past vertex n are left as they are
 int asb_gslab_solve_rows(asb_ctx* ctx, const double* Gt, long long rows, long long Np, double* Ot);
 // asb_pdsolve.hip: k_pd_untranspose, P (rows, ld) vertex-major -> out (n_sel, rows) frame-major
@@ -505,6 +489,18 @@ void asb_pd_untranspose_launch(asb_ctx* ctx, const double* P, int n_sel, long lo
 // `what` names the matrix in the messages
 int asb_csr_check32(asb_ctx* ctx, const char* who, int64_t n_rows, const int64_t* indptr, const int64_t* indices, const double* data,
                     long long n_cols, std::vector<int>& p32, std::vector<int>& c32, const char* what = "S^T");
+// the CSR it narrowed, copied on the context's stream into device arrays the caller owns: dptr of p32.size() ints, dci and
+// dval of c32.size() + 1 entries (no empty allocation for a matrix without entries).  Nothing is allocated or synchronised here: the caller drains the stream
+// before the vectors die
+static inline int asb_csr_stage(asb_ctx* ctx, const std::vector<int>& p32, const std::vector<int>& c32, const double* data, int* dptr,
+                                int* dci, double* dval) {
+    ASB_HIP(ctx, hipMemcpyAsync(dptr, p32.data(), p32.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    if (!c32.empty()) {
+        ASB_HIP(ctx, hipMemcpyAsync(dci, c32.data(), c32.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        ASB_HIP(ctx, hipMemcpyAsync(dval, data, c32.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    }
+    return ASB_OK;
+}
 
 // ASB_DEBUG_PANELS: the panel loop's trace on stderr (changes no result); read once per process
 static inline bool asb_debug_panels() {
@@ -541,7 +537,9 @@ static inline int asb_alloc(asb_ctx* ctx, T** p, size_t count) {
     return ASB_OK;
 }
 
-// two context-owned buffers change places, with their registered capacities (both owners live inside the context or its solve)
+// two context-owned buffers change places, with their registered capacities (both owners live inside the context or its
+// solve).  A capacity is keyed on the address of the owning pointer, so this is the one place where a key follows a buffer;
+// its only user is asb_cp_move below
 template <typename T>
 static inline void asb_swap_buf(asb_ctx* ctx, T** a, T** b) {
     auto cap = [&](void* key) {
@@ -554,6 +552,17 @@ static inline void asb_swap_buf(asb_ctx* ctx, T** a, T** b) {
     std::swap(*a, *b);
     if (*a) ctx->alloc_bytes[(void*)a] = cb;
     if (*b) ctx->alloc_bytes[(void*)b] = ca;
+}
+
+// An element set-up changes owner, the context to a slot of a solve: pointers, no copy.  `to`'s previous buffers pass to
+// `from` (its next asb_cproj_setup reuses them), which has no set-up afterwards
+static inline void asb_cp_move(asb_ctx* ctx, CpSetup& from, CpSetup& to) {
+    asb_swap_buf(ctx, &from.idx, &to.idx);
+    asb_swap_buf(ctx, &from.table, &to.table);
+    asb_swap_buf(ctx, &from.sptr, &to.sptr);
+    asb_swap_buf(ctx, &from.sidx, &to.sidx);
+    to.kind = from.kind, to.n = from.n, to.verts = from.verts, to.vmax = from.vmax;
+    from.kind = -1;
 }
 
 // A device buffer that lives inside one call: freed when it goes out of scope (hipFree waits for the device, so work still in

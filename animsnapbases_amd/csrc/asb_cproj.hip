@@ -35,6 +35,16 @@ template <> struct CpShape<CP_TET_STRAIN> { static constexpr int NV = 4, P = 3, 
 template <> struct CpShape<CP_TET_DEFGRAD> { static constexpr int NV = 4, P = 3, TW = 9; };
 template <> struct CpShape<CP_BEND> { static constexpr int NV = 1, P = 1, TW = 5; };
 
+// LAUNCH<KIND>(arguments) for the kind of an element set-up (asb_cproj_setup admits the five only)
+#define CP_FOR_KIND(kind, LAUNCH, ...)                                   \
+    switch (kind) {                                                      \
+        case CP_EDGE: LAUNCH<CP_EDGE>(__VA_ARGS__); break;               \
+        case CP_TRI: LAUNCH<CP_TRI>(__VA_ARGS__); break;                 \
+        case CP_TET_STRAIN: LAUNCH<CP_TET_STRAIN>(__VA_ARGS__); break;   \
+        case CP_TET_DEFGRAD: LAUNCH<CP_TET_DEFGRAD>(__VA_ARGS__); break; \
+        default: LAUNCH<CP_BEND>(__VA_ARGS__); break;                    \
+    }
+
 // one Jacobi rotation of the columns p, q of A (N rows) and of V (N rows): true when it rotated
 template <int N>
 __device__ __forceinline__ bool cp_rotate(double (&A)[N][N], double (&V)[N][N], int p, int q) {
@@ -288,7 +298,8 @@ extern "C" int asb_cproj_setup(asb_ctx* ctx, int kind, int64_t n_elem, const int
     const int nv = NV[kind], tw = TW[kind];
     const long long n_loc = ctx->n_loc;
     if (n_loc > 0x7fffffffLL || n_elem > 0x7fffffffLL / 16) ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_cproj_setup: too large for 32-bit indices");
-    ctx->cp_kind = -1;
+    CpSetup& cp = ctx->cp;
+    cp.kind = -1;
     int64_t vmax = -1;
     std::vector<int> i32((size_t)n_elem * nv), p32, s32;
     for (int64_t i = 0; i < n_elem * nv; ++i) {
@@ -318,27 +329,25 @@ extern "C" int asb_cproj_setup(asb_ctx* ctx, int kind, int64_t n_elem, const int
     ASB_HIP(ctx, hipSetDevice(ctx->dev));
     const size_t n_table = (size_t)n_elem * tw + (size_t)nnz;
     int rc;
-    if ((rc = asb_alloc(ctx, &ctx->cp_idx, i32.size()))) return rc;
-    if ((rc = asb_alloc(ctx, &ctx->cp_table, n_table))) return rc;
-    if ((rc = asb_alloc(ctx, &ctx->cp_sptr, p32.size() + 1))) return rc;
-    if ((rc = asb_alloc(ctx, &ctx->cp_sidx, s32.size() + 1))) return rc;
-    ASB_HIP(ctx, hipMemcpyAsync(ctx->cp_idx, i32.data(), i32.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    ASB_HIP(ctx, hipMemcpyAsync(ctx->cp_table, table, n_table * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (!p32.empty()) ASB_HIP(ctx, hipMemcpyAsync(ctx->cp_sptr, p32.data(), p32.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    if (!s32.empty()) ASB_HIP(ctx, hipMemcpyAsync(ctx->cp_sidx, s32.data(), s32.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = asb_alloc(ctx, &cp.idx, i32.size()))) return rc;
+    if ((rc = asb_alloc(ctx, &cp.table, n_table))) return rc;
+    if ((rc = asb_alloc(ctx, &cp.sptr, p32.size() + 1))) return rc;
+    if ((rc = asb_alloc(ctx, &cp.sidx, s32.size() + 1))) return rc;
+    ASB_HIP(ctx, hipMemcpyAsync(cp.idx, i32.data(), i32.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    ASB_HIP(ctx, hipMemcpyAsync(cp.table, table, n_table * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (!p32.empty()) ASB_HIP(ctx, hipMemcpyAsync(cp.sptr, p32.data(), p32.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    if (!s32.empty()) ASB_HIP(ctx, hipMemcpyAsync(cp.sidx, s32.data(), s32.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));          // (the staging vectors die here)
-    ctx->cp_kind = kind;
-    ctx->cp_n = n_elem;
-    ctx->cp_verts = n_loc;
-    ctx->cp_vmax = vmax;
+    cp.kind = kind, cp.n = n_elem, cp.verts = n_loc, cp.vmax = vmax;
     return ASB_OK;
 }
 
 template <int KIND>
 static void cp_launch(asb_ctx* ctx, const CpWorld& w, int f0, int fj, int n_sel, double smin, double smax, double* out) {
-    const dim3 grid((unsigned)((ctx->cp_n + CP_EB - 1) / CP_EB), (unsigned)((n_sel + 63) / 64));
-    hipLaunchKernelGGL(k_cproj<KIND>, grid, dim3(64 * CP_WAVES), 0, ctx->stream, w, ctx->cp_idx, ctx->cp_table, ctx->cp_sptr, ctx->cp_sidx,
-                       ctx->cp_table + (size_t)ctx->cp_n * CpShape<KIND>::TW, (long long)ctx->cp_n, f0, fj, n_sel, smin, smax, out);
+    const CpSetup& cp = ctx->cp;
+    const dim3 grid((unsigned)((cp.n + CP_EB - 1) / CP_EB), (unsigned)((n_sel + 63) / 64));
+    hipLaunchKernelGGL(k_cproj<KIND>, grid, dim3(64 * CP_WAVES), 0, ctx->stream, w, cp.idx, cp.table, cp.sptr, cp.sidx,
+                       cp.table + (size_t)cp.n * CpShape<KIND>::TW, (long long)cp.n, f0, fj, n_sel, smin, smax, out);
 }
 
 int asb_world_frames(asb_ctx* ctx, const char* who, int which, int64_t f0, int64_t f1, int64_t fj, int add_mean, double psf, CpWorld* w,
@@ -367,7 +376,7 @@ int asb_world_frames(asb_ctx* ctx, const char* who, int which, int64_t f0, int64
 
 int asb_cproj_world(asb_ctx* ctx, const char* who, int which, int64_t f0, int64_t f1, int64_t fj, int add_mean, double psf,
                     double sigma_min, double sigma_max, CpWorld* w, int64_t* n_sel_out) {
-    if (ctx->cp_kind < 0 || !ctx->X || ctx->cp_verts != ctx->n_loc || ctx->v0 != 0 || ctx->n_loc != ctx->N_glob)
+    if (ctx->cp.kind < 0 || !ctx->X || ctx->cp.verts != ctx->n_loc || ctx->v0 != 0 || ctx->n_loc != ctx->N_glob)
         ASB_FAIL(ctx, ASB_ERR_ARG, "%s: no element set-up for the resident tensor (asb_cproj_setup)", who);
     int rc;
     if ((rc = asb_world_frames(ctx, who, which, f0, f1, fj, add_mean, psf, w, n_sel_out))) return rc;
@@ -395,13 +404,7 @@ extern "C" int asb_cproj_run(asb_ctx* ctx, int which, int64_t f0, int64_t f1, in
     int rc;
     if ((rc = asb_cproj_world(ctx, "asb_cproj_run", which, f0, f1, fj, add_mean, psf, sigma_min, sigma_max, &w, &n_sel))) return rc;
     if ((rc = asb_cproj_invm(ctx, inv_massL, &w))) return rc;
-    switch (ctx->cp_kind) {
-        case CP_EDGE: cp_launch<CP_EDGE>(ctx, w, (int)f0, (int)fj, (int)n_sel, sigma_min, sigma_max, out_dev); break;
-        case CP_TRI: cp_launch<CP_TRI>(ctx, w, (int)f0, (int)fj, (int)n_sel, sigma_min, sigma_max, out_dev); break;
-        case CP_TET_STRAIN: cp_launch<CP_TET_STRAIN>(ctx, w, (int)f0, (int)fj, (int)n_sel, sigma_min, sigma_max, out_dev); break;
-        case CP_TET_DEFGRAD: cp_launch<CP_TET_DEFGRAD>(ctx, w, (int)f0, (int)fj, (int)n_sel, sigma_min, sigma_max, out_dev); break;
-        default: cp_launch<CP_BEND>(ctx, w, (int)f0, (int)fj, (int)n_sel, sigma_min, sigma_max, out_dev); break;
-    }
+    CP_FOR_KIND(ctx->cp.kind, cp_launch, ctx, w, (int)f0, (int)fj, (int)n_sel, sigma_min, sigma_max, out_dev);
     ASB_CHECK_LAUNCH(ctx);
     ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the caller owns out_dev and may read it on any stream
     return ASB_OK;
@@ -499,27 +502,16 @@ __global__ __launch_bounds__(64 * CP_WAVES) void k_st_apply(const int* __restric
 }
 
 template <int KIND>
-static void cf_launch(asb_ctx* ctx, const CpTables& t, const CpWorld& w, int f0, int fj, int c0, int cn, int cw, double smin, double smax,
+static void cf_launch(asb_ctx* ctx, const CpSetup& t, const CpWorld& w, int f0, int fj, int c0, int cn, int cw, double smin, double smax,
                       double* S) {
     const dim3 grid((unsigned)((t.n + CP_EB - 1) / CP_EB), (unsigned)((cn + 63) / 64));
     hipLaunchKernelGGL(k_cproj_em<KIND>, grid, dim3(64 * CP_WAVES), 0, ctx->stream, w, t.idx, t.table, t.sptr, t.sidx,
-                       t.table + (size_t)t.n * CpShape<KIND>::TW, t.n, f0, fj, c0, cn, cw, smin, smax, S);
+                       t.table + (size_t)t.n * CpShape<KIND>::TW, (long long)t.n, f0, fj, c0, cn, cw, smin, smax, S);
 }
 
-void asb_cproj_em_launch_t(asb_ctx* ctx, const CpTables& t, const CpWorld& w, int f0, int fj, int c0, int cn, int cw, double smin, double smax,
-                           double* S) {
-    switch (t.kind) {
-        case CP_EDGE: cf_launch<CP_EDGE>(ctx, t, w, f0, fj, c0, cn, cw, smin, smax, S); break;
-        case CP_TRI: cf_launch<CP_TRI>(ctx, t, w, f0, fj, c0, cn, cw, smin, smax, S); break;
-        case CP_TET_STRAIN: cf_launch<CP_TET_STRAIN>(ctx, t, w, f0, fj, c0, cn, cw, smin, smax, S); break;
-        case CP_TET_DEFGRAD: cf_launch<CP_TET_DEFGRAD>(ctx, t, w, f0, fj, c0, cn, cw, smin, smax, S); break;
-        default: cf_launch<CP_BEND>(ctx, t, w, f0, fj, c0, cn, cw, smin, smax, S); break;
-    }
-}
-
-void asb_cproj_em_launch(asb_ctx* ctx, const CpWorld& w, int f0, int fj, int c0, int cn, int cw, double smin, double smax, double* S) {
-    const CpTables t = {ctx->cp_kind, (long long)ctx->cp_n, ctx->cp_idx, ctx->cp_sptr, ctx->cp_sidx, ctx->cp_table};
-    asb_cproj_em_launch_t(ctx, t, w, f0, fj, c0, cn, cw, smin, smax, S);
+void asb_cproj_em_launch(asb_ctx* ctx, const CpSetup& t, const CpWorld& w, int f0, int fj, int c0, int cn, int cw, double smin, double smax,
+                         double* S) {
+    CP_FOR_KIND(t.kind, cf_launch, ctx, t, w, f0, fj, c0, cn, cw, smin, smax, S);
 }
 
 long long asb_cproj_rows(int kind, long long n_elem) {
@@ -574,26 +566,21 @@ extern "C" int asb_cforce_run(asb_ctx* ctx, int which, int64_t f0, int64_t f1, i
     if ((rc = asb_cproj_world(ctx, "asb_cforce_run", which, f0, f1, fj, add_mean, psf, sigma_min, sigma_max, &w, &n_sel))) return rc;
     if (chunk_frames < 0) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: chunk_frames %lld", (long long)chunk_frames);
     // ---- the CSR of S^T: one row per vertex of the tensor, columns = rows of the stacked projections, ascending in a row
-    const long long n_cols = asb_cproj_rows(ctx->cp_kind, ctx->cp_n);
+    const long long n_cols = asb_cproj_rows(ctx->cp.kind, ctx->cp.n);
     if (n_rows != ctx->n_loc)
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_cforce_run: S^T has %lld rows, the tensor %lld vertices", (long long)n_rows, (long long)ctx->n_loc);
     std::vector<int> p32, c32;
     if ((rc = asb_csr_check32(ctx, "asb_cforce_run", n_rows, indptr, indices, data, n_cols, p32, c32))) return rc;
-    const int64_t nnz = indptr[n_rows];
     const long long cw = asb_cforce_chunk_width(n_cols, chunk_frames, n_sel);
     if ((rc = asb_cproj_invm(ctx, inv_massL, &w))) return rc;
     if ((rc = asb_alloc(ctx, &ctx->cf_ptr, p32.size()))) return rc;
     if ((rc = asb_alloc(ctx, &ctx->cf_idx, c32.size() + 1))) return rc;
     if ((rc = asb_alloc(ctx, &ctx->cf_val, c32.size() + 1))) return rc;
     if ((rc = asb_alloc(ctx, &ctx->cf_scratch, (size_t)3 * n_cols * cw))) return rc;
-    ASB_HIP(ctx, hipMemcpyAsync(ctx->cf_ptr, p32.data(), p32.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    if (nnz > 0) {
-        ASB_HIP(ctx, hipMemcpyAsync(ctx->cf_idx, c32.data(), c32.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        ASB_HIP(ctx, hipMemcpyAsync(ctx->cf_val, data, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    }
+    if ((rc = asb_csr_stage(ctx, p32, c32, data, ctx->cf_ptr, ctx->cf_idx, ctx->cf_val))) return rc;
     for (long long c0 = 0; c0 < n_sel; c0 += cw) {
         const int cn = (int)(c0 + cw < n_sel ? cw : n_sel - c0);
-        asb_cproj_em_launch(ctx, w, (int)f0, (int)fj, (int)c0, cn, (int)cw, sigma_min, sigma_max, ctx->cf_scratch);
+        asb_cproj_em_launch(ctx, ctx->cp, w, (int)f0, (int)fj, (int)c0, cn, (int)cw, sigma_min, sigma_max, ctx->cf_scratch);
         asb_st_apply_launch(ctx, ctx->cf_ptr, ctx->cf_idx, ctx->cf_val, ctx->cf_scratch, (int)cw, (int)c0, cn, (long long)n_rows, accumulate,
                             out_dev);
     }

@@ -115,7 +115,6 @@ extern "C" int asb_gstep_setup(asb_ctx* ctx, int64_t n, const int64_t* indptr, c
     std::vector<int> p32, c32;
     int rc;
     if ((rc = asb_gs_check_matrix(ctx, "asb_gstep_setup", n, indptr, indices, data, p32, c32))) return rc;
-    const int64_t nnz = indptr[n];
     const int ni = (int)n, np = (ni + GS_TN - 1) / GS_TN * GS_TN;
     ASB_HIP(ctx, hipSetDevice(ctx->dev));
     asb_tmp<int> dptr, dci;
@@ -125,9 +124,7 @@ extern "C" int asb_gstep_setup(asb_ctx* ctx, int64_t n, const int64_t* indptr, c
     if ((rc = dval.alloc(ctx, c32.size() + 1))) return rc;
     if ((rc = dy.alloc(ctx, (size_t)2 * n))) return rc;
     if ((rc = asb_alloc(ctx, &ctx->gs_Ainv, (size_t)np * np))) return rc;
-    ASB_HIP(ctx, hipMemcpyAsync(dptr.get(), p32.data(), p32.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    ASB_HIP(ctx, hipMemcpyAsync(dci.get(), c32.data(), (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    ASB_HIP(ctx, hipMemcpyAsync(dval.get(), data, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = asb_csr_stage(ctx, p32, c32, data, dptr.get(), dci.get(), dval.get()))) return rc;
     ASB_HIP(ctx, hipMemsetAsync(ctx->gs_Ainv, 0, (size_t)np * np * sizeof(double), ctx->stream));
     hipLaunchKernelGGL(k_gs_fill, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, ctx->stream, dptr.get(), dci.get(), dval.get(), ni, np,
                        ctx->gs_Ainv);

@@ -14,8 +14,10 @@
 //   P   (3 N, ld) vertex-major      only after asb_pdsolve_carry: the positions at the START of the current time step (the
 //                                   reference's model.positions), laid out and padded like Q; with it the solve's own device
 //                                   copy of diag, which ctx->gs_diag is not (asb_gstep_inertia rewrites that one)
-//   slots                           per kind the device tables of an asb_cproj_setup and the CSR of its S^T, registered once:
-//                                   no host-to-device copy happens inside the iteration loop
+//   slots                           per kind the element set-up of an asb_cproj_setup (a CpSetup, moved out of the context by
+//                                   asb_cp_move) and the CSR of its S^T, registered once: no host-to-device copy happens inside
+//                                   the iteration loop.  A reduced slot owns no operator: it names a bank, and every use reads
+//                                   ctx->rf_bank[slot.bank], where the bank's buffers stay whichever bank is current
 //
 // One iteration, in stream order:
 //   per slot, in order, per chunk of frames   k_cproj_em on the iterate's world, then k_st_apply (the first slot overwrites b,
@@ -46,15 +48,13 @@
 #define PD_MAX_SLOTS 8
 
 struct PdSlot {
-    int kind = -1, reduced = 0;
-    long long n_elem = 0, n_cols = 0;
-    int *idx = nullptr, *sptr = nullptr, *sidx = nullptr;       // the tables of asb_cproj_setup, taken over from the context
-    double* table = nullptr;
+    CpSetup cp;                                                 // the element set-up of asb_cproj_setup, taken over from the context
+    int reduced = 0;
+    long long n_cols = 0;                                       // rows of its stacked projections
     int *st_ptr = nullptr, *st_idx = nullptr;                   // the CSR of S^T (not for the reduced kind)
     double* st_val = nullptr;
     double smin = 1.0, smax = 1.0;
-    long long vmax = -1;                                        // the largest vertex its tables name
-    int bank = 0;                                               // reduced: the bank of its operator and solver
+    int bank = 0;                                               // reduced: ctx->rf_bank[bank] holds its operator and solver
 };
 
 struct asb_pds {
@@ -63,7 +63,7 @@ struct asb_pds {
     double *ms = nullptr, *Q = nullptr, *b = nullptr;
     double *part = nullptr, *hist = nullptr;      // (vertex tiles, n_sel, 2) records of one iteration; (iterations, n_sel, 2)
     // asb_hyper_iterate: c = A^-1 ms (3 N, ld) vertex-major like Q; the touched rows of Q and c (3 N_t, ld).  (The touched
-    // columns of G^T belong to the banks: ctx->hy_Gc.)
+    // columns of G^T belong to the banks: RfBank::Gc.)
     double *c = nullptr, *Qc = nullptr, *cc = nullptr;
     // the time step: what asb_pdsolve_begin was given (for asb_pdsolve_carry) and what asb_pdsolve_carry made
     bool carry = false;
@@ -253,64 +253,39 @@ extern "C" int asb_pdsolve_slot(asb_ctx* ctx, double sigma_min, double sigma_max
     asb_pds* s = ctx->pds;
     if (!s || !s->begun) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_slot: no solve begun (asb_pdsolve_begin)");
     if (s->n_slots >= PD_MAX_SLOTS) ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_pdsolve_slot: more than %d kinds", PD_MAX_SLOTS);
-    if (ctx->cp_kind < 0 || ctx->cp_verts != s->n || ctx->n_loc != s->n)
+    if (ctx->cp.kind < 0 || ctx->cp.verts != s->n || ctx->n_loc != s->n)
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_slot: no element set-up for the resident tensor (asb_cproj_setup)");
     if (!(sigma_min <= sigma_max)) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_slot: sigma_min %g > sigma_max %g", sigma_min, sigma_max);
-    const long long n_cols = asb_cproj_rows(ctx->cp_kind, ctx->cp_n);
+    const long long n_cols = asb_cproj_rows(ctx->cp.kind, ctx->cp.n);
     PdSlot& p = s->slot[s->n_slots];
     int rc;
     if (reduced) {
+        const asb_ctx::RfBank& b = asb_rf_cur(ctx);
         for (int k = 0; k < s->n_slots; ++k)
             if (s->slot[k].reduced && s->slot[k].bank == ctx->rf_cur)       // (another bank: asb_rforce_bank before the operator)
                 ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_slot: a second reduced kind (the context holds one operator and one solver)");
-        if (ctx->rf_mp < 1 || ctx->rf_r < 1 || ctx->rf_n != s->n)
+        if (b.mp < 1 || b.r < 1 || b.n != s->n)
             ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_slot: no operator or solver for the tensor on the device (asb_rforce_operator, asb_rforce_solver)");
-        if (ctx->rf_pt_max >= n_cols)
-            ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_slot: an interpolation point names row %lld, the sampled elements have %lld", (long long)ctx->rf_pt_max, n_cols);
+        if (b.pt_max >= n_cols)
+            ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_slot: an interpolation point names row %lld, the sampled elements have %lld", (long long)b.pt_max, n_cols);
     } else {
         if (!indptr) return ASB_ERR_ARG;
         if (n_rows != s->n) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_slot: S^T has %lld rows, the tensor %lld vertices", (long long)n_rows, s->n);
         std::vector<int> p32, c32;
         if ((rc = asb_csr_check32(ctx, "asb_pdsolve_slot", n_rows, indptr, indices, data, n_cols, p32, c32))) return rc;
-        const int64_t nnz = indptr[n_rows];
         ASB_HIP(ctx, hipSetDevice(ctx->dev));
         if ((rc = asb_alloc(ctx, &p.st_ptr, p32.size()))) return rc;
         if ((rc = asb_alloc(ctx, &p.st_idx, c32.size() + 1))) return rc;
         if ((rc = asb_alloc(ctx, &p.st_val, c32.size() + 1))) return rc;
-        ASB_HIP(ctx, hipMemcpyAsync(p.st_ptr, p32.data(), p32.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        if (nnz > 0) {
-            ASB_HIP(ctx, hipMemcpyAsync(p.st_idx, c32.data(), c32.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-            ASB_HIP(ctx, hipMemcpyAsync(p.st_val, data, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        }
+        if ((rc = asb_csr_stage(ctx, p32, c32, data, p.st_ptr, p.st_idx, p.st_val))) return rc;
         ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));      // (the staging vectors die here)
     }
-    // the tables of asb_cproj_setup pass to the slot (the slot's previous buffers to the context, which has no set-up now)
-    asb_swap_buf(ctx, &ctx->cp_idx, &p.idx);
-    asb_swap_buf(ctx, &ctx->cp_table, &p.table);
-    asb_swap_buf(ctx, &ctx->cp_sptr, &p.sptr);
-    asb_swap_buf(ctx, &ctx->cp_sidx, &p.sidx);
-    p.kind = ctx->cp_kind, p.n_elem = ctx->cp_n, p.n_cols = n_cols, p.reduced = reduced ? 1 : 0;
-    p.smin = sigma_min, p.smax = sigma_max, p.vmax = ctx->cp_vmax, p.bank = ctx->rf_cur;
-    ctx->cp_kind = -1;
+    // the set-up of asb_cproj_setup passes to the slot (the slot's previous buffers to the context, which has no set-up now)
+    asb_cp_move(ctx, ctx->cp, p.cp);
+    p.n_cols = n_cols, p.reduced = reduced ? 1 : 0;
+    p.smin = sigma_min, p.smax = sigma_max, p.bank = ctx->rf_cur;
     ++s->n_slots;
     return ASB_OK;
-}
-
-// the per-bank buffers of the reduced slots, sized here: coef[k] doubles of coefficients and (optional) gc[k] doubles of
-// gathered columns, each allocated with its bank selected, the bank of the call restored; rv: the slots' views, taken afterwards
-static int pd_bank_alloc(asb_ctx* ctx, const asb_pds* s, const size_t* coef, const size_t* gc, RfView* rv) {
-    const int cur = ctx->rf_cur;
-    int rc = ASB_OK;
-    for (int k = 0; k < s->n_slots && rc == ASB_OK; ++k) {
-        if (!s->slot[k].reduced) continue;
-        asb_rf_select(ctx, s->slot[k].bank);
-        rc = asb_alloc(ctx, &ctx->rf_coef, coef[k]);
-        if (rc == ASB_OK && gc) rc = asb_alloc(ctx, &ctx->hy_Gc, gc[k]);
-    }
-    asb_rf_select(ctx, cur);
-    for (int k = 0; k < s->n_slots; ++k)
-        if (s->slot[k].reduced) rv[k] = asb_rf_view(ctx, s->slot[k].bank);
-    return rc;
 }
 
 extern "C" int asb_pdsolve_iterate(asb_ctx* ctx, int64_t n_iter, int64_t chunk_frames, double* out_dev, double* hist_out) {
@@ -326,16 +301,14 @@ extern "C" int asb_pdsolve_iterate(asb_ctx* ctx, int64_t n_iter, int64_t chunk_f
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_iterate: the history of step norms is not built for the slab factor (asb_gslab_setup)");
     const long long n_sel = s->n_sel, n = s->n;
     long long cw[PD_MAX_SLOTS];
-    size_t scratch = 0, coef[PD_MAX_SLOTS] = {};
-    RfView rv[PD_MAX_SLOTS] = {};
+    size_t scratch = 0;
     for (int k = 0; k < s->n_slots; ++k) {
         const PdSlot& p = s->slot[k];
         if (p.reduced) {
-            rv[k] = asb_rf_view(ctx, p.bank);
-            if (rv[k].mp < 1 || rv[k].r < 1 || rv[k].n != n || rv[k].pt_max >= p.n_cols)
+            const asb_ctx::RfBank& b = ctx->rf_bank[p.bank];
+            if (b.mp < 1 || b.r < 1 || b.n != n || b.pt_max >= p.n_cols)
                 ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_iterate: the operator or solver changed since asb_pdsolve_slot");
-            cw[k] = asb_rforce_chunk_width_r(rv[k].r, p.n_cols, n_sel);
-            coef[k] = (size_t)3 * (((size_t)rv[k].r + 3) / 4 * 4) * cw[k];
+            cw[k] = asb_rforce_chunk_width(b.r, p.n_cols, n_sel);
         } else {
             cw[k] = asb_cforce_chunk_width(p.n_cols, chunk_frames, n_sel);
         }
@@ -345,7 +318,11 @@ extern "C" int asb_pdsolve_iterate(asb_ctx* ctx, int64_t n_iter, int64_t chunk_f
     const int tiles = slab ? 0 : (int)(ctx->gs_Np / GS_TN);
     int rc;
     if ((rc = asb_alloc(ctx, &ctx->cf_scratch, scratch))) return rc;
-    if ((rc = pd_bank_alloc(ctx, s, coef, nullptr, rv))) return rc;
+    for (int k = 0; k < s->n_slots; ++k) {          // the coefficients of one chunk, per reduced slot in its bank
+        if (!s->slot[k].reduced) continue;
+        asb_ctx::RfBank& b = ctx->rf_bank[s->slot[k].bank];
+        if ((rc = asb_alloc(ctx, &b.coef, (size_t)3 * (((size_t)b.r + 3) / 4 * 4) * cw[k]))) return rc;
+    }
     if (hist_out) {
         if ((rc = asb_alloc(ctx, &s->part, (size_t)tiles * n_sel * 2))) return rc;
         if ((rc = asb_alloc(ctx, &s->hist, (size_t)n_iter * n_sel * 2))) return rc;
@@ -357,11 +334,10 @@ extern "C" int asb_pdsolve_iterate(asb_ctx* ctx, int64_t n_iter, int64_t chunk_f
     for (int64_t it = 0; it < n_iter; ++it) {
         for (int k = 0; k < s->n_slots; ++k) {
             const PdSlot& p = s->slot[k];
-            const CpTables t = {p.kind, p.n_elem, p.idx, p.sptr, p.sidx, p.table};
             for (long long c0 = 0; c0 < n_sel; c0 += cw[k]) {
                 const int cn = (int)(c0 + cw[k] < n_sel ? cw[k] : n_sel - c0);
-                asb_cproj_em_launch_t(ctx, t, wq, 0, 1, (int)c0, cn, (int)cw[k], p.smin, p.smax, ctx->cf_scratch);
-                if (p.reduced) asb_rforce_chunk_launch_v(ctx, rv[k], ctx->cf_scratch, (int)cw[k], (int)c0, cn, k > 0, s->b);
+                asb_cproj_em_launch(ctx, p.cp, wq, 0, 1, (int)c0, cn, (int)cw[k], p.smin, p.smax, ctx->cf_scratch);
+                if (p.reduced) asb_rforce_chunk_launch(ctx, ctx->rf_bank[p.bank], ctx->cf_scratch, (int)cw[k], (int)c0, cn, k > 0, s->b);
                 else asb_st_apply_launch(ctx, p.st_ptr, p.st_idx, p.st_val, ctx->cf_scratch, (int)cw[k], (int)c0, cn, n, k > 0, s->b);
             }
         }
@@ -518,8 +494,8 @@ extern "C" int asb_test_pdsolve_state(asb_ctx* ctx, int which, double* out_host,
 // the last iteration expands to all N rows.  No N^2 product is left in the loop.
 //
 //   asb_hyper_operator    k_hy_operator: Gt_d[j][m] = sum_n A^-1[n][m] M_d[n][j], one thread per (m, 8 values of j), n ascending,
-//                         one FMA accumulator per entry, never split.  Stored like rf_M, (3, mpp, Np), zero padding.  Marked
-//                         valid; asb_gstep_setup / asb_gslab_setup clear the mark of every bank, asb_rforce_operator that of
+//                         one FMA accumulator per entry, never split.  Stored in the current bank (RfBank::G) like its M, (3, mpp, Np),
+//                         zero padding.  Marked valid (RfBank::ok); asb_gstep_setup / asb_gslab_setup clear the mark of every bank, asb_rforce_operator that of
 //                         its own, and a stale G is refused.
 //   asb_hyper_iterate     c by ONE launch of k_pdsolve_gemm<false, false> on ms (gs_contract, vertex-major epilogue) into a buffer
 //                         shaped like Q.  touched given: k_hy_gather_rows copies the touched rows of Q and c, k_hy_gather_cols
@@ -657,31 +633,32 @@ __global__ __launch_bounds__(256) void k_hyper_apply(const HySegs segs, long lon
 
 extern "C" int asb_hyper_operator(asb_ctx* ctx) {
     if (!ctx) return ASB_ERR_ARG;
-    ctx->hy_ok = 0;
+    asb_ctx::RfBank& b = asb_rf_cur(ctx);
+    b.ok = 0;
     const long long ns = pd_solver_n(ctx);
     if (ns < 1) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_operator: no inverse on the device (asb_gstep_setup)");
-    if (ctx->rf_mp < 1 || !ctx->rf_M) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_operator: no operator S^T V on the device (asb_rforce_operator)");
-    if (ctx->rf_n != ns || ns != ctx->n_loc)
+    if (b.mp < 1 || !b.M) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_operator: no operator S^T V on the device (asb_rforce_operator)");
+    if (b.n != ns || ns != ctx->n_loc)
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_operator: the inverse has %lld rows, S^T V %lld, the tensor %lld vertices", ns,
-                 (long long)ctx->rf_n, (long long)ctx->n_loc);
-    const long long jb = (ctx->rf_mp + HY_JB - 1) / HY_JB;
-    if (jb > 65535) ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_hyper_operator: %lld basis vectors (at most %d)", (long long)ctx->rf_mp, 65535 * HY_JB);
+                 (long long)b.n, (long long)ctx->n_loc);
+    const long long jb = (b.mp + HY_JB - 1) / HY_JB;
+    if (jb > 65535) ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_hyper_operator: %lld basis vectors (at most %d)", (long long)b.mp, 65535 * HY_JB);
     ASB_HIP(ctx, hipSetDevice(ctx->dev));
-    const size_t len = (size_t)3 * ctx->rf_mpp * ctx->rf_Np;
+    const size_t len = (size_t)3 * b.mpp * b.Np;
     int rc;
-    if ((rc = asb_alloc(ctx, &ctx->hy_G, len))) return rc;
-    ASB_HIP(ctx, hipMemsetAsync(ctx->hy_G, 0, len * sizeof(double), ctx->stream));
-    if (asb_gslab_n(ctx) > 0) {                     // the slab factor: the 3 mpp rows of rf_M are the columns of one sweep
-        if ((rc = asb_gslab_solve_rows(ctx, ctx->rf_M, 3 * ctx->rf_mpp, ctx->rf_Np, ctx->hy_G))) return rc;
+    if ((rc = asb_alloc(ctx, &b.G, len))) return rc;
+    ASB_HIP(ctx, hipMemsetAsync(b.G, 0, len * sizeof(double), ctx->stream));
+    if (asb_gslab_n(ctx) > 0) {                     // the slab factor: the 3 mpp rows of M are the columns of one sweep
+        if ((rc = asb_gslab_solve_rows(ctx, b.M, 3 * b.mpp, b.Np, b.G))) return rc;
         ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->hy_ok = 1;
+        b.ok = 1;
         return ASB_OK;
     }
     hipLaunchKernelGGL(k_hy_operator, dim3((unsigned)((ctx->gs_n + 255) / 256), (unsigned)jb, 3), dim3(256), 0, ctx->stream, ctx->gs_Ainv,
-                       (int)ctx->gs_n, (int)ctx->gs_Np, ctx->rf_M, (long long)ctx->rf_Np, (int)ctx->rf_mp, (int)ctx->rf_mpp, ctx->hy_G);
+                       (int)ctx->gs_n, (int)ctx->gs_Np, b.M, (long long)b.Np, (int)b.mp, (int)b.mpp, b.G);
     ASB_CHECK_LAUNCH(ctx);
     ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->hy_ok = 1;
+    b.ok = 1;
     return ASB_OK;
 }
 
@@ -699,12 +676,12 @@ extern "C" int asb_hyper_iterate(asb_ctx* ctx, int64_t n_iter, int64_t n_touched
     if (pd_solver_n(ctx) != s->n || ctx->n_loc != s->n)
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: the inverse or the tensor changed since asb_pdsolve_begin");
     const int ns = s->n_slots;
-    RfView rv[PD_MAX_SLOTS] = {};
+    asb_ctx::RfBank* bank[PD_MAX_SLOTS] = {};       // the slots' banks, where they live
     for (int k = 0; k < ns; ++k) {
-        rv[k] = asb_rf_view(ctx, s->slot[k].bank);
-        if (rv[k].mp < 1 || rv[k].r < 1 || rv[k].n != s->n || rv[k].pt_max >= s->slot[k].n_cols)
+        bank[k] = &ctx->rf_bank[s->slot[k].bank];
+        if (bank[k]->mp < 1 || bank[k]->r < 1 || bank[k]->n != s->n || bank[k]->pt_max >= s->slot[k].n_cols)
             ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: the operator or solver changed since asb_pdsolve_slot");
-        if (!rv[k].ok || !rv[k].G)
+        if (!bank[k]->ok || !bank[k]->G)
             ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: no operator A^-1 S^T V for the inverse and the basis on the device (asb_hyper_operator "
                                        "after asb_gstep_setup and asb_rforce_operator): a stale one is refused");
     }
@@ -718,27 +695,26 @@ extern "C" int asb_hyper_iterate(asb_ctx* ctx, int64_t n_iter, int64_t n_touched
                 ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: touched[%lld] = %lld: ascending vertices of 0..%lld", t, (long long)touched[t], n - 1);
     }
     for (int k = 0; k < ns; ++k)
-        if (s->slot[k].vmax >= nt)
-            ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: the element set-up names vertex %lld, the iterate has %lld rows", s->slot[k].vmax, nt);
+        if (s->slot[k].cp.vmax >= nt)
+            ASB_FAIL(ctx, ASB_ERR_ARG, "asb_hyper_iterate: the element set-up names vertex %lld, the iterate has %lld rows",
+                     (long long)s->slot[k].cp.vmax, nt);
     // one chunk width for all slots: the smallest of the banks'
     long long cw = 0, cols_max = 0;
     for (int k = 0; k < ns; ++k) {
-        const long long w = asb_rforce_chunk_width_r(rv[k].r, s->slot[k].n_cols, n_sel);
+        const long long w = asb_rforce_chunk_width(bank[k]->r, s->slot[k].n_cols, n_sel);
         cw = k == 0 ? w : std::min(cw, w);
         cols_max = std::max(cols_max, s->slot[k].n_cols);
     }
     if (chunk_frames > 0) cw = std::min<long long>(cw, (chunk_frames + HY_TF - 1) / HY_TF * HY_TF);
     const long long ntp = (nt + HY_TN - 1) / HY_TN * HY_TN;
-    const long long Np = rv[0].Np;                  // (every bank's operator has the n vertices of the solve: one padding)
+    const long long Np = bank[0]->Np;                // (every bank's operator has the n vertices of the solve: one padding)
     ASB_HIP(ctx, hipSetDevice(ctx->dev));
     int rc;
-    size_t coef[PD_MAX_SLOTS] = {}, gc[PD_MAX_SLOTS] = {};
-    for (int k = 0; k < ns; ++k) {
-        coef[k] = (size_t)3 * (((size_t)rv[k].r + 3) / 4 * 4) * cw;
-        gc[k] = (size_t)3 * rv[k].mpp * ntp;
-    }
     if ((rc = asb_alloc(ctx, &ctx->cf_scratch, (size_t)3 * cols_max * cw))) return rc;
-    if ((rc = pd_bank_alloc(ctx, s, coef, compact ? gc : nullptr, rv))) return rc;
+    for (int k = 0; k < ns; ++k) {                  // per bank: the coefficients of one chunk, the touched columns of G^T
+        if ((rc = asb_alloc(ctx, &bank[k]->coef, (size_t)3 * (((size_t)bank[k]->r + 3) / 4 * 4) * cw))) return rc;
+        if (compact && (rc = asb_alloc(ctx, &bank[k]->Gc, (size_t)3 * bank[k]->mpp * ntp))) return rc;
+    }
     if ((rc = asb_alloc(ctx, &s->c, (size_t)3 * n * ld))) return rc;
     ASB_HIP(ctx, hipMemsetAsync(s->c, 0, (size_t)3 * n * ld * sizeof(double), ctx->stream));
     if (asb_gslab_n(ctx) > 0) {                     // c through the slab factor: in -> sweep -> rows
@@ -752,8 +728,8 @@ extern "C" int asb_hyper_iterate(asb_ctx* ctx, int64_t n_iter, int64_t n_touched
     HySegs full = {}, part = {};                    // the segments of the last iteration (all rows) and of the others
     full.n = part.n = ns;
     for (int k = 0; k < ns; ++k) {
-        const int rpp = ((int)rv[k].r + 3) / 4 * 4;
-        full.s[k] = HySeg{rv[k].G, rv[k].coef, (int)rv[k].mpp, rpp};
+        const int rpp = ((int)bank[k]->r + 3) / 4 * 4;
+        full.s[k] = HySeg{bank[k]->G, bank[k]->coef, (int)bank[k]->mpp, rpp};
         part.s[k] = full.s[k];
     }
     long long ldg = Np;
@@ -768,9 +744,9 @@ extern "C" int asb_hyper_iterate(asb_ctx* ctx, int64_t n_iter, int64_t n_touched
         hipLaunchKernelGGL(k_hy_gather_rows, gr, dim3(64), 0, ctx->stream, s->Q, tv.get(), ld, s->Qc);
         hipLaunchKernelGGL(k_hy_gather_rows, gr, dim3(64), 0, ctx->stream, s->c, tv.get(), ld, s->cc);
         for (int k = 0; k < ns; ++k) {              // the columns of G^T per bank
-            hipLaunchKernelGGL(k_hy_gather_cols, dim3((unsigned)(3 * rv[k].mpp), (unsigned)((ntp + 63) / 64)), dim3(64), 0, ctx->stream, rv[k].G, Np,
-                               tv.get(), (int)nt, (int)ntp, rv[k].Gc);
-            part.s[k].Gt = rv[k].Gc;
+            hipLaunchKernelGGL(k_hy_gather_cols, dim3((unsigned)(3 * bank[k]->mpp), (unsigned)((ntp + 63) / 64)), dim3(64), 0, ctx->stream, bank[k]->G, Np,
+                               tv.get(), (int)nt, (int)ntp, bank[k]->Gc);
+            part.s[k].Gt = bank[k]->Gc;
         }
         ASB_CHECK_LAUNCH(ctx);
         ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));      // (the staging vector dies here, before the loop)
@@ -785,9 +761,8 @@ extern "C" int asb_hyper_iterate(asb_ctx* ctx, int64_t n_iter, int64_t n_touched
             // launch writes the new iterate: applying kind by kind would make the Jacobi update a Gauss-Seidel one
             for (int k = 0; k < ns; ++k) {
                 const PdSlot& p = s->slot[k];
-                const CpTables tb = {p.kind, p.n_elem, p.idx, p.sptr, p.sidx, p.table};
-                asb_cproj_em_launch_t(ctx, tb, wq, 0, 1, (int)c0, cn, (int)cw, p.smin, p.smax, ctx->cf_scratch);
-                asb_rforce_coef_launch_v(ctx, rv[k], ctx->cf_scratch, (int)cw, cn);
+                asb_cproj_em_launch(ctx, p.cp, wq, 0, 1, (int)c0, cn, (int)cw, p.smin, p.smax, ctx->cf_scratch);
+                asb_rforce_coef_launch(ctx, *bank[k], ctx->cf_scratch, (int)cw, cn);
             }
             const unsigned gy = (unsigned)((cn + HY_TF - 1) / HY_TF);
             if (!last)

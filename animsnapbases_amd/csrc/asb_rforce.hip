@@ -119,7 +119,8 @@ __global__ __launch_bounds__(256) void k_rforce_gemm(const double* __restrict__ 
 extern "C" int asb_rforce_operator(asb_ctx* ctx, int64_t n_rows, const int64_t* indptr, const int64_t* indices, const double* data,
                                    int64_t v_rows, int64_t mp, const double* V) {
     if (!ctx || !indptr || !V || n_rows < 1) return ASB_ERR_ARG;
-    ctx->rf_mp = 0, ctx->rf_r = 0, ctx->hy_ok = 0;
+    asb_ctx::RfBank& b = asb_rf_cur(ctx);
+    b.mp = 0, b.r = 0, b.ok = 0;                    // this bank's operator, solver and A^-1 S^T V mark; no other bank's
     if (!ctx->X || ctx->v0 != 0 || ctx->n_loc != ctx->N_glob)
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_rforce_operator: no whole tensor on the device (one rank only)");
     if (n_rows != ctx->n_loc)
@@ -132,7 +133,6 @@ extern "C" int asb_rforce_operator(asb_ctx* ctx, int64_t n_rows, const int64_t* 
     std::vector<int> p32, c32;
     int rc;
     if ((rc = asb_csr_check32(ctx, "asb_rforce_operator", n_rows, indptr, indices, data, v_rows, p32, c32))) return rc;
-    const int64_t nnz = indptr[n_rows];
     ASB_HIP(ctx, hipSetDevice(ctx->dev));
     asb_tmp<int> dptr, dci;
     asb_tmp<double> dval, dV;
@@ -140,29 +140,26 @@ extern "C" int asb_rforce_operator(asb_ctx* ctx, int64_t n_rows, const int64_t* 
     if ((rc = dci.alloc(ctx, c32.size() + 1))) return rc;
     if ((rc = dval.alloc(ctx, c32.size() + 1))) return rc;
     if ((rc = dV.alloc(ctx, (size_t)v_rows * mp * 3))) return rc;
-    if ((rc = asb_alloc(ctx, &ctx->rf_M, (size_t)3 * mpp * Np))) return rc;
-    ASB_HIP(ctx, hipMemcpyAsync(dptr.get(), p32.data(), p32.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    if (nnz > 0) {
-        ASB_HIP(ctx, hipMemcpyAsync(dci.get(), c32.data(), c32.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        ASB_HIP(ctx, hipMemcpyAsync(dval.get(), data, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    }
+    if ((rc = asb_alloc(ctx, &b.M, (size_t)3 * mpp * Np))) return rc;
+    if ((rc = asb_csr_stage(ctx, p32, c32, data, dptr.get(), dci.get(), dval.get()))) return rc;
     ASB_HIP(ctx, hipMemcpyAsync(dV.get(), V, (size_t)v_rows * mp * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    ASB_HIP(ctx, hipMemsetAsync(ctx->rf_M, 0, (size_t)3 * mpp * Np * sizeof(double), ctx->stream));
+    ASB_HIP(ctx, hipMemsetAsync(b.M, 0, (size_t)3 * mpp * Np * sizeof(double), ctx->stream));
     const unsigned grid = (unsigned)((n_rows * mp + 255) / 256);
     hipLaunchKernelGGL(k_st_dense, dim3(grid), dim3(256), 0, ctx->stream, dptr.get(), dci.get(), dval.get(), dV.get(), (long long)n_rows,
-                       (int)mp, (int)mpp, Np, ctx->rf_M);
+                       (int)mp, (int)mpp, Np, b.M);
     ASB_CHECK_LAUNCH(ctx);
     ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the staging vectors and the temporaries die here
-    ctx->rf_n = n_rows, ctx->rf_Np = Np, ctx->rf_mp = mp, ctx->rf_mpp = mpp;
+    b.n = n_rows, b.Np = Np, b.mp = mp, b.mpp = mpp;
     return ASB_OK;
 }
 
 extern "C" int asb_rforce_solver(asb_ctx* ctx, int64_t r, int64_t npt, const double* H, const int64_t* rows) {
     if (!ctx || !H || !rows) return ASB_ERR_ARG;
-    ctx->rf_r = 0;
-    if (ctx->rf_mp < 1) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_rforce_solver: no operator on the device (asb_rforce_operator)");
-    if (r < 1 || r > ctx->rf_mp)
-        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_rforce_solver: %lld basis vectors, the operator has %lld", (long long)r, (long long)ctx->rf_mp);
+    asb_ctx::RfBank& b = asb_rf_cur(ctx);
+    b.r = 0;
+    if (b.mp < 1) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_rforce_solver: no operator on the device (asb_rforce_operator)");
+    if (r < 1 || r > b.mp)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_rforce_solver: %lld basis vectors, the operator has %lld", (long long)r, (long long)b.mp);
     if (r > 65532) ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_rforce_solver: %lld basis vectors (at most 65532)", (long long)r);
     if (npt < 1 || npt > 0x7fffffffLL / r) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_rforce_solver: %lld interpolation rows", (long long)npt);
     std::vector<int> r32((size_t)npt);
@@ -175,63 +172,32 @@ extern "C" int asb_rforce_solver(asb_ctx* ctx, int64_t r, int64_t npt, const dou
     }
     ASB_HIP(ctx, hipSetDevice(ctx->dev));
     int rc;
-    if ((rc = asb_alloc(ctx, &ctx->rf_H, (size_t)3 * r * npt))) return rc;
-    if ((rc = asb_alloc(ctx, &ctx->rf_pt, (size_t)npt))) return rc;
-    ASB_HIP(ctx, hipMemcpyAsync(ctx->rf_H, H, (size_t)3 * r * npt * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    ASB_HIP(ctx, hipMemcpyAsync(ctx->rf_pt, r32.data(), (size_t)npt * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = asb_alloc(ctx, &b.H, (size_t)3 * r * npt))) return rc;
+    if ((rc = asb_alloc(ctx, &b.pt, (size_t)npt))) return rc;
+    ASB_HIP(ctx, hipMemcpyAsync(b.H, H, (size_t)3 * r * npt * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    ASB_HIP(ctx, hipMemcpyAsync(b.pt, r32.data(), (size_t)npt * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));          // (the staging vector dies here)
-    ctx->rf_r = r, ctx->rf_npt = npt, ctx->rf_pt_max = mx;
+    b.r = r, b.npt = npt, b.pt_max = mx;
     return ASB_OK;
 }
 
 // ---------------------------------------------------------------- the banks
-// Held per bank: S^T V (rf_M), H and its rows (rf_H, rf_pt), the coefficients of one chunk (rf_coef), A^-1 S^T V with its mark
-// (hy_G, hy_ok) and its touched columns (hy_Gc).  The current bank lives in the context's rf_* / hy_* fields, which every
-// launcher reads; the others rest in ctx->rf_bank, whose entry for the current bank is empty.
-static void rf_exchange(asb_ctx* ctx, asb_ctx::RfBank& b) {
-    asb_swap_buf(ctx, &ctx->rf_M, &b.M);
-    asb_swap_buf(ctx, &ctx->rf_H, &b.H);
-    asb_swap_buf(ctx, &ctx->rf_pt, &b.pt);
-    asb_swap_buf(ctx, &ctx->rf_coef, &b.coef);
-    asb_swap_buf(ctx, &ctx->hy_G, &b.G);
-    asb_swap_buf(ctx, &ctx->hy_Gc, &b.Gc);
-    std::swap(ctx->rf_n, b.n), std::swap(ctx->rf_Np, b.Np), std::swap(ctx->rf_mp, b.mp), std::swap(ctx->rf_mpp, b.mpp);
-    std::swap(ctx->rf_r, b.r), std::swap(ctx->rf_npt, b.npt), std::swap(ctx->rf_pt_max, b.pt_max), std::swap(ctx->hy_ok, b.ok);
-}
-
-void asb_rf_select(asb_ctx* ctx, int bank) {
-    if (bank == ctx->rf_cur) return;
-    rf_exchange(ctx, ctx->rf_bank[ctx->rf_cur]);          // the current set goes to rest; the context holds an empty one
-    rf_exchange(ctx, ctx->rf_bank[bank]);
-    ctx->rf_cur = bank;
-}
-
-RfView asb_rf_view(const asb_ctx* ctx, int bank) {
-    if (bank == ctx->rf_cur)
-        return RfView{ctx->rf_M, ctx->rf_H, ctx->hy_G, ctx->rf_coef, ctx->hy_Gc, ctx->rf_pt, (long long)ctx->rf_n, (long long)ctx->rf_Np,
-                      (long long)ctx->rf_mp, (long long)ctx->rf_mpp, (long long)ctx->rf_r, (long long)ctx->rf_npt, (long long)ctx->rf_pt_max,
-                      ctx->hy_ok};
-    const asb_ctx::RfBank& b = ctx->rf_bank[bank];
-    return RfView{b.M, b.H, b.G, b.coef, b.Gc, b.pt, (long long)b.n, (long long)b.Np, (long long)b.mp, (long long)b.mpp, (long long)b.r,
-                  (long long)b.npt, (long long)b.pt_max, b.ok};
-}
-
+// Held per bank, in ctx->rf_bank[bank] and nowhere else: S^T V (M), H and its rows (H, pt), the coefficients of one chunk
+// (coef), A^-1 S^T V with its mark (G, ok) and its touched columns (Gc).  A selection is the index rf_cur: no buffer and no
+// number moves, a bank that was addressed keeps what it holds whichever bank is current, and one never addressed holds nothing.
 void asb_rf_invalidate_all(asb_ctx* ctx) {
-    ctx->hy_ok = 0;
     for (int k = 0; k < ASB_RFORCE_BANKS; ++k) ctx->rf_bank[k].ok = 0;
 }
 
 extern "C" int asb_rforce_bank(asb_ctx* ctx, int bank) {
     if (!ctx) return ASB_ERR_ARG;
     if (bank < 0 || bank >= ASB_RFORCE_BANKS) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_rforce_bank: bank %d of 0..%d", bank, ASB_RFORCE_BANKS - 1);
-    asb_rf_select(ctx, bank);
+    ctx->rf_cur = bank;
     return ASB_OK;
 }
 
 // whole frame tiles of the product, the scratch (projections + coefficients) within RF_SCRATCH_BYTES
-long long asb_rforce_chunk_width(asb_ctx* ctx, long long n_cols, long long n_sel) { return asb_rforce_chunk_width_r(ctx->rf_r, n_cols, n_sel); }
-
-long long asb_rforce_chunk_width_r(long long r, long long n_cols, long long n_sel) {
+long long asb_rforce_chunk_width(long long r, long long n_cols, long long n_sel) {
     const int rpp = ((int)r + 3) / 4 * 4;
     long long cw = (long long)(RF_SCRATCH_BYTES / (24ull * (unsigned long long)(n_cols + rpp)));
     cw = cw >= RF_TF ? cw / RF_TF * RF_TF : RF_TF;
@@ -239,23 +205,17 @@ long long asb_rforce_chunk_width_r(long long r, long long n_cols, long long n_se
     return cw > span ? span : cw;
 }
 
-void asb_rforce_coef_launch_v(asb_ctx* ctx, const RfView& v, const double* S, int cw, int cn) {
+void asb_rforce_coef_launch(asb_ctx* ctx, const asb_ctx::RfBank& v, const double* S, int cw, int cn) {
     const int r = (int)v.r, rpp = (r + 3) / 4 * 4, npt = (int)v.npt;
     hipLaunchKernelGGL(k_rforce_coef, dim3((unsigned)(cw / 64), (unsigned)rpp, 3), dim3(64), 0, ctx->stream, v.H, v.pt, r, npt, rpp, S, cw, cn,
                        v.coef);
 }
 
-void asb_rforce_chunk_launch_v(asb_ctx* ctx, const RfView& v, const double* S, int cw, int c0, int cn, int accumulate, double* out) {
+void asb_rforce_chunk_launch(asb_ctx* ctx, const asb_ctx::RfBank& v, const double* S, int cw, int c0, int cn, int accumulate, double* out) {
     const int rpp = ((int)v.r + 3) / 4 * 4;
-    asb_rforce_coef_launch_v(ctx, v, S, cw, cn);
-    hipLaunchKernelGGL(k_rforce_gemm, dim3((unsigned)(v.Np / RF_TN), (unsigned)((cn + RF_TF - 1) / RF_TF)), dim3(256), 0, ctx->stream, v.M, v.Np,
-                       (int)v.mpp, v.coef, cw, rpp, c0, cn, v.n, accumulate ? 1 : 0, out);
-}
-
-void asb_rforce_coef_launch(asb_ctx* ctx, const double* S, int cw, int cn) { asb_rforce_coef_launch_v(ctx, asb_rf_view(ctx, ctx->rf_cur), S, cw, cn); }
-
-void asb_rforce_chunk_launch(asb_ctx* ctx, const double* S, int cw, int c0, int cn, int accumulate, double* out) {
-    asb_rforce_chunk_launch_v(ctx, asb_rf_view(ctx, ctx->rf_cur), S, cw, c0, cn, accumulate, out);
+    asb_rforce_coef_launch(ctx, v, S, cw, cn);
+    hipLaunchKernelGGL(k_rforce_gemm, dim3((unsigned)(v.Np / RF_TN), (unsigned)((cn + RF_TF - 1) / RF_TF)), dim3(256), 0, ctx->stream, v.M,
+                       (long long)v.Np, (int)v.mpp, v.coef, cw, rpp, c0, cn, (long long)v.n, accumulate ? 1 : 0, out);
 }
 
 extern "C" int asb_rforce_run(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean, double psf,
@@ -265,21 +225,22 @@ extern "C" int asb_rforce_run(asb_ctx* ctx, int which, int64_t f0, int64_t f1, i
     int64_t n_sel;
     int rc;
     if ((rc = asb_cproj_world(ctx, "asb_rforce_run", which, f0, f1, fj, add_mean, psf, sigma_min, sigma_max, &w, &n_sel))) return rc;
-    if (ctx->rf_mp < 1 || ctx->rf_r < 1) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_rforce_run: no operator or solver on the device (asb_rforce_operator, asb_rforce_solver)");
-    if (ctx->rf_n != ctx->n_loc)
-        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_rforce_run: the operator has %lld rows, the tensor %lld vertices", (long long)ctx->rf_n, (long long)ctx->n_loc);
-    const long long n_cols = asb_cproj_rows(ctx->cp_kind, ctx->cp_n);
-    if (ctx->rf_pt_max >= n_cols)
-        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_rforce_run: an interpolation point names row %lld, the sampled elements have %lld", (long long)ctx->rf_pt_max, n_cols);
-    const int rpp = ((int)ctx->rf_r + 3) / 4 * 4;
-    const long long cw = asb_rforce_chunk_width(ctx, n_cols, n_sel);
+    asb_ctx::RfBank& b = asb_rf_cur(ctx);
+    if (b.mp < 1 || b.r < 1) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_rforce_run: no operator or solver on the device (asb_rforce_operator, asb_rforce_solver)");
+    if (b.n != ctx->n_loc)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_rforce_run: the operator has %lld rows, the tensor %lld vertices", (long long)b.n, (long long)ctx->n_loc);
+    const long long n_cols = asb_cproj_rows(ctx->cp.kind, ctx->cp.n);
+    if (b.pt_max >= n_cols)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_rforce_run: an interpolation point names row %lld, the sampled elements have %lld", (long long)b.pt_max, n_cols);
+    const int rpp = ((int)b.r + 3) / 4 * 4;
+    const long long cw = asb_rforce_chunk_width(b.r, n_cols, n_sel);
     if ((rc = asb_cproj_invm(ctx, inv_massL, &w))) return rc;
     if ((rc = asb_alloc(ctx, &ctx->cf_scratch, (size_t)3 * n_cols * cw))) return rc;
-    if ((rc = asb_alloc(ctx, &ctx->rf_coef, (size_t)3 * rpp * cw))) return rc;
+    if ((rc = asb_alloc(ctx, &b.coef, (size_t)3 * rpp * cw))) return rc;
     for (long long c0 = 0; c0 < n_sel; c0 += cw) {
         const int cn = (int)(c0 + cw < n_sel ? cw : n_sel - c0);
-        asb_cproj_em_launch(ctx, w, (int)f0, (int)fj, (int)c0, cn, (int)cw, sigma_min, sigma_max, ctx->cf_scratch);
-        asb_rforce_chunk_launch(ctx, ctx->cf_scratch, (int)cw, (int)c0, cn, accumulate, out_dev);
+        asb_cproj_em_launch(ctx, ctx->cp, w, (int)f0, (int)fj, (int)c0, cn, (int)cw, sigma_min, sigma_max, ctx->cf_scratch);
+        asb_rforce_chunk_launch(ctx, b, ctx->cf_scratch, (int)cw, (int)c0, cn, accumulate, out_dev);
     }
     ASB_CHECK_LAUNCH(ctx);
     ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the caller owns out_dev and may read it on any stream
