@@ -211,6 +211,8 @@ PROTOTYPES = {
     "asb_test_local_best": (c_int, [ctypes.c_void_p, c_i64, c_dp]),
     "asb_test_pick_records": (c_int, [ctypes.c_void_p, c_i64, c_dp, c_i64]),
     "asb_test_procrustes_rot": (None, [c_dp, c_dp]),
+    "asb_test_cproj_project": (c_int, [c_int, c_dp, c_i64, c_dbl, c_dbl, c_dp]),
+    "asb_test_cproj_project_dev": (c_int, [ctypes.c_void_p, c_int, c_dp, c_i64, c_dbl, c_dbl, c_dp, c_i64]),
     "asb_test_sketch_predict": (c_int, [ctypes.c_void_p, c_dp, c_dp, c_dp, c_i64, c_int, c_int, c_dp, ctypes.POINTER(c_i64),
                                         ctypes.POINTER(c_int)]),
     "asb_test_spd_inverse": (c_int, [ctypes.c_void_p, c_dp, c_i64, c_dp]),

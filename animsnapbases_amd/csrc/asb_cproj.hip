@@ -11,22 +11,17 @@
 // frames stages its p x 3 results in LDS, one row of CP_EB * 3p + 1 doubles per frame (the odd row length spreads the 64 lanes
 // of a column store over all banks), and then writes per frame the block's contiguous run of elements x 3p doubles.
 //
-// SVD: per thread, in registers, one-sided (Hestenes) Jacobi on F itself -- column pairs of A = F V are rotated until
-// orthogonal, the column norms are the singular values, u_i = a_i / sigma_i -- with a fixed bound on the sweeps and an early
-// out.  F^T F is never formed: the closed-form eigen-solve of it squares the condition number and loses sigma_3 below
-// 1e-8 sigma_1.  Every result is a function of F: sum_i g(sigma_i) u_i v_i^T does not depend on the order or signs the sweeps
-// end with.  A (frame, element) is computed by one thread from its own loads only and nothing is accumulated across threads:
-// no atomics, repeated calls and sub-ranges of frames are bit-identical.
+// SVD and "project F": asb_cproj_elem.h (host and device).  A kernel forms F from the world positions and calls
+// cp_project_tri / cp_project_tet on it; every result is a function of F.  A (frame, element) is computed by one thread from
+// its own loads only and nothing is accumulated across threads: no atomics, repeated calls and sub-ranges of frames are
+// bit-identical.
 #include "asb_common.h"
+#include "asb_cproj_elem.h"
 
 #include <vector>
 
 #define CP_EB 16            // elements per block
 #define CP_WAVES 4
-#define CP_SWEEPS 12        // bound on the Jacobi sweeps (3 x 3 converges in 4 - 6)
-#define CP_TOL 4.440892098500626e-16        // columns count as orthogonal at |a_p . a_q| <= CP_TOL |a_p| |a_q|
-
-enum { CP_EDGE = 0, CP_TRI = 1, CP_TET_STRAIN = 2, CP_TET_DEFGRAD = 3, CP_BEND = 4 };
 
 template <int KIND> struct CpShape;
 template <> struct CpShape<CP_EDGE> { static constexpr int NV = 2, P = 1, TW = 1; };
@@ -44,76 +39,6 @@ template <> struct CpShape<CP_BEND> { static constexpr int NV = 1, P = 1, TW = 5
         case CP_TET_DEFGRAD: LAUNCH<CP_TET_DEFGRAD>(__VA_ARGS__); break; \
         default: LAUNCH<CP_BEND>(__VA_ARGS__); break;                    \
     }
-
-// one Jacobi rotation of the columns p, q of A (N rows) and of V (N rows): true when it rotated
-template <int N>
-__device__ __forceinline__ bool cp_rotate(double (&A)[N][N], double (&V)[N][N], int p, int q) {
-    double al = 0.0, be = 0.0, ga = 0.0;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        al = fma(A[i][p], A[i][p], al);
-        be = fma(A[i][q], A[i][q], be);
-        ga = fma(A[i][p], A[i][q], ga);
-    }
-    if (!(fabs(ga) > CP_TOL * sqrt(al * be))) return false;
-    const double zeta = (be - al) / (2.0 * ga);
-    const double t = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-    const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const double ap = A[i][p], aq = A[i][q], vp = V[i][p], vq = V[i][q];
-        A[i][p] = c * ap - s * aq;
-        A[i][q] = s * ap + c * aq;
-        V[i][p] = c * vp - s * vq;
-        V[i][q] = s * vp + c * vq;
-    }
-    return true;
-}
-
-// F V = A with orthogonal columns; sig[i] = |a_i|; A's columns are normalised to u_i.  A column of norm 0 is completed to
-// the unit vector that makes det(U) det(V) = +1 (any choice is a valid SVD there; this one is the non-inverted one).
-__device__ __forceinline__ void cp_svd3(double (&A)[3][3], double (&V)[3][3], double (&sig)[3]) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-    for (int sw = 0; sw < CP_SWEEPS; ++sw) {
-        bool r = cp_rotate<3>(A, V, 0, 1);
-        r |= cp_rotate<3>(A, V, 0, 2);
-        r |= cp_rotate<3>(A, V, 1, 2);
-        if (!r) break;
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        sig[j] = sqrt(A[0][j] * A[0][j] + A[1][j] * A[1][j] + A[2][j] * A[2][j]);
-        if (sig[j] > 0.0) {
-            const double inv = 1.0 / sig[j];
-            A[0][j] *= inv, A[1][j] *= inv, A[2][j] *= inv;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        if (sig[j] > 0.0) continue;
-        const int a = (j + 1) % 3, b = (j + 2) % 3;
-        if (sig[a] > 0.0 && sig[b] > 0.0) {         // u_j = +- u_a x u_b with the sign of det V
-            const double dv = V[0][0] * (V[1][1] * V[2][2] - V[1][2] * V[2][1]) - V[0][1] * (V[1][0] * V[2][2] - V[1][2] * V[2][0]) +
-                              V[0][2] * (V[1][0] * V[2][1] - V[1][1] * V[2][0]);
-            const double sg = dv < 0.0 ? -1.0 : 1.0;
-            A[0][j] = sg * (A[1][a] * A[2][b] - A[2][a] * A[1][b]);
-            A[1][j] = sg * (A[2][a] * A[0][b] - A[0][a] * A[2][b]);
-            A[2][j] = sg * (A[0][a] * A[1][b] - A[1][a] * A[0][b]);
-        } else {                                    // rank <= 1: no direction is preferred, u_j = v_j
-            A[0][j] = V[0][j], A[1][j] = V[1][j], A[2][j] = V[2][j];
-        }
-    }
-}
-
-__device__ __forceinline__ double cp_det3(const double (&M)[3][3]) {
-    return M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) +
-           M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
-}
-
-__device__ __forceinline__ double cp_clip(double s, double lo, double hi) { return fmin(fmax(s, lo), hi); }
 
 // ---------------------------------------------------------------- the five projections: r[3 p] of one (element, frame)
 __device__ __forceinline__ void cp_edge(const CpWorld& w, long long f, const int* __restrict__ ix, const double* __restrict__ tb,
@@ -144,36 +69,12 @@ __device__ __forceinline__ void cp_tri(const CpWorld& w, long long f, const int*
         ds[j][0] = tb[j] * (q2[0] - q1[0]) + tb[2 + j] * (q2[1] - q1[1]) + tb[4 + j] * (q2[2] - q1[2]);
         ds[j][1] = tb[j] * (q3[0] - q1[0]) + tb[2 + j] * (q3[1] - q1[1]) + tb[4 + j] * (q3[2] - q1[2]);
     }
-    double A[2][2], V[2][2] = {{1.0, 0.0}, {0.0, 1.0}};
+    double Fm[2][2], Fh[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) A[i][j] = ds[i][0] * tb[6 + j] + ds[i][1] * tb[8 + j];
-    for (int sw = 0; sw < CP_SWEEPS; ++sw)
-        if (!cp_rotate<2>(A, V, 0, 1)) break;
-    double sg[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        sg[j] = sqrt(A[0][j] * A[0][j] + A[1][j] * A[1][j]);
-        if (sg[j] > 0.0) {
-            const double inv = 1.0 / sg[j];
-            A[0][j] *= inv, A[1][j] *= inv;
-        }
-    }
-    const double dv = V[0][0] * V[1][1] - V[0][1] * V[1][0] < 0.0 ? -1.0 : 1.0;
-    if (!(sg[0] > 0.0) && !(sg[1] > 0.0)) {
-        A[0][0] = V[0][0], A[1][0] = V[1][0], A[0][1] = V[0][1], A[1][1] = V[1][1];
-    } else if (!(sg[1] > 0.0)) {                    // u_1 = the quarter turn of u_0, signed so that det U det V = +1
-        A[0][1] = -dv * A[1][0], A[1][1] = dv * A[0][0];
-    } else if (!(sg[0] > 0.0)) {
-        A[0][0] = dv * A[1][1], A[1][0] = -dv * A[0][1];
-    }
-    const double c0 = cp_clip(sg[0], smin, smax), c1 = cp_clip(sg[1], smin, smax);
-    double Fh[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) Fh[i][j] = c0 * A[i][0] * V[j][0] + c1 * A[i][1] * V[j][1];
+        for (int j = 0; j < 2; ++j) Fm[i][j] = ds[i][0] * tb[6 + j] + ds[i][1] * tb[8 + j];
+    cp_project_tri(Fm, smin, smax, Fh);
     // pi = (P Fhat)^T: row a, column c = sum_b P[c][b] Fhat[b][a]
 #pragma unroll
     for (int a = 0; a < 2; ++a)
@@ -187,42 +88,13 @@ __device__ __forceinline__ void cp_tet(const CpWorld& w, long long f, const int*
     double q[4][3];
 #pragma unroll
     for (int i = 0; i < 4; ++i) cp_pos(w, f, ix[i], q[i]);
-    double A[3][3], V[3][3], sg[3], Fm[3][3];
+    double Fm[3][3];
     // F = [q1 - q4, q2 - q4, q3 - q4] DmInv
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            A[i][j] = (q[0][i] - q[3][i]) * tb[j] + (q[1][i] - q[3][i]) * tb[3 + j] + (q[2][i] - q[3][i]) * tb[6 + j];
-            Fm[i][j] = A[i][j];
-        }
-    cp_svd3(A, V, sg);
-    if (KIND == CP_TET_STRAIN) {
-        const bool inverted = cp_det3(Fm) < 0.0;                    // (:550-551): the SMALLEST singular value changes sign
-        int lo = sg[1] < sg[0] ? 1 : 0;
-        if (sg[2] <= sg[lo]) lo = 2;
-        double c[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            c[j] = cp_clip(sg[j], smin, smax);
-            if (inverted && j == lo) c[j] = -c[j];
-        }
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) r[3 * i + j] = c[0] * A[i][0] * V[j][0] + c[1] * A[i][1] * V[j][1] + c[2] * A[i][2] * V[j][2];
-    } else {
-        double R[3][3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) R[i][j] = A[i][0] * V[j][0] + A[i][1] * V[j][1] + A[i][2] * V[j][2];
-        if (cp_det3(R) < 0.0) R[0][2] = -R[0][2], R[1][2] = -R[1][2], R[2][2] = -R[2][2];      // (:684-685): third COLUMN of R
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) r[3 * i + j] = R[j][i];                                  // (:687) R^T
-    }
+        for (int j = 0; j < 3; ++j) Fm[i][j] = (q[0][i] - q[3][i]) * tb[j] + (q[1][i] - q[3][i]) * tb[3 + j] + (q[2][i] - q[3][i]) * tb[6 + j];
+    cp_project_tet<KIND>(Fm, smin, smax, r);
 }
 
 __device__ __forceinline__ void cp_bend(const CpWorld& w, long long f, int v, const double* __restrict__ tb, const int* __restrict__ nb,
@@ -587,4 +459,57 @@ extern "C" int asb_cforce_run(asb_ctx* ctx, int which, int64_t f0, int64_t f1, i
     ASB_CHECK_LAUNCH(ctx);
     ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the staging vectors die here; the caller owns out_dev
     return ASB_OK;
+}
+
+// ---------------------------------------------------------------- test hooks: "project F" alone (tests/cproj_cases.py)
+// m: one stored F row-major (tris_strain 2 x 2, the tet kinds 3 x 3) -> o: Fhat (2 x 2), U diag(c) V^T or R^T (3 x 3), row-major
+__host__ __device__ static inline void cp_project_one(int kind, const double* m, double smin, double smax, double* o) {
+    if (kind == CP_TRI) {
+        const double F[2][2] = {{m[0], m[1]}, {m[2], m[3]}};
+        double Fh[2][2];
+        cp_project_tri(F, smin, smax, Fh);
+        o[0] = Fh[0][0], o[1] = Fh[0][1], o[2] = Fh[1][0], o[3] = Fh[1][1];
+        return;
+    }
+    const double F[3][3] = {{m[0], m[1], m[2]}, {m[3], m[4], m[5]}, {m[6], m[7], m[8]}};
+    double r[9];
+    if (kind == CP_TET_STRAIN) cp_project_tet<CP_TET_STRAIN>(F, smin, smax, r);
+    else cp_project_tet<CP_TET_DEFGRAD>(F, smin, smax, r);
+    for (int k = 0; k < 9; ++k) o[k] = r[k];
+}
+
+static int cp_probe_width(int kind) { return kind == CP_TRI ? 4 : (kind == CP_TET_STRAIN || kind == CP_TET_DEFGRAD ? 9 : 0); }
+
+extern "C" int asb_test_cproj_project(int kind, const double* mats, int64_t n, double sigma_min, double sigma_max, double* out) {
+    const int w = cp_probe_width(kind);
+    if (!w || !mats || !out || n < 1 || !(sigma_min <= sigma_max)) return ASB_ERR_ARG;
+    for (int64_t i = 0; i < n; ++i) cp_project_one(kind, mats + i * w, sigma_min, sigma_max, out + i * w);
+    return ASB_OK;
+}
+
+// one thread per matrix, no context state
+static __global__ __launch_bounds__(64) void k_test_cproj_project(int kind, int w, const double* __restrict__ mats, long long n, double smin,
+                                                                  double smax, double* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    cp_project_one(kind, mats + i * w, smin, smax, out + i * w);
+}
+
+extern "C" int asb_test_cproj_project_dev(asb_ctx* ctx, int kind, const double* mats, int64_t n, double sigma_min, double sigma_max,
+                                          double* out, int64_t out_len) {
+    if (!ctx || !mats || !out) return ASB_ERR_ARG;
+    const int w = cp_probe_width(kind);
+    if (!w || n < 1 || n > (1 << 24) || out_len < w * n || !(sigma_min <= sigma_max))
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_cproj_project_dev: kind %d, n = %lld, out_len = %lld, clamp [%g, %g]", kind, (long long)n,
+                 (long long)out_len, sigma_min, sigma_max);
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    asb_tmp<double> dm, dout;
+    int rc = asb_test_stage(ctx, mats, (size_t)n * w, 64, dm);
+    if (!rc) rc = asb_test_stage(ctx, out, (size_t)out_len, 0, dout);
+    if (!rc) {
+        hipLaunchKernelGGL(k_test_cproj_project, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, kind, w, dm.get(), (long long)n,
+                           sigma_min, sigma_max, dout.get());
+        if (hipGetLastError() != hipSuccess) rc = ASB_ERR_HIP;
+    }
+    return asb_test_finish(ctx, rc, dout.get(), out, (size_t)out_len);
 }

@@ -1047,6 +1047,17 @@ class HipEngine(object):
         assert (out[4 * n:] == -7.25).all(), "asb_test_eig3_dev wrote behind its result"
         return out[:4 * n].reshape(n, 4)
 
+    def test_cproj_project_dev(self, kind, mats, sigma_min, sigma_max, slack=8):
+        """"Project F" of one element kind (projections.KINDS code 1, 2 or 3) on the device, one thread per matrix: mats (n, 2, 2)
+        or (n, 3, 3) -> the n projections of the same shape; `slack` doubles behind the result are asserted untouched."""
+        mats = np.ascontiguousarray(mats, dtype=np.float64)
+        n, w = mats.shape[0], mats[0].size
+        out = np.full(w * n + slack, -7.25)
+        self._ck(self.lib.asb_test_cproj_project_dev(self.h, int(kind), ptr(mats), n, float(sigma_min), float(sigma_max), ptr(out),
+                                                     out.size))
+        assert (out[w * n:] == -7.25).all(), "asb_test_cproj_project_dev wrote behind its result"
+        return out[:w * n].reshape(mats.shape)
+
     def test_deflate_step(self, k, w, wn2, s_loc=None):
         w = np.ascontiguousarray(w, dtype=np.float64)
         assert w.shape == (self.F,)

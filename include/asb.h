@@ -844,6 +844,15 @@ int asb_test_pick_records(asb_ctx* ctx, int64_t k, const double* recs, int64_t n
 /* The 3x3 rotation solve of asb_align_frames (procrustes_rot, csrc/asb_kernels.h), run on the HOST: m9 = the cross-covariance M
  * row-major, out9 = R row-major (tests/test_procrustes_rot_cpu.py). */
 void asb_test_procrustes_rot(const double* m9, double* out9);
+/* "Project F" of the constraint projections (cp_project_tri / cp_project_tet, csrc/asb_cproj_elem.h) on its own: n stored
+ * deformation gradients, row-major -- kind 1 (tris_strain) 2 x 2 -> Fhat 2 x 2; kind 2 (tets_strain) 3 x 3 -> U diag(c) V^T;
+ * kind 3 (tets_deformation_gradient) 3 x 3 -> R^T, as the kernels store it -- with the clamp [sigma_min, sigma_max].
+ * asb_test_cproj_project runs on the HOST; asb_test_cproj_project_dev on the device, one thread per matrix, no context state;
+ * all of out (out_len >= n x the kind's width) round-trips, so a write behind the result shows
+ * (tests/test_cproj_model_cpu.py, tests/test_gpu_cproj_edges.py). */
+int asb_test_cproj_project(int kind, const double* mats, int64_t n, double sigma_min, double sigma_max, double* out);
+int asb_test_cproj_project_dev(asb_ctx* ctx, int kind, const double* mats, int64_t n, double sigma_min, double sigma_max, double* out,
+                               int64_t out_len);
 /* tests: the sketch replay on host arrays -- cols (r x 3 n: column i, entry 3 v + d, the coefficient of vertex v's row d on the
  * unit direction i divided by sqrt(wn2[i])), wn2 (r), exact energies E (n) -> scores (n; max over the steps of energy / winner's
  * energy), the replay's winners pred (steps; -1 behind its end), *status = 1 (0: the exchange timed out, scores = energies) */

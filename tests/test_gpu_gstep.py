@@ -70,6 +70,7 @@ def test_product_kernel_against_longdouble(N):
         rhs = rng.standard_normal((F, N, 3)) * 10.0 ** rng.integers(-3, 4, size=(F, N, 1))
         dev = torch.from_numpy(rhs).to("cuda:%d" % eng.device_id)
         out = torch.full_like(dev, float("nan"))
+        torch.cuda.synchronize()                    # the fill is on torch's stream, the product on the engine's own
         eng.gstep_run(dev.data_ptr(), F, out.data_ptr())
         torch.cuda.synchronize()
         got = out.cpu().numpy()
