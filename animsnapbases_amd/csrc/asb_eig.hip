@@ -15,6 +15,7 @@
 // v_j is kept in row j of A (columns j+1..n-1), which the trailing block no longer touches.
 #include "asb_common.h"
 
+#include <cfloat>
 #include <cstdlib>
 
 #define TD_T 1024
@@ -620,7 +621,9 @@ __global__ __launch_bounds__(256) void k_td_back(const double* __restrict__ A, c
     const int col = blockIdx.x * wpb + wv;
     if (wv >= wpb || col >= k) return;
     double* z = zsh + (size_t)wv * n;
-    for (int r = lane; r < n; r += 64) z[r] = Z[(long long)r * k + col];
+    double nin = 0.0;
+    for (int r = lane; r < n; r += 64) { const double x = Z[(long long)r * k + col]; z[r] = x; nin += x * x; }
+    nin = wave_sum(nin);
     for (int j = n - 3; j >= 0; --j) {
         const double t = tau[j];
         if (t == 0.0) continue;
@@ -632,7 +635,13 @@ __global__ __launch_bounds__(256) void k_td_back(const double* __restrict__ A, c
         const double s = t * wave_sum(acc);
         for (int r = rs; r < n; r += 64) z[r] -= s * v[r];
     }
-    for (int r = lane; r < n; r += 64) V[(long long)r * k + col] = z[r];
+    // Q is orthogonal: |Q z| = |z|.  The stored tau_j and v_j are each rounded, so every reflector is off a unit norm by about
+    // a fraction of eps and a column drifts like a random walk over the n - 2 of them; the length it came with is put back.
+    double nout = 0.0;
+    for (int r = lane; r < n; r += 64) nout += z[r] * z[r];
+    nout = wave_sum(nout);
+    const double f = (nout > 0.0 && nout < DBL_MAX && nin > 0.0 && nin < DBL_MAX) ? sqrt(nin / nout) : 1.0;
+    for (int r = lane; r < n; r += 64) V[(long long)r * k + col] = z[r] * f;
 }
 
 // A <- (A + A^T) / 2: the Gram tiles above and below the diagonal come from different MFMA tiles

@@ -65,12 +65,74 @@ __global__ __launch_bounds__(256) void k_tri_prepare(const double* __restrict__ 
     }
 }
 
+// Blocks of a SPLIT matrix: |e[j]| <= 2 eps |T| (|T| = TRI_BNORM; the zero matrix: e[j] == 0) ends a block behind row j -- exact
+// zeros (a Gram matrix of two disjoint vertex sets) and entries that an eigenvalue of multiplicity > 1 leaves at rounding level.
+// Dropping them moves no eigenvalue by more than 4 eps |T|.  bstart[b] .. bstart[b + 1] - 1 are the rows of block b
+// (bstart[nblk] = n, nblk in bstart[n + 1]), blk_of[j] the block of row j.  Eigenvalue slot i (0 .. n - 1) stands for the
+// (i - bstart[b])-th smallest eigenvalue of block b = blk_of[i]: every eigenvalue belongs to one block, and its vector is
+// iterated on that block alone (k_tri_invit).  One block: slot i is the i-th smallest eigenvalue of T, as before.
+// last[b] = -1: no shift handed out in block b yet (k_tri_shifts).
+#define ASB_TRI_SPLIT 2.0
+__global__ __launch_bounds__(256) void k_tri_blocks(const double* __restrict__ e, int n, const double* __restrict__ sc,
+                                                    int* __restrict__ blk_of, int* __restrict__ bstart, int* __restrict__ last,
+                                                    int* __restrict__ next) {
+    __shared__ int s_cnt[256];
+    const int t = threadIdx.x, per = (n + 255) / 256;
+    const int j0 = min(t * per, n), j1 = min(j0 + per, n);
+    const double thr = ASB_TRI_SPLIT * ASB_EPS * sc[TRI_BNORM];
+    int c = 0;
+    for (int j = j0; j < j1; ++j) c += (j > 0 && fabs(e[j - 1]) <= thr) ? 1 : 0;      // blocks that START at row j > 0
+    s_cnt[t] = c;
+    __syncthreads();
+    if (t == 0) {
+        int run = 0;
+        for (int q = 0; q < 256; ++q) { const int x = s_cnt[q]; s_cnt[q] = run; run += x; }
+        bstart[0] = 0;
+        bstart[run + 1] = n;
+        bstart[n + 1] = run + 1;
+    }
+    __syncthreads();
+    int b = s_cnt[t];
+    for (int j = j0; j < j1; ++j) {
+        if (j > 0 && fabs(e[j - 1]) <= thr) bstart[++b] = j;
+        blk_of[j] = b;
+        last[j] = -1;
+        next[j] = -1;
+    }
+}
+
+// Eigenvalue slots of a split matrix -> descending order: slot i goes to position #{j : val[j] > val[i], or equal and j > i}
+// (a rank sort: deterministic, no atomics), own[position] = i.  One block: k_tri_multisect / k_tri_bisect have written
+// lam_desc themselves, own[n - 1 - i] = i.
+__global__ __launch_bounds__(64) void k_tri_order(const double* __restrict__ val, int n, const int* __restrict__ bstart,
+                                                  double* __restrict__ lam_desc, int* __restrict__ own) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    if (bstart[n + 1] == 1) { own[n - 1 - i] = i; return; }
+    const double x = val[i];
+    int r = 0;
+    for (int j = 0; j < n; ++j) {
+        const double y = val[j];
+        r += (y > x || (y == x && j > i)) ? 1 : 0;
+    }
+    lam_desc[r] = x;
+    own[r] = i;
+}
+
 // Multi-section (round 3): one WAVE per eigenvalue, its 64 lanes count at 64 interior points of the bracket at once, so a
 // round narrows it 65-fold: 9-10 rounds of the sequential Sturm recurrence instead of ~53, on 64 times as many waves (one
 // thread per eigenvalue left the GPU at 63 waves: 23 ms at n = 4000).  Same counts, same pivmin guard, same tolerance.
 __global__ __launch_bounds__(64) void k_tri_multisect(const double* __restrict__ d, const double* __restrict__ e2, int n,
-                                                      const double* __restrict__ sc, double* __restrict__ lam_desc) {
-    const int i = blockIdx.x, lane = threadIdx.x;
+                                                      const double* __restrict__ sc, const int* __restrict__ blk_of,
+                                                      const int* __restrict__ bstart, double* __restrict__ val,
+                                                      double* __restrict__ lam_desc) {
+    const int slot = blockIdx.x, lane = threadIdx.x;
+    const int s0 = bstart[blk_of[slot]], s1 = bstart[blk_of[slot] + 1], i = slot - s0;
+    double* out = bstart[n + 1] == 1 ? lam_desc + (n - 1 - slot) : val + slot;
+    if (s1 - s0 == 1) {                    // a block of order 1: its eigenvalue is d, exactly
+        if (lane == 0) *out = d[s0];
+        return;
+    }
     const double pivmin = sc[TRI_PIVMIN], atol = sc[TRI_ATOL];
     double lo = sc[TRI_GL], hi = sc[TRI_GU];
     for (int it = 0; it < 400; ++it) {
@@ -79,10 +141,10 @@ __global__ __launch_bounds__(64) void k_tri_multisect(const double* __restrict__
         double x = lo + h * (double)(lane + 1);
         if (!(x > lo)) x = lo;                      // (bracket at rounding level: the points collapse onto its ends)
         if (!(x < hi)) x = hi;
-        double q = d[0] - x;
+        double q = d[s0] - x;
         if (fabs(q) < pivmin) q = -pivmin;
         int cnt = q < 0.0 ? 1 : 0;
-        for (int j = 1; j < n; ++j) {
+        for (int j = s0 + 1; j < s1; ++j) {
             q = d[j] - x - e2[j - 1] / q;
             if (fabs(q) < pivmin) q = -pivmin;
             cnt += q < 0.0 ? 1 : 0;
@@ -102,24 +164,29 @@ __global__ __launch_bounds__(64) void k_tri_multisect(const double* __restrict__
         lo = nlo;
         hi = nhi;
     }
-    if (lane == 0) lam_desc[n - 1 - i] = 0.5 * (lo + hi);
+    if (lane == 0) *out = 0.5 * (lo + hi);
 }
 
 // thread i -> the (i+1)-th smallest eigenvalue by bisection; count(x) = #{eigenvalues < x} from the signs of the
 // Sturm sequence q_0 = d_0 - x, q_j = d_j - x - e_{j-1}^2 / q_{j-1}.  Written in DESCENDING order.
 __global__ __launch_bounds__(64) void k_tri_bisect(const double* __restrict__ d, const double* __restrict__ e2, int n,
-                                                   const double* __restrict__ sc, double* __restrict__ lam_desc) {
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
+                                                   const double* __restrict__ sc, const int* __restrict__ blk_of,
+                                                   const int* __restrict__ bstart, double* __restrict__ val,
+                                                   double* __restrict__ lam_desc) {
+    const int slot = blockIdx.x * 64 + threadIdx.x;
+    if (slot >= n) return;
+    const int s0 = bstart[blk_of[slot]], s1 = bstart[blk_of[slot] + 1], i = slot - s0;
+    double* out = bstart[n + 1] == 1 ? lam_desc + (n - 1 - slot) : val + slot;
+    if (s1 - s0 == 1) { *out = d[s0]; return; }
     const double pivmin = sc[TRI_PIVMIN], atol = sc[TRI_ATOL];
     double lo = sc[TRI_GL], hi = sc[TRI_GU];
     for (int it = 0; it < 1200; ++it) {
         const double mid = 0.5 * (lo + hi);
         if (!(mid > lo && mid < hi)) break;
-        double q = d[0] - mid;
+        double q = d[s0] - mid;
         if (fabs(q) < pivmin) q = -pivmin;
         int cnt = q < 0.0 ? 1 : 0;
-        for (int j = 1; j < n; ++j) {
+        for (int j = s0 + 1; j < s1; ++j) {
             q = d[j] - mid - e2[j - 1] / q;
             if (fabs(q) < pivmin) q = -pivmin;
             cnt += q < 0.0 ? 1 : 0;
@@ -127,18 +194,25 @@ __global__ __launch_bounds__(64) void k_tri_bisect(const double* __restrict__ d,
         if (cnt > i) hi = mid; else lo = mid;
         if (hi - lo <= atol + 2.0 * ASB_EPS * fmax(fabs(lo), fabs(hi))) break;
     }
-    lam_desc[n - 1 - i] = 0.5 * (lo + hi);
+    *out = 0.5 * (lo + hi);
 }
 
 // shifts of the inverse iteration: the k leading eigenvalues, pushed apart where two of them coincide to rounding
-// (identical shifts would give identical vectors)
-__global__ void k_tri_shifts(const double* __restrict__ lam_desc, int k, const double* __restrict__ sc, double* __restrict__ sh) {
+// (identical shifts would give identical vectors) -- within ONE block of a split matrix only: vectors of different blocks
+// have disjoint supports, and a shift moved off its own block's eigenvalue by another block's would only slow it down.
+// last[b]: the latest of the k leading positions that belongs to block b (-1: none yet).  next[p] = j: position j was pushed off
+// position p -- the chain p, next[p], next[next[p]], .. is one CLUSTER of the block (k_tri_reorth); -1: the chain ends.
+__global__ void k_tri_shifts(const double* __restrict__ lam_desc, int k, const double* __restrict__ sc, const int* __restrict__ own,
+                             const int* __restrict__ blk_of, int* __restrict__ last, int* __restrict__ next, double* __restrict__ sh) {
     if (threadIdx.x || blockIdx.x) return;
     const double floor_ = 1e-3 * ASB_EPS * sc[TRI_BNORM];
-    sh[0] = lam_desc[0];
-    for (int j = 1; j < k; ++j) {
+    for (int j = 0; j < k; ++j) {
+        const int b = blk_of[own[j]], p = last[b];
         const double pert = 10.0 * ASB_EPS * fabs(lam_desc[j]) + floor_;
-        sh[j] = (sh[j - 1] - lam_desc[j] < pert) ? sh[j - 1] - pert : lam_desc[j];
+        const bool push = p >= 0 && sh[p] - lam_desc[j] < pert;
+        sh[j] = push ? sh[p] - pert : lam_desc[j];
+        if (push) next[p] = j;
+        last[b] = j;
     }
 }
 
@@ -151,9 +225,10 @@ __global__ void k_tri_shifts(const double* __restrict__ lam_desc, int k, const d
 // caller only needs the SPAN of the vectors (Rayleigh-Ritz on the snapshot matrix follows) -- see DESIGN.md.
 // All per-vector arrays are interleaved: element i of vector v at [i * k + v].
 __global__ __launch_bounds__(64) void k_tri_invit(const double* __restrict__ d, const double* __restrict__ e, int n, int k,
-                                                  const double* __restrict__ shifts, const double* __restrict__ sc,
-                                                  double* __restrict__ work, unsigned char* __restrict__ swp,
-                                                  double* __restrict__ Z, int* __restrict__ status) {
+                                                  const double* __restrict__ shifts, const double* __restrict__ lam_desc,
+                                                  const double* __restrict__ sc, const int* __restrict__ own, const int* __restrict__ blk_of,
+                                                  const int* __restrict__ bstart, double* __restrict__ work,
+                                                  unsigned char* __restrict__ swp, double* __restrict__ Z, int* __restrict__ status) {
     const int v = blockIdx.x * 64 + threadIdx.x;
     if (v >= k) return;
     const size_t nk = (size_t)n * k;
@@ -163,18 +238,23 @@ __global__ __launch_bounds__(64) void k_tri_invit(const double* __restrict__ d, 
     double* rv4 = rv3 + nk;
     double* rv6 = Z + v;
     unsigned char* sw = swp + v;
+    // the block of T that owns this eigenvalue: rows s0 .. s1 - 1, order m; the vector is zero outside it
+    const int blk = blk_of[own[v]];
+    const int s0 = bstart[blk], s1 = bstart[blk + 1], m = s1 - s0;
+    for (int i = 0; i < s0; ++i) rv6[(size_t)i * k] = 0.0;
+    for (int i = s1; i < n; ++i) rv6[(size_t)i * k] = 0.0;
     const double x1 = shifts[v];
     const double norm = sc[TRI_BNORM];
     const double eps3 = ASB_EPS * (norm > 0.0 ? norm : 1.0);
-    const double eps4 = (double)n * eps3;
-    const double uk = eps4 / sqrt((double)n);
-    if (n == 1) { rv6[0] = 1.0; return; }
-    double u = d[0] - x1, vv = e[0];
-    for (int i = 1; i < n; ++i) {
+    const double eps4 = (double)m * eps3;
+    const double uk = eps4 / sqrt((double)m);
+    if (m == 1) { rv6[(size_t)s0 * k] = 1.0; return; }
+    double u = d[s0] - x1, vv = e[s0];
+    for (int i = s0 + 1; i < s1; ++i) {
         const double ei = e[i - 1];
-        const double enext = (i < n - 1) ? e[i] : 0.0;
+        const double enext = (i < s1 - 1) ? e[i] : 0.0;
         const size_t a = (size_t)(i - 1) * k, b = (size_t)i * k;
-        if (fabs(ei) >= fabs(u) && ei != 0.0) {      // interchange rows i-1 and i
+        if (fabs(ei) >= fabs(u)) {                   // interchange rows i-1 and i (|ei| > 2 eps |T| inside a block)
             const double xu = u / ei;
             rv4[b] = xu;
             rv1[a] = ei;
@@ -185,7 +265,6 @@ __global__ __launch_bounds__(64) void k_tri_invit(const double* __restrict__ d, 
             vv = -xu * enext;
             sw[b] = 1;
         } else {
-            if (u == 0.0) u = eps3;             // (only with e[i-1] == 0: the matrix splits here)
             const double xu = ei / u;
             rv4[b] = xu;
             rv1[a] = u;
@@ -198,15 +277,30 @@ __global__ __launch_bounds__(64) void k_tri_invit(const double* __restrict__ d, 
     }
     if (u == 0.0) u = eps3;
     {
-        const size_t a = (size_t)(n - 1) * k;
+        const size_t a = (size_t)(s1 - 1) * k;
         rv1[a] = u; rv2[a] = 0.0; rv3[a] = 0.0;
     }
-    for (int i = 0; i < n; ++i) rv6[(size_t)i * k] = uk;
+    // A shift that k_tri_shifts has pushed off its eigenvalue belongs to a value the block holds more than once to rounding:
+    // from the constant start every vector of such a cluster is the same projection onto its eigenspace.  These vectors
+    // start from a direction of their own instead (entries in [-1, 1) from a hash of (vector, row): deterministic), as
+    // LAPACK's dstein starts from random ones.  |shift - lambda| = dlt also bounds the growth of one solve by about
+    // eps4 / dlt, so the criterion nrm >= 1 is lowered to a tenth of that where it cannot be met.
+    const double dlt = fabs(lam_desc[v] - x1);
+    const double grow = (10.0 * dlt > eps4) ? 0.1 * eps4 / dlt : 1.0;
+    if (dlt == 0.0) {
+        for (int i = s0; i < s1; ++i) rv6[(size_t)i * k] = uk;
+    } else {
+        for (int i = s0; i < s1; ++i) {
+            unsigned h = (unsigned)(i - s0) * 2654435761u + (unsigned)v * 2246822519u + 374761393u;
+            h ^= h >> 15; h *= 2246822519u; h ^= h >> 13; h *= 3266489917u; h ^= h >> 16;
+            rv6[(size_t)i * k] = uk * ((double)(h >> 8) * (1.0 / 8388608.0) - 1.0);
+        }
+    }
     bool ok = false;
     int extra = 0;
     for (int its = 0; its < 6 + ASB_TRI_EXTRA; ++its) {
         double bu = 0.0, bv = 0.0, nrm = 0.0;
-        for (int i = n - 1; i >= 0; --i) {      // back substitution with U
+        for (int i = s1 - 1; i >= s0; --i) {    // back substitution with U
             const size_t a = (size_t)i * k;
             const double x = (rv6[a] - bu * rv2[a] - bv * rv3[a]) / rv1[a];
             rv6[a] = x;
@@ -215,20 +309,20 @@ __global__ __launch_bounds__(64) void k_tri_invit(const double* __restrict__ d, 
             nrm += fabs(x);
         }
         if (ok && !(nrm < DBL_MAX)) break;      // (an extra step overflowed: flagged below)
-        if (nrm >= 1.0) {
+        if (nrm >= grow) {
             ok = true;
             if (extra++ == ASB_TRI_EXTRA) break;
         } else if (ok || its >= 5) {
             break;
         }
         if (nrm == 0.0 || !(nrm == nrm)) {      // exactly orthogonal start (or overflow): a unit vector instead
-            for (int i = 0; i < n; ++i) rv6[(size_t)i * k] = 0.0;
-            rv6[(size_t)(its % n) * k] = eps4;
+            for (int i = s0; i < s1; ++i) rv6[(size_t)i * k] = 0.0;
+            rv6[(size_t)(s0 + its % m) * k] = eps4;
         } else {
             const double s = eps4 / nrm;
-            for (int i = 0; i < n; ++i) rv6[(size_t)i * k] *= s;
+            for (int i = s0; i < s1; ++i) rv6[(size_t)i * k] *= s;
         }
-        for (int i = 1; i < n; ++i) {           // forward elimination of the right-hand side with L (and the interchanges)
+        for (int i = s0 + 1; i < s1; ++i) {     // forward elimination of the right-hand side with L (and the interchanges)
             const size_t a = (size_t)(i - 1) * k, b = (size_t)i * k;
             double t = rv6[b];
             if (sw[b]) {
@@ -239,10 +333,99 @@ __global__ __launch_bounds__(64) void k_tri_invit(const double* __restrict__ d, 
         }
     }
     double s2 = 0.0;
-    for (int i = 0; i < n; ++i) { const double x = rv6[(size_t)i * k]; s2 += x * x; }
+    for (int i = s0; i < s1; ++i) { const double x = rv6[(size_t)i * k]; s2 += x * x; }
     if (!ok || !(s2 > 0.0) || !(s2 < DBL_MAX)) atomicAdd(status, 1);
     const double inv = (s2 > 0.0 && s2 < DBL_MAX) ? 1.0 / sqrt(s2) : 0.0;
-    for (int i = 0; i < n; ++i) rv6[(size_t)i * k] *= inv;
+    for (int i = s0; i < s1; ++i) rv6[(size_t)i * k] *= inv;
+}
+
+// Re-orthogonalisation inside a cluster (a chain of pushed shifts, k_tri_shifts): its vectors lie in one eigenspace, each from a
+// start direction of its own, and as a set they can be badly conditioned (a square pseudo-random coefficient matrix: cond 1e3 on a
+// plateau of eight), which costs the SPAN eps cond.  One wave per cluster, members in order, as LAPACK's dstein does inside its
+// iteration: a CANDIDATE (column v0 of `cand`) = the member, modified Gram-Schmidt against the members before, one more solve with
+// the member's own factors (k_tri_invit has left them in `work` / `swp`; the recurrences run on lane 0), Gram-Schmidt again, unit
+// norm.  The candidate replaces the member only if its residual |T z - lambda z| is no worse than four times the member's (or
+// eps |T|): where the values of a chain are NOT one eigenspace (glued blocks, eigenvalues apart by less than the shifts) the
+// orthogonal complement holds nothing to iterate on, and the vector of k_tri_invit stays.  The first member and every vector
+// outside a cluster stay as k_tri_invit wrote them.
+__device__ __forceinline__ double tri_residual2(const double* __restrict__ d, const double* __restrict__ e, int s0, int s1, int k,
+                                                const double* z, double lam, int lane) {
+    double acc = 0.0;
+    for (int i = s0 + lane; i < s1; i += 64) {
+        double r = (d[i] - lam) * z[(size_t)i * k];
+        if (i > s0) r += e[i - 1] * z[(size_t)(i - 1) * k];
+        if (i < s1 - 1) r += e[i] * z[(size_t)(i + 1) * k];
+        acc += r * r;
+    }
+    return wave_sum(acc);
+}
+__global__ __launch_bounds__(64) void k_tri_reorth(const double* __restrict__ d, const double* __restrict__ e, int n, int k,
+                                                   const double* __restrict__ shifts, const double* __restrict__ lam_desc,
+                                                   const double* __restrict__ sc, const int* __restrict__ own,
+                                                   const int* __restrict__ blk_of, const int* __restrict__ bstart,
+                                                   const int* __restrict__ next, const double* __restrict__ work,
+                                                   const unsigned char* __restrict__ swp, double* cand, double* Z) {
+    const int v0 = blockIdx.x, lane = threadIdx.x;
+    if (shifts[v0] != lam_desc[v0] || next[v0] < 0) return;      // not the first member of a cluster
+    const int blk = blk_of[own[v0]];
+    const int s0 = bstart[blk], s1 = bstart[blk + 1], m = s1 - s0;
+    if (m == 1) return;
+    const size_t nk = (size_t)n * k;
+    const double norm = sc[TRI_BNORM];
+    const double eps3 = ASB_EPS * (norm > 0.0 ? norm : 1.0);
+    const double eps4 = (double)m * eps3;
+    double* z = cand + v0;
+    for (int t = next[v0]; t >= 0; t = next[t]) {
+        for (int i = s0 + lane; i < s1; i += 64) z[(size_t)i * k] = Z[(size_t)i * k + t];
+        bool good = true;
+        for (int pass = 0; pass < 2; ++pass) {
+            for (int s = v0; s != t; s = next[s]) {
+                const double* q = Z + s;
+                double acc = 0.0;
+                for (int i = s0 + lane; i < s1; i += 64) acc += q[(size_t)i * k] * z[(size_t)i * k];
+                acc = wave_sum(acc);
+                for (int i = s0 + lane; i < s1; i += 64) z[(size_t)i * k] -= acc * q[(size_t)i * k];
+            }
+            double s2 = 0.0;
+            for (int i = s0 + lane; i < s1; i += 64) { const double x = z[(size_t)i * k]; s2 += x * x; }
+            s2 = wave_sum(s2);
+            good = good && s2 > 0.0 && s2 < DBL_MAX;
+            const double f = good ? (pass == 0 ? eps4 : 1.0) / sqrt(s2) : 0.0;
+            for (int i = s0 + lane; i < s1; i += 64) z[(size_t)i * k] *= f;
+            __syncthreads();
+            if (pass == 1) break;
+            if (lane == 0) {
+                const double* rv1 = work + t;
+                const double* rv2 = rv1 + nk;
+                const double* rv3 = rv2 + nk;
+                const double* rv4 = rv3 + nk;
+                const unsigned char* sw = swp + t;
+                for (int i = s0 + 1; i < s1; ++i) {       // forward elimination with L (and the interchanges)
+                    const size_t a = (size_t)(i - 1) * k, b = (size_t)i * k;
+                    double x = z[b];
+                    if (sw[b]) {
+                        x = z[a];
+                        z[a] = z[b];
+                    }
+                    z[b] = x - rv4[b] * z[a];
+                }
+                double bu = 0.0, bv = 0.0;
+                for (int i = s1 - 1; i >= s0; --i) {      // back substitution with U
+                    const size_t a = (size_t)i * k;
+                    const double x = (z[a] - bu * rv2[a] - bv * rv3[a]) / rv1[a];
+                    z[a] = x;
+                    bv = bu;
+                    bu = x;
+                }
+            }
+            __syncthreads();
+        }
+        const double r_new = tri_residual2(d, e, s0, s1, k, z, lam_desc[t], lane);
+        const double r_old = tri_residual2(d, e, s0, s1, k, Z + t, lam_desc[t], lane);
+        if (good && r_new <= 16.0 * fmax(r_old, eps3 * eps3))
+            for (int i = s0 + lane; i < s1; i += 64) Z[(size_t)i * k + t] = z[(size_t)i * k];
+        __syncthreads();
+    }
 }
 
 // d, e (device, n and n-1 entries) -> lam_desc (device, n, descending) and, for k > 0, the k leading unit eigenvectors in
@@ -250,23 +433,34 @@ __global__ __launch_bounds__(64) void k_tri_invit(const double* __restrict__ d, 
 int asb_tri_eig_dev(asb_ctx* ctx, const double* d, const double* e, int n, int k, double* lam_desc, double* Z, int* n_bad) {
     if (n < 1 || k < 0 || k > n) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_tri_eig_dev: n = %d, k = %d", n, k);
     int rc;
-    if ((rc = asb_alloc(ctx, &ctx->tri_work, (size_t)n + 16 + (size_t)k + 4 * (size_t)n * (k > 0 ? k : 0)))) return rc;
+    // e2 (n), sc (16), sh (k), val (n), five int arrays (blk_of n, own n, last n, next n, bstart n + 2: 3 n + 2 doubles), work (4 n k), candidates of k_tri_reorth (n k)
+    if ((rc = asb_alloc(ctx, &ctx->tri_work, (size_t)5 * n + 18 + (size_t)k + 5 * (size_t)n * (k > 0 ? k : 0)))) return rc;
     if ((rc = asb_alloc(ctx, &ctx->tri_swp, (size_t)n * (k > 0 ? k : 1)))) return rc;
     if ((rc = asb_alloc(ctx, &ctx->la_status, (size_t)4))) return rc;
     double* e2 = ctx->tri_work;
     double* sc = e2 + n;
     double* sh = sc + 16;
-    double* work = sh + k;
+    double* val = sh + k;
+    int* blk_of = (int*)(val + n);
+    int* own = blk_of + n;
+    int* last = own + n;
+    int* next = last + n;
+    int* bstart = next + n;
+    double* work = val + n + 3 * (size_t)n + 2;
     ASB_HIP(ctx, hipMemsetAsync(ctx->la_status, 0, 4 * sizeof(int), ctx->stream));
     hipLaunchKernelGGL(k_tri_prepare, dim3(1), dim3(256), 0, ctx->stream, d, e, n, e2, sc);
+    hipLaunchKernelGGL(k_tri_blocks, dim3(1), dim3(256), 0, ctx->stream, e, n, sc, blk_of, bstart, last, next);
     static const int multisect = getenv("ASB_TRI_MULTISECT") ? atoi(getenv("ASB_TRI_MULTISECT")) : 1;
-    if (multisect) hipLaunchKernelGGL(k_tri_multisect, dim3(n), dim3(64), 0, ctx->stream, d, e2, n, sc, lam_desc);
-    else hipLaunchKernelGGL(k_tri_bisect, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, d, e2, n, sc, lam_desc);
+    if (multisect) hipLaunchKernelGGL(k_tri_multisect, dim3(n), dim3(64), 0, ctx->stream, d, e2, n, sc, blk_of, bstart, val, lam_desc);
+    else hipLaunchKernelGGL(k_tri_bisect, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, d, e2, n, sc, blk_of, bstart, val, lam_desc);
+    hipLaunchKernelGGL(k_tri_order, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, val, n, bstart, lam_desc, own);
     ASB_CHECK_LAUNCH(ctx);
     if (k > 0) {
-        hipLaunchKernelGGL(k_tri_shifts, dim3(1), dim3(1), 0, ctx->stream, lam_desc, k, sc, sh);
-        hipLaunchKernelGGL(k_tri_invit, dim3((k + 63) / 64), dim3(64), 0, ctx->stream, d, e, n, k, sh, sc, work, ctx->tri_swp, Z,
-                           ctx->la_status);
+        hipLaunchKernelGGL(k_tri_shifts, dim3(1), dim3(1), 0, ctx->stream, lam_desc, k, sc, own, blk_of, last, next, sh);
+        hipLaunchKernelGGL(k_tri_invit, dim3((k + 63) / 64), dim3(64), 0, ctx->stream, d, e, n, k, sh, lam_desc, sc, own, blk_of, bstart, work,
+                           ctx->tri_swp, Z, ctx->la_status);
+        hipLaunchKernelGGL(k_tri_reorth, dim3(k), dim3(64), 0, ctx->stream, d, e, n, k, sh, lam_desc, sc, own, blk_of, bstart, next, work,
+                           ctx->tri_swp, work + 4 * (size_t)n * k, Z);
         ASB_CHECK_LAUNCH(ctx);
     }
     if (n_bad) {

@@ -550,9 +550,12 @@ def _child_tridiag():
         for c in TRIDIAG_CASES:
             t.test_tridiagonal_bisection_and_inverse_iteration(e, *c)
         t.test_tridiagonal_with_a_split_and_exact_multiplicity(e)
+        import test_gpu_symeig as s                  # every tridiagonal family of symeig_cases.py, same bars
+        for family in s.TRI_FAMILIES:
+            s.check_tri_family(e, family)
     finally:
         e.close()
-    print("bisection: %d cases OK" % (len(TRIDIAG_CASES) + 1))
+    print("bisection: %d cases, %d families OK" % (len(TRIDIAG_CASES) + 1, len(s.TRI_FAMILIES)))
 
 
 def _child_eigensolver():
@@ -561,6 +564,9 @@ def _child_eigensolver():
     shapes = PANEL_SHAPES if os.environ.get("ASB_TD_PANEL_MIN") else EIGENSOLVER_SHAPES
     for n, k in shapes:
         t.test_device_symmetric_eigensolver(n, k)
+    if os.environ.get("ASB_BACKTRANSFORM_BLOCKED") == "0":
+        import test_gpu_symeig as s                  # Q Z against the longdouble product at the (n, k) of the blocked route
+        s.check_backtransform_all()
     print("eigensolver: %d shapes OK" % len(shapes))
 
 
