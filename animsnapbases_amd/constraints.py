@@ -745,23 +745,28 @@ class constraintsComponents:  # Components == bases
         S_kept = []                     # singular values of the vectors kept by finished levels
         remaining, level = K, 0
         self.pod_power_steps = 0
-        while True:
-            S_lvl, Sb, Kx, Bbuf, keep = self._pod_level(remaining, on_dev)
-            resolved = int(np.sum(S_lvl > 3e-8 * S_lvl[0])) if S_lvl[0] > 0 else 0
-            if Kx >= remaining:         # this level delivers everything that is still wanted
-                break
-            # K reaches below what this level's Gram matrix resolves: keep what it resolved WELL (above 1e-5 of the level's
-            # largest: Gram error below 1e-6, which the subspace-iteration steps remove), deflate, go on
-            if not levels_ok or keep < 2 or level >= 8:
-                raise ArithmeticError("POD: singular value %d of the %d requested is %.3e of the largest -- below what the "
-                                      "Gram-matrix route resolves (1e-8), and the deflated levels cannot take over here (%s)"
-                                      % (K, K, S_lvl[remaining - 1] / S_lvl[0] if S_lvl[0] > 0 else 0.0,
-                                         "odd F or row count" if not levels_ok else "nothing left to resolve: the snapshot "
-                                         "matrix has numerical rank %d" % (K - remaining + resolved)))
-            eng.pod_deflate_begin(keep, Bbuf.data_ptr() if Bbuf is not None else None)
-            S_kept.extend(Sb[:keep].tolist())
-            remaining -= keep
-            level += 1
+        try:
+            while True:
+                S_lvl, Sb, Kx, Bbuf, keep = self._pod_level(remaining, on_dev)
+                resolved = int(np.sum(S_lvl > 3e-8 * S_lvl[0])) if S_lvl[0] > 0 else 0
+                if Kx >= remaining:         # this level delivers everything that is still wanted
+                    break
+                # K reaches below what this level's Gram matrix resolves: keep what it resolved WELL (above 1e-5 of the level's
+                # largest: Gram error below 1e-6, which the subspace-iteration steps remove), deflate, go on
+                if not levels_ok or keep < 2 or level >= 8:
+                    raise ArithmeticError("POD: singular value %d of the %d requested is %.3e of the largest -- below what the "
+                                          "Gram-matrix route resolves (1e-8), and the deflated levels cannot take over here (%s)"
+                                          % (K, K, S_lvl[remaining - 1] / S_lvl[0] if S_lvl[0] > 0 else 0.0,
+                                             "odd F or row count" if not levels_ok else "nothing left to resolve: the snapshot "
+                                             "matrix has numerical rank %d" % (K - remaining + resolved)))
+                eng.pod_deflate_begin(keep, Bbuf.data_ptr() if Bbuf is not None else None)
+                S_kept.extend(Sb[:keep].tolist())
+                remaining -= keep
+                level += 1
+        except BaseException:
+            if level:                   # an open level is closed before the error leaves: the engine holds the snapshots again
+                eng.pod_deflate_end(0, K - remaining)
+            raise
         if level:
             eng.pod_deflate_end(remaining, K)
             # the levels' vectors are orthogonal to one another to ~eps |A| / |A_level|: one CholeskyQR2 over all K rows

@@ -74,7 +74,9 @@ struct asb_ctx {
 
     // ---- snapshot shard, vertex-major: row r = 3*v + d, Fp doubles per row ----
     int64_t F = 0, Fp = 0, n_loc = 0, v0 = 0, N_glob = 0;
-    double* X = nullptr;      // (3*n_loc, Fp)   prepared snapshots (snapTensor)
+    // X is a VIEW, never an asb_alloc key: of X_in (what the last ingest call wrote) or, between
+    // asb_pod_deflate_begin and _end, of X_lvl (the level's deflated copy)
+    double *X = nullptr, *X_in = nullptr, *X_lvl = nullptr;   // (3*n_loc, Fp) prepared snapshots (snapTensor)
     double* mean = nullptr;   // (3*n_loc)
     bool have_mean = false;
     // per-vertex energies |X_v|^2 of the PREPARED tensor, a by-product of the last sweep that wrote it (k_scale_energy) or
@@ -280,10 +282,9 @@ struct asb_ctx {
     double* kk_tmp = nullptr;     // K x K transposed factor (asb_combine_rows)
     double *pod_g = nullptr, *pod_v = nullptr, *pod_s = nullptr, *pod_coef = nullptr;   // asb_pod.hip
     double* pod_vn = nullptr;     // (F x K) right Ritz vectors / sigma of the power step
-    // the POD in levels (asb_pod_deflate_begin / _end): bases kept by finished levels, the deflated copy of the snapshots
+    // the POD in levels (asb_pod_deflate_begin / _end): bases kept by finished levels
     double* pod_u1 = nullptr;
     int64_t pod_u1_rows = 0;
-    double *X_deflated = nullptr, *X_original = nullptr;
     int* la_status = nullptr;
     double* dn_sym = nullptr;                     // symmetric Gauss-Jordan: pivot row panel, D x panel, signed transpose, pivot block
     double *dn_work = nullptr, *dn_test = nullptr;   // asb_dense.hip: Gauss-Jordan panels; test matrix
@@ -518,6 +519,23 @@ static inline int asb_pin_alloc(asb_ctx* ctx) {
     return ASB_OK;
 }
 
+// Context-owned device buffers are registered in ctx->alloc_bytes under the address of their owning pointer (`slot`), here
+// alone.  asb_capacity: the elements registered for *slot (0: none); asb_release: freed, key erased; _all: asb_destroy
+template <typename T>
+static inline size_t asb_capacity(const asb_ctx* ctx, T* const* slot) {
+    auto it = ctx->alloc_bytes.find((void*)slot);
+    return *slot && it != ctx->alloc_bytes.end() ? it->second / sizeof(T) : 0;
+}
+template <typename T>
+static inline void asb_release(asb_ctx* ctx, T** slot) {
+    (void)hipFree(*slot);
+    *slot = nullptr;
+    ctx->alloc_bytes.erase((void*)slot);
+}
+static inline void asb_release_all(asb_ctx* ctx) {
+    while (!ctx->alloc_bytes.empty()) asb_release(ctx, (void**)ctx->alloc_bytes.begin()->first);
+}
+
 // (Re)allocates *p to hold `count` elements; an existing allocation that is already large
 // enough (and not more than 2x too large) is kept, so repeated runs on one context do not
 // pay hipMalloc/hipFree inside a timed region.
@@ -526,11 +544,7 @@ static inline int asb_alloc(asb_ctx* ctx, T** p, size_t count) {
     const size_t want = count * sizeof(T);
     auto it = ctx->alloc_bytes.find((void*)p);
     if (*p && it != ctx->alloc_bytes.end() && it->second >= want && it->second <= 2 * want + 4096) return ASB_OK;
-    if (*p) {
-        (void)hipFree(*p);
-        *p = nullptr;
-        ctx->alloc_bytes.erase((void*)p);
-    }
+    if (*p) asb_release(ctx, p);
     if (count == 0) return ASB_OK;
     ASB_HIP(ctx, hipMalloc((void**)p, want));
     ctx->alloc_bytes[(void*)p] = want;
@@ -566,7 +580,7 @@ static inline void asb_cp_move(asb_ctx* ctx, CpSetup& from, CpSetup& to) {
 }
 
 // A device buffer that lives inside one call: freed when it goes out of scope (hipFree waits for the device, so work still in
-// flight on the buffer is safe), unless release() has handed it to the context.  Buffers that outlive a call go through asb_alloc.
+// flight on the buffer is safe), unless asb_adopt has handed it to the context.  Buffers that outlive a call go through asb_alloc.
 template <typename T>
 struct asb_tmp {
     asb_tmp() = default;
@@ -585,6 +599,44 @@ struct asb_tmp {
 private:
     T* p = nullptr;
 };
+
+// The filled temporary becomes *slot's registered buffer of `count` elements; the previous one is freed
+template <typename T>
+static inline void asb_adopt(asb_ctx* ctx, T** slot, asb_tmp<T>& buf, size_t count) {
+    asb_release(ctx, slot);
+    *slot = buf.release();
+    ctx->alloc_bytes[(void*)slot] = count * sizeof(T);
+}
+// *p gets room for count_new elements and keeps its first count_keep: a buffer that is large enough stays (no upper bound),
+// otherwise a new one is filled by a copy, drained and adopted.  A failure leaves the old buffer in place (message: `who`)
+template <typename T>
+static inline int asb_grow_keep(asb_ctx* ctx, const char* who, T** p, size_t count_new, size_t count_keep) {
+    if (*p && asb_capacity(ctx, p) >= count_new) return ASB_OK;
+    asb_tmp<T> q;
+    int rc;
+    if ((rc = q.alloc(ctx, count_new))) return rc;
+    if (*p && count_keep) {
+        hipError_t e = hipMemcpyAsync(q.get(), *p, count_keep * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) ASB_FAIL(ctx, ASB_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+    asb_adopt(ctx, p, q, count_new);
+    return ASB_OK;
+}
+
+// The POD in levels (asb_pod.hip): a level is open while X views X_lvl; asb_pod_deflate_end and every ingest call drop it
+static inline bool asb_pod_level_open(const asb_ctx* ctx) { return ctx->X != ctx->X_in; }
+static inline void asb_pod_level_drop(asb_ctx* ctx) {
+    ctx->X = ctx->X_in;
+    asb_release(ctx, &ctx->X_lvl);
+    asb_release(ctx, &ctx->pod_u1);
+    ctx->pod_u1_rows = 0;
+}
+
+// asb_recon.hip: what asb_recon_sweep and asb_onmesh_run read for `which` -- 0: the training tensor, the greedy weights, the
+// device basis; 1: the held-out tensor, Z^T, Q -- checked for `kmax` components (messages: "who: idx = ...")
+struct RcOperands { const double *T, *A, *B; long long ldt, lda; int F; };
+int asb_recon_operands(asb_ctx* ctx, const char* who, const char* idx, int which, int64_t kmax, RcOperands* o);
 
 // asb_snapshots.hip: the shard [v0, v0 + n_loc) of a host tensor (F, N_glob, 3) and of its mass vector, staged on the device
 int asb_stage_shard(asb_ctx* ctx, const double* X, int64_t F, int64_t N_glob, int64_t v0, int64_t n_loc, const double* massL,

@@ -364,26 +364,12 @@ extern "C" int asb_onmesh_run(asb_ctx* ctx, int which, int64_t r, int64_t f0, in
                               double* mesh_num_out, double* mesh_den_out, double* accum_angle_out, double* stats_out,
                               double* frame_err_out, double* angle_out) {
     if (!ctx || !ctx->X || !ctx->comps || r < 0) return ASB_ERR_ARG;
-    const double *T, *A, *B;
-    long long ldt, lda;
-    int F;
-    if (which == 0) {
-        auto it = ctx->alloc_bytes.find((void*)&ctx->W);
-        const int64_t kw = (ctx->W && it != ctx->alloc_bytes.end()) ? (int64_t)(it->second / (ctx->Fp * sizeof(double))) : 0;
-        if (r > ctx->K || r > kw)
-            ASB_FAIL(ctx, ASB_ERR_ARG, "asb_onmesh_run: r = %lld but %lld components and %lld weight columns", (long long)r,
-                     (long long)ctx->K, (long long)kw);
-        T = ctx->X, ldt = ctx->Fp, F = (int)ctx->F, A = ctx->W, lda = ctx->Fp, B = ctx->comps;
-    } else if (which == 1) {
-        if (!ctx->ho_Y || ctx->ho_K != ctx->K) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_onmesh_run: no factorised held-out animation for this basis");
-        if (r > ctx->K) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_onmesh_run: r = %lld but %lld components", (long long)r, (long long)ctx->K);
-        T = ctx->ho_Y, ldt = ctx->ho_Fp, F = (int)ctx->ho_F, A = ctx->ho_Zt, lda = ctx->ho_Fp, B = ctx->ho_Q;
-    } else {
-        return ASB_ERR_ARG;
-    }
-    if (f0 < 0 || f1 > F || f0 >= f1 || fj < 1)
+    RcOperands o;
+    int rc;
+    if ((rc = asb_recon_operands(ctx, "asb_onmesh_run", "r", which, r, &o))) return rc;
+    if (f0 < 0 || f1 > o.F || f0 >= f1 || fj < 1)
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_onmesh_run: range(%lld, %lld, %lld) is not a selection of the %d frames", (long long)f0,
-                 (long long)f1, (long long)fj, F);
+                 (long long)f1, (long long)fj, o.F);
     if (add_mean && !ctx->have_mean) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_onmesh_run: no mean on the device");
     if (!(psf > 0.0) || !(denom > 0.0)) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_onmesh_run: scale %g, denominator %g", psf, denom);
     if (want_normals && ctx->om_verts != ctx->n_loc) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_onmesh_run: no mesh for this shard (asb_onmesh_mesh)");
@@ -400,7 +386,6 @@ extern "C" int asb_onmesh_run(asb_ctx* ctx, int which, int64_t r, int64_t f0, in
     if (gn > 8LL * ctx->n_cu) gn = 8LL * ctx->n_cu;
     const double inv_psf = 1.0 / psf;
     const double* mean = add_mean ? ctx->mean : nullptr;
-    int rc;
     if ((rc = asb_alloc(ctx, &ctx->om_vpart, (size_t)n_tiles * n_loc))) return rc;
     if ((rc = asb_alloc(ctx, &ctx->om_fpart, (size_t)nblk * 2 * OM_TILE))) return rc;
     if ((rc = asb_alloc(ctx, &ctx->om_spart, (size_t)(nblk + gn) * 3))) return rc;
@@ -427,8 +412,8 @@ extern "C" int asb_onmesh_run(asb_ctx* ctx, int which, int64_t r, int64_t f0, in
         d_ang = ctx->om_ang;
     }
 
-    hipLaunchKernelGGL(k_onmesh_err, dim3((unsigned)gx, (unsigned)n_tiles), dim3(64 * OM_WAVES), 0, ctx->stream, T, ldt, F, n_loc, A, lda,
-                       B, ldb, (int)r, mean, invm, inv_psf, denom, (int)f0, (int)f1, (int)fj, tile0, ctx->om_vpart, ctx->om_fpart,
+    hipLaunchKernelGGL(k_onmesh_err, dim3((unsigned)gx, (unsigned)n_tiles), dim3(64 * OM_WAVES), 0, ctx->stream, o.T, o.ldt, o.F, n_loc, o.A,
+                       o.lda, o.B, ldb, (int)r, mean, invm, inv_psf, denom, (int)f0, (int)f1, (int)fj, tile0, ctx->om_vpart, ctx->om_fpart,
                        ctx->om_spart, d_fe);
     hipLaunchKernelGGL(k_onmesh_frames, dim3((unsigned)((n_sel + 255) / 256)), dim3(256), 0, ctx->stream, ctx->om_fpart, (int)gx, tile0,
                        (int)f0, (int)fj, n_sel, d_num, d_den);
@@ -451,9 +436,9 @@ extern "C" int asb_onmesh_run(asb_ctx* ctx, int which, int64_t r, int64_t f0, in
         int first = 1;
         for (long long c0 = f0; c0 < f1; c0 += cw) {
             const long long c1 = c0 + cw < f1 ? c0 + cw : f1;
-            hipLaunchKernelGGL(k_onmesh_fill, dim3((unsigned)gf), dim3(64 * OM_WAVES), 0, ctx->stream, A, lda, B, ldb, (int)r, n_loc,
+            hipLaunchKernelGGL(k_onmesh_fill, dim3((unsigned)gf), dim3(64 * OM_WAVES), 0, ctx->stream, o.A, o.lda, o.B, ldb, (int)r, n_loc,
                                (int)c0, (int)c1, (int)cw, ctx->om_scratch);
-            hipLaunchKernelGGL(k_onmesh_normals, dim3((unsigned)gn), dim3(64 * OM_WAVES), 0, ctx->stream, T, ldt, ctx->om_scratch, (int)cw,
+            hipLaunchKernelGGL(k_onmesh_normals, dim3((unsigned)gn), dim3(64 * OM_WAVES), 0, ctx->stream, o.T, o.ldt, ctx->om_scratch, (int)cw,
                                (int)c0, (int)c1, n_loc, ctx->om_tris, ctx->om_ptr, ctx->om_star, mean, invm, inv_psf, (int)f0, (int)f1,
                                (int)fj, first, d_aa, sp, d_ang);
             first = 0;

@@ -295,6 +295,24 @@ extern "C" int asb_heldout_weights(asb_ctx* ctx, double* W_out) {
     return ASB_OK;
 }
 
+int asb_recon_operands(asb_ctx* ctx, const char* who, const char* idx, int which, int64_t kmax, RcOperands* o) {
+    if (which == 0) {
+        // the greedy weights of the deflation (K_W rows of Fp) and the device-resident basis
+        const int64_t kw = (int64_t)(asb_capacity(ctx, &ctx->W) / ctx->Fp);
+        if (kmax > ctx->K || kmax > kw)
+            ASB_FAIL(ctx, ASB_ERR_ARG, "%s: %s = %lld but %lld components and %lld weight columns", who, idx, (long long)kmax,
+                     (long long)ctx->K, (long long)kw);
+        *o = {ctx->X, ctx->W, ctx->comps, ctx->Fp, ctx->Fp, (int)ctx->F};
+    } else if (which == 1) {
+        if (!ctx->ho_Y || ctx->ho_K != ctx->K) ASB_FAIL(ctx, ASB_ERR_ARG, "%s: no factorised held-out animation for this basis", who);
+        if (kmax > ctx->K) ASB_FAIL(ctx, ASB_ERR_ARG, "%s: %s = %lld but %lld components", who, idx, (long long)kmax, (long long)ctx->K);
+        *o = {ctx->ho_Y, ctx->ho_Zt, ctx->ho_Q, ctx->ho_Fp, ctx->ho_Fp, (int)ctx->ho_F};
+    } else {
+        return ASB_ERR_ARG;
+    }
+    return ASB_OK;
+}
+
 extern "C" int asb_recon_sweep(asb_ctx* ctx, int which, const int64_t* ks, int64_t S, double* sums_out, double* max_out,
                                double* norms_out) {
     if (!ctx || !ks || S < 1 || !ctx->X || !ctx->comps) return ASB_ERR_ARG;
@@ -302,30 +320,14 @@ extern "C" int asb_recon_sweep(asb_ctx* ctx, int which, const int64_t* ks, int64
     for (int64_t s = 0; s < S; ++s)
         if (ks[s] < 0 || (s && ks[s] <= ks[s - 1])) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_recon_sweep: sweep points must increase from 0");
     const int64_t kmax = ks[S - 1];
-    const double *T, *A, *B;
-    long long ldt, lda;
-    int F;
-    if (which == 0) {
-        // the greedy weights of the deflation (K_W rows of Fp) and the device-resident basis
-        auto it = ctx->alloc_bytes.find((void*)&ctx->W);
-        const int64_t kw = (ctx->W && it != ctx->alloc_bytes.end()) ? (int64_t)(it->second / (ctx->Fp * sizeof(double))) : 0;
-        if (kmax > ctx->K || kmax > kw)
-            ASB_FAIL(ctx, ASB_ERR_ARG, "asb_recon_sweep: k = %lld but %lld components and %lld weight columns", (long long)kmax,
-                     (long long)ctx->K, (long long)kw);
-        T = ctx->X, ldt = ctx->Fp, F = (int)ctx->F, A = ctx->W, lda = ctx->Fp, B = ctx->comps;
-    } else if (which == 1) {
-        if (!ctx->ho_Y || ctx->ho_K != ctx->K) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_recon_sweep: no factorised held-out animation for this basis");
-        if (kmax > ctx->K) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_recon_sweep: k = %lld but %lld components", (long long)kmax, (long long)ctx->K);
-        T = ctx->ho_Y, ldt = ctx->ho_Fp, F = (int)ctx->ho_F, A = ctx->ho_Zt, lda = ctx->ho_Fp, B = ctx->ho_Q;
-    } else {
-        return ASB_ERR_ARG;
-    }
+    RcOperands o;
+    int rc;
+    if ((rc = asb_recon_operands(ctx, "asb_recon_sweep", "k", which, kmax, &o))) return rc;
     const int nslot = (int)(S + 1) * 4;
-    const int n_fchunks = (F + 64 * RC_NF - 1) / (64 * RC_NF);
+    const int n_fchunks = (o.F + 64 * RC_NF - 1) / (64 * RC_NF);
     const long long n_units = (ctx->n_loc + RC_VT - 1) / RC_VT * n_fchunks;
     long long nblk = (n_units + RC_WAVES - 1) / RC_WAVES;
     if (nblk > 4LL * ctx->n_cu) nblk = 4LL * ctx->n_cu;
-    int rc;
     if ((rc = asb_alloc(ctx, &ctx->rc_part, (size_t)(nblk + 1) * nslot))) return rc;
     if ((rc = asb_alloc(ctx, &ctx->rc_ks, (size_t)S))) return rc;
     std::vector<int> k32(ks, ks + S);
@@ -334,8 +336,8 @@ extern "C" int asb_recon_sweep(asb_ctx* ctx, int which, const int64_t* ks, int64
     const size_t lds = (size_t)RC_WAVES * nslot * sizeof(double);
     if (lds > 48 * 1024) ASB_HIP(ctx, hipFuncSetAttribute((const void*)k_recon_sweep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     double* out = ctx->rc_part + (size_t)nblk * nslot;
-    hipLaunchKernelGGL(k_recon_sweep, dim3((unsigned)nblk), dim3(64 * RC_WAVES), lds, ctx->stream, T, ldt, F, (long long)ctx->n_loc, A,
-                       lda, B, (long long)(3 * ctx->n_loc), ctx->rc_ks, (int)S, n_units, n_fchunks, ctx->rc_part);
+    hipLaunchKernelGGL(k_recon_sweep, dim3((unsigned)nblk), dim3(64 * RC_WAVES), lds, ctx->stream, o.T, o.ldt, o.F, (long long)ctx->n_loc,
+                       o.A, o.lda, o.B, (long long)(3 * ctx->n_loc), ctx->rc_ks, (int)S, n_units, n_fchunks, ctx->rc_part);
     hipLaunchKernelGGL(k_recon_final, dim3((unsigned)((nslot + 255) / 256)), dim3(256), 0, ctx->stream, ctx->rc_part, (int)nblk, nslot,
                        out);
     ASB_CHECK_LAUNCH(ctx);

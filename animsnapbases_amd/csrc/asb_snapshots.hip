@@ -325,17 +325,7 @@ extern "C" void asb_destroy(asb_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->dev);
     (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->X_original) {                    // a POD in levels that did not reach its end: the original snapshots own the slot
-        ctx->X = ctx->X_original;
-        ctx->X_original = nullptr;
-    }
-    if (ctx->X_deflated) (void)hipFree(ctx->X_deflated);
-    if (ctx->pod_u1) (void)hipFree(ctx->pod_u1);
-    for (auto& kv : ctx->alloc_bytes) {       // every context-owned buffer was registered by asb_alloc
-        void** slot = (void**)kv.first;
-        if (*slot) (void)hipFree(*slot);
-        *slot = nullptr;
-    }
+    asb_release_all(ctx);       // every context-owned device buffer
     asb_splocs_free(ctx);
     asb_geo_free(ctx);
     asb_pdsolve_free(ctx);
@@ -396,7 +386,10 @@ static int set_shape(asb_ctx* ctx, int64_t F, int64_t N_glob, int64_t v0, int64_
     ctx->have_mean = false;
     { ctx->e0_valid = false; ctx->ev_valid = false; }
     int rc;
-    if ((rc = asb_alloc(ctx, &ctx->X, (size_t)n_loc * 3 * ctx->Fp))) return rc;
+    asb_pod_level_drop(ctx);        // new snapshots end an open POD level
+    rc = asb_alloc(ctx, &ctx->X_in, (size_t)n_loc * 3 * ctx->Fp);
+    ctx->X = ctx->X_in;
+    if (rc) return rc;
     if ((rc = asb_alloc(ctx, &ctx->mean, (size_t)n_loc * 3))) return rc;
     if (clear) ASB_HIP(ctx, hipMemsetAsync(ctx->X, 0, (size_t)n_loc * 3 * ctx->Fp * sizeof(double), ctx->stream));
     ASB_HIP(ctx, hipMemsetAsync(ctx->mean, 0, (size_t)n_loc * 3 * sizeof(double), ctx->stream));

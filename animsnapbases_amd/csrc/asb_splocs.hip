@@ -670,7 +670,7 @@ extern "C" int asb_test_splocs_state(asb_ctx* ctx, double* U, double* Lambda, do
 
 void asb_splocs_free(asb_ctx* ctx) {
     if (ctx->splocs) {
-        delete ctx->splocs;       // device buffers are released through ctx->alloc_bytes
+        delete ctx->splocs;       // (the buffers went with the context's registered allocations)
         ctx->splocs = nullptr;
     }
 }

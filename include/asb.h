@@ -477,7 +477,8 @@ int asb_pod_power(asb_ctx* ctx, const double* B_dev);
  * asb_pod_deflate_begin(ctx, B_dev, keep): the first `keep` rows of the basis are kept (behind what earlier levels kept) and the
  * context's snapshots become A_2 (a second buffer; even `keep`, F and row count); the POD entry points then work on A_2.
  * asb_pod_deflate_end(ctx, last): the snapshots are the original ones again, the basis is [kept rows of all levels ; the first
- * `last` rows of the current basis]. */
+ * `last` rows of the current basis].  Ingesting new snapshots ends an open level: the kept rows are dropped and a later
+ * asb_pod_deflate_end is refused. */
 int asb_pod_deflate_begin(asb_ctx* ctx, const double* B_dev, int64_t keep);
 int asb_pod_deflate_end(asb_ctx* ctx, int64_t last);
 /* constProj_basis_type 'pod' (compute_pod_for_nonlinear_snapshots_tensor, :274-294): one SVD per (constraint row, coordinate)

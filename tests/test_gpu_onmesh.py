@@ -274,3 +274,21 @@ def test_refusals():
         comp.post_process_components()
     comp.comps = np.array(comp.comps)                                       # the setter clears the refusal too
     assert comp.on_mesh_accuracy(2)["accum_norm"].shape == (verts.shape[1],)
+
+
+def test_r_beyond_the_weight_columns_is_refused():
+    """a residual run of K = 4 leaves four weight columns; an uploaded basis of six rows does not add any"""
+    from animsnapbases_amd import HipEngine
+    rng = np.random.default_rng(6)
+    X = rng.uniform(-1, 1, size=(20, 50, 3))
+    e = HipEngine(0)
+    try:
+        e.upload(X, 0, 50)
+        e.deflate_begin(4, False)
+        e.run_global(0, 4)
+        e.components_upload(rng.normal(size=(6, 50, 3)))
+        with pytest.raises(RuntimeError, match="asb_onmesh_run: r = 5 but 6 components and 4 weight columns"):
+            e.onmesh_run(0, 5, 0, 20, 1, False, None, False, 1.0, 1.0)
+        assert e.onmesh_run(0, 4, 0, 20, 1, False, None, False, 1.0, 1.0)["accum_norm"].shape == (50,)
+    finally:
+        e.close()

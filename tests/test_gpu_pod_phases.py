@@ -627,6 +627,60 @@ def test_pod_deflate_end_refuses_last_above_k():
         e.close()
 
 
+def _small_bases(rng, n):
+    return [_orthonormal(rng, 3 * n, k).T.reshape(k, n, 3) for k in (6, 4, 4)]
+
+
+@pytest.mark.parametrize("F2,n2", [(8, 6), (10, 8)], ids=("same shape", "other shape"))
+def test_ingest_inside_an_open_level_drops_it(F2, n2):
+    """new snapshots end an open level: they are what the context holds, asb_pod_deflate_end finds no level, and a cycle of
+    levels on them gives the bits of a fresh engine (no row count and no deflated copy left over from the dropped level)"""
+    rng = np.random.default_rng(9650 + F2)
+    e, X, C, Bt = _refusal_engine(rng, 8, 6, 6)
+    X2 = _two_groups(rng, F2, n2)
+    bases = _small_bases(rng, n2)
+    where = "ingest in a level F=%d n=%d" % (F2, n2)
+    try:
+        e.pod_deflate_begin(2, Bt.data_ptr())
+        assert not np.array_equal(e.download_snapshots(), X)
+        e.upload(X2, 0, n2)
+        assert np.array_equal(e.download_snapshots(), X2), (where, "the context does not hold the new snapshots")
+        with pytest.raises(RuntimeError, match="without asb_pod_deflate_begin"):
+            e.pod_deflate_end(0, 0)
+        assert np.array_equal(e.download_snapshots(), X2)
+        got = _cycle(e, X2, bases, 2, where)
+    finally:
+        e.close()
+    fresh = _engine(X2)
+    try:
+        ref = _cycle(fresh, X2, bases, 2, where + " fresh")
+    finally:
+        fresh.close()
+    for a, b in zip(got, ref):
+        assert np.array_equal(a, b), (where, "a cycle after the dropped level differs from the same cycle on a fresh engine")
+
+
+def test_level_buffers_are_registered():
+    """the level's deflated copy and kept rows belong to the context: an engine closed inside a level leaves nothing behind, and
+    after asb_pod_deflate_end has released them a second cycle on the same engine repeats the first bit for bit"""
+    rng = np.random.default_rng(9660)
+    e, X, C, Bt = _refusal_engine(rng, 8, 6, 6)
+    try:
+        e.pod_deflate_begin(2, Bt.data_ptr())
+        assert not np.array_equal(e.download_snapshots(), X)
+    finally:
+        e.close()
+    bases = _small_bases(rng, 6)
+    e = _engine(X)
+    try:
+        first = _cycle(e, X, bases, 2, "registered")
+        again = _cycle(e, X, bases, 2, "registered again")
+    finally:
+        e.close()
+    for a, b in zip(first, again):
+        assert np.array_equal(a, b), "a second cycle on the same engine differs from the first"
+
+
 @pytest.mark.parametrize("F,n,K", [(8, 6, 6), (70, 130, 64)], ids=("small", "big"))
 def test_b_in_the_context_or_in_a_callers_tensor(F, n, K):
     """project -> rotate -> power and project -> rotate -> deflate_begin with B left in the context (B_dev = NULL throughout)

@@ -293,3 +293,21 @@ def test_errors():
         with pytest.raises(ValueError):
             comp.reconstruction_errors(*bad)
     assert len(comp.reconstruction_errors(0, 4, 1)[0]) == 5
+
+
+def test_sweep_point_beyond_the_weight_columns_is_refused():
+    """a residual run of K = 4 leaves four weight columns; an uploaded basis of six rows does not add any"""
+    from animsnapbases_amd import HipEngine
+    rng = np.random.default_rng(5)
+    X = rng.uniform(-1, 1, size=(20, 50, 3))
+    e = HipEngine(0)
+    try:
+        e.upload(X, 0, 50)
+        e.deflate_begin(4, False)
+        e.run_global(0, 4)
+        e.components_upload(rng.normal(size=(6, 50, 3)))
+        with pytest.raises(RuntimeError, match="asb_recon_sweep: k = 5 but 6 components and 4 weight columns"):
+            e.recon_sweep(0, [0, 5])
+        assert e.recon_sweep(0, [0, 4])[0].shape == (2, 3)
+    finally:
+        e.close()

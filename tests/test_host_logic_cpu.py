@@ -289,3 +289,50 @@ def test_constraints_diagnostics_against_the_reference(capsys):
     assert abs(constraintsComponents.frobenius_error(g["snapTensor"], g["rec"]) - float(g["frobenius"])) < 1e-12 * float(g["frobenius"])
     assert np.allclose(constraintsComponents.relative_error_per_component(g["snapTensor"], g["rec"]), g["relative"], rtol=1e-13)
     assert abs(constraintsComponents.max_pointwise_error(g["snapTensor"], g["rec"]) - float(g["max_pointwise"])) < 1e-14
+
+
+class _RecordingEngine:
+    """the calls the level loop of compute_pod_for_vectorized_nonlinear_snapshots_tensor makes on its engine, recorded"""
+
+    def __init__(self):
+        self.calls = []
+
+    def pod_deflate_begin(self, keep, B_dev_ptr=None):
+        self.calls.append(("pod_deflate_begin", keep, B_dev_ptr))
+
+    def pod_deflate_end(self, last, K_total):
+        self.calls.append(("pod_deflate_end", last, K_total))
+
+
+@pytest.mark.parametrize("kept", [True, False], ids=("one level kept", "no level kept"))
+def test_pod_level_loop_closes_an_open_level_before_it_raises(kept, tmp_path, monkeypatch):
+    """A level that resolves nothing ends the vectorised POD with ArithmeticError; a level opened before it (pod_deflate_begin)
+    is closed first with pod_deflate_end(0, rows kept so far), and the error leaves with its own type and message."""
+    from animsnapbases_amd.constraints import constraintsComponents
+    monkeypatch.chdir(tmp_path)                     # (log_time writes its timing file into the working directory)
+    F, K = 8, 6
+    eng = _RecordingEngine()
+    cc = constraintsComponents.__new__(constraintsComponents)
+    cc.param = types.SimpleNamespace(deim_desired_num_components=K)
+    cc.nonlinearSnapshots = types.SimpleNamespace(_engine=eng, _comm=types.SimpleNamespace(multi=False), frs=F, _shards=[(0, 4)])
+    S1 = np.geomspace(1.0, 1e-12, F)
+    script = ([(S1, S1[:2].copy(), 2, None, 2)] if kept else []) + [(np.zeros(F), None, 0, None, 0)]
+    asked = []
+
+    def pod_level(remaining, on_dev):
+        asked.append(remaining)
+        return script[len(asked) - 1]
+
+    cc._pod_level = pod_level
+    with pytest.raises(ArithmeticError) as err:
+        cc.compute_pod_for_vectorized_nonlinear_snapshots_tensor()
+    rank = 2 if kept else 0
+    assert str(err.value) == ("POD: singular value %d of the %d requested is %.3e of the largest -- below what the Gram-matrix "
+                              "route resolves (1e-8), and the deflated levels cannot take over here (nothing left to resolve: "
+                              "the snapshot matrix has numerical rank %d)" % (K, K, 0.0, rank))
+    if kept:
+        assert asked == [K, K - 2]
+        assert eng.calls == [("pod_deflate_begin", 2, None), ("pod_deflate_end", 0, 2)]
+    else:
+        assert asked == [K]
+        assert eng.calls == []
