@@ -192,6 +192,11 @@ PROTOTYPES = {
     "asb_pdsolve_advance": (c_int, [ctypes.c_void_p]),
     "asb_pdsolve_positions": (c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "asb_test_pdsolve_state": (c_int, [ctypes.c_void_p, c_int, c_dp, c_i64, c_i64]),
+    "asb_pins_set": (c_int, [ctypes.c_void_p, c_i64, c_dp, c_dp, c_dp, c_i64, c_dp, c_int]),
+    "asb_pins_clear": (c_int, [ctypes.c_void_p]),
+    "asb_pins_term": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, ctypes.c_void_p]),
+    "asb_fm_add": (c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i64]),
+    "asb_pdsolve_pins": (c_int, [ctypes.c_void_p, c_i64]),
     "asb_splocs_begin": (c_int, [ctypes.c_void_p]),
     "asb_splocs_gram": (c_int, [ctypes.c_void_p, c_dp, c_dp, ctypes.POINTER(c_dbl)]),
     "asb_splocs_weights": (c_int, [ctypes.c_void_p, c_dp, c_dp, c_dp, c_dp]),

@@ -365,6 +365,14 @@ struct asb_ctx {
     int64_t gs_n = 0, gs_Np = 0;      // its vertices (0: no set-up); rounded up to the kernel's 32
     double* gs_diag = nullptr;        // (n_loc) asb_gstep_inertia: masses / h^2
     asb_pds* pds = nullptr;           // the solve in progress and its buffers (asb_pdsolve.hip)
+    // positional constraints (asb_pins_set, asb_pdsolve.hip): checked and uploaded once, read by every later pin term
+    struct Pins {
+        int64_t P = 0, n = 0, T = 0;      // pins (0: none), the vertices they were checked against, rows of shift (0: fixed pins)
+        int per_pin = 0;                  // shift is (T, P, 3) instead of (T, 3)
+        int* v = nullptr;                 // (P) vertices, no two equal
+        double *wi = nullptr, *p0 = nullptr, *shift = nullptr;        // (P) weights, (P, 3) targets, the shift
+    };
+    Pins pins;
     // the global step's second solver (asb_gslab.hip): the block-tridiagonal slab factor of A_N.  The context holds EITHER
     // gs_Ainv (gs_n > 0) or the factor (asb_gslab_n(ctx) > 0): each set-up releases the other
     asb_gsl* gsl = nullptr;

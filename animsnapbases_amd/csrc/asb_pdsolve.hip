@@ -1,6 +1,7 @@
 // The local/global iterations of the reference's projective-dynamics solver (projective_dynamics/Simulators.py:494-526) for a
 // batch of frames of the resident animation: q_0 given, q_{k+1} = A^-1 (sum_i S_i^T p_i(q_k) + M/h^2 s), s fixed.  Every
-// selected frame is its own solve.  Collisions and positional constraints are not modelled.  The end of the reference's step
+// selected frame is its own solve.  Collisions are not modelled; positional constraints (pins) are a constant added to ms, at
+// the end of this file.  The end of the reference's step
 // (:531-532: velocities = (q - positions) / dt, positions = q) is asb_pdsolve_advance below: a roll-out is iterate, advance, iterate ...
 //
 // State of a solve over the n_sel frames range(f0, f1, fj), owned by the context and reused by the next solve:
@@ -72,6 +73,9 @@ struct asb_pds {
     double acc[3] = {0.0, 0.0, 0.0};
     std::vector<double> diag_host;
     double *P = nullptr, *diag = nullptr;
+    // the context's pins bound to this solve (asb_pdsolve_pins): their term is in ms; row of shift = pin_row0 + frame + pin_step
+    bool pins = false;
+    long long pin_row0 = 0, pin_step = 0;
     int n_slots = 0;
     PdSlot slot[PD_MAX_SLOTS];
 };
@@ -203,7 +207,7 @@ static long long pd_solver_n(const asb_ctx* ctx) {
 extern "C" int asb_pdsolve_begin(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean,
                                  double psf, const double* diag, int mode, const double* acc3, int start, const double* start_dev) {
     if (!ctx || !diag || !acc3) return ASB_ERR_ARG;
-    if (ctx->pds) ctx->pds->begun = false, ctx->pds->n_slots = 0, ctx->pds->carry = false;
+    if (ctx->pds) ctx->pds->begun = false, ctx->pds->n_slots = 0, ctx->pds->carry = false, ctx->pds->pins = false;
     if (fj >= 1 && f1 > f0 && ((f1 - f0 + fj - 1) / fj + 63) / 64 > 65535)        // on the count alone, before any tensor is looked at
         ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_pdsolve_begin: %lld frames in one solve (at most %d)", (long long)((f1 - f0 + fj - 1) / fj), 65535 * 64);
     if (mode != 0 && mode != 1) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_begin: mode %d (0: s = x, 1: s = 2 x - x_prev)", mode);
@@ -416,6 +420,162 @@ void asb_pd_untranspose_launch(asb_ctx* ctx, const double* P, int n_sel, long lo
                        ld, out);
 }
 
+// ================================================================ positional constraints (pins)
+// PositionalConstraint of the reference (Constraint_projections.py:77-113; the first summand of b, Simulators.py:401-413,
+// :513-520): pin i holds vertex v_i at p0_i + shift[row] with weight wi_i.  It adds wi_i to A's diagonal (the host's matrix)
+// and the constant wi_i (p0_i + shift[row]) to the right-hand side, which does not depend on q: the term lives in ms, and the
+// iterations -- plain, hyper-reduced, under either solver -- read ms and are not changed.
+// Arithmetic, per pin i, coordinate d and row r (pin_term, the one place):
+//   t = fl(p0 + shift[r]) (p0 without a shift),  term = fl(wi t) rounded on its own (no contraction with the add behind it),
+//   out = term (STORE)  or  out = fl(out + term) (ADD).
+// k_pins_fm: grid (pins / 4, frame tiles of 64), wave w of a block = pin 4 b + w, lane = frame: one thread owns one
+// (frame, pin) and its three coordinates of the frame-major tensor (n_sel, n, 3).  No two pins share a vertex (asb_pins_set),
+// so no entry has two writers: no atomics.  Tails: pins >= P, frames >= n_sel.  Entries of vertices that are not pinned are not
+// touched (a STORE pass is preceded by a memset of the whole tensor: +0.0 there).  Traffic: P n_sel 24 bytes written (and read
+// with ADD) plus the tables -- next to the 24 N n_sel bytes of every other pass over ms; the layout is not a performance question.
+struct PinsDev {
+    const int* v;
+    const double *wi, *p0, *shift;      // shift NULL: fixed pins
+    int P, per_pin;
+    long long n;
+};
+
+__device__ __forceinline__ double pin_term(const PinsDev& p, int i, int d, long long row) {
+#pragma clang fp contract(off)
+    double t = p.p0[3 * i + d];
+    if (p.shift) t = t + p.shift[(p.per_pin ? row * p.P + i : row) * 3 + d];
+    return p.wi[i] * t;
+}
+
+template <bool ADD>
+__global__ __launch_bounds__(256) void k_pins_fm(PinsDev p, long long row_base, int fj, int n_sel, double* __restrict__ out) {
+#pragma clang fp contract(off)
+    const int i = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    const int c = (int)blockIdx.y * 64 + (int)(threadIdx.x & 63);
+    if (i >= p.P || c >= n_sel) return;
+    const long long row = row_base + (long long)c * fj;
+    double* o = out + ((long long)c * p.n + p.v[i]) * 3;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const double term = pin_term(p, i, d, row);
+        o[d] = ADD ? o[d] + term : term;
+    }
+}
+
+// the pin term of the frames c = 0 .. n_sel - 1, rows row_base + c fj, into (ADD: onto) a frame-major tensor (n_sel, n, 3)
+template <bool ADD>
+static void asb_pins_launch(asb_ctx* ctx, long long row_base, int fj, int n_sel, double* out) {
+    const asb_ctx::Pins& h = ctx->pins;
+    const PinsDev p = {h.v, h.wi, h.p0, h.T > 0 ? h.shift : nullptr, (int)h.P, h.per_pin, (long long)h.n};
+    hipLaunchKernelGGL(k_pins_fm<ADD>, dim3((unsigned)((h.P + 3) / 4), (unsigned)((n_sel + 63) / 64)), dim3(256), 0, ctx->stream, p, row_base, fj,
+                       n_sel, out);
+}
+
+// the pins fit the tensor and the rows row_base + c fj, c < n_sel, lie inside shift
+static int asb_pins_rows_ok(asb_ctx* ctx, const char* who, long long n, long long row_base, long long fj, long long n_sel) {
+    const asb_ctx::Pins& h = ctx->pins;
+    if (h.P < 1) ASB_FAIL(ctx, ASB_ERR_ARG, "%s: no pins on the device (asb_pins_set)", who);
+    if (h.n != n) ASB_FAIL(ctx, ASB_ERR_ARG, "%s: the pins were checked against %lld vertices, the tensor has %lld", who, (long long)h.n, n);
+    if (h.T > 0 && (row_base < 0 || row_base + (n_sel - 1) * fj >= h.T))
+        ASB_FAIL(ctx, ASB_ERR_ARG, "%s: row %lld of the shift is needed, it has %lld", who, row_base + (n_sel - 1) * fj, (long long)h.T);
+    return ASB_OK;
+}
+
+static int asb_pd_pins_check(asb_ctx* ctx, const asb_pds* s, const char* who, long long step) {
+    return asb_pins_rows_ok(ctx, who, s->n, s->pin_row0 + s->f0 + step, s->fj, s->n_sel);
+}
+
+extern "C" int asb_pins_clear(asb_ctx* ctx) {
+    if (!ctx) return ASB_ERR_ARG;
+    ctx->pins.P = ctx->pins.n = ctx->pins.T = 0;
+    if (ctx->pds) ctx->pds->pins = false;
+    return ASB_OK;
+}
+
+extern "C" int asb_pins_set(asb_ctx* ctx, int64_t P, const int64_t* verts, const double* wi, const double* p0, int64_t T_s, const double* shift,
+                            int per_pin) {
+    if (!ctx) return ASB_ERR_ARG;
+    asb_pins_clear(ctx);
+    const int64_t n = ctx->n_loc;
+    if (n < 1) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pins_set: no tensor on the device");
+    if (P < 1 || P > n || T_s < 0 || (T_s > 0 && !shift) || !verts || !wi || !p0)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pins_set: %lld pins on %lld vertices, %lld rows of shift", (long long)P, (long long)n, (long long)T_s);
+    std::vector<char> seen((size_t)n, 0);
+    std::vector<int> v32((size_t)P);
+    for (int64_t i = 0; i < P; ++i) {
+        if (verts[i] < 0 || verts[i] >= n) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pins_set: pin %lld names vertex %lld of %lld", (long long)i, (long long)verts[i], (long long)n);
+        if (seen[verts[i]]) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pins_set: vertex %lld is pinned twice", (long long)verts[i]);
+        seen[verts[i]] = 1, v32[i] = (int)verts[i];
+        if (!std::isfinite(wi[i]) || wi[i] < 0.0) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pins_set: wi[%lld] is not finite and >= 0", (long long)i);
+        for (int d = 0; d < 3; ++d)
+            if (!std::isfinite(p0[3 * i + d])) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pins_set: the position of pin %lld is not finite", (long long)i);
+    }
+    const size_t n_shift = (size_t)T_s * (per_pin ? (size_t)P : 1) * 3;
+    for (size_t k = 0; k < n_shift; ++k)
+        if (!std::isfinite(shift[k])) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pins_set: shift[%lld] is not finite", (long long)k);
+    asb_ctx::Pins& h = ctx->pins;
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    int rc;
+    if ((rc = asb_alloc(ctx, &h.v, (size_t)P))) return rc;
+    if ((rc = asb_alloc(ctx, &h.wi, (size_t)P))) return rc;
+    if ((rc = asb_alloc(ctx, &h.p0, (size_t)3 * P))) return rc;
+    if ((rc = asb_alloc(ctx, &h.shift, n_shift))) return rc;
+    ASB_HIP(ctx, hipMemcpyAsync(h.v, v32.data(), (size_t)P * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    ASB_HIP(ctx, hipMemcpyAsync(h.wi, wi, (size_t)P * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    ASB_HIP(ctx, hipMemcpyAsync(h.p0, p0, (size_t)3 * P * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (n_shift) ASB_HIP(ctx, hipMemcpyAsync(h.shift, shift, n_shift * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the host arrays may go
+    h.P = P, h.n = n, h.T = T_s, h.per_pin = per_pin ? 1 : 0;
+    return ASB_OK;
+}
+
+extern "C" int asb_pins_term(asb_ctx* ctx, int64_t f0, int64_t f1, int64_t fj, int64_t row0, int accumulate, double* out_dev) {
+    if (!ctx || !out_dev) return ASB_ERR_ARG;
+    if (fj < 1 || f0 < 0 || f1 <= f0) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pins_term: empty frame range (%lld, %lld, %lld)", (long long)f0, (long long)f1, (long long)fj);
+    const long long n_sel = (f1 - f0 + fj - 1) / fj;
+    if ((n_sel + 63) / 64 > 65535) ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_pins_term: %lld frames in one call (at most %d)", n_sel, 65535 * 64);
+    int rc;
+    if ((rc = asb_pins_rows_ok(ctx, "asb_pins_term", ctx->n_loc, row0 + f0, fj, n_sel))) return rc;
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    if (accumulate) {
+        asb_pins_launch<true>(ctx, row0 + f0, (int)fj, (int)n_sel, out_dev);
+    } else {
+        ASB_HIP(ctx, hipMemsetAsync(out_dev, 0, (size_t)n_sel * ctx->n_loc * 3 * sizeof(double), ctx->stream));
+        asb_pins_launch<false>(ctx, row0 + f0, (int)fj, (int)n_sel, out_dev);
+    }
+    ASB_CHECK_LAUNCH(ctx);
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the caller owns out_dev and may read it on any stream
+    return ASB_OK;
+}
+
+// a[i] = fl(a[i] + b[i]) on two caller-owned device tensors of len doubles: k_pd_add, the add of an iteration
+extern "C" int asb_fm_add(asb_ctx* ctx, double* a_dev, const double* b_dev, int64_t len) {
+    if (!ctx || !a_dev || !b_dev || len < 1) return ASB_ERR_ARG;
+    if (a_dev < b_dev + len && b_dev < a_dev + len) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_fm_add: the two tensors overlap");
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    hipLaunchKernelGGL(k_pd_add, dim3((unsigned)std::min<long long>((len + 255) / 256, 1 << 20)), dim3(256), 0, ctx->stream, a_dev, b_dev, (long long)len);
+    ASB_CHECK_LAUNCH(ctx);
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ASB_OK;
+}
+
+extern "C" int asb_pdsolve_pins(asb_ctx* ctx, int64_t row0) {
+    if (!ctx) return ASB_ERR_ARG;
+    asb_pds* s = ctx->pds;
+    if (!s || !s->begun) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_pins: no solve begun (asb_pdsolve_begin)");
+    if (s->pins) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_pins: the solve has its pins already (their term is in the inertia term)");
+    if (row0 < 0) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_pins: row0 %lld", (long long)row0);
+    if (ctx->n_loc != s->n) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_pins: the tensor changed since asb_pdsolve_begin");
+    s->pin_row0 = row0, s->pin_step = 0;
+    int rc;
+    if ((rc = asb_pd_pins_check(ctx, s, "asb_pdsolve_pins", 0))) return rc;
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    asb_pins_launch<true>(ctx, row0 + s->f0, s->fj, (int)s->n_sel, s->ms);
+    ASB_CHECK_LAUNCH(ctx);
+    s->pins = true;
+    return ASB_OK;
+}
+
 extern "C" int asb_pdsolve_carry(asb_ctx* ctx, const double* pos_dev) {
     if (!ctx) return ASB_ERR_ARG;
     asb_pds* s = ctx->pds;
@@ -449,10 +609,16 @@ extern "C" int asb_pdsolve_advance(asb_ctx* ctx) {
     if (!s || !s->begun) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_advance: no solve begun (asb_pdsolve_begin)");
     if (!s->carry || !s->P || !s->diag)
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_advance: the solve carries no previous positions (asb_pdsolve_carry after asb_pdsolve_begin)");
+    int rc;
+    if (s->pins && (rc = asb_pd_pins_check(ctx, s, "asb_pdsolve_advance", s->pin_step + 1))) return rc;       // before any launch
     ASB_HIP(ctx, hipSetDevice(ctx->dev));
     const dim3 grid((unsigned)((3 * s->n + 63) / 64), (unsigned)((s->n_sel + 63) / 64));
     hipLaunchKernelGGL(k_pd_advance, grid, dim3(256), 0, ctx->stream, s->Q, s->P, s->diag, (int)s->n_sel, 3 * s->n, s->ld, s->acc[0], s->acc[1],
                        s->acc[2], s->ms);
+    if (s->pins) {                                  // ms of the next step is rewritten: its pin term, one row of shift later
+        ++s->pin_step;
+        asb_pins_launch<true>(ctx, s->pin_row0 + s->f0 + s->pin_step, s->fj, (int)s->n_sel, s->ms);
+    }
     ASB_CHECK_LAUNCH(ctx);
     return ASB_OK;
 }

@@ -1,7 +1,7 @@
 """``ResidentDynamics`` -- what ``posSnapshots`` offers beyond the reference's class: the pieces of the reference's
 projective-dynamics solver (Simulators.py) evaluated on the device for the frames of the resident animation -- constraint
 projections, constraint forces, their DEIM reduction, the global step, the solver's iterations and its time steps, with the choice of the global step's solver and
-of how many kinds a solve may reduce.
+of how many kinds a solve may reduce, and the positional constraints (pins) of every such call.
 A public call checks its arguments into the named records below before the engine is touched; the helpers take the records.
 """
 import collections
@@ -40,6 +40,10 @@ Explicit = collections.namedtuple("Explicit", "mode acc diag masses dt")
 Reduced = collections.namedtuple("Reduced", "index setup St operator op")
 # One kind with a basis: what ``reduced_constraint_forces`` and the ``reduced_*_errors`` methods check their arguments into.
 ReducedPlan = collections.namedtuple("ReducedPlan", "term frames operator")
+# The positional constraints of a call (the reference's PositionalConstraint, one per vertex): ``vertices`` (P,) int64, ``wi`` (P,),
+# ``p0`` (P, 3) the targets at rest, ``shift`` None (fixed) or (T_s, 3) / (T_s, P, 3) (p0 + shift[row]), ``start``: the row of
+# frame 0's first step, and ``St``: the (N, P) CSR with wi_i at (v_i, i).  Not a kind: no slot, no reduction, no dependence on q.
+Pins = collections.namedtuple("Pins", "vertices wi p0 shift start St")
 
 
 class ResidentDynamics(object):
@@ -83,14 +87,68 @@ class ResidentDynamics(object):
                 raise ValueError("%s: no elements given%s" % (kind, " and the snapshots have no triangles" if kind == "verts_bending" else ""))
             elements = self.tris
         if rest_positions is None:
-            if self.verts is not None:
-                rest_positions = self.verts[0]
-            else:                                   # an adopted device tensor: frame 0 back in world space
-                rest_positions = self.snapTensor[0] / self.pre_scale_factor + (self.mean if self._standarize else 0.0)
+            rest_positions = self._rest()
         rest = np.asarray(rest_positions, dtype=np.float64)
         if rest.shape != (self.nVerts, 3):
             raise ValueError("rest positions of shape %s: (%d, 3) expected" % (rest.shape, self.nVerts))
         return _proj.build_setup(kind, elements, rest)
+
+    def _rest(self):
+        """The rest positions a call takes when none are given: frame 0 of the world-space input."""
+        if self.verts is not None:
+            return self.verts[0]
+        # an adopted device tensor: frame 0 back in world space
+        return self.snapTensor[0] / self.pre_scale_factor + (self.mean if self._standarize else 0.0)
+
+    def _pins(self, who, pins, frames=None, steps=1):
+        """The checked ``Pins`` of a public call (None for None), before anything touches the device.  With ``frames``: every row
+        of the shift that ``steps`` time steps from those frames read must exist."""
+        if pins is None:
+            return None
+        known = ("vertices", "wi", "positions", "shift", "shift_start")
+        if not isinstance(pins, dict) or "vertices" not in pins or "wi" not in pins:
+            raise ValueError("%s: pins must be a dict with 'vertices' and 'wi' (and %s), not %r" % (who, ", ".join(known[2:]), pins))
+        extra = sorted(set(pins) - set(known))
+        if extra:
+            raise ValueError("%s: pins: unknown key %r (one of %s)" % (who, extra[0], ", ".join(known)))
+        N = self.nVerts
+        v = np.asarray(pins["vertices"])
+        if v.ndim != 1 or v.size < 1 or v.dtype.kind not in "iu":
+            raise ValueError("%s: pins: vertices must be a non-empty list of integers" % who)
+        v = v.astype(np.int64)
+        if v.min() < 0 or v.max() >= N:
+            raise ValueError("%s: pins: vertex %d is outside 0 .. %d" % (who, int(v[(v < 0) | (v >= N)][0]), N - 1))
+        if np.unique(v).size != v.size:
+            raise ValueError("%s: pins: a vertex is pinned twice" % who)
+        P = v.size
+        try:
+            w = np.asarray(pins["wi"], dtype=np.float64)
+        except (TypeError, ValueError):
+            w = np.full(1, np.nan)
+        if w.shape not in ((), (P,)):
+            raise ValueError("%s: pins: wi of shape %s: a scalar or (%d,) expected" % (who, w.shape, P))
+        if not np.isfinite(w).all() or (w < 0.0).any():
+            raise ValueError("%s: pins: every weight wi must be finite and >= 0" % who)
+        w = np.ascontiguousarray(np.broadcast_to(w, (P,)))
+        pos = pins.get("positions")
+        p0 = np.asarray(self._rest(), dtype=np.float64)[v] if pos is None else np.asarray(pos, dtype=np.float64)
+        if p0.shape != (P, 3) or not np.isfinite(p0).all():
+            raise ValueError("%s: pins: positions of shape %s: finite (%d, 3) expected" % (who, p0.shape, P))
+        shift = pins.get("shift")
+        if shift is not None:
+            shift = np.ascontiguousarray(shift, dtype=np.float64)
+            if shift.ndim not in (2, 3) or shift.shape[0] < 1 or shift.shape[1:] not in ((3,), (P, 3)) or not np.isfinite(shift).all():
+                raise ValueError("%s: pins: shift of shape %s: finite (T_s, 3) or (T_s, %d, 3) expected" % (who, shift.shape, P))
+        start = pins.get("shift_start", 0)
+        if isinstance(start, bool) or not isinstance(start, (int, np.integer)) or start < 0:
+            raise ValueError("%s: pins: shift_start %r: a non-negative integer" % (who, start))
+        out = Pins(v, w, np.ascontiguousarray(p0), shift, int(start), _proj.pins_ST(v, w, N))
+        if frames is not None and shift is not None:
+            last = out.start + range(frames.start, frames.end, frames.jump)[-1] + steps - 1
+            if last >= shift.shape[0]:
+                raise ValueError("%s: pins: row %d of shift is needed (shift_start %d, last frame %d, %d step%s), it has %d"
+                                 % (who, last, out.start, last - out.start - steps + 1, steps, "" if steps == 1 else "s", shift.shape[0]))
+        return out
 
     def _plan(self, kinds, chunk_frames=None):
         """The checks of ``constraint_forces`` on its kinds, in its order: one ``Term`` per kind."""
@@ -163,20 +221,28 @@ class ResidentDynamics(object):
         return torch.empty((frames.n_sel, self.nVerts if rows is None else rows, 3), dtype=torch.float64,
                            device="cuda:%d" % self._engine.device_id)
 
-    def _leave(self, terms):
+    def _leave(self, terms, pins=None):
         self.assembly_ST = {t.kind: t.St for t in terms}
+        if pins is not None:
+            self.assembly_ST["positional"] = pins.St
         self.bending_indices = next((t.setup.bending_indices for t in terms if t.kind == "verts_bending"), None)
 
-    def _cforce_run(self, plan, frames, chunk_frames):
-        """``constraint_forces`` for a plan of ``_plan``."""
+    def _cforce_run(self, plan, frames, chunk_frames, pins=None):
+        """``constraint_forces`` for a plan of ``_plan``; ``pins``: their term is added behind the kinds'."""
         frames.upload(self)
         out = self._alloc(frames)
         for i, t in enumerate(plan):
             self._engine.cproj_setup(t.setup)
             self._engine.cforce_run(*frames.args(self), t.sigma_min, t.sigma_max, t.St, i > 0,
                                     0 if chunk_frames is None else int(chunk_frames), out.data_ptr())
-        self._leave(plan)
+        if pins is not None:
+            self._pins_set(pins)
+            self._engine.pins_term(frames.start, frames.end, frames.jump, pins.start, True, out.data_ptr())
+        self._leave(plan, pins)
         return out
+
+    def _pins_set(self, pins):
+        self._engine.pins_set(pins.vertices, pins.wi, pins.p0, pins.shift)
 
     def _rforce_term(self, term, op, frames):
         """One reduced term with the operator of the engine: only the sampled elements are set up and projected."""
@@ -186,9 +252,17 @@ class ResidentDynamics(object):
         self._engine.rforce_run(*frames.args(self), term.sigma_min, term.sigma_max, False, out.data_ptr())
         return out
 
-    def _step(self, b, ex, frames):
-        """A^-1 (b + M / dt^2 s) of the selected frames; the inertia term is added onto ``b``."""
-        self._engine.gstep_inertia(*frames.args(self), ex.diag, ex.mode, ex.acc, b.data_ptr())
+    def _step(self, b, ex, frames, pins=None):
+        """A^-1 (b + M / dt^2 s) of the selected frames; the inertia term is added onto ``b``.  With ``pins`` the constant of a
+        solve is formed first, as a solve forms it: c = fl(fl(M / dt^2 s) + pin term), then b = fl(b + c)."""
+        if pins is None:
+            self._engine.gstep_inertia(*frames.args(self), ex.diag, ex.mode, ex.acc, b.data_ptr())
+            return self.global_solve(b)
+        c = self._alloc(frames)
+        self._pins_set(pins)
+        self._engine.pins_term(frames.start, frames.end, frames.jump, pins.start, False, c.data_ptr())
+        self._engine.gstep_inertia(*frames.args(self), ex.diag, ex.mode, ex.acc, c.data_ptr())
+        self._engine.fm_add(b.data_ptr(), c.data_ptr(), b.numel())
         return self.global_solve(b)
 
     def _errors(self, plan, r_values, per_frame, full, reduced, hyper=None):
@@ -253,7 +327,7 @@ class ResidentDynamics(object):
             self.assembly_ST = {kind: St}
         return out, frames.n_sel, setup.rows
 
-    def constraint_forces(self, kinds, animation="train", frame_start=0, frame_end=None, frame_jump=1, chunk_frames=None):
+    def constraint_forces(self, kinds, animation="train", frame_start=0, frame_end=None, frame_jump=1, chunk_frames=None, pins=None):
         """Extra (not in the reference's class): the constraint term of the global step's right-hand side,
         b[f] = sum_k S_k^T p_k(q_f) (``get_sum_ST_p``, Simulators.py:643-724), for the frames
         range(frame_start, frame_end, frame_jump) of the resident animation -- on the device, the projections p never formed
@@ -264,11 +338,21 @@ class ResidentDynamics(object):
         in list order.  ``chunk_frames``: frames per pass of the device (rounded up to a multiple of 16; None: as many as a
         256 MB scratch holds), which bounds the scratch and changes no bit of the result.
 
+        ``pins``: None or the positional constraints of the reference (``PositionalConstraint``,
+        Constraint_projections.py:77-113; ``project_to_positional_constraint_manifold``, Simulators.py:401-413), a dict
+        ``{"vertices": (P,) distinct integers, "wi": a scalar or (P,) >= 0, "positions": None or (P, 3), "shift": None or
+        (T_s, 3) or (T_s, P, 3), "shift_start": 0}``: vertex v_i is held at positions[i] (None: the rest positions at those
+        vertices, the reference's ``p0``) + shift[row] (None: ``motion_type='fixed'``, else ``'user_defined'``) with weight
+        wi_i, which adds wi_i (positions[i] + shift[row]) to b at v_i.  The row of selected frame f is shift_start + f -- the
+        reference indexes with its step counter, which is f when it steps from the state of frame f; a row beyond T_s is a
+        ValueError (the reference: IndexError).  Pins are not a kind: they take no slot and cannot be reduced.
+
         Returns ``(tensor, F')``: a ``torch.float64`` device tensor (F', N, 3) in world space, allocated here through torch
-        and owned by the caller -- the layout ``posSnapshots.from_device`` adopts.  Leaves ``self.assembly_ST`` (kind -> CSR)
-        and ``self.bending_indices``.  One rank only."""
+        and owned by the caller -- the layout ``posSnapshots.from_device`` adopts.  Leaves ``self.assembly_ST`` (kind -> CSR;
+        with ``pins`` also "positional", the (N, P) CSR ``projections.pins_ST``) and ``self.bending_indices``.  One rank only."""
         frames = self._frames(animation, frame_start, frame_end, frame_jump)
-        return self._cforce_run(self._plan(kinds, chunk_frames), frames, chunk_frames), frames.n_sel
+        pins = self._pins("constraint_forces", pins, frames)
+        return self._cforce_run(self._plan(kinds, chunk_frames), frames, chunk_frames, pins), frames.n_sel
 
     def reduced_constraint_forces(self, kind, basis, num_components, elements=None, wi=1.0, reduction="deim_pod",
                                   rest_positions=None, sigma_min=1.0, sigma_max=1.0, animation="train", frame_start=0,
@@ -314,7 +398,7 @@ class ResidentDynamics(object):
                             lambda op: self._rforce_term(plan.term, op, plan.frames))
 
     # ------------------------------------------------------------------ the global step of projective dynamics
-    def global_solve_setup(self, kinds, dt, masses=None):
+    def global_solve_setup(self, kinds, dt, masses=None, pins=None):
         """Extra (not in the reference's class): prepares the global step of the reference's projective-dynamics solver,
         ``prepare_global_matrix`` (Simulators.py:117-145), for this mesh: A = M / dt^2 + sum_i w_i S_i^T S_i is assembled on
         the host from the rest tables (``projections.global_matrix``: one N x N matrix serves the three coordinates) and
@@ -325,9 +409,12 @@ class ResidentDynamics(object):
         ``self.global_solve_residual`` = max |A (A^-1 1) - 1| as the device computed it.  Cost: the host assembly and symmetry
         check, and on the device a dense N x N inversion (N^3 flop, 8 N^2 bytes); a set-up whose matrix equals the one the
         device already holds keeps that inverse.  N <= 46 000, one rank only.  Under ``set_global_solver("slab")`` the matrix is
-        factorised over breadth-first slabs instead (no limit on N but memory) and ``self.global_solve_slabs`` is left too."""
+        factorised over breadth-first slabs instead (no limit on N but memory) and ``self.global_solve_slabs`` is left too.
+        ``pins`` (the dict of ``constraint_forces``): every wi_i is added to A at (v_i, v_i), as the reference's triplets are
+        (Constraint_projections.py:106-113); only ``vertices`` and ``wi`` matter here."""
         self._one_rank("global_solve_setup")
-        self._matrix(self._plan(kinds), self._masses(masses), dt)
+        pins = self._pins("global_solve_setup", pins)
+        self._matrix(self._plan(kinds), self._masses(masses), dt, pins)
 
     def set_global_solver(self, kind="inverse", slab_target=None):
         """Extra: how every later call of this object applies A^-1 -- ``global_solve``, ``global_step``, ``solve_frames``,
@@ -361,10 +448,13 @@ class ResidentDynamics(object):
         kind, target = getattr(self, "_global_solver", ("inverse", None))
         return None if kind == "inverse" else (_proj.SLAB_TARGET if target is None else target)
 
-    def _matrix(self, plan, masses, dt):
-        """A of the plan, inverted (or, under the slab solver, factorised) on the device unless the device holds that very
-        matrix."""
-        A = _proj.global_matrix([(t.setup, t.wi) for t in plan], self.nVerts, masses, dt)
+    def _matrix(self, plan, masses, dt, pins=None):
+        """A of the plan (and the pins' weights on its diagonal), inverted (or, under the slab solver, factorised) on the device
+        unless the device holds that very matrix."""
+        if pins is None:
+            A = _proj.global_matrix([(t.setup, t.wi) for t in plan], self.nVerts, masses, dt)
+        else:
+            A = _proj.global_matrix([(t.setup, t.wi) for t in plan], self.nVerts, masses, dt, (pins.vertices, pins.wi))
         self.global_matrix, self.global_solve_residual = None, None
         target = self._slab_solver()
         if target is not None:
@@ -401,7 +491,7 @@ class ResidentDynamics(object):
         return out
 
     def global_step(self, kinds, dt, masses=None, velocity="difference", gravity=(0.0, 0.0, 0.0), animation="train",
-                    frame_start=0, frame_end=None, frame_jump=1, chunk_frames=None):
+                    frame_start=0, frame_end=None, frame_jump=1, chunk_frames=None, pins=None):
         """Extra: one local/global iteration of the reference's solver started at every selected frame of the resident
         animation (Simulators.py:494-526 with ``num_iterations`` = 1 and q = x_f):
         Phi(x_f; s_f) = A^-1 (M / dt^2 s_f + sum_k S_k^T p_k(x_f)), on the device.
@@ -411,21 +501,27 @@ class ResidentDynamics(object):
         is paid only when the matrix differs from the one the device holds.  ``velocity``: "zero" takes the explicit state
         s_f = x_f + dt^2 g, "difference"
         s_f = 2 x_f - x_{f-1} + dt^2 g with f - 1 the ANIMATION's previous frame whatever ``frame_jump`` is (at frame 0:
-        x_0), the velocity the reference carries from step to step (:531).  ``gravity``: the acceleration g.
+        x_0), the velocity the reference carries from step to step (:531).  ``gravity``: the acceleration g.  ``pins``: the
+        positional constraints of ``constraint_forces`` -- their weights join A, their term the right-hand side, frame f with
+        row shift_start + f of the shift.
 
         Returns ``(tensor, F')``: a ``torch.float64`` device tensor (F', N, 3) in world space, owned by the caller.  Further
         iterations are ``solve_frames``: they keep s_f fixed while q moves, which re-adopting the result with ``from_device``
         and stepping again would not.  One rank only."""
         ex = self._explicit("global_step", dt, velocity, gravity, masses)
         frames = self._frames(animation, frame_start, frame_end, frame_jump)
+        pins = self._pins("global_step", pins, frames)
         plan = self._plan(kinds, chunk_frames)
-        self._matrix(plan, ex.masses, ex.dt)
-        return self._step(self._cforce_run(plan, frames, chunk_frames), ex, frames), frames.n_sel
+        self._matrix(plan, ex.masses, ex.dt, pins)
+        out = self._step(self._cforce_run(plan, frames, chunk_frames), ex, frames, pins)
+        if pins is not None:
+            self._leave(plan, pins)
+        return out, frames.n_sel
 
     def reduced_global_step_errors(self, kind, basis, r_values, dt, masses=None, velocity="difference", gravity=(0.0, 0.0, 0.0),
                                    elements=None, wi=1.0, reduction="deim_pod", rest_positions=None, sigma_min=1.0,
                                    sigma_max=1.0, animation="train", frame_start=0, frame_end=None, frame_jump=1,
-                                   per_frame=False):
+                                   per_frame=False, pins=None):
         """Extra: how far the reduced right-hand side moves the vertices -- ``reduced_force_errors`` one line further down the
         iteration.  Cost beside that method's: the work of ``global_solve_setup`` once, one solve plus one per r.
         For every r of ``r_values`` the three metrics of ``(q, q~_r)``: q = ``global_step`` of this kind and
@@ -433,20 +529,26 @@ class ResidentDynamics(object):
         as ``reduced_force_errors`` plus ``dt``, ``masses``, ``velocity``, ``gravity`` of ``global_step``; the same five lists
         ``fro, max, rel_x, rel_y, rel_z`` and, with ``per_frame``, the (len(r_values), F') array |q[f] - q~_r[f]| / |q[f]|.
         The full step is computed once; every tensor stays on the device.  The sweep keeps its one kind whatever
-        ``set_reduced_kinds`` allows: multi-kind sweeps are out of scope."""
+        ``set_reduced_kinds`` allows: multi-kind sweeps are out of scope.  ``pins`` (as ``global_step``) are part of both steps,
+        unreduced."""
         ex = self._explicit("reduced_global_step_errors", dt, velocity, gravity, masses)
         spec = dict(kind=kind, elements=elements, wi=wi, rest_positions=rest_positions, sigma_min=sigma_min, sigma_max=sigma_max)
-        plan = self._reduced_plan(spec, basis, reduction, self._frames(animation, frame_start, frame_end, frame_jump))
+        frames = self._frames(animation, frame_start, frame_end, frame_jump)
+        pins = self._pins("reduced_global_step_errors", pins, frames)
+        plan = self._reduced_plan(spec, basis, reduction, frames)
 
         def full():
-            self._matrix([plan.term], ex.masses, ex.dt)
-            return self._step(self._cforce_run([plan.term], plan.frames, None), ex, plan.frames)
-        return self._errors(plan, r_values, per_frame, full,
-                            lambda op: self._step(self._rforce_term(plan.term, op, plan.frames), ex, plan.frames))
+            self._matrix([plan.term], ex.masses, ex.dt, pins)
+            return self._step(self._cforce_run([plan.term], plan.frames, None), ex, plan.frames, pins)
+        out = self._errors(plan, r_values, per_frame, full,
+                           lambda op: self._step(self._rforce_term(plan.term, op, plan.frames), ex, plan.frames, pins))
+        if pins is not None and self.assembly_ST is not None:
+            self.assembly_ST["positional"] = pins.St
+        return out
 
     # ------------------------------------------------------------------ the solver's iterations
-    _SOLVE_SCOPE = """Out of scope, as for ``global_step``: collision handling (``resolve_collision`` and the self-collision passes),
-        positional constraints and several ranks.  Every selected frame is an independent solve; further time steps from its
+    _SOLVE_SCOPE = """Out of scope, as for ``global_step``: collision handling (``resolve_collision`` and the self-collision passes)
+        and several ranks.  Every selected frame is an independent solve; further time steps from its
         result, the velocity carried along, are ``simulate_frames``.
 
         ``hyper`` (None, "touched" or "all"): the hyper-reduced operator A^-1 S^T V, as the reference's reduced simulator holds
@@ -464,7 +566,12 @@ class ResidentDynamics(object):
         groups' terms are summed before its one solve --, "touched" running on the union of the kinds' touched vertices
         (DESIGN.md 3.18).  Out of scope for ``hyper`` unless ``set_reduced_kinds`` raises the limit: several reduced kinds in one solve; always:
         the history, a reduction of the positions themselves (a basis U of q), several ranks.  Not part of a solve, with or
-        without ``hyper``: velocities carried between frames or steps -- that is ``simulate_frames``, which takes ``hyper`` too."""
+        without ``hyper``: velocities carried between frames or steps -- that is ``simulate_frames``, which takes ``hyper`` too.
+
+        ``pins``: the positional constraints of ``constraint_forces``.  Their weights join A; their term wi (p0 + shift[row]) does
+        not depend on q and joins the constant M / dt^2 s_f of the solve, the row of frame f being shift_start + f.  Pins are
+        not a kind: they take none of the 8 slots, do not count for ``set_reduced_kinds``, and ``hyper`` -- which needs every
+        listed KIND reduced -- carries them unreduced inside c."""
 
     def _solve_args(self, who, dt, velocity, gravity, num_iterations, start, masses):
         """The checks of the solve's own arguments, before anything touches the device: (``Explicit``, K)."""
@@ -605,7 +712,7 @@ class ResidentDynamics(object):
                 eng.pdsolve_slot(t.sigma_min, t.sigma_max, t.St)
         return touched
 
-    def _solve_run(self, plan, reds, frames, ex, begin, K, chunk_frames, history, hyper=None):
+    def _solve_run(self, plan, reds, frames, ex, begin, K, chunk_frames, history, hyper=None, pins=None):
         """The solve (matrix on the device); ``reds``: the ``Reduced`` of the plan with their ``op``; ``begin``: what
         ``_solve_start`` gave.  ``hyper``: every kind is in ``reds`` and their A^-1 S^T V are on the device."""
         eng = self._engine
@@ -614,24 +721,29 @@ class ResidentDynamics(object):
             import torch
             torch.cuda.current_stream(start.device).synchronize()   # whatever produced start is done before the engine reads it
         frames.upload(self)
+        if pins is not None:
+            self._pins_set(pins)
         eng.pdsolve_begin(*frames.args(self), ex.diag, ex.mode, ex.acc, code, None if start is None else start.data_ptr())
+        if pins is not None:
+            eng.pdsolve_pins(pins.start)
         if hyper is not None:
             touched = self._solve_slots(plan, reds, hyper)
             out = self._alloc(frames)
             eng.hyper_iterate(K, None if hyper == "all" else touched, 0 if chunk_frames is None else int(chunk_frames), out.data_ptr())
-            self._leave(plan)
+            self._leave(plan, pins)
             return out, frames.n_sel
         self._solve_slots(plan, reds, None)
         out = self._alloc(frames)
         hist = eng.pdsolve_iterate(K, 0 if chunk_frames is None else int(chunk_frames), out.data_ptr(), history)
-        self._leave(plan)
+        self._leave(plan, pins)
         if history:
             with np.errstate(divide='ignore', invalid='ignore'):
                 return out, frames.n_sel, np.sqrt(hist[:, :, 0]) / np.sqrt(hist[:, :, 1])
         return out, frames.n_sel
 
     def solve_frames(self, kinds, dt, num_iterations=10, masses=None, velocity="difference", gravity=(0.0, 0.0, 0.0), start="explicit",
-                     animation="train", frame_start=0, frame_end=None, frame_jump=1, chunk_frames=None, history=False, hyper=None):
+                     animation="train", frame_start=0, frame_end=None, frame_jump=1, chunk_frames=None, history=False, pins=None,
+                     hyper=None):
         """Extra: the local/global iterations of the reference's solver (Simulators.py:494-526) for every selected frame of
         the resident animation, on the device: q_0 given, q_{k+1} = A^-1 (M / dt^2 s_f + sum_i S_i^T p_i(q_k)) for
         ``num_iterations`` iterations, the explicit state s_f held fixed while q moves.  The iterate stays on the device
@@ -657,18 +769,19 @@ class ResidentDynamics(object):
                              "product kernel and are out of scope for the slab solver" % who)
         ex, K = self._solve_args(who, dt, velocity, gravity, num_iterations, start, masses)
         frames = self._frames(animation, frame_start, frame_end, frame_jump)
+        pins = self._pins(who, pins, frames)
         plan, reds = self._solve_plan(who, kinds, chunk_frames)
         begin = self._solve_start(who, start, frames.n_sel)
         reds = self._chosen(reds, kinds)
-        self._matrix(plan, ex.masses, ex.dt)
-        return self._with_operators(reds, hyper, lambda: self._solve_run(plan, reds, frames, ex, begin, K, chunk_frames, history, hyper))
+        self._matrix(plan, ex.masses, ex.dt, pins)
+        return self._with_operators(reds, hyper, lambda: self._solve_run(plan, reds, frames, ex, begin, K, chunk_frames, history, hyper, pins))
 
     solve_frames.__doc__ %= _SOLVE_SCOPE
 
     def reduced_solve_errors(self, kind, basis, r_values, dt, num_iterations=10, masses=None, velocity="difference",
                              gravity=(0.0, 0.0, 0.0), start="explicit", elements=None, wi=1.0, reduction="deim_pod", rest_positions=None,
                              sigma_min=1.0, sigma_max=1.0, animation="train", frame_start=0, frame_end=None, frame_jump=1,
-                             per_frame=False, hyper=None):
+                             per_frame=False, pins=None, hyper=None):
         """Extra: how far the DEIM-reduced simulation is from the full one after the solver's iterations -- for every r of
         ``r_values`` the three metrics of ``(q, q~_r)``, q = ``solve_frames`` of this kind and q~_r the same solve with the kind
         reduced to r components (same A^-1, same inertia term, same start).  Arguments as ``reduced_global_step_errors`` plus
@@ -684,15 +797,20 @@ class ResidentDynamics(object):
         ex, K = self._solve_args(who, dt, velocity, gravity, num_iterations, start, masses)
         spec = dict(kind=kind, elements=elements, wi=wi, rest_positions=rest_positions, sigma_min=sigma_min, sigma_max=sigma_max)
         frames = self._frames(animation, frame_start, frame_end, frame_jump)
+        pins = self._pins(who, pins, frames)
         terms, (red,) = self._solve_plan(who, [dict(spec, basis=basis, num_components=0, reduction=reduction)], None)
         begin = self._solve_start(who, start, frames.n_sel)
-        run = lambda rd: self._solve_run(terms, () if rd is None else (rd,), frames, ex, begin, K, None, False, None if rd is None else hyper)[0]
+        run = lambda rd: self._solve_run(terms, () if rd is None else (rd,), frames, ex, begin, K, None, False, None if rd is None else hyper,
+                                         pins)[0]
 
         def full():
-            self._matrix(terms, ex.masses, ex.dt)
+            self._matrix(terms, ex.masses, ex.dt, pins)
             return run(None)
-        return self._errors(ReducedPlan(terms[0], frames, red.operator), r_values, per_frame, full,
-                            lambda op: run(red._replace(op=op)), hyper)
+        out = self._errors(ReducedPlan(terms[0], frames, red.operator), r_values, per_frame, full,
+                           lambda op: run(red._replace(op=op)), hyper)
+        if pins is not None and self.assembly_ST is not None:
+            self.assembly_ST["positional"] = pins.St
+        return out
 
     reduced_solve_errors.__doc__ %= _SOLVE_SCOPE
 
@@ -727,13 +845,15 @@ class ResidentDynamics(object):
             if t.dim() != 3 or tuple(t.shape) != (n_sel, self.nVerts, 3) or not t.is_contiguous():
                 raise ValueError("%s: state of shape %s: contiguous (%d, %d, 3) tensors expected" % (who, tuple(t.shape), n_sel, self.nVerts))
 
-    def _rollout_run(self, plan, reds, frames, ex, state, K, T, chunk_frames, every, hyper=None):
+    def _rollout_run(self, plan, reds, frames, ex, state, K, T, chunk_frames, every, hyper=None, pins=None):
         """The roll-out (matrix on the device; ``reds``, ``hyper`` as ``_solve_run``): ``(q, q_prev, records or None, steps)``."""
         import torch
         eng = self._engine
         if state is not None:
             torch.cuda.current_stream(state[0].device).synchronize()    # whatever produced the state is done before the engine reads it
         frames.upload(self)
+        if pins is not None:
+            self._pins_set(pins)
         if state is None:
             eng.pdsolve_begin(*frames.args(self), ex.diag, ex.mode, ex.acc, 0, None)
             eng.pdsolve_carry(None)
@@ -741,6 +861,8 @@ class ResidentDynamics(object):
             eng.pdsolve_begin(*frames.args(self), ex.diag, ex.mode, ex.acc, 2, state[0].data_ptr())
             eng.pdsolve_carry(state[1].data_ptr())
             eng.pdsolve_advance()
+        if pins is not None:                        # behind the advance of a continuation, which rewrites the inertia term
+            eng.pdsolve_pins(pins.start)
         touched = self._solve_slots(plan, reds, hyper)
         steps = [] if every is None else list(range(every, T + 1, every))
         records = None
@@ -759,12 +881,12 @@ class ResidentDynamics(object):
                 eng.pdsolve_iterate(K, cf, ptr, False)
         q_prev = self._alloc(frames)
         eng.pdsolve_positions(q_prev.data_ptr())
-        self._leave(plan)
+        self._leave(plan, pins)
         return q, q_prev, records, steps
 
     def simulate_frames(self, kinds, dt, num_steps, num_iterations=10, masses=None, velocity="difference", gravity=(0.0, 0.0, 0.0),
                         state=None, animation="train", frame_start=0, frame_end=None, frame_jump=1, chunk_frames=None,
-                        record_every=None, hyper=None):
+                        record_every=None, hyper=None, pins=None):
         """Extra: ``num_steps`` time steps of the reference's solver (Simulators.py ``step()``, :494-532) from every selected
         frame of the resident animation, on the device.  Every selected frame is an independent initial condition: positions
         x_f, velocity (x_f - x_{f-1}) / dt (``velocity`` "difference", f - 1 as in ``global_step``) or 0 ("zero").  A step is
@@ -778,32 +900,37 @@ class ResidentDynamics(object):
         ``chunk_frames`` and ``hyper``: as ``solve_frames``, with its refusals.  ``state``: a pair ``(q, q_prev)`` of contiguous
         ``torch.float64`` device tensors (F', N, 3), the positions now and one step earlier: the roll-out continues from them
         (``velocity`` is then ignored and the animation only selects F'), and T1 steps continued by T2 equal T1 + T2 steps bit
-        for bit.  ``record_every`` = r: also the positions after the steps r, 2 r, .. <= ``num_steps``.
+        for bit.  ``record_every`` = r: also the positions after the steps r, 2 r, .. <= ``num_steps``.  ``pins``: the positional
+        constraints of ``constraint_forces`` and ``solve_frames``; step t = 1, 2, .. of the roll-out from frame f reads row
+        shift_start + f + t - 1 of the shift (the reference's step counter), so a continuation with ``state=`` passes
+        ``shift_start`` raised by the steps already taken and then equals the longer roll-out bit for bit; a row beyond T_s is
+        a ValueError before the device is touched.
 
         Returns ``(q, q_prev, F')``: the positions after the last step and one step earlier (for ``num_steps`` = 1: x_f, or
         ``state[0]``), two ``torch.float64`` device tensors (F', N, 3) owned by the caller -- the pair ``state=`` takes.  With
         ``record_every`` a fourth value ``(records, steps)``: a caller-owned (R, F', N, 3) device tensor, each record written
         by the last iteration of its step straight into its slice, and the list of those step numbers; when the last step is
         recorded, ``q`` is the view ``records[-1]``.  Device memory held by the engine beside that of ``solve_frames``: one more
-        tensor of the iterate's size.  Out of scope: collisions, positional constraints, forces other than constant gravity,
+        tensor of the iterate's size.  Out of scope: collisions, forces other than constant gravity,
         more reduced kinds than ``set_reduced_kinds`` allows (1 unless set), the history of step norms, several ranks."""
         who = "simulate_frames"
         self._hyper_check(who, hyper, kinds, False)
         ex, K = self._solve_args(who, dt, velocity, gravity, num_iterations, "explicit", masses)
         T, every = self._rollout_args(who, num_steps, record_every, state)
         frames = self._frames(animation, frame_start, frame_end, frame_jump)
+        pins = self._pins(who, pins, frames, T)
         plan, reds = self._solve_plan(who, kinds, chunk_frames)
         self._rollout_state(who, state, frames.n_sel)
         reds = self._chosen(reds, kinds)
-        self._matrix(plan, ex.masses, ex.dt)
+        self._matrix(plan, ex.masses, ex.dt, pins)
         q, q_prev, records, steps = self._with_operators(
-            reds, hyper, lambda: self._rollout_run(plan, reds, frames, ex, state, K, T, chunk_frames, every, hyper))
+            reds, hyper, lambda: self._rollout_run(plan, reds, frames, ex, state, K, T, chunk_frames, every, hyper, pins))
         return (q, q_prev, frames.n_sel) + (() if every is None else ((records, steps),))
 
     def reduced_rollout_errors(self, kind, basis, r_values, dt, num_steps, num_iterations=10, masses=None, velocity="difference",
                                gravity=(0.0, 0.0, 0.0), elements=None, wi=1.0, reduction="deim_pod", rest_positions=None,
                                sigma_min=1.0, sigma_max=1.0, animation="train", frame_start=0, frame_end=None, frame_jump=1,
-                               record_every=1, hyper=None):
+                               record_every=1, hyper=None, pins=None):
         """Extra: how far the DEIM-reduced SIMULATION drifts from the full one along a trajectory -- ``reduced_solve_errors``
         carried through ``num_steps`` time steps of ``simulate_frames``.  For every r of ``r_values`` and every recorded step
         (``record_every`` = r0: the steps r0, 2 r0, .. <= ``num_steps``) the three metrics of ``(q_t, q~_{r,t})``: both roll-outs
@@ -815,7 +942,9 @@ class ResidentDynamics(object):
 
         Returns ``(fro, max, rel_x, rel_y, rel_z, steps)``: five (len(r_values), R) arrays and the list of the R recorded
         steps.  With ``num_steps=1, record_every=1`` the numbers are those of ``reduced_solve_errors``.  The sweep keeps its
-        one kind whatever ``set_reduced_kinds`` allows: multi-kind sweeps are out of scope."""
+        one kind whatever ``set_reduced_kinds`` allows: multi-kind sweeps are out of scope.  ``pins`` (as ``simulate_frames``)
+        hold both roll-outs, unreduced: the hanging cloth, the clamped bar.  Out of scope: floor collision
+        (``resolve_collision``), self-collisions, several ranks, a reduction of the positions."""
         who = "reduced_rollout_errors"
         self._hyper_check(who, hyper, [dict(basis=basis, num_components=0)], False)
         ex, K = self._solve_args(who, dt, velocity, gravity, num_iterations, "explicit", masses)
@@ -824,6 +953,7 @@ class ResidentDynamics(object):
             raise ValueError("%s: record_every %r: a positive number of time steps" % (who, record_every))
         spec = dict(kind=kind, elements=elements, wi=wi, rest_positions=rest_positions, sigma_min=sigma_min, sigma_max=sigma_max)
         frames = self._frames(animation, frame_start, frame_end, frame_jump)
+        pins = self._pins(who, pins, frames, T)
         terms, (red,) = self._solve_plan(who, [dict(spec, basis=basis, num_components=0, reduction=reduction)], None)
         r_values = [int(r) for r in r_values]
         ops = [red.operator(r) for r in r_values]
@@ -831,8 +961,9 @@ class ResidentDynamics(object):
         out = np.zeros((5, len(ops), len(steps)))
         if not ops:
             return tuple(out) + (steps,)
-        run = lambda rd: self._rollout_run(terms, () if rd is None else (rd,), frames, ex, None, K, T, None, every, None if rd is None else hyper)[2]
-        self._matrix(terms, ex.masses, ex.dt)
+        run = lambda rd: self._rollout_run(terms, () if rd is None else (rd,), frames, ex, None, K, T, None, every, None if rd is None else hyper,
+                                           pins)[2]
+        self._matrix(terms, ex.masses, ex.dt, pins)
         full = run(None)
         self._engine.rforce_operator(terms[0].St, ops[int(np.argmax(r_values))].V)
         if hyper is not None:

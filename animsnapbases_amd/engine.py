@@ -736,6 +736,36 @@ class HipEngine(object):
         self._ck(self.lib.asb_test_pdsolve_state(self.h, int(which), ptr(out), out.shape[0], ld))
         return out
 
+    # ------------------------------------------------------------------ positional constraints (pins)
+    def pins_set(self, vertices, wi, p0, shift=None):
+        """The pins of every later ``pins_term`` / ``pdsolve_pins``: ``vertices`` (P,) of the resident tensor, no two equal,
+        ``wi`` (P,) >= 0, ``p0`` (P, 3), ``shift`` None, (T_s, 3) or (T_s, P, 3); checked and uploaded once."""
+        v = np.ascontiguousarray(vertices, dtype=np.int64)
+        P = int(v.shape[0])
+        wi, p0 = self._vec(wi, (P,)), self._vec(p0, (P, 3))
+        if shift is not None:
+            shift = np.ascontiguousarray(shift, dtype=np.float64)
+            assert shift.shape[1:] in ((3,), (P, 3))
+        self._ck(self.lib.asb_pins_set(self.h, P, ptr(v), ptr(wi), ptr(p0), 0 if shift is None else int(shift.shape[0]), ptr(shift),
+                                       int(shift is not None and shift.ndim == 3)))
+
+    def pins_clear(self):
+        self._ck(self.lib.asb_pins_clear(self.h))
+
+    def pins_term(self, f0, f1, fj, row0, accumulate, out_dev_ptr):
+        """The pin term wi (p0 + shift[row0 + f]) of the frames range(f0, f1, fj) into (``accumulate``: onto the pinned entries
+        of) the caller's device buffer of (F', N, 3) float64."""
+        self._ck(self.lib.asb_pins_term(self.h, int(f0), int(f1), int(fj), int(row0), int(bool(accumulate)), ctypes.c_void_p(int(out_dev_ptr))))
+
+    def fm_add(self, a_dev_ptr, b_dev_ptr, length):
+        """a += b on two device buffers of ``length`` float64 that do not overlap: the add of a solver iteration."""
+        self._ck(self.lib.asb_fm_add(self.h, ctypes.c_void_p(int(a_dev_ptr)), ctypes.c_void_p(int(b_dev_ptr)), int(length)))
+
+    def pdsolve_pins(self, row0=0):
+        """Binds the pins of ``pins_set`` to the solve in progress: their term joins the inertia term, frame f with row
+        ``row0`` + f of the shift, and every later ``pdsolve_advance`` renews it one row further."""
+        self._ck(self.lib.asb_pdsolve_pins(self.h, int(row0)))
+
     # ------------------------------------------------------------------ SPLOCS
     def splocs_begin(self):
         self._ck(self.lib.asb_splocs_begin(self.h))

@@ -336,7 +336,25 @@ def assembly_ST(setup, n_verts, wi=1.0):
     return St
 
 
-def global_matrix(specs, n_verts, masses, dt):
+def pins_ST(vertices, wi, n_verts):
+    """The weighted selection operator of positional constraints, (n_verts, P) CSR with wi_i at (v_i, i): what the reference's
+    ``positional_assembly_ST`` holds (``PositionalConstraint.build_SiT``, Constraint_projections.py:90-92), so that
+    ``pins_ST @ targets`` is the pins' term of the global step's right-hand side (Simulators.py:401-413).  ``vertices`` (P,):
+    integers of 0 .. n_verts - 1, no two equal; ``wi``: a scalar or (P,), finite and >= 0."""
+    from scipy import sparse
+    n_verts = int(n_verts)
+    v = np.asarray(vertices, dtype=np.int64).reshape(-1)
+    w = np.broadcast_to(np.asarray(wi, dtype=np.float64), v.shape)
+    if v.size < 1 or v.min() < 0 or v.max() >= n_verts or np.unique(v).size != v.size:
+        raise ValueError("pins: the vertices must be distinct integers of 0 .. %d" % (n_verts - 1))
+    if not np.isfinite(w).all() or (w < 0.0).any():
+        raise ValueError("pins: every weight wi must be finite and >= 0")
+    St = sparse.coo_matrix((w, (v, np.arange(v.size))), shape=(n_verts, v.size)).tocsr()
+    St.sort_indices()
+    return St
+
+
+def global_matrix(specs, n_verts, masses, dt, pins=None):
     """The system matrix of the global step, A_N = diag(masses) / dt^2 + sum_i w_i S_i^T S_i, (n_verts, n_verts) CSR with sorted
     indices and duplicates summed.  The reference assembles kron(A_N, I_3) from the triplets of ``get_wi_SiT_AiT_Ai_Si``
     (Simulators.py:117-145): no entry couples two coordinates and the three diagonal blocks are equal, so one N x N matrix
@@ -348,6 +366,9 @@ def global_matrix(specs, n_verts, masses, dt):
       tets_*        wi |V0| G G^T on (v1 .. v4), G = [DmInv ; -colsum(DmInv)] (4 x 3) (:559-584, :802-827)
       verts_bending wi_v s s^T, s the constraint's selection row (sum(w) at the vertex, -w_j at every star neighbour, :189-191)
                     and wi_v = wi * (a third of the incident triangle area, :119)
+
+    ``pins``: None or ``(vertices, wi)`` of positional constraints (checked as ``pins_ST`` checks them): wi_i is added at
+    (v_i, v_i), the triplets of ``PositionalConstraint.get_wi_SiT_AiT_Ai_Si`` (:106-113); the pattern does not change.
 
     The reference drops triplets of |value| <= 1e-12 before summing; here nothing is dropped (the matrix stays linear in wi).
     Both triangles are averaged, so the result is symmetric to the bit.  Raises ValueError for a ``dt`` that is not finite and
@@ -370,6 +391,11 @@ def global_matrix(specs, n_verts, masses, dt):
         raise ValueError("global_matrix: every vertex mass must be finite and positive")
     diag = np.arange(n_verts, dtype=np.int64)
     rows, cols, vals = [diag], [diag], [m * (1.0 / (h * h))]
+    if pins is not None:
+        St = pins_ST(pins[0], pins[1], n_verts).tocoo()
+        rows.append(St.row.astype(np.int64))
+        cols.append(St.row.astype(np.int64))
+        vals.append(St.data)
     for spec in specs:
         try:
             setup, wi = spec

@@ -720,12 +720,12 @@ int asb_test_gslab_gemm_time(asb_ctx* ctx, int64_t sp, int64_t w, double* ms_out
 /* The local/global loop of Simulators.py:494-526 for the frames range(f0, f1, fj) of the training (which 0) or held-out (1)
  * tensor, every frame an independent solve: q_{k+1} = A^-1 (sum_i S_i^T p_i(q_k) + M / h^2 s_f) with s_f fixed.  The iterate
  * stays on the device between iterations, vertex-major (row 3 v + d, the frames contiguous, padded to 64), the layout the
- * projection kernels read.  No collisions, no positional constraints.  One rank.  The end of a time step (:531-532) is
- * asb_pdsolve_advance below.
+ * projection kernels read.  No collisions.  Positional constraints: asb_pins_set and asb_pdsolve_pins below.  One rank.  The
+ * end of a time step (:531-532) is asb_pdsolve_advance below.
  * asb_pdsolve_begin: after asb_gstep_setup.  Arguments two to eleven as asb_gstep_inertia; the inertia term diag s_f is
  * formed once with that entry's arithmetic.  start 0: q_0 = s_f (the reference's), 1: q_0 = x_f, 2: q_0 = start_dev, a DEVICE
  * tensor (n_sel, n, 3).  More than 65535 * 64 selected frames: ASB_ERR_LIMIT, judged on the count alone before anything
- * else.  Drops the kinds of the previous solve; its buffers are reused. */
+ * else.  Drops the kinds of the previous solve and its binding of the pins; its buffers are reused. */
 int asb_pdsolve_begin(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean, double psf,
                       const double* diag, int mode, const double* acc3, int start, const double* start_dev);
 /* Registers the kind of the preceding asb_cproj_setup as the next term of the right-hand side: its device tables pass to
@@ -780,6 +780,34 @@ int asb_pdsolve_advance(asb_ctx* ctx);
 int asb_pdsolve_positions(asb_ctx* ctx, double* out_dev);
 /* test hook: the iterate (which 0) or P (1) as stored, (rows = 3 n, ld = n_sel rounded up to 64) with its padding, to the host */
 int asb_test_pdsolve_state(asb_ctx* ctx, int which, double* out_host, int64_t rows, int64_t ld);
+
+/* ------------------------------------------------ projective dynamics: positional constraints (pins) ----------- */
+/* PositionalConstraint of the reference (Constraint_projections.py:77-113), the first summand of b (Simulators.py:401-413,
+ * :513-520): pin i holds vertex verts[i] at p0[i] + shift[row] with weight wi[i].  The weight on A's diagonal is the host's
+ * business (the matrix of asb_gstep_setup / asb_gslab_setup); here the constant wi (p0 + shift[row]) of the right-hand side.
+ * Pins are no kind: they take no slot and do not depend on q.
+ * asb_pins_set: host arrays verts (P) in [0, n) of the tensor on the device, no two equal; wi (P) finite, >= 0; p0 (P, 3) finite;
+ * shift NULL with T_s = 0 (fixed pins) or finite, (T_s, 3) (per_pin 0) or (T_s, P, 3) (per_pin != 0).  Checked, then uploaded once
+ * into buffers the context owns; replaces the previous pins and drops their binding to a solve.  Any violation: ASB_ERR_ARG,
+ * no pins are left.  asb_pins_clear: no pins, no binding (the buffers stay for the next set).
+ * Arithmetic, everywhere: t = fl(p0 + shift[row]) (p0 without a shift), term = fl(wi t) rounded on its own, then the add.
+ * asb_pins_term: the term of the frames range(f0, f1, fj), frame f with row row0 + f, into the caller's DEVICE tensor
+ * (n_sel, n, 3).  accumulate 0: every entry is written, +0.0 where a vertex is not pinned; != 0: out = fl(out + term) at the
+ * pinned entries, nothing else touched.  A row outside shift: ASB_ERR_ARG, nothing launched.  One thread per (frame, pin), no
+ * atomics.  Returns after the stream has drained.
+ * asb_fm_add: a = fl(a + b) entry by entry on two caller-owned DEVICE tensors of len doubles that do not overlap: the add of an
+ * iteration (b += ms), for a caller that forms fl(sum of the kinds + fl(fl(diag s) + pin term)) as a solve does.
+ * asb_pdsolve_pins: after asb_pdsolve_begin (ASB_ERR_ARG before, or a second time).  Binds the context's pins to the solve in
+ * progress and adds their term to the inertia term: frame f reads row row0 + f.  From then on asb_pdsolve_advance launches the
+ * same kernel behind its own with the row raised by one per advance; an advance (or this call) that would read a row >= T_s
+ * returns ASB_ERR_ARG and launches nothing.  asb_pdsolve_iterate, asb_hyper_iterate and the slab path read the inertia term
+ * and are not changed.  In stream order; the call does not wait. */
+int asb_pins_set(asb_ctx* ctx, int64_t P, const int64_t* verts, const double* wi, const double* p0, int64_t T_s, const double* shift,
+                 int per_pin);
+int asb_pins_clear(asb_ctx* ctx);
+int asb_pins_term(asb_ctx* ctx, int64_t f0, int64_t f1, int64_t fj, int64_t row0, int accumulate, double* out_dev);
+int asb_fm_add(asb_ctx* ctx, double* a_dev, const double* b_dev, int64_t len);
+int asb_pdsolve_pins(asb_ctx* ctx, int64_t row0);
 
 /* ------------------------------------------------ SPLOCS refinement ----------- */
 /* posComponents.splocs_glob_optimization, snapbases/posComponents.py:132-189.
