@@ -182,6 +182,10 @@ PROTOTYPES = {
     "asb_gslab_info": (c_int, [ctypes.c_void_p, c_dp]),
     "asb_test_gslab_solve": (c_int, [ctypes.c_void_p, c_dp, c_i64, c_dp]),
     "asb_test_gslab_gemm_time": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_dp]),
+    "asb_gsub_setup": (c_int, [ctypes.c_void_p, c_i64, c_dp, c_dp, c_dp, c_i64, c_dp, c_dp, ctypes.POINTER(c_dbl)]),
+    "asb_gsub_info": (c_int, [ctypes.c_void_p, c_dp]),
+    "asb_test_gsub_apply": (c_int, [ctypes.c_void_p, c_dp, c_i64, c_int, c_dp]),
+    "asb_test_gsub_state": (c_int, [ctypes.c_void_p, c_int, c_dp, c_i64]),
     "asb_pdsolve_begin": (c_int, [ctypes.c_void_p, c_int, c_i64, c_i64, c_i64, c_dp, c_int, c_dbl, c_dp, c_int, c_dp, c_int,
                                   ctypes.c_void_p]),
     "asb_pdsolve_slot": (c_int, [ctypes.c_void_p, c_dbl, c_dbl, c_int, c_i64, c_dp, c_dp, c_dp]),

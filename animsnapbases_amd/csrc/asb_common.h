@@ -37,6 +37,7 @@ struct asb_splocs;
 struct asb_geo;
 struct asb_pds;
 struct asb_gsl;
+struct asb_gsb;
 
 // world positions of the resident tensor (asb_cproj.hip): x = (T * inv_psf + mean) * invm_v
 struct CpWorld {
@@ -376,6 +377,8 @@ struct asb_ctx {
     // the global step's second solver (asb_gslab.hip): the block-tridiagonal slab factor of A_N.  The context holds EITHER
     // gs_Ainv (gs_n > 0) or the factor (asb_gslab_n(ctx) > 0): each set-up releases the other
     asb_gsl* gsl = nullptr;
+    // the third solver (asb_gsub.hip): the step in a position subspace q = o + U z.  One of the three is held at a time
+    asb_gsb* gsb = nullptr;
 
     // ---- profiling of the dominant streaming kernel ----
     bool prof = false;
@@ -393,6 +396,7 @@ void asb_splocs_free(asb_ctx* ctx);
 void asb_geo_free(asb_ctx* ctx);
 void asb_pdsolve_free(asb_ctx* ctx);
 void asb_gslab_free(asb_ctx* ctx);
+void asb_gsub_free(asb_ctx* ctx);
 #define ASB_GEO_CACHE_SLABS 64          // x 64 distance fields
 const double* asb_geo_cached_field(asb_ctx* ctx, long long slot, long long* n_out);
 // small dense linear algebra on the device (asb_linalg.hip)
@@ -492,8 +496,20 @@ int asb_gslab_solve_fm(asb_ctx* ctx, const double* rhs, long long F, double* Qv,
 // Gt (rows, Np) with the n vertices contiguous in a row (the layout of RfBank::M) -> Ot, same layout: Ot[r] = A^-1 Gt[r]; the
 // entries of Ot past vertex n are left as they are
 int asb_gslab_solve_rows(asb_ctx* ctx, const double* Gt, long long rows, long long Np, double* Ot);
-// asb_pdsolve.hip: k_pd_untranspose, P (rows, ld) vertex-major -> out (n_sel, rows) frame-major
+// asb_gsub.hip, the roles of the asb_gslab_* calls above for the position subspace q = o + U z.  asb_gsub_n: the vertices of the
+// subspace the context holds (0: none); asb_gsub_release: freed (every other set-up calls it).  solve_fm: the AFFINE map
+// o' + P rhs with the arguments of asb_gslab_solve_fm (columns [F, ld) of Qv are not written); solve_rows: the LINEAR part P Gt[r]
+// alone, with the arguments of asb_gslab_solve_rows (Np: the subspace's padding, rows = 3 mpp <= 65535)
+long long asb_gsub_n(const asb_ctx* ctx);
+void asb_gsub_release(asb_ctx* ctx);
+int asb_gsub_solve_fm(asb_ctx* ctx, const double* rhs, long long F, double* Qv, double* out);
+int asb_gsub_solve_rows(asb_ctx* ctx, const double* Gt, long long rows, long long Np, double* Ot);
+// asb_rforce.hip: k_st_dense on device arrays, Mt (3, mpp, Np) = (S^T V_d)^T for the CSR (ptr, ci, val) of n_rows rows and V (rows, mp, 3)
+void asb_st_dense_launch(asb_ctx* ctx, const int* ptr, const int* ci, const double* val, const double* V, long long n_rows, int mp, int mpp,
+                         long long Np, double* Mt);
+// asb_pdsolve.hip: k_pd_untranspose, P (rows, ld) vertex-major -> out (n_sel, rows) frame-major; k_pd_transpose, the other way
 void asb_pd_untranspose_launch(asb_ctx* ctx, const double* P, int n_sel, long long rows, long long ld, double* out);
+void asb_pd_transpose_launch(asb_ctx* ctx, const double* in, int n_sel, long long rows, double* Q, long long ld);
 // a host CSR checked (offsets from 0 and not decreasing, columns < n_cols and strictly ascending in a row) and narrowed to int;
 // `what` names the matrix in the messages
 int asb_csr_check32(asb_ctx* ctx, const char* who, int64_t n_rows, const int64_t* indptr, const int64_t* indices, const double* data,

@@ -298,6 +298,7 @@ extern "C" int asb_gslab_setup(asb_ctx* ctx, int64_t n, const int64_t* indptr, c
     asb_rf_invalidate_all(ctx);
     (void)asb_alloc(ctx, &ctx->gs_Ainv, 0);
     asb_gslab_release(ctx);
+    asb_gsub_release(ctx);
     if (nslab > n) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_gslab_setup: %lld slabs for %lld vertices", (long long)nslab, (long long)n);
     if (n + 16 * nslab > 0x7fffffffLL)
         ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_gslab_setup: %lld vertices in %lld slabs: the padded rows do not fit 32-bit indices", (long long)n, (long long)nslab);

@@ -27,6 +27,7 @@
 //                      stores the same values instead of adding them (asb_gs_inertia_launch, for asb_pdsolve_begin).
 // The context holds this inverse OR the block-tridiagonal slab factor of asb_gslab.hip (each set-up releases the other): with the
 // factor held asb_gstep_run goes through its sweep and asb_test_gstep_inverse is refused; with the inverse held nothing changed.
+// The third holder is the position subspace of asb_gsub.hip: asb_gstep_run then applies its affine map o' + P rhs.
 #include "asb_gstep_tile.h"
 
 #include <algorithm>
@@ -110,6 +111,7 @@ extern "C" int asb_gstep_setup(asb_ctx* ctx, int64_t n, const int64_t* indptr, c
     ctx->gs_n = 0;
     asb_rf_invalidate_all(ctx);
     asb_gslab_release(ctx);                                   // the context holds one solver
+    asb_gsub_release(ctx);
     if (n > GS_MAX_N)
         ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_gstep_setup: %lld vertices are too many for an explicit inverse (at most %d)", (long long)n, GS_MAX_N);
     std::vector<int> p32, c32;
@@ -159,7 +161,8 @@ __global__ __launch_bounds__(256) void k_gstep_gemm(const double* __restrict__ r
 
 extern "C" int asb_gstep_run(asb_ctx* ctx, const double* rhs_dev, int64_t n_frames, double* out_dev) {
     if (!ctx || !rhs_dev || !out_dev) return ASB_ERR_ARG;
-    const long long n_slab = asb_gslab_n(ctx);
+    const long long n_sub = asb_gsub_n(ctx);
+    const long long n_slab = n_sub > 0 ? n_sub : asb_gslab_n(ctx);    // (either: the vertices of the solver that is no inverse)
     if (n_slab < 1 && (ctx->gs_n < 1 || !ctx->gs_Ainv)) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_gstep_run: no inverse on the device (asb_gstep_setup)");
     if (n_frames < 1 || (n_frames + GS_TF - 1) / GS_TF > 65535)
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_gstep_run: %lld frames in one call (1 .. %d)", (long long)n_frames, 65535 * GS_TF);
@@ -167,6 +170,12 @@ extern "C" int asb_gstep_run(asb_ctx* ctx, const double* rhs_dev, int64_t n_fram
     if (rhs_dev < out_dev + len && out_dev < rhs_dev + len)
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_gstep_run: the right-hand side and the output overlap (the product is not done in place)");
     ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    if (n_sub > 0) {                                          // the position subspace: in -> reduce -> expand, frame-major too
+        int rc;
+        if ((rc = asb_gsub_solve_fm(ctx, rhs_dev, n_frames, nullptr, out_dev))) return rc;
+        ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return ASB_OK;
+    }
     if (n_slab > 0) {                                         // the slab factor: in -> sweep -> rows -> k_pd_untranspose
         int rc;
         if ((rc = asb_gslab_solve_fm(ctx, rhs_dev, n_frames, nullptr, out_dev))) return rc;

@@ -39,6 +39,8 @@
 // Nothing is split and nothing is atomic: repeats, frame sub-ranges and any chunk width give identical bits.
 // With the slab factor of asb_gslab.hip held instead of the inverse, the product of an iteration, c of a hyper-reduced solve and
 // the operator A^-1 S^T V go through that unit's sweep (asb_gslab_solve_fm / _rows); the history is then refused.
+// With the position subspace of asb_gsub.hip held, the same three go through asb_gsub_solve_fm (the affine map o' + P rhs: the
+// product of an iteration, c) and asb_gsub_solve_rows (its linear part P S^T V: the operator); the history is refused too.
 #include "asb_gstep_tile.h"
 
 #include <algorithm>
@@ -197,10 +199,11 @@ __global__ __launch_bounds__(256) void k_pd_hist(const double* __restrict__ part
     rec[f * 2 + 1] = n2;
 }
 
-// the vertices of the solver the context holds, the explicit inverse or the slab factor (asb_gslab.hip); 0: none
+// the vertices of the solver the context holds: the explicit inverse, the slab factor (asb_gslab.hip) or the position subspace
+// (asb_gsub.hip); 0: none
 static long long pd_solver_n(const asb_ctx* ctx) {
-    const long long m = asb_gslab_n(ctx);
-    return m > 0 ? m : (ctx->gs_Ainv ? ctx->gs_n : 0);
+    const long long m = asb_gslab_n(ctx), u = asb_gsub_n(ctx);
+    return u > 0 ? u : (m > 0 ? m : (ctx->gs_Ainv ? ctx->gs_n : 0));
 }
 
 // ---------------------------------------------------------------- entry points
@@ -300,9 +303,11 @@ extern "C" int asb_pdsolve_iterate(asb_ctx* ctx, int64_t n_iter, int64_t chunk_f
     if (chunk_frames < 0) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_iterate: chunk_frames %lld", (long long)chunk_frames);
     if (pd_solver_n(ctx) != s->n || ctx->n_loc != s->n)
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_iterate: the inverse or the tensor changed since asb_pdsolve_begin");
-    const bool slab = asb_gslab_n(ctx) > 0;
+    const bool slab = asb_gslab_n(ctx) > 0, sub = asb_gsub_n(ctx) > 0;
     if (slab && hist_out)
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_iterate: the history of step norms is not built for the slab factor (asb_gslab_setup)");
+    if (sub && hist_out)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_iterate: the history of step norms is not built for the position subspace (asb_gsub_setup)");
     const long long n_sel = s->n_sel, n = s->n;
     long long cw[PD_MAX_SLOTS];
     size_t scratch = 0;
@@ -319,7 +324,7 @@ extern "C" int asb_pdsolve_iterate(asb_ctx* ctx, int64_t n_iter, int64_t chunk_f
         scratch = std::max<size_t>(scratch, (size_t)3 * p.n_cols * cw[k]);
     }
     ASB_HIP(ctx, hipSetDevice(ctx->dev));
-    const int tiles = slab ? 0 : (int)(ctx->gs_Np / GS_TN);
+    const int tiles = slab || sub ? 0 : (int)(ctx->gs_Np / GS_TN);
     int rc;
     if ((rc = asb_alloc(ctx, &ctx->cf_scratch, scratch))) return rc;
     for (int k = 0; k < s->n_slots; ++k) {          // the coefficients of one chunk, per reduced slot in its bank
@@ -347,6 +352,10 @@ extern "C" int asb_pdsolve_iterate(asb_ctx* ctx, int64_t n_iter, int64_t chunk_f
         }
         hipLaunchKernelGGL(k_pd_add, dim3(g_add), dim3(256), 0, ctx->stream, s->b, s->ms, len);
         const bool fm = out_dev && it == n_iter - 1;
+        if (sub) {                                  // in -> reduce -> expand into the iterate (frame-major too)
+            if ((rc = asb_gsub_solve_fm(ctx, s->b, n_sel, s->Q, fm ? out_dev : nullptr))) return rc;
+            continue;
+        }
         if (slab) {                                 // in -> sweep -> rows into the iterate (-> k_pd_untranspose)
             if ((rc = asb_gslab_solve_fm(ctx, s->b, n_sel, s->Q, fm ? out_dev : nullptr))) return rc;
             continue;
@@ -413,6 +422,11 @@ __global__ __launch_bounds__(256) void k_pd_untranspose(const double* __restrict
     __syncthreads();
     for (int fl = wv; fl < 64; fl += 4)
         if (t0 + fl < n_sel && r0 + lane < rows) out[(long long)(t0 + fl) * rows + r0 + lane] = tile[fl * PD_LDQ + lane];
+}
+
+void asb_pd_transpose_launch(asb_ctx* ctx, const double* in, int n_sel, long long rows, double* Q, long long ld) {
+    hipLaunchKernelGGL(k_pd_transpose, dim3((unsigned)((rows + 63) / 64), (unsigned)((n_sel + 63) / 64)), dim3(256), 0, ctx->stream, in, n_sel, rows,
+                       Q, ld);
 }
 
 void asb_pd_untranspose_launch(asb_ctx* ctx, const double* P, int n_sel, long long rows, long long ld, double* out) {
@@ -814,6 +828,12 @@ extern "C" int asb_hyper_operator(asb_ctx* ctx) {
     int rc;
     if ((rc = asb_alloc(ctx, &b.G, len))) return rc;
     ASB_HIP(ctx, hipMemsetAsync(b.G, 0, len * sizeof(double), ctx->stream));
+    if (asb_gsub_n(ctx) > 0) {                      // the position subspace: G = P S^T V, the linear part of its map
+        if ((rc = asb_gsub_solve_rows(ctx, b.M, 3 * b.mpp, b.Np, b.G))) return rc;
+        ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        b.ok = 1;
+        return ASB_OK;
+    }
     if (asb_gslab_n(ctx) > 0) {                     // the slab factor: the 3 mpp rows of M are the columns of one sweep
         if ((rc = asb_gslab_solve_rows(ctx, b.M, 3 * b.mpp, b.Np, b.G))) return rc;
         ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -883,7 +903,9 @@ extern "C" int asb_hyper_iterate(asb_ctx* ctx, int64_t n_iter, int64_t n_touched
     }
     if ((rc = asb_alloc(ctx, &s->c, (size_t)3 * n * ld))) return rc;
     ASB_HIP(ctx, hipMemsetAsync(s->c, 0, (size_t)3 * n * ld * sizeof(double), ctx->stream));
-    if (asb_gslab_n(ctx) > 0) {                     // c through the slab factor: in -> sweep -> rows
+    if (asb_gsub_n(ctx) > 0) {                      // c = o' + P ms through the position subspace
+        if ((rc = asb_gsub_solve_fm(ctx, s->ms, n_sel, s->c, nullptr))) return rc;
+    } else if (asb_gslab_n(ctx) > 0) {              // c through the slab factor: in -> sweep -> rows
         if ((rc = asb_gslab_solve_fm(ctx, s->ms, n_sel, s->c, nullptr))) return rc;
     } else {
         hipLaunchKernelGGL((k_pdsolve_gemm<false, false>), dim3((unsigned)(ctx->gs_Np / GS_TN), (unsigned)((n_sel + GS_TF - 1) / GS_TF)), dim3(256), 0,

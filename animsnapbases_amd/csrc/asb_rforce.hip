@@ -116,6 +116,11 @@ __global__ __launch_bounds__(256) void k_rforce_gemm(const double* __restrict__ 
     }
 }
 
+void asb_st_dense_launch(asb_ctx* ctx, const int* ptr, const int* ci, const double* val, const double* V, long long n_rows, int mp, int mpp,
+                         long long Np, double* Mt) {
+    hipLaunchKernelGGL(k_st_dense, dim3((unsigned)((n_rows * mp + 255) / 256)), dim3(256), 0, ctx->stream, ptr, ci, val, V, n_rows, mp, mpp, Np, Mt);
+}
+
 extern "C" int asb_rforce_operator(asb_ctx* ctx, int64_t n_rows, const int64_t* indptr, const int64_t* indices, const double* data,
                                    int64_t v_rows, int64_t mp, const double* V) {
     if (!ctx || !indptr || !V || n_rows < 1) return ASB_ERR_ARG;

@@ -1,7 +1,8 @@
 """``ResidentDynamics`` -- what ``posSnapshots`` offers beyond the reference's class: the pieces of the reference's
 projective-dynamics solver (Simulators.py) evaluated on the device for the frames of the resident animation -- constraint
 projections, constraint forces, their DEIM reduction, the global step, the solver's iterations and its time steps, with the choice of the global step's solver and
-of how many kinds a solve may reduce, and the positional constraints (pins) of every such call.
+of how many kinds a solve may reduce, the positional constraints (pins) of every such call, and the global step in a position
+subspace q = o + U z.
 A public call checks its arguments into the named records below before the engine is touched; the helpers take the records.
 """
 import collections
@@ -50,7 +51,8 @@ class ResidentDynamics(object):
     """Mixin of ``posSnapshots``.  Reads from the host object: ``_engine``, ``_comm``, ``nVerts``, ``frs``, ``verts``, ``tris``,
     ``test_verts``, ``mass``, ``massL``, ``invMassL``, ``_standarize``, ``pre_scale_factor``, ``mean`` and ``snapTensor``.
     Leaves: ``assembly_ST``, ``bending_indices``, ``global_matrix``, ``global_solve_residual`` and, under the slab solver
-    (``set_global_solver``), ``global_solve_slabs`` = (slabs, vertices of the largest)."""
+    (``set_global_solver``), ``global_solve_slabs`` = (slabs, vertices of the largest); under the position subspace,
+    ``global_solve_subspace`` = r."""
 
     # ------------------------------------------------------------------ the records of a call
     def _frames(self, animation, frame_start, frame_end, frame_jump):
@@ -416,7 +418,7 @@ class ResidentDynamics(object):
         pins = self._pins("global_solve_setup", pins)
         self._matrix(self._plan(kinds), self._masses(masses), dt, pins)
 
-    def set_global_solver(self, kind="inverse", slab_target=None):
+    def set_global_solver(self, kind="inverse", slab_target=None, basis=None, num_components=None, origin=None):
         """Extra: how every later call of this object applies A^-1 -- ``global_solve``, ``global_step``, ``solve_frames``,
         ``simulate_frames`` and the four ``reduced_*_errors`` sweeps that solve.
 
@@ -428,9 +430,28 @@ class ResidentDynamics(object):
         ``projections.SLAB_TARGET`` (256); only with "slab".  Results of the two solvers agree to rounding (64 eps kappa(A)
         max |q| each), not to the bit; under either, repeats, frame sub-ranges and chunk widths give identical bits.
         Out of scope under "slab": ``history=True`` of ``solve_frames`` (ValueError).  The arguments are checked before the
-        device is touched; the device's solver is replaced by the next call that needs the matrix."""
-        if kind not in ("inverse", "slab"):
-            raise ValueError("set_global_solver: kind must be 'inverse' or 'slab', not %r" % (kind,))
+        device is touched; the device's solver is replaced by the next call that needs the matrix.
+
+        "subspace": the global step in a POSITION subspace q = o + U z, the reference's ``reduced_position`` branch
+        (Simulators.py:38-41, :144-155, which it leaves unimplemented): per coordinate the Galerkin step
+        q_d = o_d + U_d (U_d^T A U_d)^-1 U_d^T (rhs_d - A o_d) replaces A^-1 rhs_d everywhere (csrc/asb_gsub.hip).
+        This is no approximation of A^-1 to rounding: results differ from the other two solvers by the part of the step outside
+        the subspace.  ``basis``: a world-space array (K, N, 3), the path of a ``.npy`` holding one, or a ``posComponents`` (its
+        ``comps``, taken back to world space with its snapshots' ``invMassL`` where they live in the mass-weighted space); only
+        the span matters (``projections.subspace_basis`` orthonormalises per coordinate and refuses a rank-deficient basis).
+        ``num_components`` = r: the first r components (None: all K).  ``origin``: None takes the rest positions (frame 0 of the
+        world-space input, resolved when the matrix is set up) or an (N, 3) array.  The three are for "subspace" only.  Pins need
+        nothing new: their weights are in A, their term in the right-hand side.  Held on the device: 2 x 3 r N doubles and
+        3 r F' more in a solve.  Out of scope under "subspace": ``history=True`` (ValueError), a roll-out whose state lives in z,
+        an M-orthogonal basis, several ranks.  Limits under "subspace": r <= min(N, 8192) (ValueError here, before the device is
+        touched); with ``hyper`` a reduced kind of at most 21 845 basis vectors (the engine refuses more; 65 532 under the other
+        two solvers: the operator's rows go through one grid dimension).  Leaves ``self.global_solve_subspace`` = r after the next set-up."""
+        if kind not in ("inverse", "slab", "subspace"):
+            raise ValueError("set_global_solver: kind must be 'inverse' or 'slab', not %r (or 'subspace', with a basis)" % (kind,))
+        if kind != "subspace":
+            for name, given in (("basis", basis), ("num_components", num_components), ("origin", origin)):
+                if given is not None:
+                    raise ValueError("set_global_solver: %s is for kind='subspace' only" % name)
         if slab_target is not None:
             if kind != "slab":
                 raise ValueError("set_global_solver: slab_target is for kind='slab' only")
@@ -441,12 +462,38 @@ class ResidentDynamics(object):
             if t != slab_target or isinstance(slab_target, bool) or t < 1:
                 raise ValueError("set_global_solver: slab_target %r: a positive number of vertices per slab or None" % (slab_target,))
             slab_target = t
-        self._global_solver = (kind, slab_target)
+        subspace = None
+        if kind == "subspace":
+            subspace = self._subspace_args("set_global_solver", basis, num_components, origin)
+        self._global_solver, self._global_subspace = (kind, slab_target), subspace
+
+    def _subspace_args(self, who, basis, num_components, origin):
+        """The checked ``(Qt, origin or None)`` of a position subspace: Qt (3, r, N) from ``projections.subspace_basis``."""
+        if basis is None:
+            raise ValueError("%s: kind='subspace' needs a basis: a (K, N, 3) array, the path of a .npy or a posComponents" % who)
+        try:
+            Qt = _proj.subspace_basis(basis, num_components, self.nVerts)
+        except ValueError as e:
+            raise ValueError("%s: %s" % (who, e))
+        if Qt.shape[1] > _proj.SUBSPACE_MAX_R:
+            raise ValueError("%s: %d components: the engine holds at most %d per coordinate" % (who, Qt.shape[1], _proj.SUBSPACE_MAX_R))
+        if origin is not None:
+            try:
+                origin = np.array(origin, dtype=np.float64)
+            except (TypeError, ValueError):
+                origin = np.zeros(0)
+            if origin.shape != (self.nVerts, 3) or not np.isfinite(origin).all():
+                raise ValueError("%s: origin of shape %s: a finite (%d, 3) array or None expected" % (who, origin.shape, self.nVerts))
+        return Qt, origin
 
     def _slab_solver(self):
-        """None under the explicit inverse, else the slab target in force."""
+        """None under the explicit inverse and under the position subspace, else the slab target in force."""
         kind, target = getattr(self, "_global_solver", ("inverse", None))
-        return None if kind == "inverse" else (_proj.SLAB_TARGET if target is None else target)
+        return None if kind != "slab" else (_proj.SLAB_TARGET if target is None else target)
+
+    def _subspace_solver(self):
+        """None unless the position subspace is selected, else its ``(Qt, origin or None)``."""
+        return getattr(self, "_global_subspace", None) if getattr(self, "_global_solver", ("inverse", None))[0] == "subspace" else None
 
     def _matrix(self, plan, masses, dt, pins=None):
         """A of the plan (and the pins' weights on its diagonal), inverted (or, under the slab solver, factorised) on the device
@@ -456,6 +503,16 @@ class ResidentDynamics(object):
         else:
             A = _proj.global_matrix([(t.setup, t.wi) for t in plan], self.nVerts, masses, dt, (pins.vertices, pins.wi))
         self.global_matrix, self.global_solve_residual = None, None
+        sub = self._subspace_solver()
+        if sub is not None:
+            self.global_solve_subspace = None
+            Qt, origin = sub
+            origin = np.ascontiguousarray(self._rest() if origin is None else origin, dtype=np.float64)
+            resid = self._engine.gsub_held(A, Qt, origin)
+            if resid is None:
+                resid = self._engine.gsub_setup(A, Qt, origin)
+            self.global_matrix, self.global_solve_residual, self.global_solve_subspace = A, resid, int(Qt.shape[1])
+            return
         target = self._slab_solver()
         if target is not None:
             self.global_solve_slabs = None
@@ -474,7 +531,9 @@ class ResidentDynamics(object):
     def global_solve(self, rhs):
         """Extra: q = A^-1 rhs per coordinate for the matrix of the last ``global_solve_setup``.  ``rhs``: a caller-owned
         ``torch.float64`` device tensor (F', N, 3), contiguous; returns a new one of the same shape, owned by the caller.  The
-        sum over the vertices is never split: a frame's result does not depend on the frames around it."""
+        sum over the vertices is never split: a frame's result does not depend on the frames around it.  Under
+        ``set_global_solver("subspace")`` the result is the AFFINE Galerkin step o' + P rhs, o' = o - P A o: a zero rhs gives o', not
+        zero, and q - o always lies in span(U)."""
         self._one_rank("global_solve")
         if getattr(self, "global_matrix", None) is None:
             raise ValueError("global_solve: no system matrix on the device, call global_solve_setup first")
@@ -565,7 +624,8 @@ class ResidentDynamics(object):
         q_{k+1} = c + sum_k G_k coef_k(q_k), every coef_k from the OLD iterate -- the Jacobi update of the reference, whose
         groups' terms are summed before its one solve --, "touched" running on the union of the kinds' touched vertices
         (DESIGN.md 3.18).  Out of scope for ``hyper`` unless ``set_reduced_kinds`` raises the limit: several reduced kinds in one solve; always:
-        the history, a reduction of the positions themselves (a basis U of q), several ranks.  Not part of a solve, with or
+        the history, several ranks.  (No longer on this list: a reduction of the positions themselves, a basis U of q, is
+        ``set_global_solver("subspace")`` and combines with ``hyper``.)  Not part of a solve, with or
         without ``hyper``: velocities carried between frames or steps -- that is ``simulate_frames``, which takes ``hyper`` too.
 
         ``pins``: the positional constraints of ``constraint_forces``.  Their weights join A; their term wi (p0 + shift[row]) does
@@ -767,6 +827,9 @@ class ResidentDynamics(object):
         if history and self._slab_solver() is not None:
             raise ValueError("%s: history=True under set_global_solver('slab'): the step norms are formed by the explicit inverse's "
                              "product kernel and are out of scope for the slab solver" % who)
+        if history and self._subspace_solver() is not None:
+            raise ValueError("%s: history=True under set_global_solver('subspace'): the step norms are formed by the explicit inverse's "
+                             "product kernel and are out of scope for the position subspace" % who)
         ex, K = self._solve_args(who, dt, velocity, gravity, num_iterations, start, masses)
         frames = self._frames(animation, frame_start, frame_end, frame_jump)
         pins = self._pins(who, pins, frames)
@@ -813,6 +876,40 @@ class ResidentDynamics(object):
         return out
 
     reduced_solve_errors.__doc__ %= _SOLVE_SCOPE
+
+    def subspace_solve_errors(self, kinds, basis, r_values, dt, num_iterations=10, masses=None, velocity="difference",
+                              gravity=(0.0, 0.0, 0.0), start="explicit", animation="train", frame_start=0, frame_end=None, frame_jump=1,
+                              chunk_frames=None, per_frame=False, pins=None, origin=None):
+        """Extra: how far the POSITION-reduced solve is from the full one -- for every r of ``r_values`` the three metrics of
+        ``(q, q~_r)``, q = ``solve_frames`` of these kinds under the solver selected now ("inverse" or "slab") and q~_r the same
+        solve under ``set_global_solver("subspace", basis=basis, num_components=r, origin=origin)``.  Arguments as
+        ``solve_frames`` without ``hyper`` and ``history`` (entries of ``kinds`` may be reduced), ``basis`` and ``origin`` as
+        ``set_global_solver``; every r is checked (rank included) before the device is touched.  The same five lists
+        ``fro, max, rel_x, rel_y, rel_z`` and, with ``per_frame``, the (len(r_values), F') array |q[f] - q~_r[f]| / |q[f]|.  The
+        full solve runs once, one subspace set-up and solve per r; every tensor stays on the device and is compared there.  The
+        solver selected for this object is the same afterwards.  Out of scope: sweeps over r along roll-outs."""
+        who = "subspace_solve_errors"
+        if self._subspace_solver() is not None:
+            raise ValueError("%s: the full solve runs under 'inverse' or 'slab': set_global_solver('subspace') is in force" % who)
+        subs = [self._subspace_args(who, basis, r, origin) for r in r_values]     # (r unchanged: 2.5 and True are refused)
+        args = dict(masses=masses, velocity=velocity, gravity=gravity, start=start, animation=animation, frame_start=frame_start,
+                    frame_end=frame_end, frame_jump=frame_jump, chunk_frames=chunk_frames, pins=pins)
+        if not subs:
+            return self._diff_metrics(None, [], 0, per_frame)
+        full, n_sel = self.solve_frames(kinds, dt, num_iterations, **args)
+        selected = (self._global_solver if hasattr(self, "_global_solver") else None, getattr(self, "_global_subspace", None))
+
+        def under(sub):
+            self._global_solver, self._global_subspace = ("subspace", None), sub
+            return self.solve_frames(kinds, dt, num_iterations, **args)[0]
+        try:
+            return self._diff_metrics(full, (under(sub) for sub in subs), n_sel, per_frame)
+        finally:
+            if selected[0] is None:
+                del self._global_solver
+            else:
+                self._global_solver = selected[0]
+            self._global_subspace = selected[1]
 
     # ------------------------------------------------------------------ time steps: the velocity carried from step to step
     @staticmethod
@@ -944,7 +1041,7 @@ class ResidentDynamics(object):
         steps.  With ``num_steps=1, record_every=1`` the numbers are those of ``reduced_solve_errors``.  The sweep keeps its
         one kind whatever ``set_reduced_kinds`` allows: multi-kind sweeps are out of scope.  ``pins`` (as ``simulate_frames``)
         hold both roll-outs, unreduced: the hanging cloth, the clamped bar.  Out of scope: floor collision
-        (``resolve_collision``), self-collisions, several ranks, a reduction of the positions."""
+        (``resolve_collision``), self-collisions, several ranks, a sweep over the ranks of a position subspace."""
         who = "reduced_rollout_errors"
         self._hyper_check(who, hyper, [dict(basis=basis, num_components=0)], False)
         ex, K = self._solve_args(who, dt, velocity, gravity, num_iterations, "explicit", masses)

@@ -590,7 +590,7 @@ class HipEngine(object):
         the context.  Returns max |A (A^-1 1) - 1|."""
         n, indptr, indices, data = self._csr(A)
         res = ctypes.c_double()
-        self._gstep = self._gslab = None            # (the context holds one solver: the set-up releases a slab factor)
+        self._gstep = self._gslab = self._gsub = None       # (the context holds one solver: the set-up releases the others)
         self._ck(self.lib.asb_gstep_setup(self.h, n, ptr(indptr), ptr(indices), ptr(data), ctypes.byref(res)))
         self._gstep = (indptr.copy(), indices.copy(), data.copy(), res.value)      # (copies: A stays the caller's)
         return res.value
@@ -630,7 +630,7 @@ class HipEngine(object):
         order = np.ascontiguousarray(plan.order, dtype=np.int64)
         sptr = np.ascontiguousarray(plan.slab_ptr, dtype=np.int64)
         res = ctypes.c_double()
-        self._gstep = self._gslab = None
+        self._gstep = self._gslab = self._gsub = None
         self._ck(self.lib.asb_gslab_setup(self.h, n, ptr(indptr), ptr(indices), ptr(data), int(sptr.shape[0]) - 1, ptr(sptr),
                                           ptr(order), ctypes.byref(res)))
         info = self.gslab_info()
@@ -665,6 +665,61 @@ class HipEngine(object):
         out = np.empty_like(rhs)
         self._ck(self.lib.asb_test_gslab_solve(self.h, ptr(rhs), int(rhs.shape[1]), ptr(out)))
         return out
+
+    def gsub_setup(self, A, Qt, origin):
+        """The position subspace q = o + U z as the global step's solver: ``A`` as ``gstep_setup`` takes it, ``Qt`` (3, r, N) the
+        transposed basis per coordinate (``projections.subspace_basis``: orthonormal rows) and ``origin`` (N, 3).  The subspace
+        replaces the explicit inverse or the slab factor in the context; every later ``gstep_run``, ``pdsolve_*`` and ``hyper_*``
+        call applies o' + U (U^T A U)^-1 U^T rhs (``hyper_operator``: its linear part).  Returns max |U^T (A (P 1) - 1)|."""
+        n, indptr, indices, data = self._csr(A)
+        Qt = np.ascontiguousarray(Qt, dtype=np.float64)
+        assert Qt.ndim == 3 and Qt.shape[0] == 3 and Qt.shape[2] == n
+        origin = self._vec(origin, (n, 3))
+        res = ctypes.c_double()
+        self._gstep = self._gslab = self._gsub = None
+        self._ck(self.lib.asb_gsub_setup(self.h, n, ptr(indptr), ptr(indices), ptr(data), int(Qt.shape[1]), ptr(Qt), ptr(origin),
+                                         ctypes.byref(res)))
+        self._gsub = (indptr.copy(), indices.copy(), data.copy(), Qt.copy(), origin.copy(), res.value)
+        return res.value
+
+    def gsub_held(self, A, Qt, origin):
+        """The residual of the last ``gsub_setup`` if its matrix, basis and origin were these entry for entry (the subspace is
+        still on the device), else None."""
+        held = getattr(self, "_gsub", None)
+        if held is None or held[0].shape[0] != A.shape[0] + 1:
+            return None
+        same = all(np.array_equal(h, a) for h, a in zip(held[:5], (A.indptr, A.indices, A.data, Qt, origin)))
+        return held[5] if same else None
+
+    def gsub_info(self):
+        """(r, r rounded up to 16, N rounded up to 32, r rounded up to 4) of the subspace on the device."""
+        out = np.zeros(4, dtype=np.int64)
+        self._ck(self.lib.asb_gsub_info(self.h, ptr(out)))
+        return out
+
+    def gsub_apply(self, rhs, affine=True, out=None):
+        """Test hook: o' + P ``rhs`` (``affine`` False: P ``rhs``) for a host array (3 N, w), row 3 v + d, through the device's
+        two products.  Returns the whole (3 N, ld) matrix, ld = w rounded up to 64, as it came back: its columns past w are
+        those of ``out`` (default NaN), which the device must not have written."""
+        rhs = np.ascontiguousarray(rhs, dtype=np.float64)
+        assert rhs.ndim == 2 and rhs.shape[0] == 3 * self.N_glob and rhs.shape[1] >= 1
+        ld = (rhs.shape[1] + 63) // 64 * 64
+        out = np.full((rhs.shape[0], ld), np.nan) if out is None else np.ascontiguousarray(out, dtype=np.float64)
+        assert out.shape == (rhs.shape[0], ld)
+        self._ck(self.lib.asb_test_gsub_apply(self.h, ptr(rhs), int(rhs.shape[1]), int(bool(affine)), ptr(out)))
+        return out
+
+    def gsub_state(self):
+        """Test hook: what ``gsub_setup`` left -- ``(W, Ainv, origin', Ut)``: W_d = (U_d^T A U_d)^-1 U_d^T (3, r, N), the inverses
+        (3, r, r), o' (N, 3) and the basis as uploaded (3, r, N), without their padding."""
+        r, rq, Np, rp = (int(x) for x in self.gsub_info())
+        n = self.N_glob
+        raw = []
+        for which, shape in enumerate(((3, Np, rq), (3, rq, rq), (n, 3), (3, rp, Np))):
+            a = np.empty(shape)
+            self._ck(self.lib.asb_test_gsub_state(self.h, which, ptr(a), int(a.size)))
+            raw.append(a)
+        return (np.ascontiguousarray(raw[0][:, :n, :r].transpose(0, 2, 1)), raw[1][:, :r, :r].copy(), raw[2], raw[3][:, :r, :n].copy())
 
     # ------------------------------------------------------------------ solver iterations of projective dynamics
     def pdsolve_begin(self, which, f0, f1, fj, inv_massL, add_mean, psf, diag, mode, acc, start, start_dev_ptr=None):

@@ -486,6 +486,64 @@ def check_slab_plan(A_perm, slab_ptr):
                          % (rows[e], A_perm.indices[e], slab[rows[e]], slab[A_perm.indices[e]]))
 
 
+SUBSPACE_MAX_R = 8192       # the engine's limit of a position subspace (GB_MAX_R of csrc/asb_gsub.hip): three dense r x r inverses
+
+
+def subspace_basis(basis, num_components=None, n_verts=None):
+    """The host preparation of the global step's position subspace q = o + U z (csrc/asb_gsub.hip): per coordinate d a thin
+    Euclidean QR of U_d = comps[:r, :, d].T (N x r); returns ``Qt`` (3, r, N) float64 with Qt[d] = Q_d^T.  Q_d spans what U_d
+    spans, so the Galerkin projection is the same, and kappa(Q_d^T A Q_d) <= kappa(A).
+
+    ``basis``: a world-space array (K, N, 3), the path of a ``.npy`` holding one, or a ``posComponents`` -- its ``comps``,
+    multiplied by its snapshots' ``invMassL`` where they live in the mass-weighted space (snapshots with masses, unless
+    ``post_process_components`` has run with ``q_massWeight`` and taken them back: the class's ``_comps_post_processed``
+    says so); scale does not matter, only the span.  ``num_components`` = r: the first
+    r components, None: all K.  ``n_verts``: the N the basis must have (None: not checked).  The input is left untouched.
+    ValueError: a wrong shape, r outside 1 .. K, r > N, entries that are not finite, and a rank-deficient U_d, named by its
+    coordinate -- min |R_ii| <= N eps max |R_ii| (the convention of ``numpy.linalg.matrix_rank``)."""
+    if isinstance(basis, (str, bytes)) or hasattr(basis, "__fspath__"):
+        try:
+            comps = np.load(basis)
+        except (OSError, ValueError) as e:
+            raise ValueError("subspace_basis: no array could be read from %r (%s)" % (basis, e))
+    elif hasattr(basis, "comps"):
+        comps = np.asarray(basis.comps, dtype=np.float64)
+        snaps = getattr(basis, "pos_snapshots", None)
+        inv = getattr(snaps, "invMassL", None)
+        # un-weighted already only where post_process_components HAS run with q_massWeight (the class's own flag says whether)
+        done = bool(getattr(basis, "_comps_post_processed", False)) and bool(getattr(getattr(basis, "param", None), "q_massWeight", False))
+        if inv is not None and comps.ndim == 3 and not done:
+            comps = comps * np.asarray(inv, dtype=np.float64)[None, :, None]
+    else:
+        comps = basis
+    try:
+        comps = np.asarray(comps, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("subspace_basis: the basis is no numeric array")
+    if comps.ndim != 3 or comps.shape[2] != 3 or comps.shape[0] < 1 or comps.shape[1] < 1:
+        raise ValueError("subspace_basis: a basis of shape %s: (K, N, 3) expected" % (comps.shape,))
+    K, N = comps.shape[:2]
+    if n_verts is not None and N != n_verts:
+        raise ValueError("subspace_basis: the basis has %d vertices, the snapshots %d" % (N, n_verts))
+    r = K if num_components is None else num_components
+    if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 1 <= r <= K:
+        raise ValueError("subspace_basis: num_components %r: an integer 1 .. %d (the basis' components) or None" % (num_components, K))
+    r = int(r)
+    if r > N:
+        raise ValueError("subspace_basis: %d components for %d vertices: at most N per coordinate" % (r, N))
+    if not np.isfinite(comps[:r]).all():
+        raise ValueError("subspace_basis: the basis holds entries that are not finite")
+    Qt = np.empty((3, r, N))
+    for d in range(3):
+        Q, R = np.linalg.qr(comps[:r, :, d].T)
+        diag = np.abs(np.diag(R))
+        if diag.min() <= N * np.finfo(np.float64).eps * diag.max():
+            raise ValueError("subspace_basis: the first %d components are rank deficient in coordinate %s (min |R_ii| = %.3g, max %.3g)"
+                             % (r, "xyz"[d], diag.min(), diag.max()))
+        Qt[d] = Q.T
+    return Qt
+
+
 def project_host(setup, positions, sigma_min=1.0, sigma_max=1.0):
     """NumPy restatement of ``get_pi`` for every element and frame: positions (F, N, 3) -> (F, n p, 3).  For scale and for
     checks on small shapes only; the product path is the device kernel."""

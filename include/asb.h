@@ -692,7 +692,8 @@ int asb_test_gstep_inverse(asb_ctx* ctx, double* out_host, int64_t n);
 
 /* ------------------------------- global step: the block-tridiagonal slab factor (asb_gslab.hip) ---- */
 /* The second solver of the global step, for any n that fits the memory.  The context holds EITHER the explicit inverse of
- * asb_gstep_setup OR this factor: each set-up releases the other and invalidates the operator of asb_hyper_operator.  With the
+ * asb_gstep_setup OR this factor (or the position subspace of asb_gsub_setup below): each set-up releases the others and
+ * invalidates the operator of asb_hyper_operator.  With the
  * factor held, asb_gstep_run, asb_pdsolve_begin / _iterate, asb_hyper_operator and asb_hyper_iterate apply A^-1 through it;
  * asb_pdsolve_iterate with a history and asb_test_gstep_inverse are refused (ASB_ERR_ARG).
  * asb_gslab_setup: A_N as the HOST CSR of asb_gstep_setup, with that entry's checks, plus a slab plan (projections.slab_plan):
@@ -715,6 +716,33 @@ int asb_test_gslab_solve(asb_ctx* ctx, const double* rhs_host, int64_t w, double
 /* timing hook: ms_out (2) = best of three of the sweep's product kernel and of asb_gemm_nn on the same (sp x sp) (sp x w) product
  * of zero-filled device buffers; sp a multiple of 16 (<= 8192), w of 64 */
 int asb_test_gslab_gemm_time(asb_ctx* ctx, int64_t sp, int64_t w, double* ms_out);
+
+/* ------------------------------- global step in a position subspace q = o + U z (asb_gsub.hip) ---- */
+/* The third solver of the global step: per coordinate d the Galerkin step q_d = o_d + U_d (U_d^T A U_d)^-1 U_d^T (rhs_d - A o_d)
+ * = o'_d + P_d rhs_d for a basis U_d (n x r) of full column rank and an origin o (the reference's reduced_position branch,
+ * Simulators.py:38-41, :144-155).  The context holds exactly ONE of the explicit inverse, the slab factor and this subspace:
+ * each set-up releases the other two and invalidates the operator of asb_hyper_operator in every bank.  With the subspace held,
+ * asb_gstep_run and the product of asb_pdsolve_iterate apply the AFFINE map, c of asb_hyper_iterate is o' + P ms, and
+ * asb_hyper_operator forms G = P S^T V (the LINEAR part); asb_pdsolve_iterate with a history is refused (ASB_ERR_ARG).
+ * asb_gsub_setup: A_N as the HOST CSR of asb_gstep_setup with that entry's checks; Qt_host (3, r, n) = U_d^T (any basis of the
+ * span; the host passes orthonormal columns, projections.subspace_basis); origin_host (n, 3).  n < 1, r < 1 or a NULL pointer:
+ * ASB_ERR_ARG, judged on the counts before anything behind a pointer is read; r > n and values that are not finite:
+ * ASB_ERR_ARG; r > 8192: ASB_ERR_LIMIT.  A U_d by the sparse x dense kernel of asb_rforce_operator, U_d^T (A U_d) and its SPD
+ * inverse (padded to a multiple of 16 by an identity block) by the dense layer; not positive definite: ASB_ERR_NUMERIC, no
+ * solver is left.  Kept: U^T (3, rp, Np), W^T = U (U^T A U)^-1 (3, Np, rq), the inverses, o' (rp, rq: r rounded up to 4 and 16,
+ * Np: n to 32).  resid_out (optional): max_d max |U_d^T (A (P_d 1) - 1)| as the device computed it.
+ * The map is two f64-MFMA products, Y = W R over all vertices (never split between blocks) and Q = o' + U Y; no atomics: an
+ * entry does not depend on the columns around it, on chunk_frames, on the touched set or on a repeat. */
+int asb_gsub_setup(asb_ctx* ctx, int64_t n, const int64_t* indptr, const int64_t* indices, const double* data, int64_t r,
+                   const double* Qt_host, const double* origin_host, double* resid_out);
+/* counts_out (4): r, rq, Np, rp */
+int asb_gsub_info(asb_ctx* ctx, int64_t* counts_out);
+/* test hook: rhs_host (3 n, w) vertex-major (row 3 v + d), any w >= 1; out_host (3 n, ld), ld = w rounded up to 64, is read and
+ * written: columns [0, w) become o' affine + P rhs (affine 0: the linear part), the others come back as they went in */
+int asb_test_gsub_apply(asb_ctx* ctx, const double* rhs_host, int64_t w, int affine, double* out_host);
+/* test hook: what the set-up left, as it lies on the device; which 0: W^T (3, Np, rq), 1: the inverses (3, rq, rq), 2: o' (n, 3),
+ * 3: U^T (3, rp, Np); len = the doubles of out_host (checked) */
+int asb_test_gsub_state(asb_ctx* ctx, int which, double* out_host, int64_t len);
 
 /* ------------------------------------------------ projective dynamics: the solver's iterations (asb_pdsolve.hip) ----------- */
 /* The local/global loop of Simulators.py:494-526 for the frames range(f0, f1, fj) of the training (which 0) or held-out (1)
