@@ -186,6 +186,16 @@ PROTOTYPES = {
     "asb_gsub_info": (c_int, [ctypes.c_void_p, c_dp]),
     "asb_test_gsub_apply": (c_int, [ctypes.c_void_p, c_dp, c_i64, c_int, c_dp]),
     "asb_test_gsub_state": (c_int, [ctypes.c_void_p, c_int, c_dp, c_i64]),
+    "asb_gsub_coordinates": (c_int, [ctypes.c_void_p, c_int, c_i64, c_i64, c_i64, c_dp, c_int, c_dbl, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
+    "asb_gsub_expand": (c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
+    "asb_zroll_operator": (c_int, [ctypes.c_void_p]),
+    "asb_zroll_begin": (c_int, [ctypes.c_void_p, c_int, c_i64, c_i64, c_i64, c_dp, c_int, c_dbl, c_dp, c_int, c_dp, c_i64, c_dp,
+                                ctypes.c_void_p, ctypes.c_void_p]),
+    "asb_zroll_slot": (c_int, [ctypes.c_void_p, c_dbl, c_dbl]),
+    "asb_zroll_pins": (c_int, [ctypes.c_void_p, c_i64]),
+    "asb_zroll_steps": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, ctypes.c_void_p]),
+    "asb_zroll_state": (c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "asb_test_zroll_affine": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, c_int, c_dp]),
     "asb_pdsolve_begin": (c_int, [ctypes.c_void_p, c_int, c_i64, c_i64, c_i64, c_dp, c_int, c_dbl, c_dp, c_int, c_dp, c_int,
                                   ctypes.c_void_p]),
     "asb_pdsolve_slot": (c_int, [ctypes.c_void_p, c_dbl, c_dbl, c_int, c_i64, c_dp, c_dp, c_dp]),

@@ -38,6 +38,7 @@ struct asb_geo;
 struct asb_pds;
 struct asb_gsl;
 struct asb_gsb;
+struct asb_zr;
 
 // world positions of the resident tensor (asb_cproj.hip): x = (T * inv_psf + mean) * invm_v
 struct CpWorld {
@@ -357,6 +358,8 @@ struct asb_ctx {
         int ok = 0;                       // G belongs to the current solver and M (a new system matrix clears it in every
                                           // bank, asb_rforce_operator in its own)
         double* Gc = nullptr;             // asb_hyper_iterate: the touched columns of G, (3, mpp, N_t rounded up to 32, zero padding)
+        double* Gz = nullptr;             // asb_zroll_operator: (At^-1 U^T M_d)^T, (3, mpp, rq), zero padding
+        int zok = 0;                      // Gz belongs to the subspace held and to M: cleared wherever ok is by a set-up or a new M
     };
     RfBank rf_bank[ASB_RFORCE_BANKS];
     int rf_cur = 0;
@@ -379,6 +382,7 @@ struct asb_ctx {
     asb_gsl* gsl = nullptr;
     // the third solver (asb_gsub.hip): the step in a position subspace q = o + U z.  One of the three is held at a time
     asb_gsb* gsb = nullptr;
+    asb_zr* zr = nullptr;             // the roll-out whose state lives in z (asb_zroll.hip)
 
     // ---- profiling of the dominant streaming kernel ----
     bool prof = false;
@@ -397,6 +401,7 @@ void asb_geo_free(asb_ctx* ctx);
 void asb_pdsolve_free(asb_ctx* ctx);
 void asb_gslab_free(asb_ctx* ctx);
 void asb_gsub_free(asb_ctx* ctx);
+void asb_zroll_free(asb_ctx* ctx);
 #define ASB_GEO_CACHE_SLABS 64          // x 64 distance fields
 const double* asb_geo_cached_field(asb_ctx* ctx, long long slot, long long* n_out);
 // small dense linear algebra on the device (asb_linalg.hip)
@@ -504,6 +509,21 @@ long long asb_gsub_n(const asb_ctx* ctx);
 void asb_gsub_release(asb_ctx* ctx);
 int asb_gsub_solve_fm(asb_ctx* ctx, const double* rhs, long long F, double* Qv, double* out);
 int asb_gsub_solve_rows(asb_ctx* ctx, const double* Gt, long long rows, long long Np, double* Ot);
+// what asb_zroll.hip takes from the subspace: its numbers and buffers (Un: U in W's layout (3, Np, rq); o, Ao (n, 3)); 0: none held
+struct GsubView {
+    long long n, r, rp, rq, Np, gen;    // gen: one number per asb_gsub_setup
+    const double *Ut, *Wn, *Un, *o, *Ao;
+};
+int asb_gsub_view(asb_ctx* ctx, GsubView* v);
+// the work matrices R (3 Np, ld; rows past 3 n zero) and Y (3, rq, ld) for rows of ld doubles; Y = W R (basis 1: U^T R) into Y
+int asb_gsub_work(asb_ctx* ctx, long long ld, double** R, double** Y);
+void asb_gsub_reduce_launch(asb_ctx* ctx, int basis, long long ld, double* Y);
+// k_gsub_expand on a basis Ut (3, rp, Np) of the subspace's r (gathered rows: any Np a multiple of 32): Q (3 n, ld) = base (n, 3)
+// + U Y, columns [0, F); out (optional): the same frame-major
+void asb_gsub_expand_launch(asb_ctx* ctx, const double* Ut, long long Np, const double* Y, long long ld, const double* base, double* Q,
+                            long long F, long long n, double* out);
+// the first half of asb_gsub_solve_rows: Y (3, rq, ld) = W Mt^T for the operator rows Mt (3 mpp, Np), ld = mpp rounded up to 64
+int asb_gsub_rows_in(asb_ctx* ctx, const double* Mt, long long rows, long long Np, long long* ld_out, double** Y);
 // asb_rforce.hip: k_st_dense on device arrays, Mt (3, mpp, Np) = (S^T V_d)^T for the CSR (ptr, ci, val) of n_rows rows and V (rows, mp, 3)
 void asb_st_dense_launch(asb_ctx* ctx, const int* ptr, const int* ci, const double* val, const double* V, long long n_rows, int mp, int mpp,
                          long long Np, double* Mt);

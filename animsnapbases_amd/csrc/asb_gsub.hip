@@ -45,8 +45,10 @@ struct asb_gsb {
     long long n = 0, r = 0, rp = 0, rq = 0, Np = 0;   // vertices (0: no subspace), basis vectors, rounded up to 4 and 16; N to 32
     double *Ut = nullptr, *Wn = nullptr, *Ai = nullptr, *op = nullptr;    // (3, rp, Np), (3, Np, rq), (3, rq, rq), (n, 3)
     double *R = nullptr, *Y = nullptr, *V = nullptr;  // work matrix (3 Np, ld), (3, rq, ld), vertex-major result of asb_gstep_run
+    double *Un = nullptr, *o = nullptr, *Ao = nullptr;        // for asb_zroll.hip: U in W's layout (3, Np, rq), the origin (n, 3), A o (n, 3)
     const double* R_at = nullptr;                     // the R whose padding is known to be zero for rows of R_ld doubles
     long long R_ld = 0;
+    long long gen = 0;                                // which set-up this is: asb_zroll.hip refuses what another one formed
 };
 
 long long asb_gsub_n(const asb_ctx* ctx) { return ctx->gsb ? ctx->gsb->n : 0; }
@@ -57,6 +59,7 @@ void asb_gsub_release(asb_ctx* ctx) {
     s->n = 0, s->R_at = nullptr;
     (void)asb_alloc(ctx, &s->Ut, 0), (void)asb_alloc(ctx, &s->Wn, 0), (void)asb_alloc(ctx, &s->Ai, 0), (void)asb_alloc(ctx, &s->op, 0);
     (void)asb_alloc(ctx, &s->R, 0), (void)asb_alloc(ctx, &s->Y, 0), (void)asb_alloc(ctx, &s->V, 0);
+    (void)asb_alloc(ctx, &s->Un, 0), (void)asb_alloc(ctx, &s->o, 0), (void)asb_alloc(ctx, &s->Ao, 0);
 }
 
 void asb_gsub_free(asb_ctx* ctx) {                // (the buffers went with the context's registered allocations)
@@ -273,6 +276,52 @@ int asb_gsub_solve_rows(asb_ctx* ctx, const double* Mt, long long rows, long lon
     return ASB_OK;
 }
 
+// ---------------------------------------------------------------- what asb_zroll.hip takes from this unit
+int asb_gsub_view(asb_ctx* ctx, GsubView* v) {
+    const asb_gsb* s = ctx->gsb;
+    if (!s || s->n < 1) return 0;
+    *v = GsubView{s->n, s->r, s->rp, s->rq, s->Np, s->gen, s->Ut, s->Wn, s->Un, s->o, s->Ao};
+    return 1;
+}
+
+int asb_gsub_work(asb_ctx* ctx, long long ld, double** R, double** Y) {
+    asb_gsb* s = ctx->gsb;
+    int rc;
+    if ((rc = gsb_work(ctx, s, ld))) return rc;
+    *R = s->R, *Y = s->Y;
+    return ASB_OK;
+}
+
+void asb_gsub_reduce_launch(asb_ctx* ctx, int basis, long long ld, double* Y) {
+    const asb_gsb* s = ctx->gsb;
+    gsb_reduce_launch(ctx, basis ? s->Un : s->Wn, s->Np, (int)s->rq, s->R, ld, Y);
+}
+
+void asb_gsub_expand_launch(asb_ctx* ctx, const double* Ut, long long Np, const double* Y, long long ld, const double* base, double* Q,
+                            long long F, long long n, double* out) {
+    const asb_gsb* s = ctx->gsb;
+    const dim3 ge((unsigned)(Np / GB_TN), (unsigned)(ld / GB_TF));
+    if (out)
+        hipLaunchKernelGGL((k_gsub_expand<true>), ge, dim3(256), 0, ctx->stream, Ut, Np, (int)s->rp, Y, (int)s->rq, ld, base, 1, Q, (int)F, (int)n, out);
+    else
+        hipLaunchKernelGGL((k_gsub_expand<false>), ge, dim3(256), 0, ctx->stream, Ut, Np, (int)s->rp, Y, (int)s->rq, ld, base, 1, Q, (int)F, (int)n,
+                           nullptr);
+}
+
+int asb_gsub_rows_in(asb_ctx* ctx, const double* Mt, long long rows, long long Np, long long* ld_out, double** Y) {
+    asb_gsb* s = ctx->gsb;
+    if (Np != s->Np || rows < 3 || rows % 3 || rows > 65535)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_zroll_operator: an operator of %lld rows of %lld doubles (the subspace pads to %lld)", rows, Np, s->Np);
+    const long long mpp = rows / 3, ld = (mpp + 63) / 64 * 64;
+    int rc;
+    if ((rc = gsb_work(ctx, s, ld))) return rc;
+    const dim3 gr((unsigned)((s->n + 255) / 256), (unsigned)rows);
+    hipLaunchKernelGGL(k_gsub_rows<true>, gr, dim3(256), 0, ctx->stream, const_cast<double*>(Mt), Np, (int)mpp, s->R, ld, (int)s->n);
+    gsb_reduce_launch(ctx, s->Wn, s->Np, (int)s->rq, s->R, ld, s->Y);
+    *ld_out = ld, *Y = s->Y;
+    return ASB_OK;
+}
+
 // ---------------------------------------------------------------- set-up
 extern "C" int asb_gsub_setup(asb_ctx* ctx, int64_t n, const int64_t* indptr, const int64_t* indices, const double* data, int64_t r,
                               const double* Qt_host, const double* origin_host, double* resid_out) {
@@ -308,23 +357,24 @@ extern "C" int asb_gsub_setup(asb_ctx* ctx, int64_t n, const int64_t* indptr, co
         }
     if (!ctx->gsb) ctx->gsb = new asb_gsb();
     asb_gsb* s = ctx->gsb;
-    s->r = r, s->rp = rp, s->rq = rq, s->Np = Np;
+    static long long generation = 0;
+    s->r = r, s->rp = rp, s->rq = rq, s->Np = Np, s->gen = ++generation;
     const long long ld = 64;
     if ((rc = asb_alloc(ctx, &s->Ut, ut.size()))) return rc;
     if ((rc = asb_alloc(ctx, &s->Wn, un.size()))) return rc;
     if ((rc = asb_alloc(ctx, &s->Ai, (size_t)3 * rq * rq))) return rc;
     if ((rc = asb_alloc(ctx, &s->op, (size_t)3 * n))) return rc;
     asb_tmp<int> dptr, dci;
-    asb_tmp<double> dval, Un, dV, AUt, AUn, od, Qv, xs;
+    asb_tmp<double> dval, dV, AUt, AUn, Qv, xs;
     if ((rc = dptr.alloc(ctx, p32.size())) || (rc = dci.alloc(ctx, c32.size() + 1)) || (rc = dval.alloc(ctx, c32.size() + 1))) return rc;
-    if ((rc = Un.alloc(ctx, un.size())) || (rc = dV.alloc(ctx, uv.size())) || (rc = AUt.alloc(ctx, (size_t)3 * std::max(rp, 4LL) * Np))) return rc;
-    if ((rc = AUn.alloc(ctx, (size_t)Np * rp)) || (rc = od.alloc(ctx, (size_t)3 * n)) || (rc = Qv.alloc(ctx, (size_t)3 * n * ld))) return rc;
-    if ((rc = xs.alloc(ctx, (size_t)3 * n))) return rc;
+    if ((rc = asb_alloc(ctx, &s->Un, un.size())) || (rc = dV.alloc(ctx, uv.size())) || (rc = AUt.alloc(ctx, (size_t)3 * std::max(rp, 4LL) * Np))) return rc;
+    if ((rc = AUn.alloc(ctx, (size_t)Np * rp)) || (rc = asb_alloc(ctx, &s->o, (size_t)3 * n)) || (rc = Qv.alloc(ctx, (size_t)3 * n * ld))) return rc;
+    if ((rc = xs.alloc(ctx, (size_t)3 * n)) || (rc = asb_alloc(ctx, &s->Ao, (size_t)3 * n))) return rc;
     if ((rc = asb_csr_stage(ctx, p32, c32, data, dptr.get(), dci.get(), dval.get()))) return rc;
     ASB_HIP(ctx, hipMemcpyAsync(s->Ut, ut.data(), ut.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    ASB_HIP(ctx, hipMemcpyAsync(Un.get(), un.data(), un.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    ASB_HIP(ctx, hipMemcpyAsync(s->Un, un.data(), un.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     ASB_HIP(ctx, hipMemcpyAsync(dV.get(), uv.data(), uv.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    ASB_HIP(ctx, hipMemcpyAsync(od.get(), origin_host, (size_t)3 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    ASB_HIP(ctx, hipMemcpyAsync(s->o, origin_host, (size_t)3 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     // ---- (A U_d)^T (3, rp, Np), then per coordinate At_d = U_d^T (A U_d), its inverse, W_d^T = U_d At_d^-1
     ASB_HIP(ctx, hipMemsetAsync(AUt.get(), 0, (size_t)3 * rp * Np * sizeof(double), ctx->stream));
     asb_st_dense_launch(ctx, dptr.get(), dci.get(), dval.get(), dV.get(), n, (int)r, (int)rp, Np, AUt.get());
@@ -332,7 +382,7 @@ extern "C" int asb_gsub_setup(asb_ctx* ctx, int64_t n, const int64_t* indptr, co
     ASB_CHECK_LAUNCH(ctx);
     for (int d = 0; d < 3; ++d) {
         double* At = s->Ai + (size_t)d * rq * rq;
-        const double* Ud = Un.get() + (size_t)d * Np * rq;
+        const double* Ud = s->Un + (size_t)d * Np * rq;
         if ((rc = asb_transpose(ctx, AUt.get() + (size_t)d * rp * Np, rp, Np, AUn.get()))) return rc;
         if ((rc = asb_gemm_tn_s(ctx, Ud, rq, 1, AUn.get(), rp, Np, (int)rp, (int)rp, At, rq, 1))) return rc;
         if (rq > r) hipLaunchKernelGGL(k_gsub_eye, dim3((unsigned)((rq - r + 255) / 256)), dim3(256), 0, ctx->stream, At, (int)r, (int)rq);
@@ -346,13 +396,15 @@ extern "C" int asb_gsub_setup(asb_ctx* ctx, int64_t n, const int64_t* indptr, co
     if ((rc = gsb_work(ctx, s, ld))) return fail(rc);
     const unsigned g3 = (unsigned)((3 * n + 255) / 256);
     ASB_HIP(ctx, hipMemsetAsync(AUt.get(), 0, (size_t)3 * 4 * Np * sizeof(double), ctx->stream));
-    asb_st_dense_launch(ctx, dptr.get(), dci.get(), dval.get(), od.get(), n, 1, 4, Np, AUt.get());
+    asb_st_dense_launch(ctx, dptr.get(), dci.get(), dval.get(), s->o, n, 1, 4, Np, AUt.get());
     hipLaunchKernelGGL(k_gsub_cols, dim3(g3), dim3(256), 0, ctx->stream, AUt.get(), Np, (int)n, s->R, ld);
+    ASB_HIP(ctx, hipMemcpy2DAsync(s->Ao, sizeof(double), s->R, (size_t)ld * sizeof(double), sizeof(double), (size_t)3 * n,      // column 0: A o, kept
+                                  hipMemcpyDeviceToDevice, ctx->stream));
     gsb_apply(ctx, s, s->Wn, ld, 2, 0, Qv.get(), nullptr);
-    hipLaunchKernelGGL(k_gsub_origin, dim3(g3), dim3(256), 0, ctx->stream, od.get(), Qv.get(), ld, (int)n, s->op, xs.get());
+    hipLaunchKernelGGL(k_gsub_origin, dim3(g3), dim3(256), 0, ctx->stream, s->o, Qv.get(), ld, (int)n, s->op, xs.get());
     asb_st_dense_launch(ctx, dptr.get(), dci.get(), dval.get(), xs.get(), n, 1, 4, Np, AUt.get());
     hipLaunchKernelGGL(k_gsub_rcol, dim3(g3), dim3(256), 0, ctx->stream, AUt.get(), Np, (int)n, s->R, ld);
-    gsb_apply(ctx, s, Un.get(), ld, 1, 0, nullptr, nullptr);                  // Y = U^T (A x - 1): the basis in place of W
+    gsb_apply(ctx, s, s->Un, ld, 1, 0, nullptr, nullptr);                  // Y = U^T (A x - 1): the basis in place of W
     if (hipGetLastError() != hipSuccess) return fail(ASB_ERR_HIP);
     std::vector<double> y((size_t)3 * rq * ld);
     if (hipMemcpyAsync(y.data(), s->Y, y.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||

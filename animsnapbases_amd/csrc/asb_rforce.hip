@@ -125,7 +125,7 @@ extern "C" int asb_rforce_operator(asb_ctx* ctx, int64_t n_rows, const int64_t* 
                                    int64_t v_rows, int64_t mp, const double* V) {
     if (!ctx || !indptr || !V || n_rows < 1) return ASB_ERR_ARG;
     asb_ctx::RfBank& b = asb_rf_cur(ctx);
-    b.mp = 0, b.r = 0, b.ok = 0;                    // this bank's operator, solver and A^-1 S^T V mark; no other bank's
+    b.mp = 0, b.r = 0, b.ok = 0, b.zok = 0;                    // this bank's operator, solver and A^-1 S^T V mark; no other bank's
     if (!ctx->X || ctx->v0 != 0 || ctx->n_loc != ctx->N_glob)
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_rforce_operator: no whole tensor on the device (one rank only)");
     if (n_rows != ctx->n_loc)
@@ -191,7 +191,7 @@ extern "C" int asb_rforce_solver(asb_ctx* ctx, int64_t r, int64_t npt, const dou
 // (coef), A^-1 S^T V with its mark (G, ok) and its touched columns (Gc).  A selection is the index rf_cur: no buffer and no
 // number moves, a bank that was addressed keeps what it holds whichever bank is current, and one never addressed holds nothing.
 void asb_rf_invalidate_all(asb_ctx* ctx) {
-    for (int k = 0; k < ASB_RFORCE_BANKS; ++k) ctx->rf_bank[k].ok = 0;
+    for (int k = 0; k < ASB_RFORCE_BANKS; ++k) ctx->rf_bank[k].ok = ctx->rf_bank[k].zok = 0;
 }
 
 extern "C" int asb_rforce_bank(asb_ctx* ctx, int bank) {

@@ -331,6 +331,7 @@ extern "C" void asb_destroy(asb_ctx* ctx) {
     asb_pdsolve_free(ctx);
     asb_gslab_free(ctx);
     asb_gsub_free(ctx);
+    asb_zroll_free(ctx);
     if (ctx->host_pin) (void)hipHostFree(ctx->host_pin);
     if (ctx->res_pin) (void)hipHostFree(ctx->res_pin);
     if (ctx->dl_stream) { (void)hipStreamSynchronize(ctx->dl_stream); (void)hipStreamDestroy(ctx->dl_stream); }

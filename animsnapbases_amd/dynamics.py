@@ -1,8 +1,8 @@
 """``ResidentDynamics`` -- what ``posSnapshots`` offers beyond the reference's class: the pieces of the reference's
 projective-dynamics solver (Simulators.py) evaluated on the device for the frames of the resident animation -- constraint
 projections, constraint forces, their DEIM reduction, the global step, the solver's iterations and its time steps, with the choice of the global step's solver and
-of how many kinds a solve may reduce, the positional constraints (pins) of every such call, and the global step in a position
-subspace q = o + U z.
+of how many kinds a solve may reduce, the positional constraints (pins) of every such call, the global step in a position
+subspace q = o + U z and roll-outs whose state lives in z.
 A public call checks its arguments into the named records below before the engine is touched; the helpers take the records.
 """
 import collections
@@ -441,9 +441,9 @@ class ResidentDynamics(object):
         the span matters (``projections.subspace_basis`` orthonormalises per coordinate and refuses a rank-deficient basis).
         ``num_components`` = r: the first r components (None: all K).  ``origin``: None takes the rest positions (frame 0 of the
         world-space input, resolved when the matrix is set up) or an (N, 3) array.  The three are for "subspace" only.  Pins need
-        nothing new: their weights are in A, their term in the right-hand side.  Held on the device: 2 x 3 r N doubles and
-        3 r F' more in a solve.  Out of scope under "subspace": ``history=True`` (ValueError), a roll-out whose state lives in z,
-        an M-orthogonal basis, several ranks.  Limits under "subspace": r <= min(N, 8192) (ValueError here, before the device is
+        nothing new: their weights are in A, their term in the right-hand side.  Held on the device: 3 x 3 r N doubles and
+        3 r F' more in a solve.  Out of scope under "subspace": ``history=True`` (ValueError),
+        an M-orthogonal basis, several ranks.  (A roll-out whose state lives in z is ``simulate_subspace``.)  Limits under "subspace": r <= min(N, 8192) (ValueError here, before the device is
         touched); with ``hyper`` a reduced kind of at most 21 845 basis vectors (the engine refuses more; 65 532 under the other
         two solvers: the operator's rows go through one grid dimension).  Leaves ``self.global_solve_subspace`` = r after the next set-up."""
         if kind not in ("inverse", "slab", "subspace"):
@@ -748,18 +748,7 @@ class ResidentDynamics(object):
         their touched vertices, which is returned."""
         eng, multi = self._engine, len(reds) > 1
         red = {r.index: (b, r) for b, r in enumerate(reds)}
-        sub = {i: _proj.subset_setup(r.setup, r.op.elements) for i, (b, r) in red.items()}
-        touched = None
-        if hyper == "all":
-            touched = np.arange(self.nVerts, dtype=np.int64)
-            sub = {i: _proj.touched_setup(u, self.nVerts)[1] for i, u in sub.items()}
-        elif hyper is not None and not multi:           # one kind: its own touched set, found once
-            (i, u), = sub.items()
-            touched, u = _proj.touched_setup(u)
-            sub = {i: u}
-        elif hyper is not None:
-            touched = _proj.touched_union([sub[i] for i in sorted(sub)])
-            sub = {i: _proj.touched_setup(u, into=touched)[1] for i, u in sub.items()}
+        touched, sub = self._sampled(reds, hyper)
         for i, t in enumerate(plan):
             if i in red:
                 if multi:
@@ -771,6 +760,24 @@ class ResidentDynamics(object):
                 eng.cproj_setup(t.setup)
                 eng.pdsolve_slot(t.sigma_min, t.sigma_max, t.St)
         return touched
+
+    def _sampled(self, reds, hyper):
+        """(touched or None, index -> the sampled elements' set-up) of the reduced kinds; with ``hyper`` numbered in the union of
+        their touched vertices."""
+        multi = len(reds) > 1
+        sub = {r.index: _proj.subset_setup(r.setup, r.op.elements) for r in reds}
+        touched = None
+        if hyper == "all":
+            touched = np.arange(self.nVerts, dtype=np.int64)
+            sub = {i: _proj.touched_setup(u, self.nVerts)[1] for i, u in sub.items()}
+        elif hyper is not None and not multi:           # one kind: its own touched set, found once
+            (i, u), = sub.items()
+            touched, u = _proj.touched_setup(u)
+            sub = {i: u}
+        elif hyper is not None:
+            touched = _proj.touched_union([sub[i] for i in sorted(sub)])
+            sub = {i: _proj.touched_setup(u, into=touched)[1] for i, u in sub.items()}
+        return touched, sub
 
     def _solve_run(self, plan, reds, frames, ex, begin, K, chunk_frames, history, hyper=None, pins=None):
         """The solve (matrix on the device); ``reds``: the ``Reduced`` of the plan with their ``op``; ``begin``: what
@@ -1070,3 +1077,136 @@ class ResidentDynamics(object):
             for j in range(len(steps)):
                 out[:, i, j] = [m[0] for m in self._diff_metrics(full[j], [rec[j]], frames.n_sel, False)]
         return tuple(out) + (steps,)
+
+    # ------------------------------------------------------------------ roll-outs whose state lives in z
+    def _subspace_held(self, who):
+        """r of the subspace on the device, or the ValueError of a call that needs one."""
+        self._one_rank(who)
+        if self._subspace_solver() is None or getattr(self, "global_solve_subspace", None) is None or getattr(self, "global_matrix", None) is None:
+            raise ValueError("%s: no position subspace on the device: set_global_solver('subspace', basis=...) and global_solve_setup "
+                             "(or a solve) first" % who)
+        return int(self.global_solve_subspace)
+
+    def _z_tensor(self, who, name, t, rows, n_sel=None):
+        """A caller's ``torch.float64`` device tensor (F', rows, 3), contiguous, on the snapshots' device; F' = ``n_sel`` if given."""
+        import torch
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_cuda:
+            raise ValueError("%s: %s must be a torch.float64 device tensor" % (who, name))
+        if t.device.index != self._engine.device_id:
+            raise ValueError("%s: %s lives on %s, the snapshots on device %d" % (who, name, t.device, self._engine.device_id))
+        if t.dim() != 3 or t.shape[0] < 1 or tuple(t.shape[1:]) != (rows, 3) or (n_sel is not None and t.shape[0] != n_sel) or not t.is_contiguous():
+            raise ValueError("%s: %s of shape %s: a contiguous (%s, %d, 3) expected" % (who, name, tuple(t.shape), "F'" if n_sel is None else n_sel, rows))
+        return t
+
+    def subspace_coordinates(self, positions="train", frame_start=0, frame_end=None, frame_jump=1):
+        """Extra: the coordinates z = U^T (x - o) of positions in the subspace the device holds (``set_global_solver("subspace")``
+        and a matrix set-up), per coordinate the Euclidean projection onto the orthonormalised basis.  ``positions``: "train" or
+        "test" with the frame range of ``constraint_forces``, or a contiguous ``torch.float64`` device tensor (F', N, 3) in world
+        space.  Returns a caller-owned ``torch.float64`` device tensor (F', r, 3).  One pass over N; the sum over the vertices is
+        never split.  One rank only."""
+        import torch
+        who = "subspace_coordinates"
+        r = self._subspace_held(who)
+        eng = self._engine
+        if isinstance(positions, str):
+            if positions not in ("train", "test"):
+                raise ValueError("%s: positions must be 'train', 'test' or a torch.float64 device tensor (F', %d, 3), not %r" % (who, self.nVerts, positions))
+            frames = self._frames(positions, frame_start, frame_end, frame_jump)
+            frames.upload(self)
+            out = self._alloc(frames, r)
+            eng.gsub_coordinates(*frames.args(self), out.data_ptr())
+            return out
+        x = self._z_tensor(who, "positions", positions, self.nVerts)
+        torch.cuda.current_stream(x.device).synchronize()           # whatever produced the tensor is done before the engine reads it
+        out = torch.empty((x.shape[0], r, 3), dtype=torch.float64, device=x.device)
+        eng.gsub_coordinates(0, 0, 1, 1, None, False, 1.0, out.data_ptr(), x.data_ptr(), x.shape[0])
+        return out
+
+    def subspace_expand(self, z):
+        """Extra: q = o + U z for a contiguous ``torch.float64`` device tensor ``z`` (F', r, 3) of coordinates in the subspace the
+        device holds: a caller-owned device tensor (F', N, 3) in world space.  One rank only."""
+        import torch
+        who = "subspace_expand"
+        r = self._subspace_held(who)
+        z = self._z_tensor(who, "z", z, r)
+        torch.cuda.current_stream(z.device).synchronize()
+        out = torch.empty((z.shape[0], self.nVerts, 3), dtype=torch.float64, device=z.device)
+        self._engine.gsub_expand(z.data_ptr(), z.shape[0], out.data_ptr())
+        return out
+
+    def simulate_subspace(self, kinds, dt, num_steps, num_iterations=10, masses=None, velocity="difference", gravity=(0.0, 0.0, 0.0),
+                          state=None, animation="train", frame_start=0, frame_end=None, frame_jump=1, chunk_frames=None,
+                          record_every=None, pins=None):
+        """Extra: ``simulate_frames(hyper="touched")`` under ``set_global_solver("subspace")`` with the STATE kept in the subspace
+        coordinates z of q = o + U z -- the reference's fully reduced simulator (Simulators.py:144-155, :195, :239, where it raises
+        "not yet implemented").  Per coordinate, with At = U^T A U: a step is y = 2 z_t - z_{t-1}, c_z = kappa + T y + E target,
+        then ``num_iterations`` times z <- c_z + sum_k Gz_k coef_k(q) with q = o + U z formed at the touched vertices only.
+        T = At^-1 U^T (M / dt^2) U, kappa, E (the pins) and Gz_k = At^-1 U^T S_k^T V_k are formed once per call; a time step
+        reads and writes nothing of size N.  For frames inside o + span(U) this is ``simulate_frames(hyper=)``
+        under the subspace up to rounding; frames outside start from their Euclidean projection z_0 = U^T (x_f - o).
+
+        Arguments as ``simulate_frames`` without ``hyper``; EVERY kind must be reduced (up to ``set_reduced_kinds`` of them).
+        ``state``: a pair ``(z, z_prev)`` of contiguous ``torch.float64`` device tensors (F', r, 3) continues a roll-out
+        (``velocity`` is then ignored, the animation only selects F'; pins take ``shift_start`` raised by the steps already taken):
+        T1 steps continued by T2 equal T1 + T2 steps bit for bit.  Returns ``(z, z_prev, F')``: caller-owned device tensors
+        (F', r, 3); with ``record_every`` also ``(records (R, F', r, 3), steps)``.  ``subspace_expand`` gives the positions.
+        ValueError before the device is touched: no subspace selected, a plain kind, a bad ``state``, a row of the pins' shift
+        beyond T_s.  Out of scope: plain kinds, the history of step norms, collisions, several ranks."""
+        import torch
+        who = "simulate_subspace"
+        self._one_rank(who)
+        sub = self._subspace_solver()
+        if sub is None:
+            raise ValueError("%s: the state lives in the coordinates of a position subspace: set_global_solver('subspace', basis=...) first" % who)
+        r = int(sub[0].shape[1])
+        limit = getattr(self, "_reduced_limit", 1)
+        if not (isinstance(kinds, (list, tuple)) and len(kinds) >= 1 and all(
+                isinstance(k, dict) and "basis" in k and "num_components" in k for k in kinds)):
+            raise ValueError("%s: every kind must be reduced ('basis' and 'num_components'): up to %d of them under set_reduced_kinds(%d), "
+                             "none left plain" % (who, limit, limit))
+        ex, K = self._solve_args(who, dt, velocity, gravity, num_iterations, "explicit", masses)
+        T, every = self._rollout_args(who, num_steps, record_every, None)
+        frames = self._frames(animation, frame_start, frame_end, frame_jump)
+        pins = self._pins(who, pins, frames, T)
+        plan, reds = self._solve_plan(who, kinds, chunk_frames)
+        if state is not None:
+            if not isinstance(state, (list, tuple)) or len(state) != 2:
+                raise ValueError("%s: state must be a pair (z, z_prev) of torch.float64 device tensors" % who)
+            state = tuple(self._z_tensor(who, "state", t, r, frames.n_sel) for t in state)
+        reds = self._chosen(reds, kinds)
+        self._matrix(plan, ex.masses, ex.dt, pins)
+        eng, multi = self._engine, len(reds) > 1
+        try:
+            for b, rd in enumerate(reds):
+                if multi:
+                    eng.rforce_bank(b)
+                eng.rforce_operator(rd.St, rd.op.V)
+                eng.zroll_operator()
+            if state is not None:
+                torch.cuda.current_stream(state[0].device).synchronize()
+            frames.upload(self)
+            if pins is not None:
+                self._pins_set(pins)
+            touched, sampled = self._sampled(reds, "touched")
+            eng.zroll_begin(*frames.args(self), ex.diag, ex.mode, ex.acc, touched,
+                            None if state is None else state[0].data_ptr(), None if state is None else state[1].data_ptr())
+            if pins is not None:
+                eng.zroll_pins(pins.start)
+            for b, rd in enumerate(reds):
+                if multi:
+                    eng.rforce_bank(b)
+                eng.cproj_setup(sampled[rd.index])
+                eng.rforce_solver(rd.op.H, rd.op.local_rows)
+                eng.zroll_slot(plan[rd.index].sigma_min, plan[rd.index].sigma_max)
+            steps = [] if every is None else list(range(every, T + 1, every))
+            dev = "cuda:%d" % eng.device_id
+            records = None if every is None else torch.empty((len(steps), frames.n_sel, r, 3), dtype=torch.float64, device=dev)
+            eng.zroll_steps(T, K, 0 if chunk_frames is None else int(chunk_frames), 0 if every is None else every,
+                            None if records is None or not steps else records.data_ptr())
+            z, z_prev = self._alloc(frames, r), self._alloc(frames, r)
+            eng.zroll_state(z.data_ptr(), z_prev.data_ptr())
+        finally:
+            if multi:
+                eng.rforce_bank(0)
+        self._leave(plan, pins)
+        return (z, z_prev, frames.n_sel) + (() if every is None else ((records, steps),))

@@ -721,6 +721,69 @@ class HipEngine(object):
             raw.append(a)
         return (np.ascontiguousarray(raw[0][:, :n, :r].transpose(0, 2, 1)), raw[1][:, :r, :r].copy(), raw[2], raw[3][:, :r, :n].copy())
 
+    # ------------------------------------------------------------------ roll-outs with the state in z (csrc/asb_zroll.hip)
+    def gsub_coordinates(self, which, f0, f1, fj, inv_massL, add_mean, psf, out_dev_ptr, pos_dev_ptr=None, n_frames=0):
+        """z = U^T (x - o) of the frames range(f0, f1, fj) of the tensor ``which`` -- or of the caller's device tensor
+        (``n_frames``, N, 3) -- into the caller's device buffer of (F', r, 3) float64."""
+        inv_massL = self._invm(inv_massL)
+        self._ck(self.lib.asb_gsub_coordinates(self.h, int(which), int(f0), int(f1), int(fj), ptr(inv_massL), int(bool(add_mean)), float(psf),
+                                               ctypes.c_void_p(int(pos_dev_ptr)) if pos_dev_ptr else None, int(n_frames),
+                                               ctypes.c_void_p(int(out_dev_ptr))))
+
+    def gsub_expand(self, z_dev_ptr, n_frames, out_dev_ptr):
+        """o + U z of the caller's (``n_frames``, r, 3) into the caller's device buffer of (``n_frames``, N, 3) float64."""
+        self._ck(self.lib.asb_gsub_expand(self.h, ctypes.c_void_p(int(z_dev_ptr)), int(n_frames), ctypes.c_void_p(int(out_dev_ptr))))
+
+    def zroll_operator(self):
+        """(U^T A U)^-1 U^T S^T V of the current bank from the subspace of ``gsub_setup`` and the operator of ``rforce_operator``;
+        either call afterwards invalidates it."""
+        self._ck(self.lib.asb_zroll_operator(self.h))
+
+    def zroll_begin(self, which, f0, f1, fj, inv_massL, add_mean, psf, diag, mode, acc, touched, z_dev_ptr=None, zprev_dev_ptr=None):
+        """Begins a roll-out in z over the frames range(f0, f1, fj): T, kappa, the ``touched`` rows of U and the state -- the
+        projections of the frames (``mode`` 1: z_prev from the previous frame, 0: z_prev = z) or the caller's pair (F', r, 3)."""
+        inv_massL = self._invm(inv_massL)
+        diag, acc = self._vec(diag, (self.N_glob,)), self._vec(acc, (3,))
+        touched = np.ascontiguousarray(touched, dtype=np.int64)
+        assert touched.ndim == 1
+        self._ck(self.lib.asb_zroll_begin(self.h, int(which), int(f0), int(f1), int(fj), ptr(inv_massL), int(bool(add_mean)), float(psf),
+                                          ptr(diag), int(mode), ptr(acc), int(touched.shape[0]), ptr(touched),
+                                          ctypes.c_void_p(int(z_dev_ptr)) if z_dev_ptr else None,
+                                          ctypes.c_void_p(int(zprev_dev_ptr)) if zprev_dev_ptr else None))
+
+    def zroll_slot(self, sigma_min, sigma_max):
+        """The kind of the last ``cproj_setup`` (numbered in the touched vertices) becomes the next reduced kind of the roll-out."""
+        self._ck(self.lib.asb_zroll_slot(self.h, float(sigma_min), float(sigma_max)))
+
+    def zroll_pins(self, row0=0):
+        """Binds the pins of ``pins_set`` to the roll-out in z: step t from frame f reads row ``row0`` + f + t - 1 of the shift."""
+        self._ck(self.lib.asb_zroll_pins(self.h, int(row0)))
+
+    def zroll_steps(self, n_steps, n_iter, chunk_frames=0, record_every=0, records_dev_ptr=None):
+        """``n_steps`` time steps of ``n_iter`` iterations in stream order, one drain at the end; ``record_every`` > 0: z after
+        every such step into the caller's device buffer (R, F', r, 3)."""
+        self._ck(self.lib.asb_zroll_steps(self.h, int(n_steps), int(n_iter), int(chunk_frames), int(record_every),
+                                          ctypes.c_void_p(int(records_dev_ptr)) if records_dev_ptr else None))
+
+    def zroll_state(self, z_dev_ptr, zprev_dev_ptr):
+        """z and z_prev of the roll-out into the caller's two device buffers of (F', r, 3) float64."""
+        self._ck(self.lib.asb_zroll_state(self.h, ctypes.c_void_p(int(z_dev_ptr)), ctypes.c_void_p(int(zprev_dev_ptr))))
+
+    def zroll_affine(self, Ms, Xs, base):
+        """Test hook: base + sum_s Ms[s] @ Xs[s] per coordinate through the product kernel alone.  ``Ms[s]`` (3, r, k_s), ``Xs[s]``
+        (3, k_s, w), ``base`` (3, r, w) or (3, r) (broadcast).  Returns the whole padded (3, rq, ld) result."""
+        Ms = [np.ascontiguousarray(M, dtype=np.float64) for M in Ms]
+        Xs = [np.ascontiguousarray(X, dtype=np.float64) for X in Xs]
+        base = np.ascontiguousarray(base, dtype=np.float64)
+        r, w = Ms[0].shape[1], Xs[0].shape[2]
+        assert all(M.shape[:2] == (3, r) and X.shape == (3, M.shape[2], w) for M, X in zip(Ms, Xs)) and base.shape in ((3, r), (3, r, w))
+        klen = np.array([M.shape[2] for M in Ms], dtype=np.int64)
+        Mh = np.concatenate([M.ravel() for M in Ms])
+        Xh = np.concatenate([X.ravel() for X in Xs])
+        out = np.empty((3, (r + 15) // 16 * 16, (w + 63) // 64 * 64))
+        self._ck(self.lib.asb_test_zroll_affine(self.h, r, w, len(Ms), ptr(klen), ptr(Mh), ptr(Xh), ptr(base), int(base.ndim == 2), ptr(out)))
+        return out
+
     # ------------------------------------------------------------------ solver iterations of projective dynamics
     def pdsolve_begin(self, which, f0, f1, fj, inv_massL, add_mean, psf, diag, mode, acc, start, start_dev_ptr=None):
         """Begins a solve over the frames range(f0, f1, fj) after ``gstep_setup``: the inertia term diag * s (``mode``, ``acc`` as

@@ -730,7 +730,7 @@ int asb_test_gslab_gemm_time(asb_ctx* ctx, int64_t sp, int64_t w, double* ms_out
  * ASB_ERR_ARG; r > 8192: ASB_ERR_LIMIT.  A U_d by the sparse x dense kernel of asb_rforce_operator, U_d^T (A U_d) and its SPD
  * inverse (padded to a multiple of 16 by an identity block) by the dense layer; not positive definite: ASB_ERR_NUMERIC, no
  * solver is left.  Kept: U^T (3, rp, Np), W^T = U (U^T A U)^-1 (3, Np, rq), the inverses, o' (rp, rq: r rounded up to 4 and 16,
- * Np: n to 32).  resid_out (optional): max_d max |U_d^T (A (P_d 1) - 1)| as the device computed it.
+ * Np: n to 32), and for the asb_zroll_* entries below U in W's layout (3, Np, rq), o and A o (n, 3).  resid_out (optional): max_d max |U_d^T (A (P_d 1) - 1)| as the device computed it.
  * The map is two f64-MFMA products, Y = W R over all vertices (never split between blocks) and Q = o' + U Y; no atomics: an
  * entry does not depend on the columns around it, on chunk_frames, on the touched set or on a repeat. */
 int asb_gsub_setup(asb_ctx* ctx, int64_t n, const int64_t* indptr, const int64_t* indices, const double* data, int64_t r,
@@ -743,6 +743,47 @@ int asb_test_gsub_apply(asb_ctx* ctx, const double* rhs_host, int64_t w, int aff
 /* test hook: what the set-up left, as it lies on the device; which 0: W^T (3, Np, rq), 1: the inverses (3, rq, rq), 2: o' (n, 3),
  * 3: U^T (3, rp, Np); len = the doubles of out_host (checked) */
 int asb_test_gsub_state(asb_ctx* ctx, int which, double* out_host, int64_t len);
+
+/* ------------------------------- roll-outs with the state in z under the position subspace (asb_zroll.hip) ---- */
+/* With the subspace of asb_gsub_setup held and EVERY kind reduced, a time step of the hyper-reduced solver is carried in the
+ * coordinates z of q = o + U z: per coordinate z' = c_z + sum_k Gz_k coef_k(q at the touched vertices), c_z = kappa + T y + E target,
+ * y = 2 z - z_prev.  T, kappa, E and the touched rows of U are formed once per asb_zroll_begin, Gz_k = (U^T A U)^-1 U^T S^T V_k once per
+ * asb_zroll_operator; a step reads and writes nothing of size N.  Without a subspace every entry returns ASB_ERR_ARG.
+ * asb_gsub_coordinates: out_dev (F', r, 3) = U^T (x_f - o) of the frames range(f0, f1, fj) of the tensor `which` (the leading
+ *   arguments of asb_pdsolve_begin), or, with pos_dev != NULL, of the caller's contiguous device tensor (n_frames, n, 3).  The chain
+ *   of an entry walks the n vertices in ascending order and is never split.
+ * asb_gsub_expand: out_dev (n_frames, n, 3) = o + U z for z_dev (n_frames, r, 3).
+ * asb_zroll_operator: Gz of the CURRENT bank from its S^T V (asb_rforce_operator) and the subspace; marked valid, and invalidated
+ *   exactly when that bank's operator of asb_hyper_operator is: by every solver set-up (all banks) and by asb_rforce_operator (its own).
+ * asb_zroll_begin: the frame arguments, diag = masses / h^2 (n), mode (0: z_prev = z, 1: z_prev from the animation's previous
+ *   frame) and acc3 = h^2 g of asb_pdsolve_begin; touched: the n_touched ascending vertices the slots' element set-ups are numbered
+ *   in; z_dev, zprev_dev: both NULL, or the state (F', r, 3) of a continuation (mode is then ignored).  Counts are judged before
+ *   pointers (ASB_ERR_ARG); more than 65535 * 64 frames: ASB_ERR_LIMIT.
+ * asb_zroll_slot: the set-up of the last asb_cproj_setup becomes the next kind, reduced, with the operator and solver of the
+ *   current bank (one kind per bank; at most 8).
+ * asb_zroll_pins: binds the pins of asb_pins_set; step t = 1, 2, .. from frame f reads row row0 + f + t - 1 of the shift.
+ * asb_zroll_steps: n_steps steps of n_iter iterations, all in stream order with ONE drain at the end.  record_every = e > 0: z after
+ *   the steps e, 2 e, .. into records_dev (R, F', r, 3).  A stale Gz, a subspace or pins that changed since asb_zroll_begin, and a
+ *   row of the shift that does not exist are refused (ASB_ERR_ARG) before anything is launched.  chunk_frames as asb_hyper_iterate.
+ * asb_zroll_state: z and z_prev (F', r, 3) after the steps taken so far.
+ * Nothing is split between blocks and nothing is atomic: repeats, frame sub-ranges, chunk widths and continuations give the bits
+ * of the whole. */
+int asb_gsub_coordinates(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean, double psf,
+                         const double* pos_dev, int64_t n_frames, double* out_dev);
+int asb_gsub_expand(asb_ctx* ctx, const double* z_dev, int64_t n_frames, double* out_dev);
+int asb_zroll_operator(asb_ctx* ctx);
+int asb_zroll_begin(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean, double psf,
+                    const double* diag, int mode, const double* acc3, int64_t n_touched, const int64_t* touched, const double* z_dev,
+                    const double* zprev_dev);
+int asb_zroll_slot(asb_ctx* ctx, double sigma_min, double sigma_max);
+int asb_zroll_pins(asb_ctx* ctx, int64_t row0);
+int asb_zroll_steps(asb_ctx* ctx, int64_t n_steps, int64_t n_iter, int64_t chunk_frames, int64_t record_every, double* records_dev);
+int asb_zroll_state(asb_ctx* ctx, double* z_dev, double* zprev_dev);
+/* test hook: the affine product kernel alone, Out = base + sum_s M_s X_s on host arrays.  r rows, w columns, n_seg <= 8 segments of
+ * lengths klen[s]; M_host: the (3, r, klen[s]) one behind the other, X_host: the (3, klen[s], w); base_host (3, r, w), or (3, r)
+ * broadcast over the columns with bcast; out_host (3, rq, ld), rq = r rounded up to 16 and ld = w to 64: the whole padded result */
+int asb_test_zroll_affine(asb_ctx* ctx, int64_t r, int64_t w, int64_t n_seg, const int64_t* klen, const double* M_host, const double* X_host,
+                          const double* base_host, int bcast, double* out_host);
 
 /* ------------------------------------------------ projective dynamics: the solver's iterations (asb_pdsolve.hip) ----------- */
 /* The local/global loop of Simulators.py:494-526 for the frames range(f0, f1, fj) of the training (which 0) or held-out (1)
