@@ -248,6 +248,7 @@ PROTOTYPES = {
     "asb_test_geodesic_field1": (c_int, [ctypes.c_void_p, c_i64, c_dp]),
     "asb_test_support_weights": (c_int, [ctypes.c_void_p, c_dp, c_i64, c_i64, c_i64, c_dbl, c_dbl, c_dp]),
     "asb_test_geodesic_cached": (c_int, [ctypes.c_void_p, c_i64, c_dp]),
+    "asb_test_prep_state": (c_int, [ctypes.c_void_p, c_dp, c_dp, c_dp, c_dp, c_dp]),
 }
 
 

@@ -12,14 +12,17 @@ extern "C" int asb_snapshots_center(asb_ctx* ctx, int rest_shape, int subtract, 
 // Tiled transpose (F, C) <-> (C, Fp) through LDS; optional scaling of column c by
 // colscale[c/3] (mass weighting, posSnapshots.py:82).  32x32 tiles, 256 threads.
 //   out[c * ld_out + r] = in[r * ld_in + c] * scale(c)      r < rows_in, c < cols_in
+// The 3 n_loc side is the long one (the frames are at most 32768) and goes on grid.x, whichever side of the input it is:
+// rows_on_x = 0: column strips on grid.x, row tiles on grid.y (upload); 1: the other way round (download).
 // --------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_transpose(const double* __restrict__ in, long long rows_in,
                                                    long long cols_in, long long ld_in,
                                                    double* __restrict__ out, long long ld_out,
-                                                   const double* __restrict__ colscale, int scale_on_in_col) {
+                                                   const double* __restrict__ colscale, int scale_on_in_col, int rows_on_x) {
     __shared__ double tile[32][33];
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
-    const long long c0 = (long long)blockIdx.x * 32, r0 = (long long)blockIdx.y * 32;
+    const long long c0 = (long long)(rows_on_x ? blockIdx.y : blockIdx.x) * 32;
+    const long long r0 = (long long)(rows_on_x ? blockIdx.x : blockIdx.y) * 32;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const long long r = r0 + ty + i * 8, c = c0 + tx;
@@ -402,7 +405,7 @@ static int transpose_in(asb_ctx* ctx, const double* stage_dev, const double* mas
     const long long C = ctx->n_loc * 3;
     dim3 grid((unsigned)((C + 31) / 32), (unsigned)((ctx->F + 31) / 32));
     hipLaunchKernelGGL(k_transpose, grid, dim3(256), 0, ctx->stream, stage_dev, (long long)ctx->F, C, C, ctx->X,
-                       (long long)ctx->Fp, massL_dev, 1);
+                       (long long)ctx->Fp, massL_dev, 1, 0);
     ASB_CHECK_LAUNCH(ctx);
     return ASB_OK;
 }
@@ -561,6 +564,31 @@ extern "C" int asb_snapshots_scale(asb_ctx* ctx, double a) {
     return ASB_OK;
 }
 
+// test hook: what the preparation left on the device, every pointer optional (include/asb.h)
+extern "C" int asb_test_prep_state(asb_ctx* ctx, double* X_raw, double* E0, double* EV, double* scalars10, int* flags3) {
+    if (!ctx) return ASB_ERR_ARG;
+    if (X_raw && !ctx->X) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_prep_state: no snapshot tensor on the device");
+    if ((E0 && !ctx->E0) || (EV && !ctx->EV) || (scalars10 && asb_capacity(ctx, &ctx->e0_sc) < 6))
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_prep_state: no energies on the device (asb_snapshots_scale has not run)");
+    if ((E0 && asb_capacity(ctx, &ctx->E0) < (size_t)ctx->n_loc) || (EV && asb_capacity(ctx, &ctx->EV) < (size_t)ctx->n_loc))
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_test_prep_state: the energies belong to an earlier, smaller tensor");
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    const size_t d = sizeof(double);
+    if (X_raw) ASB_HIP(ctx, hipMemcpyAsync(X_raw, ctx->X, (size_t)ctx->n_loc * 3 * ctx->Fp * d, hipMemcpyDeviceToHost, ctx->stream));
+    if (E0) ASB_HIP(ctx, hipMemcpyAsync(E0, ctx->E0, (size_t)ctx->n_loc * d, hipMemcpyDeviceToHost, ctx->stream));
+    if (EV) ASB_HIP(ctx, hipMemcpyAsync(EV, ctx->EV, (size_t)ctx->n_loc * d, hipMemcpyDeviceToHost, ctx->stream));
+    if (scalars10) ASB_HIP(ctx, hipMemcpyAsync(scalars10, ctx->e0_sc, 6 * d, hipMemcpyDeviceToHost, ctx->stream));
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (scalars10) {
+        scalars10[6] = ctx->ev_cv2;
+        scalars10[7] = ctx->mean_frac;
+        scalars10[8] = ctx->mean_energy;
+        scalars10[9] = ctx->prep_normx2;
+    }
+    if (flags3) { flags3[0] = ctx->e0_valid; flags3[1] = ctx->ev_valid; flags3[2] = ctx->have_mean; }
+    return ASB_OK;
+}
+
 extern "C" int asb_snapshots_get_mean(asb_ctx* ctx, double* mean_out) {
     if (!ctx || !ctx->X || !mean_out) return ASB_ERR_ARG;
     if (!ctx->have_mean) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_snapshots_get_mean before asb_snapshots_center");
@@ -576,9 +604,10 @@ int asb_download_vertex_major(asb_ctx* ctx, const double* src, double* out) {
     asb_tmp<double> stage;
     int rc;
     if ((rc = stage.alloc(ctx, (size_t)ctx->F * C))) return rc;
-    dim3 grid((unsigned)((ctx->F + 31) / 32), (unsigned)((C + 31) / 32));
+    // the strips of the C rows on grid.x: grid.y stays at (F + 31) / 32 <= 1024 blocks however many vertices the shard has
+    dim3 grid((unsigned)((C + 31) / 32), (unsigned)((ctx->F + 31) / 32));
     hipLaunchKernelGGL(k_transpose, grid, dim3(256), 0, ctx->stream, src, C, (long long)ctx->F, (long long)ctx->Fp,
-                       stage.get(), C, (const double*)nullptr, 0);
+                       stage.get(), C, (const double*)nullptr, 0, 1);
     ASB_CHECK_LAUNCH(ctx);
     ASB_HIP(ctx, hipMemcpyAsync(out, stage.get(), (size_t)ctx->F * C * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));

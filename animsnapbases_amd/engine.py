@@ -1229,6 +1229,24 @@ class HipEngine(object):
                                                  ptr(R)))
         return dict(energy=energy, pmax=pmax, pidx=pidx, psum=psum, nblk=nblk, nblk_cap=cap, scal=scal, W=W, R=R)
 
+    def test_prep_state(self, want_X=False, want_energies=True):
+        """dict of what the snapshot preparation left (tests/test_gpu_prep.py): flags e0_valid / ev_valid / have_mean; on request
+        X (n_loc, 3, Fp) with its padding; with want_energies (after `scale`) E0, EV (n_loc), sc (the six device scalars |X|^2,
+        max E0, sum m_v, -, sum EV, sum EV^2) and the host fields ev_cv2, mean_frac, mean_energy, prep_normx2.  The energies are
+        those of the last scaling sweep: they describe the current tensor only while e0_valid / ev_valid are set."""
+        Fp = (self.F + 15) // 16 * 16
+        X = np.empty((self.n_loc, 3, Fp)) if want_X else None
+        E0 = np.empty(self.n_loc) if want_energies else None
+        EV = np.empty(self.n_loc) if want_energies else None
+        sc = np.empty(10) if want_energies else None
+        flags = np.zeros(3, dtype=np.int32)
+        self._ck(self.lib.asb_test_prep_state(self.h, ptr(X), ptr(E0), ptr(EV), ptr(sc), ptr(flags)))
+        out = dict(X=X, E0=E0, EV=EV, e0_valid=bool(flags[0]), ev_valid=bool(flags[1]), have_mean=bool(flags[2]))
+        if want_energies:
+            out.update(sc=sc[:6].copy(), ev_cv2=float(sc[6]), mean_frac=float(sc[7]), mean_energy=float(sc[8]),
+                       prep_normx2=float(sc[9]))
+        return out
+
     def test_local_best(self, k):
         rec = np.empty(self.xchg_len())
         self._ck(self.lib.asb_test_local_best(self.h, int(k), ptr(rec)))

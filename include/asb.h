@@ -1000,6 +1000,14 @@ int asb_test_geodesic_field1(asb_ctx* ctx, int64_t src, double* phi_out);
 int asb_test_support_weights(asb_ctx* ctx, const double* phi, int64_t n, int64_t v0, int64_t n_loc, double dmin, double dmax,
                              double* s_out);
 int asb_test_geodesic_cached(asb_ctx* ctx, int64_t slot, double* out);
+/* test hook of the snapshot preparation (tests/test_gpu_prep.py): what the context holds, every pointer optional.  X_raw: the
+ * vertex-major tensor (3 n_loc x Fp) WITH its padding; E0, EV (n_loc each): the per-vertex energies of the last scaling sweep;
+ * scalars10: the six device scalars [|X|^2, largest E0, energy along the constant-in-time direction, -, sum EV, sum EV^2]
+ * followed by the host fields ev_cv2, mean_frac, mean_energy, prep_normx2; flags3: e0_valid, ev_valid, have_mean.
+ * The energies, scalars and host fields are whatever the last scaling sweep on this context left: they describe the CURRENT
+ * tensor only while e0_valid / ev_valid are set (a later writer of X clears the flags and leaves the arrays as they are).
+ * ASB_ERR_ARG with a message where a buffer that was asked for does not exist (no ingest call / no scaling sweep yet). */
+int asb_test_prep_state(asb_ctx* ctx, double* X_raw, double* E0, double* EV, double* scalars10, int* flags3);
 
 #ifdef __cplusplus
 }
