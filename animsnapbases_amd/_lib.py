@@ -193,6 +193,7 @@ PROTOTYPES = {
                                 ctypes.c_void_p, ctypes.c_void_p]),
     "asb_zroll_slot": (c_int, [ctypes.c_void_p, c_dbl, c_dbl]),
     "asb_zroll_pins": (c_int, [ctypes.c_void_p, c_i64]),
+    "asb_zroll_forces": (c_int, [ctypes.c_void_p, c_i64]),
     "asb_zroll_steps": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, ctypes.c_void_p]),
     "asb_zroll_state": (c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "asb_test_zroll_affine": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_dp, c_dp, c_dp, c_dp, c_int, c_dp]),
@@ -211,6 +212,9 @@ PROTOTYPES = {
     "asb_pins_term": (c_int, [ctypes.c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, ctypes.c_void_p]),
     "asb_fm_add": (c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i64]),
     "asb_pdsolve_pins": (c_int, [ctypes.c_void_p, c_i64]),
+    "asb_ext_set": (c_int, [ctypes.c_void_p, c_i64, c_dp, c_int, c_int, c_dbl]),
+    "asb_ext_clear": (c_int, [ctypes.c_void_p]),
+    "asb_pdsolve_external": (c_int, [ctypes.c_void_p, c_i64]),
     "asb_splocs_begin": (c_int, [ctypes.c_void_p]),
     "asb_splocs_gram": (c_int, [ctypes.c_void_p, c_dp, c_dp, ctypes.POINTER(c_dbl)]),
     "asb_splocs_weights": (c_int, [ctypes.c_void_p, c_dp, c_dp, c_dp, c_dp]),

@@ -377,6 +377,15 @@ struct asb_ctx {
         double *wi = nullptr, *p0 = nullptr, *shift = nullptr;        // (P) weights, (P, 3) targets, the shift
     };
     Pins pins;
+    // external forces and the floor of the time steps (asb_ext_set, asb_pdsolve.hip): checked and uploaded once, read by
+    // asb_pdsolve_external and every advance of a solve they are bound to
+    struct Ext {
+        int64_t n = 0, T = 0;             // the vertices they were checked against (0: nothing set); rows of fa (0: constant, or no table)
+        int force = 0, floor = 0, axis = 1;       // a table is held; the floor is on, along this coordinate
+        double height = 0.0;
+        double* fa = nullptr;             // (max(T, 1), 3 n) the displacements dt^2 force / mass, row 3 v + d contiguous
+    };
+    Ext ext;
     // the global step's second solver (asb_gslab.hip): the block-tridiagonal slab factor of A_N.  The context holds EITHER
     // gs_Ainv (gs_n > 0) or the factor (asb_gslab_n(ctx) > 0): each set-up releases the other
     asb_gsl* gsl = nullptr;

@@ -1,7 +1,7 @@
 // The local/global iterations of the reference's projective-dynamics solver (projective_dynamics/Simulators.py:494-526) for a
 // batch of frames of the resident animation: q_0 given, q_{k+1} = A^-1 (sum_i S_i^T p_i(q_k) + M/h^2 s), s fixed.  Every
-// selected frame is its own solve.  Collisions are not modelled; positional constraints (pins) are a constant added to ms, at
-// the end of this file.  The end of the reference's step
+// selected frame is its own solve.  Self-collisions are not modelled; positional constraints (pins) are a constant added to ms,
+// external forces and the floor (resolve_collision) act on s before the iterations: both further down.  The end of the reference's step
 // (:531-532: velocities = (q - positions) / dt, positions = q) is asb_pdsolve_advance below: a roll-out is iterate, advance, iterate ...
 //
 // State of a solve over the n_sel frames range(f0, f1, fj), owned by the context and reused by the next solve:
@@ -78,6 +78,11 @@ struct asb_pds {
     // the context's pins bound to this solve (asb_pdsolve_pins): their term is in ms; row of shift = pin_row0 + frame + pin_step
     bool pins = false;
     long long pin_row0 = 0, pin_step = 0;
+    // the context's forces and floor bound to this solve (asb_pdsolve_external): row of fa = ext_row0 + frame + ext_step
+    bool ext = false;
+    long long ext_row0 = 0, ext_step = 0;
+    int mode = 0;                                 // of asb_pdsolve_begin
+    bool q_is_s = false;                          // the iterate holds the explicit state: begun with start 0, or advanced
     int n_slots = 0;
     PdSlot slot[PD_MAX_SLOTS];
 };
@@ -210,7 +215,7 @@ static long long pd_solver_n(const asb_ctx* ctx) {
 extern "C" int asb_pdsolve_begin(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean,
                                  double psf, const double* diag, int mode, const double* acc3, int start, const double* start_dev) {
     if (!ctx || !diag || !acc3) return ASB_ERR_ARG;
-    if (ctx->pds) ctx->pds->begun = false, ctx->pds->n_slots = 0, ctx->pds->carry = false, ctx->pds->pins = false;
+    if (ctx->pds) ctx->pds->begun = false, ctx->pds->n_slots = 0, ctx->pds->carry = false, ctx->pds->pins = false, ctx->pds->ext = false;
     if (fj >= 1 && f1 > f0 && ((f1 - f0 + fj - 1) / fj + 63) / 64 > 65535)        // on the count alone, before any tensor is looked at
         ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_pdsolve_begin: %lld frames in one solve (at most %d)", (long long)((f1 - f0 + fj - 1) / fj), 65535 * 64);
     if (mode != 0 && mode != 1) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_begin: mode %d (0: s = x, 1: s = 2 x - x_prev)", mode);
@@ -251,6 +256,7 @@ extern "C" int asb_pdsolve_begin(asb_ctx* ctx, int which, int64_t f0, int64_t f1
     s->w = w, s->f0 = (int)f0, s->fj = (int)fj;
     s->acc[0] = acc3[0], s->acc[1] = acc3[1], s->acc[2] = acc3[2];
     s->diag_host.assign(diag, diag + n);
+    s->mode = mode, s->q_is_s = start == 0;
     return ASB_OK;
 }
 
@@ -590,6 +596,209 @@ extern "C" int asb_pdsolve_pins(asb_ctx* ctx, int64_t row0) {
     return ASB_OK;
 }
 
+// ================================================================ external forces and the floor
+// The start of the reference's step (Simulators.py:494-498): explicit = positions + dt velocities + dt^2 fext / mass, then
+// resolve_collision on every vertex (Constraint_projections.py:1287-1298: a coordinate below the floor is set onto it); sn and
+// the first iterate are both taken from the result.  The host forms fa = dt^2 force / mass without gravity (gravity stays in
+// acc); the device holds fa as (T, 3 n) rows, or one row for a constant force.  Per entry (row r = 3 v + d, frame column c,
+// table row rho(c) = row0 + f0 + c fj + step), after today's s = fl(fl(2 Q - P) + acc[d]):
+//   x = fl(s + fa[rho(c)][r])                        (a table is held)
+//   if (d == axis && x < height) x = height          (the floor is on; a comparison: NaN stays NaN, in its own frame)
+//   Q <- x,  ms <- fl(diag[v] x)
+// pd_ext_apply is the one place of the two lines; contraction is off, so the add is rounded on its own.  The iterations read ms
+// and Q and are not changed; pins go onto ms afterwards.
+// pd_ext_body: the tiling of k_pd_advance (a block owns 64 rows x 64 frames; wave w takes rows w, w + 4, .., lanes along the
+// frames).  rho(c) differs per lane, so a direct read of fa would be a gather with a stride of fj 3 n doubles.  Instead the LDS
+// tile is filled first, wave = frame, lanes along r: 512-byte runs of fa, entry (frame fl, row rl) at fl * 65 + rl -- the ms
+// store in reverse.  After a barrier each thread reads its entry tile[lane * 65 + rl] and later overwrites THE SAME address
+// with diag x: same thread, same slot, no further barrier before the one k_pd_advance has, and no LDS beyond its 33 280 bytes.
+// A constant force (FORCE 1) is a broadcast load of fa[r] per wave and needs no fill.  Tail predicates as k_pd_advance: rows >=
+// 3 n and frames >= n_sel neither read nor write; the padding columns of Q and P are never written.  No atomics.
+// ADV: the fused advance (reads Q and P; writes P, Q, ms).  Otherwise the correction: reads S, which holds s (Q itself, or a
+// scratch tensor when the iterate is not the explicit state), writes Qw (NULL: the iterate is left alone) and ms.
+template <int FORCE, bool FLOOR>
+__device__ __forceinline__ double pd_ext_apply(double x, double f, int d, int axis, double height) {
+#pragma clang fp contract(off)
+    if (FORCE) x = x + f;
+    if (FLOOR && d == axis && x < height) x = height;
+    return x;
+}
+
+struct PdExt {
+    const double* fa;           // FORCE 1: (rows); 2: the table's row 0
+    long long row_base;         // FORCE 2: frame column c reads row row_base + c fj
+    int fj, axis;
+    double height;
+};
+
+template <int FORCE, bool FLOOR, bool ADV>
+__device__ __forceinline__ void pd_ext_body(double* tile, const double* S, double* Qw, double* P, const double* __restrict__ diag, int n_sel,
+                                            long long rows, long long ld, double acc0, double acc1, double acc2, const PdExt& e,
+                                            double* __restrict__ ms) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long long r0 = (long long)blockIdx.x * 64;
+    const int t0 = (int)blockIdx.y * 64;
+    if (FORCE == 2) {
+        for (int fl = wv; fl < 64; fl += 4)
+            if (t0 + fl < n_sel && r0 + lane < rows)
+                tile[fl * PD_LDQ + lane] = e.fa[(e.row_base + (long long)(t0 + fl) * e.fj) * rows + r0 + lane];
+        __syncthreads();
+    }
+    for (int rl = wv; rl < 64; rl += 4) {
+        const long long r = r0 + rl;
+        if (r < rows && t0 + lane < n_sel) {
+            const long long at = r * ld + t0 + lane;
+            const int d = (int)(r % 3);
+            double x;
+            if (ADV) {
+                const double q = S[at];
+                x = 2.0 * q - P[at];
+                x = x + (d == 0 ? acc0 : (d == 1 ? acc1 : acc2));
+                P[at] = q;
+            } else {
+                x = S[at];
+            }
+            const double f = FORCE == 2 ? tile[lane * PD_LDQ + rl] : (FORCE == 1 ? e.fa[r] : 0.0);
+            x = pd_ext_apply<FORCE, FLOOR>(x, f, d, e.axis, e.height);
+            if (Qw) Qw[at] = x;
+            tile[lane * PD_LDQ + rl] = diag[r / 3] * x;
+        }
+    }
+    __syncthreads();
+    for (int fl = wv; fl < 64; fl += 4)
+        if (t0 + fl < n_sel && r0 + lane < rows) ms[(long long)(t0 + fl) * rows + r0 + lane] = tile[fl * PD_LDQ + lane];
+}
+
+// grid (row tiles of 64, frame tiles of 64): k_pd_advance with the force and the floor in the same pass
+template <int FORCE, bool FLOOR>
+__global__ __launch_bounds__(256) void k_pd_advance_ext(double* Q, double* P, const double* __restrict__ diag, int n_sel, long long rows,
+                                                        long long ld, double acc0, double acc1, double acc2, PdExt e,
+                                                        double* __restrict__ ms) {
+    __shared__ double tile[64 * PD_LDQ];
+    pd_ext_body<FORCE, FLOOR, true>(tile, Q, Q, P, diag, n_sel, rows, ld, acc0, acc1, acc2, e, ms);
+}
+
+// grid as above: the correction of a state that holds s already (S; S == Qw, or Qw NULL)
+template <int FORCE, bool FLOOR>
+__global__ __launch_bounds__(256) void k_pd_external(const double* S, double* Qw, const double* __restrict__ diag, int n_sel, long long rows,
+                                                     long long ld, PdExt e, double* __restrict__ ms) {
+    __shared__ double tile[64 * PD_LDQ];
+    pd_ext_body<FORCE, FLOOR, false>(tile, S, Qw, nullptr, diag, n_sel, rows, ld, 0.0, 0.0, 0.0, e, ms);
+}
+
+static PdExt pd_ext_dev(const asb_ctx* ctx, const asb_pds* s, long long step) {
+    const asb_ctx::Ext& h = ctx->ext;
+    return PdExt{h.fa, s->ext_row0 + s->f0 + step, s->fj, h.axis, h.height};
+}
+
+// the forces and the floor fit the solve, and step `step` finds its rows in the table
+static int asb_pd_ext_check(asb_ctx* ctx, const asb_pds* s, const char* who, long long row0, long long step) {
+    const asb_ctx::Ext& h = ctx->ext;
+    if (h.n < 1 || (!h.force && !h.floor)) ASB_FAIL(ctx, ASB_ERR_ARG, "%s: no forces and no floor on the device (asb_ext_set)", who);
+    if (h.n != s->n || ctx->n_loc != s->n)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "%s: the forces were checked against %lld vertices, the solve has %lld", who, (long long)h.n, s->n);
+    const long long last = row0 + s->f0 + step + (s->n_sel - 1) * s->fj;
+    if (h.force && h.T > 0 && last >= h.T) ASB_FAIL(ctx, ASB_ERR_ARG, "%s: row %lld of the force table is needed, it has %lld", who, last, (long long)h.T);
+    return ASB_OK;
+}
+
+extern "C" int asb_ext_clear(asb_ctx* ctx) {
+    if (!ctx) return ASB_ERR_ARG;
+    ctx->ext.n = ctx->ext.T = 0;
+    ctx->ext.force = ctx->ext.floor = 0;
+    if (ctx->pds) ctx->pds->ext = false;
+    return ASB_OK;
+}
+
+extern "C" int asb_ext_set(asb_ctx* ctx, int64_t T_s, const double* table_host, int floor_on, int axis, double height) {
+    if (!ctx) return ASB_ERR_ARG;
+    asb_ext_clear(ctx);
+    const int64_t n = ctx->n_loc;
+    if (n < 1) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_ext_set: no tensor on the device");
+    if (T_s < 0 || (T_s > 0 && !table_host)) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_ext_set: %lld rows of a table that is %s", (long long)T_s, table_host ? "given" : "missing");
+    if (!table_host && !floor_on) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_ext_set: neither a force table nor a floor");
+    if (floor_on && (axis < 0 || axis > 2 || !std::isfinite(height)))
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_ext_set: floor along axis %d at height %g (an axis 0..2, a finite height)", axis, height);
+    const size_t len = table_host ? (size_t)(T_s > 0 ? T_s : 1) * 3 * (size_t)n : 0;
+    if (len > ((size_t)1 << 31) / sizeof(double))
+        ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_ext_set: a force table of %lld x %lld doubles, %.3g GiB (at most 2 GiB)", (long long)(T_s > 0 ? T_s : 1), (long long)(3 * n),
+                 (double)len * sizeof(double) / 1073741824.0);
+    for (size_t k = 0; k < len; ++k)
+        if (!std::isfinite(table_host[k])) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_ext_set: entry %lld of the force table is not finite", (long long)k);
+    asb_ctx::Ext& h = ctx->ext;
+    if (len) {
+        ASB_HIP(ctx, hipSetDevice(ctx->dev));
+        int rc;
+        if ((rc = asb_alloc(ctx, &h.fa, len))) return rc;
+        ASB_HIP(ctx, hipMemcpyAsync(h.fa, table_host, len * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the host array may go
+    }
+    h.n = n, h.T = table_host ? T_s : 0, h.force = table_host ? 1 : 0;
+    h.floor = floor_on ? 1 : 0, h.axis = floor_on ? axis : 1, h.height = floor_on ? height : 0.0;
+    return ASB_OK;
+}
+
+template <int FORCE, bool FLOOR>
+static void pd_external_launch(asb_ctx* ctx, asb_pds* s, const double* S, double* Qw, const PdExt& e) {
+    const dim3 grid((unsigned)((3 * s->n + 63) / 64), (unsigned)((s->n_sel + 63) / 64));
+    hipLaunchKernelGGL((k_pd_external<FORCE, FLOOR>), grid, dim3(256), 0, ctx->stream, S, Qw, s->diag, (int)s->n_sel, 3 * s->n, s->ld, e, s->ms);
+}
+
+template <int FORCE, bool FLOOR>
+static void pd_advance_ext_launch(asb_ctx* ctx, asb_pds* s, const PdExt& e) {
+    const dim3 grid((unsigned)((3 * s->n + 63) / 64), (unsigned)((s->n_sel + 63) / 64));
+    hipLaunchKernelGGL((k_pd_advance_ext<FORCE, FLOOR>), grid, dim3(256), 0, ctx->stream, s->Q, s->P, s->diag, (int)s->n_sel, 3 * s->n, s->ld,
+                       s->acc[0], s->acc[1], s->acc[2], e, s->ms);
+}
+
+extern "C" int asb_pdsolve_external(asb_ctx* ctx, int64_t row0) {
+    if (!ctx) return ASB_ERR_ARG;
+    asb_pds* s = ctx->pds;
+    if (!s || !s->begun) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_external: no solve begun (asb_pdsolve_begin)");
+    if (s->pins)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_external: the solve has its pins already: this call rewrites the inertia term and their term would be lost "
+                                   "(asb_pdsolve_external before asb_pdsolve_pins)");
+    if (s->ext) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_external: the solve has its forces and floor already");
+    if (row0 < 0) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_external: row0 %lld", (long long)row0);
+    int rc;
+    if ((rc = asb_pd_ext_check(ctx, s, "asb_pdsolve_external", row0, 0))) return rc;      // before any launch, the solve untouched
+    s->ext_row0 = row0, s->ext_step = 0;
+    if (!s->q_is_s && s->w.T != ctx->X && s->w.T != ctx->ho_Y)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_external: the tensor changed since asb_pdsolve_begin");
+    const long long n = s->n, n_sel = s->n_sel, ld = s->ld;
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    if (!s->carry) {                                // the solve's own copy of diag, as asb_pdsolve_carry makes it
+        if ((rc = asb_alloc(ctx, &s->diag, (size_t)n))) return rc;
+        ASB_HIP(ctx, hipMemcpyAsync(s->diag, s->diag_host.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    }
+    const double* S = s->Q;
+    double* Qw = s->Q;
+    if (!s->q_is_s) {
+        // the iterate is x_f or the caller's tensor, not s: s is formed as k_pd_init(start 0) forms it, into the buffer of c
+        // (asb_hyper_iterate rewrites c from ms in every call), and the iterate is left alone
+        if ((rc = asb_alloc(ctx, &s->c, (size_t)3 * n * ld))) return rc;
+        hipLaunchKernelGGL(k_pd_init, dim3((unsigned)((3 * n + 3) / 4), (unsigned)((n_sel + 63) / 64)), dim3(256), 0, ctx->stream, s->w, s->f0, s->fj,
+                           (int)n_sel, n, 0, s->mode, s->acc[0], s->acc[1], s->acc[2], s->c, ld);
+        S = s->c, Qw = nullptr;
+    }
+    const PdExt e = pd_ext_dev(ctx, s, 0);
+    const asb_ctx::Ext& h = ctx->ext;
+    const int force = h.force ? (h.T > 0 ? 2 : 1) : 0;
+    if (h.floor) {
+        if (force == 2) pd_external_launch<2, true>(ctx, s, S, Qw, e);
+        else if (force == 1) pd_external_launch<1, true>(ctx, s, S, Qw, e);
+        else pd_external_launch<0, true>(ctx, s, S, Qw, e);
+    } else {
+        if (force == 2) pd_external_launch<2, false>(ctx, s, S, Qw, e);
+        else pd_external_launch<1, false>(ctx, s, S, Qw, e);
+    }
+    ASB_CHECK_LAUNCH(ctx);
+    ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));          // (diag_host was read)
+    s->ext = true;
+    return ASB_OK;
+}
+
 extern "C" int asb_pdsolve_carry(asb_ctx* ctx, const double* pos_dev) {
     if (!ctx) return ASB_ERR_ARG;
     asb_pds* s = ctx->pds;
@@ -625,10 +834,26 @@ extern "C" int asb_pdsolve_advance(asb_ctx* ctx) {
         ASB_FAIL(ctx, ASB_ERR_ARG, "asb_pdsolve_advance: the solve carries no previous positions (asb_pdsolve_carry after asb_pdsolve_begin)");
     int rc;
     if (s->pins && (rc = asb_pd_pins_check(ctx, s, "asb_pdsolve_advance", s->pin_step + 1))) return rc;       // before any launch
+    if (s->ext && (rc = asb_pd_ext_check(ctx, s, "asb_pdsolve_advance", s->ext_row0, s->ext_step + 1))) return rc;
     ASB_HIP(ctx, hipSetDevice(ctx->dev));
     const dim3 grid((unsigned)((3 * s->n + 63) / 64), (unsigned)((s->n_sel + 63) / 64));
-    hipLaunchKernelGGL(k_pd_advance, grid, dim3(256), 0, ctx->stream, s->Q, s->P, s->diag, (int)s->n_sel, 3 * s->n, s->ld, s->acc[0], s->acc[1],
-                       s->acc[2], s->ms);
+    if (s->ext) {                                   // the same pass with the force and the floor of the next step in it
+        const PdExt e = pd_ext_dev(ctx, s, ++s->ext_step);
+        const asb_ctx::Ext& h = ctx->ext;
+        const int force = h.force ? (h.T > 0 ? 2 : 1) : 0;
+        if (h.floor) {
+            if (force == 2) pd_advance_ext_launch<2, true>(ctx, s, e);
+            else if (force == 1) pd_advance_ext_launch<1, true>(ctx, s, e);
+            else pd_advance_ext_launch<0, true>(ctx, s, e);
+        } else {
+            if (force == 2) pd_advance_ext_launch<2, false>(ctx, s, e);
+            else pd_advance_ext_launch<1, false>(ctx, s, e);
+        }
+    } else {
+        hipLaunchKernelGGL(k_pd_advance, grid, dim3(256), 0, ctx->stream, s->Q, s->P, s->diag, (int)s->n_sel, 3 * s->n, s->ld, s->acc[0], s->acc[1],
+                           s->acc[2], s->ms);
+    }
+    s->q_is_s = true;
     if (s->pins) {                                  // ms of the next step is rewritten: its pin term, one row of shift later
         ++s->pin_step;
         asb_pins_launch<true>(ctx, s->pin_row0 + s->f0 + s->pin_step, s->fj, (int)s->n_sel, s->ms);

@@ -57,6 +57,11 @@ struct asb_zr {
     double *Tt = nullptr, *kap = nullptr, *Et = nullptr, *tgt = nullptr;       // (3, rq, rq) T^T; (3, rq); (3, Pp, rq) E^T; (3, Pp, ld)
     double *Utt = nullptr, *ot = nullptr, *ota = nullptr, *diag = nullptr;     // (3, rp, ntp); (nt, 3) o_t and o_t + a; (n)
     int* tv = nullptr;
+    // the context's force table bound to this roll-out (asb_zroll_forces): Phi^T (3, fTn, rq) k-major like E^T, the touched rows of
+    // fa (fTn, 3 nt), and the base of a step's affine product Cb = kappa + Phi[:, rho(c)] (3, rq, ld); fT 0: a constant force
+    bool forces = false;
+    long long f_row0 = 0, fT = 0, fTn = 0;
+    double *Phit = nullptr, *fat = nullptr, *Cb = nullptr;
     int n_slots = 0;
     ZrSlot slot[ZR_MAX_SLOTS];
 };
@@ -217,6 +222,43 @@ __global__ __launch_bounds__(256) void k_zr_pin_cols(const int* __restrict__ pv,
     R[(3LL * pv[i] + d) * ld + i] = wi[i];
 }
 
+// ---- external forces (asb_zroll_forces).  With D fa = force up to the host's rounding, Phi_d = W_d (D o fa_d) (r x rows) joins c_z:
+// c_z = kappa + T y + E target + Phi[:, rho(c)], and the touched rows of the first iterate become fl(fl(o_t + a + U_t y) + fa[rho(c)]).
+// grid (rows / 4, ldT / 64), as k_zr_cols: column c < Tn of the work matrix is D fa[c] (row 3 v + d), the others 0
+__global__ __launch_bounds__(256) void k_zr_force_cols(const double* __restrict__ fa, int Tn, const double* __restrict__ diag, long long n_verts,
+                                                       double* __restrict__ R, long long ld) {
+    const int lane = threadIdx.x & 63;
+    const long long e = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long long c = (long long)blockIdx.y * 64 + lane;
+    if (e >= 3 * n_verts) return;
+    R[e * ld + c] = c < Tn ? diag[e / 3] * fa[c * 3 * n_verts + e] : 0.0;
+}
+// grid (blocks of 256 over 3 nt, Tn): fat[row][3 t + d] = fa[row][3 tv[t] + d]
+__global__ __launch_bounds__(256) void k_zr_force_gather(const double* __restrict__ fa, long long n_verts, const int* __restrict__ tv, int nt,
+                                                         double* __restrict__ fat) {
+    const int e = (int)blockIdx.x * 256 + threadIdx.x;
+    const long long row = blockIdx.y;
+    if (e >= 3 * nt) return;
+    fat[row * 3 * nt + e] = fa[row * 3 * n_verts + 3LL * tv[e / 3] + e % 3];
+}
+// grid (ld / 64, rq, 3): Cb[d][j][c] = fl(kappa[d][j] + Phi^T[d][rho(c)][j]), rho(c) = row_base + c fj, for c < n_sel; kappa elsewhere
+__global__ __launch_bounds__(64) void k_zr_force_base(const double* __restrict__ kap, const double* __restrict__ Phit, long long Tn, int rq,
+                                                      long long row_base, int fj, int n_sel, long long ld, double* __restrict__ Cb) {
+    const int j = blockIdx.y, d = blockIdx.z;
+    const long long c = (long long)blockIdx.x * 64 + threadIdx.x;
+    double v = kap[(long long)d * rq + j];
+    if (c < n_sel) v = v + Phit[((long long)d * Tn + row_base + c * fj) * rq + j];
+    Cb[((long long)d * rq + j) * ld + c] = v;
+}
+// grid (3 nt / 4, ld / 64): wave = one touched row 3 t + d x 64 frames: Qc = fl(Qc + fat[rho(c)][3 t + d]) for c < n_sel
+__global__ __launch_bounds__(256) void k_zr_force_touched(const double* __restrict__ fat, long long nt3, long long row_base, int fj, int n_sel,
+                                                          long long ld, double* __restrict__ Qc) {
+    const long long e = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long long c = (long long)blockIdx.y * 64 + (threadIdx.x & 63);
+    if (e >= nt3 || c >= n_sel) return;
+    Qc[e * ld + c] = Qc[e * ld + c] + fat[(row_base + c * fj) * nt3 + e];
+}
+
 static void zr_tr_launch(asb_ctx* ctx, const double* Y, long long ldy, int col0, int valid, int rows_out, int rq, double* Out) {
     hipLaunchKernelGGL(k_zr_tr, dim3((unsigned)((rq + 63) / 64), (unsigned)rows_out, 3), dim3(64), 0, ctx->stream, Y, ldy, col0, valid, rows_out, rq, Out);
 }
@@ -313,7 +355,7 @@ extern "C" int asb_zroll_begin(asb_ctx* ctx, int which, int64_t f0, int64_t f1, 
                                const double* diag, int mode, const double* acc3, int64_t n_touched, const int64_t* touched, const double* z_dev,
                                const double* zprev_dev) {
     if (!ctx || n_touched < 1 || !diag || !acc3 || !touched) return ASB_ERR_ARG;
-    if (ctx->zr) ctx->zr->begun = false, ctx->zr->n_slots = 0, ctx->zr->pins = false;
+    if (ctx->zr) ctx->zr->begun = false, ctx->zr->n_slots = 0, ctx->zr->pins = false, ctx->zr->forces = false;
     if (fj >= 1 && f1 > f0 && ((f1 - f0 + fj - 1) / fj + 63) / 64 > 65535)        // on the count alone, before any tensor is looked at
         ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_zroll_begin: %lld frames in one roll-out (at most %d)", (long long)((f1 - f0 + fj - 1) / fj), 65535 * 64);
     if (mode != 0 && mode != 1) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_zroll_begin: mode %d (0: z_prev = z, 1: z_prev from the previous frame)", mode);
@@ -441,6 +483,46 @@ extern "C" int asb_zroll_pins(asb_ctx* ctx, int64_t row0) {
     return ASB_OK;
 }
 
+// Binds the force table of asb_ext_set to the roll-out.  ALL rows of the table are prepared here, once (Tn = T_s, or 1 for a constant
+// force): which rows a later asb_zroll_steps(n_steps) reads is not known yet, and a continuation reads further ones.  Phi = W (D fa^T)
+// through the reduce of asb_gsub.hip, the table's rows its columns: one chain over N per entry, ascending, never split.
+extern "C" int asb_zroll_forces(asb_ctx* ctx, int64_t row0) {
+    if (!ctx) return ASB_ERR_ARG;
+    asb_zr* s = ctx->zr;
+    if (!s || !s->begun) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_zroll_forces: no roll-out begun (asb_zroll_begin)");
+    if (s->forces) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_zroll_forces: the roll-out has its forces already");
+    if (row0 < 0) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_zroll_forces: row0 %lld", (long long)row0);
+    const asb_ctx::Ext& h = ctx->ext;
+    if (h.n < 1 || !h.force) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_zroll_forces: no force table on the device (asb_ext_set)");
+    if (h.floor) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_zroll_forces: a floor is set: a clamp on vertex coordinates has no form in z");
+    if (h.n != s->n || ctx->n_loc != s->n)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_zroll_forces: the forces were checked against %lld vertices, the roll-out has %lld", (long long)h.n, s->n);
+    const long long Tn = h.T > 0 ? h.T : 1;
+    if (Tn > 65535) ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_zroll_forces: %lld rows of the force table (at most 65535: they sit on one grid dimension)", Tn);
+    if (h.T > 0 && row0 + s->f0 + (s->n_sel - 1) * s->fj + s->step >= h.T)
+        ASB_FAIL(ctx, ASB_ERR_ARG, "asb_zroll_forces: row %lld of the force table is needed, it has %lld", row0 + s->f0 + (s->n_sel - 1) * s->fj + s->step,
+                 (long long)h.T);
+    GsubView g;
+    int rc;
+    if ((rc = zr_view(ctx, "asb_zroll_forces", &g))) return rc;
+    if (g.gen != s->gen) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_zroll_forces: the subspace changed since asb_zroll_begin");
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    const long long ldT = (Tn + 63) / 64 * 64;
+    if ((rc = asb_alloc(ctx, &s->Phit, (size_t)3 * Tn * s->rq)) || (rc = asb_alloc(ctx, &s->fat, (size_t)Tn * 3 * s->nt))) return rc;
+    if ((rc = asb_alloc(ctx, &s->Cb, (size_t)3 * s->rq * s->ld))) return rc;
+    double *R = nullptr, *Y = nullptr;
+    if ((rc = asb_gsub_work(ctx, ldT, &R, &Y))) return rc;
+    hipLaunchKernelGGL(k_zr_force_cols, dim3((unsigned)((3 * s->n + 3) / 4), (unsigned)(ldT / 64)), dim3(256), 0, ctx->stream, h.fa, (int)Tn, s->diag, s->n,
+                       R, ldT);
+    asb_gsub_reduce_launch(ctx, 0, ldT, Y);
+    zr_tr_launch(ctx, Y, ldT, 0, (int)Tn, (int)Tn, (int)s->rq, s->Phit);
+    hipLaunchKernelGGL(k_zr_force_gather, dim3((unsigned)((3 * s->nt + 255) / 256), (unsigned)Tn), dim3(256), 0, ctx->stream, h.fa, s->n, s->tv,
+                       (int)s->nt, s->fat);
+    ASB_CHECK_LAUNCH(ctx);
+    s->f_row0 = row0, s->fT = h.T, s->fTn = Tn, s->forces = true;
+    return ASB_OK;
+}
+
 extern "C" int asb_zroll_steps(asb_ctx* ctx, int64_t n_steps, int64_t n_iter, int64_t chunk_frames, int64_t record_every, double* records_dev) {
     if (!ctx) return ASB_ERR_ARG;
     asb_zr* s = ctx->zr;
@@ -469,6 +551,12 @@ extern "C" int asb_zroll_steps(asb_ctx* ctx, int64_t n_steps, int64_t n_iter, in
         if (h.P != s->P || h.n != s->n) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_zroll_steps: the pins changed since asb_zroll_pins");
         const long long last = s->pin_row0 + s->f0 + (s->n_sel - 1) * s->fj + s->step + n_steps - 1;
         if (h.T > 0 && last >= h.T) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_zroll_steps: row %lld of the shift is needed, it has %lld", last, (long long)h.T);
+    }
+    if (s->forces) {
+        const asb_ctx::Ext& e = ctx->ext;
+        if (!e.force || e.n != s->n || e.T != s->fT) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_zroll_steps: the forces changed since asb_zroll_forces");
+        const long long last = s->f_row0 + s->f0 + (s->n_sel - 1) * s->fj + s->step + n_steps - 1;
+        if (s->fT > 0 && last >= s->fT) ASB_FAIL(ctx, ASB_ERR_ARG, "asb_zroll_steps: row %lld of the force table is needed, it has %lld", last, s->fT);
     }
     const long long n_sel = s->n_sel, ld = s->ld, rq = s->rq;
     long long cw = 0, cols_max = 0;
@@ -501,8 +589,19 @@ extern "C" int asb_zroll_steps(asb_ctx* ctx, int64_t n_steps, int64_t n_iter, in
         if (s->pins)
             hipLaunchKernelGGL(k_zr_targets, dim3((unsigned)(ld / 64), (unsigned)s->Pp), dim3(64), 0, ctx->stream, zp, s->pin_row0 + s->f0 + s->step, s->fj,
                                (int)n_sel, (int)s->Pp, ld, s->tgt);
-        zr_affine_launch(ctx, adv, (int)rq, s->kap, true, s->Cz, ld, 0, ld);
-        asb_gsub_expand_launch(ctx, s->Utt, s->ntp, s->Z, ld, s->ota, s->Qc, n_sel, s->nt, nullptr);
+        if (s->forces) {                            // two launches more: the base with Phi's column of every frame, and fa on the touched rows
+            const long long fr = s->fT > 0 ? s->f_row0 + s->f0 + s->step : 0;
+            const int ffj = s->fT > 0 ? s->fj : 0;
+            hipLaunchKernelGGL(k_zr_force_base, dim3((unsigned)(ld / 64), (unsigned)rq, 3), dim3(64), 0, ctx->stream, s->kap, s->Phit, s->fTn, (int)rq, fr,
+                               ffj, (int)n_sel, ld, s->Cb);
+            zr_affine_launch(ctx, adv, (int)rq, s->Cb, false, s->Cz, ld, 0, ld);
+            asb_gsub_expand_launch(ctx, s->Utt, s->ntp, s->Z, ld, s->ota, s->Qc, n_sel, s->nt, nullptr);
+            hipLaunchKernelGGL(k_zr_force_touched, dim3((unsigned)((3 * s->nt + 3) / 4), (unsigned)(ld / 64)), dim3(256), 0, ctx->stream, s->fat, 3 * s->nt,
+                               fr, ffj, (int)n_sel, ld, s->Qc);
+        } else {
+            zr_affine_launch(ctx, adv, (int)rq, s->kap, true, s->Cz, ld, 0, ld);
+            asb_gsub_expand_launch(ctx, s->Utt, s->ntp, s->Z, ld, s->ota, s->Qc, n_sel, s->nt, nullptr);
+        }
         for (int64_t it = 0; it < n_iter; ++it) {
             for (long long c0 = 0; c0 < n_sel; c0 += cw) {
                 const int cn = (int)(c0 + cw < n_sel ? cw : n_sel - c0);

@@ -2,7 +2,7 @@
 projective-dynamics solver (Simulators.py) evaluated on the device for the frames of the resident animation -- constraint
 projections, constraint forces, their DEIM reduction, the global step, the solver's iterations and its time steps, with the choice of the global step's solver and
 of how many kinds a solve may reduce, the positional constraints (pins) of every such call, the global step in a position
-subspace q = o + U z and roll-outs whose state lives in z.
+subspace q = o + U z, roll-outs whose state lives in z, and the external forces and the floor of the time steps.
 A public call checks its arguments into the named records below before the engine is touched; the helpers take the records.
 """
 import collections
@@ -45,6 +45,14 @@ ReducedPlan = collections.namedtuple("ReducedPlan", "term frames operator")
 # ``p0`` (P, 3) the targets at rest, ``shift`` None (fixed) or (T_s, 3) / (T_s, P, 3) (p0 + shift[row]), ``start``: the row of
 # frame 0's first step, and ``St``: the (N, P) CSR with wi_i at (v_i, i).  Not a kind: no slot, no reduction, no dependence on q.
 Pins = collections.namedtuple("Pins", "vertices wi p0 shift start St")
+# The external forces of a call (the reference's fext without gravity): ``table`` (3 N,) (constant) or (T_s, 3 N), the displacements
+# fa = dt^2 force / mass, dense, row 3 v + d; ``start``: the row of frame 0's first step.
+Forces = collections.namedtuple("Forces", "table start")
+# The floor of a call (the reference's resolve_collision): coordinate ``axis`` of the explicit state is kept >= ``height``.
+Floor = collections.namedtuple("Floor", "height axis")
+# What a time step takes from outside: ``forces`` and ``floor``, either None (not both: that is ext = None).
+External = collections.namedtuple("External", "forces floor")
+FORCE_TABLE_BYTES = 2 ** 31       # the largest force table the device holds
 
 
 class ResidentDynamics(object):
@@ -151,6 +159,87 @@ class ResidentDynamics(object):
                 raise ValueError("%s: pins: row %d of shift is needed (shift_start %d, last frame %d, %d step%s), it has %d"
                                  % (who, last, out.start, last - out.start - steps + 1, steps, "" if steps == 1 else "s", shift.shape[0]))
         return out
+
+    def _external(self, who, forces, floor, ex, frames, steps=1):
+        """The checked ``External`` of a public call (None when both are None), before anything touches the device: ``Forces``
+        with the displacement table fa = dt^2 (force / masses) in f64, the reference's order (Simulators.py:494-495), the
+        ``vertices`` form expanded to dense, every row that ``steps`` time steps from ``frames`` read present; ``Floor``."""
+        if forces is None and floor is None:
+            return None
+        N = self.nVerts
+        F = None
+        if forces is not None:
+            known = ("force", "vertices", "start")
+            if not isinstance(forces, dict) or "force" not in forces:
+                raise ValueError("%s: forces must be a dict with 'force' (and %s), not %r" % (who, ", ".join(known[1:]), forces))
+            extra = sorted(set(forces) - set(known))
+            if extra:
+                raise ValueError("%s: forces: unknown key %r (one of %s)" % (who, extra[0], ", ".join(known)))
+            rows = N
+            v = forces.get("vertices")
+            if v is not None:
+                v = np.asarray(v)
+                if v.ndim != 1 or v.size < 1 or v.dtype.kind not in "iu":
+                    raise ValueError("%s: forces: vertices must be a non-empty list of integers" % who)
+                v = v.astype(np.int64)
+                if v.min() < 0 or v.max() >= N:
+                    raise ValueError("%s: forces: vertex %d is outside 0 .. %d" % (who, int(v[(v < 0) | (v >= N)][0]), N - 1))
+                if np.unique(v).size != v.size:
+                    raise ValueError("%s: forces: a vertex is listed twice" % who)
+                rows = v.size
+            try:
+                f = np.asarray(forces["force"], dtype=np.float64)
+            except (TypeError, ValueError):
+                f = np.full(1, np.nan)
+            if f.ndim not in (2, 3) or f.shape[0] < 1 or f.shape[-2:] != (rows, 3) or not np.isfinite(f).all():
+                raise ValueError("%s: forces: force of shape %s: finite (%d, 3) or (T_s, %d, 3) expected" % (who, f.shape, rows, rows))
+            start = forces.get("start", 0)
+            if isinstance(start, bool) or not isinstance(start, (int, np.integer)) or start < 0:
+                raise ValueError("%s: forces: start %r: a non-negative integer" % (who, start))
+            if f.ndim == 3:
+                last = int(start) + range(frames.start, frames.end, frames.jump)[-1] + steps - 1
+                if last >= f.shape[0]:
+                    raise ValueError("%s: forces: row %d of force is needed (start %d, last frame %d, %d step%s), it has %d"
+                                     % (who, last, start, last - start - steps + 1, steps, "" if steps == 1 else "s", f.shape[0]))
+            nbytes = (f.shape[0] if f.ndim == 3 else 1) * 3 * N * 8
+            if nbytes > FORCE_TABLE_BYTES:
+                raise ValueError("%s: forces: the dense table of %d rows x %d doubles takes %d bytes on the device, more than the %d it may "
+                                 "(fewer rows per call: continue with state= and start raised)" % (who, nbytes // (24 * N), 3 * N, nbytes, FORCE_TABLE_BYTES))
+            if ex.masses.shape != (N,) or not (ex.masses > 0.0).all():
+                raise ValueError("%s: forces: masses of shape %s: %d positive numbers expected" % (who, ex.masses.shape, N))
+            if v is not None:
+                dense = np.zeros(f.shape[:-2] + (N, 3))
+                dense[..., v, :] = f
+                f = dense
+            fa = (ex.dt * ex.dt) * (f / ex.masses[:, None])
+            if not np.isfinite(fa).all():
+                raise ValueError("%s: forces: dt^2 force / mass is not finite" % who)
+            F = Forces(np.ascontiguousarray(fa.reshape(fa.shape[:-2] + (3 * N,))), int(start))
+        L = None
+        if floor is not None:
+            known = ("height", "axis")
+            if not isinstance(floor, dict) or "height" not in floor:
+                raise ValueError("%s: floor must be a dict with 'height' (and axis), not %r" % (who, floor))
+            extra = sorted(set(floor) - set(known))
+            if extra:
+                raise ValueError("%s: floor: unknown key %r (one of %s)" % (who, extra[0], ", ".join(known)))
+            try:
+                h = float(floor["height"])
+            except (TypeError, ValueError):
+                h = float("nan")
+            if not np.isfinite(h):
+                raise ValueError("%s: floor: height %r: a finite number" % (who, floor["height"]))
+            axis = floor.get("axis", 1)
+            if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)) or axis not in (0, 1, 2):
+                raise ValueError("%s: floor: axis %r: 0, 1 or 2" % (who, axis))
+            L = Floor(h, int(axis))
+        return External(F, L)
+
+    def _ext_set(self, ext):
+        self._engine.ext_set(None if ext.forces is None else ext.forces.table, None if ext.floor is None else tuple(ext.floor))
+
+    def _ext_bind(self, ext):
+        self._engine.pdsolve_external(0 if ext.forces is None else ext.forces.start)
 
     def _plan(self, kinds, chunk_frames=None):
         """The checks of ``constraint_forces`` on its kinds, in its order: one ``Term`` per kind."""
@@ -606,8 +695,9 @@ class ResidentDynamics(object):
         return out
 
     # ------------------------------------------------------------------ the solver's iterations
-    _SOLVE_SCOPE = """Out of scope, as for ``global_step``: collision handling (``resolve_collision`` and the self-collision passes)
-        and several ranks.  Every selected frame is an independent solve; further time steps from its
+    _SOLVE_SCOPE = """Out of scope, as for ``global_step``: the self-collision passes and several ranks (external forces and the
+        floor, ``resolve_collision``, are ``forces=`` / ``floor=`` of ``solve_frames`` and ``simulate_frames``; the one-shot error
+        sweeps do not take them).  Every selected frame is an independent solve; further time steps from its
         result, the velocity carried along, are ``simulate_frames``.
 
         ``hyper`` (None, "touched" or "all"): the hyper-reduced operator A^-1 S^T V, as the reference's reduced simulator holds
@@ -779,9 +869,10 @@ class ResidentDynamics(object):
             sub = {i: _proj.touched_setup(u, into=touched)[1] for i, u in sub.items()}
         return touched, sub
 
-    def _solve_run(self, plan, reds, frames, ex, begin, K, chunk_frames, history, hyper=None, pins=None):
+    def _solve_run(self, plan, reds, frames, ex, begin, K, chunk_frames, history, hyper=None, pins=None, ext=None):
         """The solve (matrix on the device); ``reds``: the ``Reduced`` of the plan with their ``op``; ``begin``: what
-        ``_solve_start`` gave.  ``hyper``: every kind is in ``reds`` and their A^-1 S^T V are on the device."""
+        ``_solve_start`` gave.  ``hyper``: every kind is in ``reds`` and their A^-1 S^T V are on the device.  ``ext``: the
+        ``External`` of the call; it is bound before the pins, whose term goes onto the inertia term it rewrites."""
         eng = self._engine
         code, start = begin
         if code == 2:
@@ -790,7 +881,11 @@ class ResidentDynamics(object):
         frames.upload(self)
         if pins is not None:
             self._pins_set(pins)
+        if ext is not None:
+            self._ext_set(ext)
         eng.pdsolve_begin(*frames.args(self), ex.diag, ex.mode, ex.acc, code, None if start is None else start.data_ptr())
+        if ext is not None:
+            self._ext_bind(ext)
         if pins is not None:
             eng.pdsolve_pins(pins.start)
         if hyper is not None:
@@ -809,8 +904,8 @@ class ResidentDynamics(object):
         return out, frames.n_sel
 
     def solve_frames(self, kinds, dt, num_iterations=10, masses=None, velocity="difference", gravity=(0.0, 0.0, 0.0), start="explicit",
-                     animation="train", frame_start=0, frame_end=None, frame_jump=1, chunk_frames=None, history=False, pins=None,
-                     hyper=None):
+                     animation="train", frame_start=0, frame_end=None, frame_jump=1, chunk_frames=None, history=False, forces=None,
+                     floor=None, pins=None, hyper=None):
         """Extra: the local/global iterations of the reference's solver (Simulators.py:494-526) for every selected frame of
         the resident animation, on the device: q_0 given, q_{k+1} = A^-1 (M / dt^2 s_f + sum_i S_i^T p_i(q_k)) for
         ``num_iterations`` iterations, the explicit state s_f held fixed while q moves.  The iterate stays on the device
@@ -824,7 +919,9 @@ class ResidentDynamics(object):
         ``start``: "explicit" (q_0 = s_f, the reference's), "frame" (q_0 = x_f; one iteration is then ``global_step`` bit for
         bit) or a contiguous ``torch.float64`` device tensor (F', N, 3) -- a solve continued from an earlier result equals the
         longer solve bit for bit.  ``history``: also the (num_iterations, F') array of |q_{k+1} - q_k| / |q_{k+1}| (Frobenius
-        norms of the frame); refused under ``set_global_solver("slab")``.
+        norms of the frame); refused under ``set_global_solver("slab")``.  ``forces`` / ``floor``: as ``simulate_frames``, on the
+        explicit state of the one step a solve is -- frame f reads row ``start`` + f of a per-step force --; they form the inertia
+        term under every ``start``, and the first iterate too where that is the explicit state.
 
         Returns ``(tensor, F')`` (``(tensor, F', steps)`` with ``history``): a ``torch.float64`` device tensor (F', N, 3) in
         world space, owned by the caller.  Device memory held by the engine beside A^-1: three times the result plus the
@@ -840,11 +937,12 @@ class ResidentDynamics(object):
         ex, K = self._solve_args(who, dt, velocity, gravity, num_iterations, start, masses)
         frames = self._frames(animation, frame_start, frame_end, frame_jump)
         pins = self._pins(who, pins, frames)
+        ext = self._external(who, forces, floor, ex, frames)
         plan, reds = self._solve_plan(who, kinds, chunk_frames)
         begin = self._solve_start(who, start, frames.n_sel)
         reds = self._chosen(reds, kinds)
         self._matrix(plan, ex.masses, ex.dt, pins)
-        return self._with_operators(reds, hyper, lambda: self._solve_run(plan, reds, frames, ex, begin, K, chunk_frames, history, hyper, pins))
+        return self._with_operators(reds, hyper, lambda: self._solve_run(plan, reds, frames, ex, begin, K, chunk_frames, history, hyper, pins, ext))
 
     solve_frames.__doc__ %= _SOLVE_SCOPE
 
@@ -949,7 +1047,7 @@ class ResidentDynamics(object):
             if t.dim() != 3 or tuple(t.shape) != (n_sel, self.nVerts, 3) or not t.is_contiguous():
                 raise ValueError("%s: state of shape %s: contiguous (%d, %d, 3) tensors expected" % (who, tuple(t.shape), n_sel, self.nVerts))
 
-    def _rollout_run(self, plan, reds, frames, ex, state, K, T, chunk_frames, every, hyper=None, pins=None):
+    def _rollout_run(self, plan, reds, frames, ex, state, K, T, chunk_frames, every, hyper=None, pins=None, ext=None, ext_held=False):
         """The roll-out (matrix on the device; ``reds``, ``hyper`` as ``_solve_run``): ``(q, q_prev, records or None, steps)``."""
         import torch
         eng = self._engine
@@ -958,6 +1056,8 @@ class ResidentDynamics(object):
         frames.upload(self)
         if pins is not None:
             self._pins_set(pins)
+        if ext is not None and not ext_held:        # (a sweep uploads the table once, before its roll-outs)
+            self._ext_set(ext)
         if state is None:
             eng.pdsolve_begin(*frames.args(self), ex.diag, ex.mode, ex.acc, 0, None)
             eng.pdsolve_carry(None)
@@ -965,6 +1065,8 @@ class ResidentDynamics(object):
             eng.pdsolve_begin(*frames.args(self), ex.diag, ex.mode, ex.acc, 2, state[0].data_ptr())
             eng.pdsolve_carry(state[1].data_ptr())
             eng.pdsolve_advance()
+        if ext is not None:                         # on the explicit state of step 1, also the one a continuation's advance made
+            self._ext_bind(ext)
         if pins is not None:                        # behind the advance of a continuation, which rewrites the inertia term
             eng.pdsolve_pins(pins.start)
         touched = self._solve_slots(plan, reds, hyper)
@@ -990,7 +1092,7 @@ class ResidentDynamics(object):
 
     def simulate_frames(self, kinds, dt, num_steps, num_iterations=10, masses=None, velocity="difference", gravity=(0.0, 0.0, 0.0),
                         state=None, animation="train", frame_start=0, frame_end=None, frame_jump=1, chunk_frames=None,
-                        record_every=None, hyper=None, pins=None):
+                        record_every=None, hyper=None, forces=None, floor=None, pins=None):
         """Extra: ``num_steps`` time steps of the reference's solver (Simulators.py ``step()``, :494-532) from every selected
         frame of the resident animation, on the device.  Every selected frame is an independent initial condition: positions
         x_f, velocity (x_f - x_{f-1}) / dt (``velocity`` "difference", f - 1 as in ``global_step``) or 0 ("zero").  A step is
@@ -1008,14 +1110,22 @@ class ResidentDynamics(object):
         constraints of ``constraint_forces`` and ``solve_frames``; step t = 1, 2, .. of the roll-out from frame f reads row
         shift_start + f + t - 1 of the shift (the reference's step counter), so a continuation with ``state=`` passes
         ``shift_start`` raised by the steps already taken and then equals the longer roll-out bit for bit; a row beyond T_s is
-        a ValueError before the device is touched.
+        a ValueError before the device is touched.  ``forces``: None or a dict ``{force, vertices (None), start (0)}``, the
+        reference's ``fext`` without gravity (Simulators.py:494-495): ``force`` (N, 3), constant, or (T_s, N, 3), one row per step;
+        with ``vertices`` (P,), unique and in range, (P, 3) / (T_s, P, 3) and zero elsewhere.  Step t from frame f reads row
+        ``start`` + f + t - 1, the pins' rule, and a continuation passes ``start`` raised by the steps taken.  The explicit state of
+        a step becomes s + dt^2 force / mass (the table is formed on the host in f64, dense, at most 2^31 bytes on the device: a
+        ValueError naming the size).  ``floor``: None or a dict ``{height, axis (1)}``, the reference's ``resolve_collision``
+        (:497-498): coordinate ``axis`` of every vertex of the explicit state that lies below ``height`` is set onto it, before the
+        iterations take their inertia term and first iterate from it.  Both are one pass with the carry; with
+        both None nothing changes.  Unknown keys, wrong shapes, non-finite values, a missing row: ValueError before the device.
 
         Returns ``(q, q_prev, F')``: the positions after the last step and one step earlier (for ``num_steps`` = 1: x_f, or
         ``state[0]``), two ``torch.float64`` device tensors (F', N, 3) owned by the caller -- the pair ``state=`` takes.  With
         ``record_every`` a fourth value ``(records, steps)``: a caller-owned (R, F', N, 3) device tensor, each record written
         by the last iteration of its step straight into its slice, and the list of those step numbers; when the last step is
         recorded, ``q`` is the view ``records[-1]``.  Device memory held by the engine beside that of ``solve_frames``: one more
-        tensor of the iterate's size.  Out of scope: collisions, forces other than constant gravity,
+        tensor of the iterate's size, and the force table.  Out of scope: the self-collision passes, friction and repulsion,
         more reduced kinds than ``set_reduced_kinds`` allows (1 unless set), the history of step norms, several ranks."""
         who = "simulate_frames"
         self._hyper_check(who, hyper, kinds, False)
@@ -1023,18 +1133,19 @@ class ResidentDynamics(object):
         T, every = self._rollout_args(who, num_steps, record_every, state)
         frames = self._frames(animation, frame_start, frame_end, frame_jump)
         pins = self._pins(who, pins, frames, T)
+        ext = self._external(who, forces, floor, ex, frames, T)
         plan, reds = self._solve_plan(who, kinds, chunk_frames)
         self._rollout_state(who, state, frames.n_sel)
         reds = self._chosen(reds, kinds)
         self._matrix(plan, ex.masses, ex.dt, pins)
         q, q_prev, records, steps = self._with_operators(
-            reds, hyper, lambda: self._rollout_run(plan, reds, frames, ex, state, K, T, chunk_frames, every, hyper, pins))
+            reds, hyper, lambda: self._rollout_run(plan, reds, frames, ex, state, K, T, chunk_frames, every, hyper, pins, ext))
         return (q, q_prev, frames.n_sel) + (() if every is None else ((records, steps),))
 
     def reduced_rollout_errors(self, kind, basis, r_values, dt, num_steps, num_iterations=10, masses=None, velocity="difference",
                                gravity=(0.0, 0.0, 0.0), elements=None, wi=1.0, reduction="deim_pod", rest_positions=None,
                                sigma_min=1.0, sigma_max=1.0, animation="train", frame_start=0, frame_end=None, frame_jump=1,
-                               record_every=1, hyper=None, pins=None):
+                               record_every=1, hyper=None, forces=None, floor=None, pins=None):
         """Extra: how far the DEIM-reduced SIMULATION drifts from the full one along a trajectory -- ``reduced_solve_errors``
         carried through ``num_steps`` time steps of ``simulate_frames``.  For every r of ``r_values`` and every recorded step
         (``record_every`` = r0: the steps r0, 2 r0, .. <= ``num_steps``) the three metrics of ``(q_t, q~_{r,t})``: both roll-outs
@@ -1047,8 +1158,9 @@ class ResidentDynamics(object):
         Returns ``(fro, max, rel_x, rel_y, rel_z, steps)``: five (len(r_values), R) arrays and the list of the R recorded
         steps.  With ``num_steps=1, record_every=1`` the numbers are those of ``reduced_solve_errors``.  The sweep keeps its
         one kind whatever ``set_reduced_kinds`` allows: multi-kind sweeps are out of scope.  ``pins`` (as ``simulate_frames``)
-        hold both roll-outs, unreduced: the hanging cloth, the clamped bar.  Out of scope: floor collision
-        (``resolve_collision``), self-collisions, several ranks, a sweep over the ranks of a position subspace."""
+        hold both roll-outs, unreduced: the hanging cloth, the clamped bar.  ``forces`` / ``floor`` (as ``simulate_frames``) act on
+        both roll-outs alike: the drift under a load the basis was not trained on.  Out of scope: self-collisions, several ranks,
+        a sweep over the ranks of a position subspace."""
         who = "reduced_rollout_errors"
         self._hyper_check(who, hyper, [dict(basis=basis, num_components=0)], False)
         ex, K = self._solve_args(who, dt, velocity, gravity, num_iterations, "explicit", masses)
@@ -1058,6 +1170,7 @@ class ResidentDynamics(object):
         spec = dict(kind=kind, elements=elements, wi=wi, rest_positions=rest_positions, sigma_min=sigma_min, sigma_max=sigma_max)
         frames = self._frames(animation, frame_start, frame_end, frame_jump)
         pins = self._pins(who, pins, frames, T)
+        ext = self._external(who, forces, floor, ex, frames, T)
         terms, (red,) = self._solve_plan(who, [dict(spec, basis=basis, num_components=0, reduction=reduction)], None)
         r_values = [int(r) for r in r_values]
         ops = [red.operator(r) for r in r_values]
@@ -1066,8 +1179,10 @@ class ResidentDynamics(object):
         if not ops:
             return tuple(out) + (steps,)
         run = lambda rd: self._rollout_run(terms, () if rd is None else (rd,), frames, ex, None, K, T, None, every, None if rd is None else hyper,
-                                           pins)[2]
+                                           pins, ext, True)[2]
         self._matrix(terms, ex.masses, ex.dt, pins)
+        if ext is not None:
+            self._ext_set(ext)
         full = run(None)
         self._engine.rforce_operator(terms[0].St, ops[int(np.argmax(r_values))].V)
         if hyper is not None:
@@ -1136,7 +1251,7 @@ class ResidentDynamics(object):
 
     def simulate_subspace(self, kinds, dt, num_steps, num_iterations=10, masses=None, velocity="difference", gravity=(0.0, 0.0, 0.0),
                           state=None, animation="train", frame_start=0, frame_end=None, frame_jump=1, chunk_frames=None,
-                          record_every=None, pins=None):
+                          record_every=None, pins=None, forces=None, floor=None):
         """Extra: ``simulate_frames(hyper="touched")`` under ``set_global_solver("subspace")`` with the STATE kept in the subspace
         coordinates z of q = o + U z -- the reference's fully reduced simulator (Simulators.py:144-155, :195, :239, where it raises
         "not yet implemented").  Per coordinate, with At = U^T A U: a step is y = 2 z_t - z_{t-1}, c_z = kappa + T y + E target,
@@ -1151,13 +1266,21 @@ class ResidentDynamics(object):
         T1 steps continued by T2 equal T1 + T2 steps bit for bit.  Returns ``(z, z_prev, F')``: caller-owned device tensors
         (F', r, 3); with ``record_every`` also ``(records (R, F', r, 3), steps)``.  ``subspace_expand`` gives the positions.
         ValueError before the device is touched: no subspace selected, a plain kind, a bad ``state``, a row of the pins' shift
-        beyond T_s.  Out of scope: plain kinds, the history of step norms, collisions, several ranks."""
+        beyond T_s.  ``forces``: the dict of ``simulate_frames`` (a continuation passes ``start`` raised by the steps taken): with
+        Phi = At^-1 U^T applied to the table's rows, formed once per call, c_z gains Phi[:, row] and the touched rows of a step's first
+        iterate gain fa[row]; at most 65 535 rows.  ``floor`` is refused (ValueError): a clamp on vertex coordinates
+        has no form in z without the O(N) pass this roll-out exists to avoid -- ``simulate_frames`` under
+        ``set_global_solver("subspace")`` takes it.  Out of scope: plain kinds, the history of step norms, several ranks."""
         import torch
         who = "simulate_subspace"
         self._one_rank(who)
         sub = self._subspace_solver()
         if sub is None:
             raise ValueError("%s: the state lives in the coordinates of a position subspace: set_global_solver('subspace', basis=...) first" % who)
+        if floor is not None:
+            raise ValueError("%s: floor=: a clamp on vertex coordinates has no form in the subspace coordinates z without the O(N) pass "
+                             "over the vertices that this roll-out exists to avoid; simulate_frames under set_global_solver('subspace') takes "
+                             "floor= (and forces=)" % who)
         r = int(sub[0].shape[1])
         limit = getattr(self, "_reduced_limit", 1)
         if not (isinstance(kinds, (list, tuple)) and len(kinds) >= 1 and all(
@@ -1168,6 +1291,10 @@ class ResidentDynamics(object):
         T, every = self._rollout_args(who, num_steps, record_every, None)
         frames = self._frames(animation, frame_start, frame_end, frame_jump)
         pins = self._pins(who, pins, frames, T)
+        ext = self._external(who, forces, None, ex, frames, T)
+        if ext is not None and ext.forces.table.ndim == 2 and ext.forces.table.shape[0] > 65535:
+            raise ValueError("%s: forces: %d rows of force, at most 65535 in a roll-out in z (continue with state= and start raised)"
+                             % (who, ext.forces.table.shape[0]))
         plan, reds = self._solve_plan(who, kinds, chunk_frames)
         if state is not None:
             if not isinstance(state, (list, tuple)) or len(state) != 2:
@@ -1187,9 +1314,13 @@ class ResidentDynamics(object):
             frames.upload(self)
             if pins is not None:
                 self._pins_set(pins)
+            if ext is not None:
+                self._ext_set(ext)
             touched, sampled = self._sampled(reds, "touched")
             eng.zroll_begin(*frames.args(self), ex.diag, ex.mode, ex.acc, touched,
                             None if state is None else state[0].data_ptr(), None if state is None else state[1].data_ptr())
+            if ext is not None:
+                eng.zroll_forces(ext.forces.start)
             if pins is not None:
                 eng.zroll_pins(pins.start)
             for b, rd in enumerate(reds):

@@ -759,6 +759,10 @@ class HipEngine(object):
         """Binds the pins of ``pins_set`` to the roll-out in z: step t from frame f reads row ``row0`` + f + t - 1 of the shift."""
         self._ck(self.lib.asb_zroll_pins(self.h, int(row0)))
 
+    def zroll_forces(self, row0=0):
+        """Binds the force table of ``ext_set`` (no floor) to the roll-out in z: step t from frame f reads row ``row0`` + f + t - 1."""
+        self._ck(self.lib.asb_zroll_forces(self.h, int(row0)))
+
     def zroll_steps(self, n_steps, n_iter, chunk_frames=0, record_every=0, records_dev_ptr=None):
         """``n_steps`` time steps of ``n_iter`` iterations in stream order, one drain at the end; ``record_every`` > 0: z after
         every such step into the caller's device buffer (R, F', r, 3)."""
@@ -883,6 +887,25 @@ class HipEngine(object):
         """Binds the pins of ``pins_set`` to the solve in progress: their term joins the inertia term, frame f with row
         ``row0`` + f of the shift, and every later ``pdsolve_advance`` renews it one row further."""
         self._ck(self.lib.asb_pdsolve_pins(self.h, int(row0)))
+
+    # ------------------------------------------------------------------ external forces and the floor
+    def ext_set(self, table=None, floor=None):
+        """The forces and the floor of every later ``pdsolve_external``: ``table`` None, (3 N,) (a constant force) or (T_s, 3 N),
+        the displacements dt^2 force / mass; ``floor`` None or (height, axis); checked and uploaded once."""
+        if table is not None:
+            table = np.ascontiguousarray(table, dtype=np.float64)
+        h, axis = (0.0, 1) if floor is None else floor
+        self._ck(self.lib.asb_ext_set(self.h, 0 if table is None or table.ndim == 1 else int(table.shape[0]), ptr(table),
+                                      int(floor is not None), int(axis), float(h)))
+
+    def ext_clear(self):
+        self._ck(self.lib.asb_ext_clear(self.h))
+
+    def pdsolve_external(self, row0=0):
+        """Binds the forces and the floor of ``ext_set`` to the solve in progress, before ``pdsolve_pins``: the explicit state of
+        frame f takes row ``row0`` + f of the table and is clamped to the floor, the inertia term is rewritten, and every later
+        ``pdsolve_advance`` does both in its own pass, one row further."""
+        self._ck(self.lib.asb_pdsolve_external(self.h, int(row0)))
 
     # ------------------------------------------------------------------ SPLOCS
     def splocs_begin(self):

@@ -777,6 +777,13 @@ int asb_zroll_begin(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj,
                     const double* zprev_dev);
 int asb_zroll_slot(asb_ctx* ctx, double sigma_min, double sigma_max);
 int asb_zroll_pins(asb_ctx* ctx, int64_t row0);
+/* asb_zroll_forces: after asb_zroll_begin and an asb_ext_set WITH a table and WITHOUT a floor (a floor is refused: a clamp on vertex
+ * coordinates has no form in z).  Binds the table: Phi_d = W_d (D o fa_d) joins c_z and the touched rows of a step's first iterate take
+ * fl(. + fa[row]); step t = 1, 2, .. from frame f reads row row0 + f + t - 1 (a constant table: its one row).  ALL T_s rows are prepared
+ * here, once -- what a later asb_zroll_steps reads is not known yet --, by the reduce of asb_gsub.hip, the chain over N never split; at
+ * most 65535 rows (ASB_ERR_LIMIT).  A step is two launches longer.  asb_zroll_steps checks the last row it will read before its first
+ * launch (ASB_ERR_ARG).  A new asb_zroll_begin drops the binding.  In stream order; the call does not wait. */
+int asb_zroll_forces(asb_ctx* ctx, int64_t row0);
 int asb_zroll_steps(asb_ctx* ctx, int64_t n_steps, int64_t n_iter, int64_t chunk_frames, int64_t record_every, double* records_dev);
 int asb_zroll_state(asb_ctx* ctx, double* z_dev, double* zprev_dev);
 /* test hook: the affine product kernel alone, Out = base + sum_s M_s X_s on host arrays.  r rows, w columns, n_seg <= 8 segments of
@@ -789,7 +796,8 @@ int asb_test_zroll_affine(asb_ctx* ctx, int64_t r, int64_t w, int64_t n_seg, con
 /* The local/global loop of Simulators.py:494-526 for the frames range(f0, f1, fj) of the training (which 0) or held-out (1)
  * tensor, every frame an independent solve: q_{k+1} = A^-1 (sum_i S_i^T p_i(q_k) + M / h^2 s_f) with s_f fixed.  The iterate
  * stays on the device between iterations, vertex-major (row 3 v + d, the frames contiguous, padded to 64), the layout the
- * projection kernels read.  No collisions.  Positional constraints: asb_pins_set and asb_pdsolve_pins below.  One rank.  The
+ * projection kernels read.  No self-collisions.  Positional constraints: asb_pins_set and asb_pdsolve_pins below; external forces
+ * and the floor: asb_ext_set and asb_pdsolve_external below.  One rank.  The
  * end of a time step (:531-532) is asb_pdsolve_advance below.
  * asb_pdsolve_begin: after asb_gstep_setup.  Arguments two to eleven as asb_gstep_inertia; the inertia term diag s_f is
  * formed once with that entry's arithmetic.  start 0: q_0 = s_f (the reference's), 1: q_0 = x_f, 2: q_0 = start_dev, a DEVICE
@@ -877,6 +885,32 @@ int asb_pins_clear(asb_ctx* ctx);
 int asb_pins_term(asb_ctx* ctx, int64_t f0, int64_t f1, int64_t fj, int64_t row0, int accumulate, double* out_dev);
 int asb_fm_add(asb_ctx* ctx, double* a_dev, const double* b_dev, int64_t len);
 int asb_pdsolve_pins(asb_ctx* ctx, int64_t row0);
+
+/* ------------------------------------------------ projective dynamics: external forces and the floor ----------- */
+/* The start of the reference's step (Simulators.py:494-498): explicit = positions + dt velocities + dt^2 fext / mass, then
+ * resolve_collision (Constraint_projections.py:1287-1298) on every vertex of it -- a coordinate below the floor is set onto it --,
+ * and both the inertia term and the first iterate are taken from the result.  Gravity stays in acc3 of asb_pdsolve_begin; the
+ * table holds fa = dt^2 force / mass of the remaining forces, formed by the host.  Arithmetic, per entry (row 3 v + d, frame
+ * column c, table row rho(c) = row0 + f0 + c fj + step), after s = fl(fl(2 q - P) + acc[d]) of asb_pdsolve_advance (or the s
+ * of asb_pdsolve_begin):  x = fl(s + fa[rho(c)][3 v + d]);  if (d == axis && x < height) x = height;  iterate = x,
+ * inertia term = fl(diag[v] x).  The add is rounded on its own; the floor is a comparison, so NaN stays NaN in its frame.
+ * asb_ext_set: table_host (T_s, 3 n) finite doubles with T_s > 0, one row per step; (3 n) with T_s = 0, a constant force; NULL:
+ * no forces (floor only).  floor_on != 0: the floor along axis (0..2) at the finite height.  Checked against the n vertices of
+ * the tensor on the device, then uploaded once into a buffer the context owns; replaces the previous forces and floor and drops
+ * their binding to a solve.  A table of more than 2^31 bytes: ASB_ERR_LIMIT; any other violation, or neither a table nor a
+ * floor: ASB_ERR_ARG; nothing is left set.  asb_ext_clear: nothing set, no binding (the buffer stays for the next set).
+ * asb_pdsolve_external: after asb_pdsolve_begin (and asb_pdsolve_carry, and the asb_pdsolve_advance of a continuation), BEFORE
+ * asb_pdsolve_pins -- this call rewrites the inertia term, so with the pins bound it is refused, as it is before a begin, a
+ * second time, with nothing set, and with forces checked against another n.  Checks the rows step 0 needs (a missing row:
+ * ASB_ERR_ARG, nothing launched), binds, and corrects the state in one pass: the iterate holds s, the two lines above are
+ * applied to it and the inertia term is rewritten.  With start 1 or 2 of asb_pdsolve_begin the iterate is not s: s is then
+ * formed as start 0 forms it into a scratch tensor, only the inertia term is rewritten and the iterate is left alone.  From
+ * then on asb_pdsolve_advance first checks the next step's row (missing: ASB_ERR_ARG, nothing launched, the state untouched)
+ * and runs its pass with the two lines fused in, one row further per advance: T1 steps continued by T2 (row0 raised by T1)
+ * equal T1 + T2 steps bit for bit.  A new asb_pdsolve_begin drops the binding.  Returns after the stream has drained. */
+int asb_ext_set(asb_ctx* ctx, int64_t T_s, const double* table_host, int floor_on, int axis, double height);
+int asb_ext_clear(asb_ctx* ctx);
+int asb_pdsolve_external(asb_ctx* ctx, int64_t row0);
 
 /* ------------------------------------------------ SPLOCS refinement ----------- */
 /* posComponents.splocs_glob_optimization, snapbases/posComponents.py:132-189.
