@@ -188,6 +188,7 @@ PROTOTYPES = {
     "asb_test_gsub_state": (c_int, [ctypes.c_void_p, c_int, c_dp, c_i64]),
     "asb_gsub_coordinates": (c_int, [ctypes.c_void_p, c_int, c_i64, c_i64, c_i64, c_dp, c_int, c_dbl, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
     "asb_gsub_expand": (c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
+    "asb_gsub_expand_diff": (c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i64, c_dp, c_dp, c_dp, c_dp]),
     "asb_zroll_operator": (c_int, [ctypes.c_void_p]),
     "asb_zroll_begin": (c_int, [ctypes.c_void_p, c_int, c_i64, c_i64, c_i64, c_dp, c_int, c_dbl, c_dp, c_int, c_dp, c_i64, c_dp,
                                 ctypes.c_void_p, ctypes.c_void_p]),

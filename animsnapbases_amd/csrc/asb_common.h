@@ -536,6 +536,19 @@ int asb_gsub_rows_in(asb_ctx* ctx, const double* Mt, long long rows, long long N
 // asb_rforce.hip: k_st_dense on device arrays, Mt (3, mpp, Np) = (S^T V_d)^T for the CSR (ptr, ci, val) of n_rows rows and V (rows, mp, 3)
 void asb_st_dense_launch(asb_ctx* ctx, const int* ptr, const int* ci, const double* val, const double* V, long long n_rows, int mp, int mpp,
                          long long Np, double* Mt);
+// asb_rforce.hip, the record of asb_force_diff for one frame / for all: [0..2] sum (a - b)^2 per axis, [3..5] sum a^2 per axis,
+// [6] max |a - b|, [7] max a.  asb_force_diff_final_launch: rec[F] = the records rec[0 .. F) combined (k_force_diff_final)
+#define FD_REC 8
+__device__ __forceinline__ void fd_combine(double (&x)[FD_REC], const double* y) {
+#pragma unroll
+    for (int q = 0; q < 6; ++q) x[q] += y[q];
+    x[6] = fmax(x[6], y[6]);
+    x[7] = fmax(x[7], y[7]);
+}
+void asb_force_diff_final_launch(asb_ctx* ctx, double* rec, long long F);
+// the host's side of asb_force_diff: rec ((F + 1) x FD_REC, device) read back behind the stream and handed out
+int asb_force_diff_outputs(asb_ctx* ctx, const double* rec_dev, long long F, double* sums_out, double* max_out, double* norms_out,
+                           double* per_frame_out);
 // asb_pdsolve.hip: k_pd_untranspose, P (rows, ld) vertex-major -> out (n_sel, rows) frame-major; k_pd_transpose, the other way
 void asb_pd_untranspose_launch(asb_ctx* ctx, const double* P, int n_sel, long long rows, long long ld, double* out);
 void asb_pd_transpose_launch(asb_ctx* ctx, const double* in, int n_sel, long long rows, double* Q, long long ld);

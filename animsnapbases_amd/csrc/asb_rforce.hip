@@ -253,15 +253,8 @@ extern "C" int asb_rforce_run(asb_ctx* ctx, int which, int64_t f0, int64_t f1, i
 }
 
 // ---------------------------------------------------------------- the error of b against a
-// record of one frame / of all: [0..2] sum (a - b)^2 per axis, [3..5] sum a^2 per axis, [6] max |a - b|, [7] max a
-#define FD_REC 8
-
-__device__ __forceinline__ void fd_combine(double (&x)[FD_REC], const double* y) {
-#pragma unroll
-    for (int q = 0; q < 6; ++q) x[q] += y[q];
-    x[6] = fmax(x[6], y[6]);
-    x[7] = fmax(x[7], y[7]);
-}
+// record of one frame / of all (FD_REC, fd_combine: asb_common.h): [0..2] sum (a - b)^2 per axis, [3..5] sum a^2 per axis,
+// [6] max |a - b|, [7] max a
 
 // the block's 256 records -> thread 0's, by a fixed tree
 __device__ __forceinline__ void fd_block_reduce(double (&x)[FD_REC], double* sm) {
@@ -320,18 +313,27 @@ extern "C" int asb_force_diff(asb_ctx* ctx, const double* a_dev, const double* b
     int rc;
     if ((rc = asb_alloc(ctx, &ctx->fd_part, (size_t)(F + 1) * FD_REC))) return rc;
     hipLaunchKernelGGL(k_force_diff, dim3((unsigned)F), dim3(256), 0, ctx->stream, a_dev, b_dev, (long long)N, ctx->fd_part);
-    hipLaunchKernelGGL(k_force_diff_final, dim3(1), dim3(256), 0, ctx->stream, ctx->fd_part, (long long)F);
+    asb_force_diff_final_launch(ctx, ctx->fd_part, (long long)F);
     ASB_CHECK_LAUNCH(ctx);
+    return asb_force_diff_outputs(ctx, ctx->fd_part, (long long)F, sums_out, max_out, norms_out, per_frame_out);
+}
+
+void asb_force_diff_final_launch(asb_ctx* ctx, double* rec, long long F) {
+    hipLaunchKernelGGL(k_force_diff_final, dim3(1), dim3(256), 0, ctx->stream, rec, F);
+}
+
+int asb_force_diff_outputs(asb_ctx* ctx, const double* rec_dev, long long F, double* sums_out, double* max_out, double* norms_out,
+                           double* per_frame_out) {
     std::vector<double> rec((size_t)(F + 1) * FD_REC);
     const size_t skip = per_frame_out ? 0 : (size_t)F * FD_REC;
-    ASB_HIP(ctx, hipMemcpyAsync(rec.data() + skip, ctx->fd_part + skip, (rec.size() - skip) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    ASB_HIP(ctx, hipMemcpyAsync(rec.data() + skip, rec_dev + skip, (rec.size() - skip) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const double* tot = rec.data() + (size_t)F * FD_REC;
     if (sums_out) sums_out[0] = tot[0], sums_out[1] = tot[1], sums_out[2] = tot[2];
     if (norms_out) norms_out[0] = tot[3], norms_out[1] = tot[4], norms_out[2] = tot[5], norms_out[3] = tot[7];
     if (max_out) max_out[0] = tot[6];
     if (per_frame_out)
-        for (int64_t f = 0; f < F; ++f) {
+        for (long long f = 0; f < F; ++f) {
             const double* x = rec.data() + (size_t)f * FD_REC;
             per_frame_out[2 * f] = x[0] + x[1] + x[2];
             per_frame_out[2 * f + 1] = x[3] + x[4] + x[5];

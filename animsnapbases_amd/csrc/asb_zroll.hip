@@ -19,6 +19,8 @@
 //                    padded (rows to rq, k to a multiple of 4, frames to 64) with zeros.  base: C_z (row stride ld, column
 //                    stride 1) or kappa broadcast (1, 0).  An entry does not depend on the chunk, the tile or its neighbours.
 //   element-wise     k_zr_carry, k_zr_targets, k_zr_in / k_zr_out (the public (F', r, 3) <-> (3, rq, ld)) and the set-up's fills.
+//   k_gsub_expand_diff   a record of a roll-out judged without expanding it: q~ = o + U z formed tile by tile as k_gsub_expand forms it
+//                    and compared in registers with a full (F', N, 3) tensor read once (asb_gsub_expand_diff, described at the kernel).
 // asb_zroll_steps enqueues every step in stream order and drains ONCE at the end; no host read between steps.
 #include "asb_common.h"
 
@@ -348,6 +350,142 @@ extern "C" int asb_gsub_expand(asb_ctx* ctx, const double* z_dev, int64_t n_fram
     ASB_CHECK_LAUNCH(ctx);
     ASB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return ASB_OK;
+}
+
+// ---------------------------------------------------------------- the expansion compared where it is formed (asb_gsub_expand_diff)
+// The metrics of asb_force_diff(a, o + U z) without o + U z in memory.  A block of 4 waves owns 64 frames and the vertex tiles
+// [blockIdx.y tpg, + tpg) of 32, walked in ascending order; per tile
+//   q~      the MFMA chain of k_gsub_expand (asb_gsub.hip) operand for operand: A = U^T (vertices x k), B = Z (k x frames), k ascending
+//           from a zero accumulator, then fl(o + acc) -- the bits of asb_gsub_expand, whatever the tile, the width or the neighbours
+//   a       the tile's 64 runs of 96 doubles (32 vertices x 3) are read once, coalesced -- half a wave reads 32 consecutive doubles
+//           of a frame's run, a thread 3 x 8 of them -- into registers BEFORE the chain of the tile, which hides them, and go through
+//           LDS rows of 97 doubles into the accumulator layout (the FM branch of k_gsub_expand, run backwards): lane (i, g) of
+//           wave w reads frame 16 w + i, vertices g + 4 q and 16 + g + 4 q
+//   record  the arithmetic of k_force_diff per entry, in a lane ascending in the vertex over all its tiles; the 4 lanes of a frame
+//           are combined g = 0, 1, 2, 3 and lane g = 0 writes the record of (group, frame) -- no atomics
+// Vertices >= n and frames >= F contribute nothing (their records stay 0 / -inf) and no address is formed for them.
+// k_gsub_diff_frames then adds a frame's groups in ascending order into the FD_REC records k_force_diff_final combines.  The
+// split into groups depends on N alone: a frame's record does not depend on the number of frames or on the frames beside it.
+#define ZD_TN 32            // vertices per tile and frames per block: those of k_gsub_expand
+#define ZD_TF 64
+#define ZD_GROUPS 256       // at most this many blocks share the vertices of a frame tile
+
+// grid (ld / 64, groups); Ut (3, rp, Np); Z (3, rq, ld); o (n, 3); a (F, n, 3); part (groups, ld, FD_REC)
+__global__ __launch_bounds__(256) void k_gsub_expand_diff(const double* __restrict__ Ut, long long Np, int rp, const double* __restrict__ Z, int rq,
+                                                          long long ld, const double* __restrict__ o, const double* __restrict__ a, int F, int n,
+                                                          int tpg, double* __restrict__ part) {
+    constexpr int RUN = ZD_TN * 3, ROW = RUN + 1, NJ = ZD_TF / 8;
+    __shared__ double stage[ZD_TF * ROW];
+    const int lane = threadIdx.x & 63, i = lane & 15, g = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int t0 = (int)blockIdx.x * ZD_TF;
+    const int nf = F - t0 < ZD_TF ? F - t0 : ZD_TF;
+    const int fl = wave * 16 + i;
+    const bool fok = fl < nf;
+    const int tiles = (int)(Np / ZD_TN), tb = (int)blockIdx.y * tpg, te = tb + tpg < tiles ? tb + tpg : tiles;
+    const int col = threadIdx.x & 31, fr0 = threadIdx.x >> 5;          // a: doubles col, col + 32, col + 64 of the runs of frames fr0 + 8 j
+    double x[FD_REC] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, -INFINITY};
+    const double* pb = Z + t0 + wave * 16 + i;                        // B: k = g, frame i of the wave's 16
+    for (int tile = tb; tile < te; ++tile) {
+        const int v0 = tile * ZD_TN;                                  // (v0 < n always: Np - n < 32)
+        const int run = (n - v0 < ZD_TN ? n - v0 : ZD_TN) * 3;
+        double ar[NJ][3];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int fr = fr0 + 8 * j;
+            const double* row = a + ((long long)(t0 + fr) * n + v0) * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) ar[j][c] = (fr < nf && col + 32 * c < run) ? row[col + 32 * c] : 0.0;
+        }
+        zr_d4 acc[3][2];
+#pragma unroll
+        for (int d = 0; d < 3; ++d)
+#pragma unroll
+            for (int y = 0; y < 2; ++y) acc[d][y] = zr_d4{0.0, 0.0, 0.0, 0.0};
+        const double* pa = Ut + v0 + i;                               // A: vertex i of 16, k = g
+        for (int k0 = 0; k0 < rp; k0 += 4) {
+            const int k = k0 + g;
+#pragma unroll
+            for (int d = 0; d < 3; ++d) {
+                const double* ua = pa + ((long long)d * rp + k) * Np;
+                const double b = pb[((long long)d * rq + k) * ld];
+                acc[d][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(ua[0], b, acc[d][0], 0, 0, 0);
+                acc[d][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(ua[16], b, acc[d][1], 0, 0, 0);
+            }
+        }
+        __syncthreads();                                              // the tile before has been read out of the stage
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) stage[(fr0 + 8 * j) * ROW + col + 32 * c] = ar[j][c];
+        __syncthreads();
+        // accumulator q of lane (i, g): vertex g + 4 q of the 16, frame i of the wave's 16
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+#pragma unroll
+            for (int y = 0; y < 2; ++y)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int vl = 16 * y + g + 4 * q;
+                    if (fok && v0 + vl < n) {
+                        const double val = o[3LL * (v0 + vl) + d] + acc[d][y][q];
+                        const double av = stage[fl * ROW + vl * 3 + d], e = av - val;
+                        x[d] = fma(e, e, x[d]);
+                        x[3 + d] = fma(av, av, x[3 + d]);
+                        x[6] = fmax(x[6], fabs(e));
+                        x[7] = fmax(x[7], av);
+                    }
+                }
+        }
+    }
+    // the frame's four lanes, g ascending
+#pragma unroll
+    for (int s = 1; s < 4; ++s) {
+        double y[FD_REC];
+#pragma unroll
+        for (int q = 0; q < FD_REC; ++q) y[q] = __shfl(x[q], i + 16 * s, 64);
+        if (g == 0) fd_combine(x, y);
+    }
+    if (g == 0) {
+        double* p = part + ((long long)blockIdx.y * ld + t0 + fl) * FD_REC;
+#pragma unroll
+        for (int q = 0; q < FD_REC; ++q) p[q] = x[q];
+    }
+}
+
+// blocks of 256 over the frames: rec[f] = the records of frame f's groups, ascending
+__global__ __launch_bounds__(256) void k_gsub_diff_frames(const double* __restrict__ part, long long ld, int groups, int F, double* __restrict__ rec) {
+    const long long f = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (f >= F) return;
+    double x[FD_REC] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, -INFINITY};
+    for (int gi = 0; gi < groups; ++gi) fd_combine(x, part + ((long long)gi * ld + f) * FD_REC);
+#pragma unroll
+    for (int q = 0; q < FD_REC; ++q) rec[f * FD_REC + q] = x[q];
+}
+
+extern "C" int asb_gsub_expand_diff(asb_ctx* ctx, const double* a_dev, const double* z_dev, int64_t n_frames, double* sums_out, double* max_out,
+                                    double* norms_out, double* per_frame_out) {
+    if (!ctx || n_frames < 1 || !a_dev || !z_dev) return ASB_ERR_ARG;
+    if ((n_frames + 63) / 64 > 65535)
+        ASB_FAIL(ctx, ASB_ERR_LIMIT, "asb_gsub_expand_diff: %lld frames in one call (at most %d)", (long long)n_frames, 65535 * 64);
+    GsubView g;
+    int rc;
+    if ((rc = zr_view(ctx, "asb_gsub_expand_diff", &g))) return rc;
+    ASB_HIP(ctx, hipSetDevice(ctx->dev));
+    const long long ld = (n_frames + 63) / 64 * 64, tiles = g.Np / ZD_TN;
+    const long long tpg = (tiles + ZD_GROUPS - 1) / ZD_GROUPS, groups = (tiles + tpg - 1) / tpg;
+    asb_tmp<double> Z, part, rec;
+    if ((rc = Z.alloc(ctx, (size_t)3 * g.rq * ld)) || (rc = part.alloc(ctx, (size_t)groups * ld * FD_REC)) ||
+        (rc = rec.alloc(ctx, (size_t)(n_frames + 1) * FD_REC)))
+        return rc;
+    hipLaunchKernelGGL(k_zr_in, dim3((unsigned)(ld / 64), (unsigned)g.rq, 3), dim3(64), 0, ctx->stream, z_dev, (int)n_frames, (int)g.r, (int)g.rq, ld, Z.get());
+    hipLaunchKernelGGL(k_gsub_expand_diff, dim3((unsigned)(ld / ZD_TF), (unsigned)groups), dim3(256), 0, ctx->stream, g.Ut, g.Np, (int)g.rp, Z.get(),
+                       (int)g.rq, ld, g.o, a_dev, (int)n_frames, (int)g.n, (int)tpg, part.get());
+    hipLaunchKernelGGL(k_gsub_diff_frames, dim3((unsigned)((n_frames + 255) / 256)), dim3(256), 0, ctx->stream, part.get(), ld, (int)groups,
+                       (int)n_frames, rec.get());
+    asb_force_diff_final_launch(ctx, rec.get(), (long long)n_frames);
+    ASB_CHECK_LAUNCH(ctx);
+    return asb_force_diff_outputs(ctx, rec.get(), (long long)n_frames, sums_out, max_out, norms_out, per_frame_out);
 }
 
 // ---------------------------------------------------------------- the roll-out

@@ -2,7 +2,7 @@
 projective-dynamics solver (Simulators.py) evaluated on the device for the frames of the resident animation -- constraint
 projections, constraint forces, their DEIM reduction, the global step, the solver's iterations and its time steps, with the choice of the global step's solver and
 of how many kinds a solve may reduce, the positional constraints (pins) of every such call, the global step in a position
-subspace q = o + U z, roll-outs whose state lives in z, and the external forces and the floor of the time steps (DESIGN.md 3.10-3.22).
+subspace q = o + U z, roll-outs whose state lives in z, and the external forces and the floor of the time steps (DESIGN.md 3.10-3.23).
 A public call checks its arguments into the named records below before the engine is touched; the helpers take the records.
 """
 import collections
@@ -372,20 +372,27 @@ class ResidentDynamics(object):
         self._leave([plan.term])
         return out
 
+    @staticmethod
+    def _metrics(sums, m, norms, pf):
+        """``(fro, max, rel_x, rel_y, rel_z, per frame or None)`` from what ``force_diff`` / ``gsub_expand_diff`` return."""
+        with np.errstate(divide='ignore', invalid='ignore'):
+            rel = [float(np.sqrt(sums[d]) / np.sqrt(norms[d])) for d in range(3)]
+            return (float(np.sqrt(sums.sum())), float(m / norms[3]), rel[0], rel[1], rel[2],
+                    None if pf is None else np.sqrt(pf[:, 0]) / np.sqrt(pf[:, 1]))
+
     def _diff_metrics(self, full, others, n_sel, per_frame):
         """The reference's three metrics (constraintsComponents.py:524-556) of ``(full, t)`` for every device tensor ``t`` of
         ``others`` (made one at a time), through ``asb_force_diff``: the lists ``fro, max, rel_x, rel_y, rel_z`` and, with
         ``per_frame``, the (len(others), F') array of |full[f] - t[f]| / |full[f]|."""
         fro, mx, rel, frames = [], [], [[], [], []], []
         for t in others:
-            sums, m, norms, pf = self._engine.force_diff(full.data_ptr(), t.data_ptr(), n_sel, self.nVerts, per_frame)
-            with np.errstate(divide='ignore', invalid='ignore'):
-                fro.append(float(np.sqrt(sums.sum())))
-                mx.append(float(m / norms[3]))
-                for d in range(3):
-                    rel[d].append(float(np.sqrt(sums[d]) / np.sqrt(norms[d])))
-                if per_frame:
-                    frames.append(np.sqrt(pf[:, 0]) / np.sqrt(pf[:, 1]))
+            one = self._metrics(*self._engine.force_diff(full.data_ptr(), t.data_ptr(), n_sel, self.nVerts, per_frame))
+            fro.append(one[0])
+            mx.append(one[1])
+            for d in range(3):
+                rel[d].append(one[2 + d])
+            if per_frame:
+                frames.append(one[5])
         out = (fro, mx, rel[0], rel[1], rel[2])
         return out + (np.array(frames).reshape(len(fro), -1) if fro else np.zeros((0, 0)),) if per_frame else out
 
@@ -532,7 +539,7 @@ class ResidentDynamics(object):
         world-space input, resolved when the matrix is set up) or an (N, 3) array.  The three are for "subspace" only.  Pins need
         nothing new: their weights are in A, their term in the right-hand side.  Held on the device: 3 x 3 r N doubles and
         3 r F' more in a solve.  Out of scope under "subspace": ``history=True`` (ValueError),
-        an M-orthogonal basis, several ranks.  (A roll-out whose state lives in z is ``simulate_subspace``.)  Limits under "subspace": r <= min(N, 8192) (ValueError here, before the device is
+        an M-orthogonal basis, several ranks.  (A roll-out whose state lives in z is ``simulate_subspace``, the sweep over r along such roll-outs ``subspace_rollout_errors``.)  Limits under "subspace": r <= min(N, 8192) (ValueError here, before the device is
         touched); with ``hyper`` a reduced kind of at most 21 845 basis vectors (the engine refuses more; 65 532 under the other
         two solvers: the operator's rows go through one grid dimension).  Leaves ``self.global_solve_subspace`` = r after the next set-up."""
         if kind not in ("inverse", "slab", "subspace"):
@@ -992,7 +999,7 @@ class ResidentDynamics(object):
         ``set_global_solver``; every r is checked (rank included) before the device is touched.  The same five lists
         ``fro, max, rel_x, rel_y, rel_z`` and, with ``per_frame``, the (len(r_values), F') array |q[f] - q~_r[f]| / |q[f]|.  The
         full solve runs once, one subspace set-up and solve per r; every tensor stays on the device and is compared there.  The
-        solver selected for this object is the same afterwards.  Out of scope: sweeps over r along roll-outs."""
+        solver selected for this object is the same afterwards.  (Along roll-outs: ``subspace_rollout_errors``.)"""
         who = "subspace_solve_errors"
         if self._subspace_solver() is not None:
             raise ValueError("%s: the full solve runs under 'inverse' or 'slab': set_global_solver('subspace') is in force" % who)
@@ -1159,8 +1166,8 @@ class ResidentDynamics(object):
         steps.  With ``num_steps=1, record_every=1`` the numbers are those of ``reduced_solve_errors``.  The sweep keeps its
         one kind whatever ``set_reduced_kinds`` allows: multi-kind sweeps are out of scope.  ``pins`` (as ``simulate_frames``)
         hold both roll-outs, unreduced: the hanging cloth, the clamped bar.  ``forces`` / ``floor`` (as ``simulate_frames``) act on
-        both roll-outs alike: the drift under a load the basis was not trained on.  Out of scope: self-collisions, several ranks,
-        a sweep over the ranks of a position subspace."""
+        both roll-outs alike: the drift under a load the basis was not trained on.  Out of scope: self-collisions, several ranks.
+        (The sweep over the ranks of a position subspace is ``subspace_rollout_errors``.)"""
         who = "reduced_rollout_errors"
         self._hyper_check(who, hyper, [dict(basis=basis, num_components=0)], False)
         ex, K = self._solve_args(who, dt, velocity, gravity, num_iterations, "explicit", masses)
@@ -1341,3 +1348,95 @@ class ResidentDynamics(object):
                 eng.rforce_bank(0)
         self._leave(plan, pins)
         return (z, z_prev, frames.n_sel) + (() if every is None else ((records, steps),))
+
+    # ------------------------------------------------------------------ the position subspace judged along roll-outs
+    def subspace_distance(self, positions, z, per_frame=False):
+        """Extra: the reference's three metrics (constraintsComponents.py:524-556) of ``(positions, o + U z)`` for the subspace
+        the device holds -- ``fro, max, rel_x, rel_y, rel_z`` as scalars, with the arithmetic of the ``reduced_*_errors`` sweeps --
+        and, with ``per_frame``, a sixth value: the (F',) array |x_f - q~_f| / |x_f|.  ``positions``: a contiguous
+        ``torch.float64`` device tensor (F', N, 3) in world space; ``z``: one of (F', r, 3).  o + U z is formed tile by tile with the
+        bits of ``subspace_expand`` and compared in registers (csrc/asb_zroll.hip): ``positions`` is read once and
+        no (F', N, 3) tensor is written.  Both tensors are checked, F' included, before the device is touched.  One rank only."""
+        import torch
+        who = "subspace_distance"
+        r = self._subspace_held(who)
+        x = self._z_tensor(who, "positions", positions, self.nVerts)
+        z = self._z_tensor(who, "z", z, r, int(x.shape[0]))
+        torch.cuda.current_stream(z.device).synchronize()           # whatever produced the tensors is done before the engine reads them
+        out = self._metrics(*self._engine.gsub_expand_diff(x.data_ptr(), z.data_ptr(), int(x.shape[0]), per_frame))
+        return out if per_frame else out[:5]
+
+    def subspace_rollout_errors(self, kinds, basis, r_values, dt, num_steps, num_iterations=10, masses=None, velocity="difference",
+                                gravity=(0.0, 0.0, 0.0), animation="train", frame_start=0, frame_end=None, frame_jump=1, chunk_frames=None,
+                                record_every=1, pins=None, forces=None, origin=None, baseline="reduced"):
+        """Extra: how far a roll-out in a POSITION subspace drifts from one without it -- ``subspace_solve_errors`` carried through
+        ``num_steps`` time steps.  For every r of ``r_values`` and every recorded step (``record_every`` = r0: the steps r0, 2 r0, ..
+        <= ``num_steps``) the three metrics of ``(q_t, o + U_r z_t)``: q_t from ONE baseline roll-out with records under the solver
+        selected now ("inverse" or "slab"; under "subspace" a ValueError), z_t from ``simulate_subspace`` under
+        ``set_global_solver("subspace", basis=basis, num_components=r, origin=origin)`` with the same arguments.  ``baseline``
+        "reduced": ``simulate_frames(kinds, .., hyper="touched")``, so the drift is the position subspace's alone; "full": the same
+        call with the reduction keys of every kind taken off and no ``hyper``, the drift of the whole reduced simulator against the
+        unreduced one.  Arguments as ``simulate_subspace`` (EVERY kind reduced; no ``state``, and no ``floor``, which it refuses).
+
+        A roll-out in z starts from the Euclidean projection z_0 = U^T (x_f - o) of the frames (z_-1 likewise), the baseline from the
+        frames themselves: the errors of every step INCLUDE the projection error of the start, carried through the dynamics.
+
+        Per r: one subspace set-up (kept if the device holds that very one), one roll-out in z with its records, and per recorded
+        step one fused expansion + comparison on the slices (``full[j]``, ``z[j]``) -- no expansion is stored and no (F', N, 3)
+        tensor is made per r.  Memory held by the call: the baseline's R records, 24 R F' N bytes, and the R records
+        of one roll-out in z, 24 R F' r bytes.  Checked before the device is touched: every r (rank included), every kind reduced,
+        ``record_every``, ``baseline``, the rows of ``pins`` and ``forces`` for ``num_steps``, at most 65 535 rows of force.
+
+        Returns ``(fro, max, rel_x, rel_y, rel_z, steps)``: five (len(r_values), R) arrays and the list of the R recorded steps,
+        the shape of ``reduced_rollout_errors``; an empty ``r_values`` gives (0, R) arrays and touches no engine.  The solver
+        selected for this object is the same afterwards, also after an exception.  One rank only."""
+        who = "subspace_rollout_errors"
+        self._one_rank(who)
+        if self._subspace_solver() is not None:
+            raise ValueError("%s: the full solve runs under 'inverse' or 'slab': set_global_solver('subspace') is in force" % who)
+        if baseline not in ("reduced", "full"):
+            raise ValueError("%s: baseline must be 'reduced' or 'full', not %r" % (who, baseline))
+        subs = [self._subspace_args(who, basis, r, origin) for r in r_values]     # (r unchanged: 2.5 and True are refused)
+        limit = getattr(self, "_reduced_limit", 1)
+        keys = ("basis", "num_components", "reduction")
+        if not (isinstance(kinds, (list, tuple)) and len(kinds) >= 1 and all(
+                isinstance(k, dict) and "basis" in k and "num_components" in k for k in kinds)):
+            raise ValueError("%s: every kind must be reduced ('basis' and 'num_components'): up to %d of them under set_reduced_kinds(%d), "
+                             "none left plain" % (who, limit, limit))
+        if baseline == "reduced":
+            self._hyper_check(who, "touched", kinds, False)
+        ex, K = self._solve_args(who, dt, velocity, gravity, num_iterations, "explicit", masses)
+        T, every = self._rollout_args(who, num_steps, record_every, None)
+        if every is None:
+            raise ValueError("%s: record_every %r: a positive number of time steps" % (who, record_every))
+        frames = self._frames(animation, frame_start, frame_end, frame_jump)
+        self._pins(who, pins, frames, T)
+        ext = self._external(who, forces, None, ex, frames, T)
+        if ext is not None and ext.forces.table.ndim == 2 and ext.forces.table.shape[0] > 65535:
+            raise ValueError("%s: forces: %d rows of force, at most 65535 in a roll-out in z (continue with state= and start raised)"
+                             % (who, ext.forces.table.shape[0]))
+        self._solve_plan(who, kinds, chunk_frames)
+        steps = list(range(every, T + 1, every))
+        out = np.zeros((5, len(subs), len(steps)))
+        if not subs:
+            return tuple(out) + (steps,)
+        args = dict(masses=masses, velocity=velocity, gravity=gravity, animation=animation, frame_start=frame_start, frame_end=frame_end,
+                    frame_jump=frame_jump, chunk_frames=chunk_frames, record_every=every, pins=pins, forces=forces)
+        if baseline == "reduced":
+            full = self.simulate_frames(kinds, dt, T, K, hyper="touched", **args)[3][0]
+        else:
+            full = self.simulate_frames([{k: v for k, v in spec.items() if k not in keys} for spec in kinds], dt, T, K, hyper=None, **args)[3][0]
+        selected = (self._global_solver if hasattr(self, "_global_solver") else None, getattr(self, "_global_subspace", None))
+        try:
+            for i, sub in enumerate(subs):
+                self._global_solver, self._global_subspace = ("subspace", None), sub
+                zrec = self.simulate_subspace(kinds, dt, T, K, **args)[3][0]
+                for j in range(len(steps)):
+                    out[:, i, j] = self._metrics(*self._engine.gsub_expand_diff(full[j].data_ptr(), zrec[j].data_ptr(), frames.n_sel))[:5]
+        finally:
+            if selected[0] is None:
+                del self._global_solver
+            else:
+                self._global_solver = selected[0]
+            self._global_subspace = selected[1]
+        return tuple(out) + (steps,)

@@ -734,6 +734,15 @@ class HipEngine(object):
         """o + U z of the caller's (``n_frames``, r, 3) into the caller's device buffer of (``n_frames``, N, 3) float64."""
         self._ck(self.lib.asb_gsub_expand(self.h, ctypes.c_void_p(int(z_dev_ptr)), int(n_frames), ctypes.c_void_p(int(out_dev_ptr))))
 
+    def gsub_expand_diff(self, a_dev_ptr, z_dev_ptr, n_frames, per_frame=False):
+        """What ``force_diff(a, o + U z)`` returns for the caller's device tensors ``a`` (``n_frames``, N, 3) and ``z``
+        (``n_frames``, r, 3), with o + U z formed and consumed in one kernel and never stored."""
+        sums, mx, norms = np.empty(3), np.empty(1), np.empty(4)
+        pf = np.empty((int(n_frames), 2)) if per_frame else None
+        self._ck(self.lib.asb_gsub_expand_diff(self.h, ctypes.c_void_p(int(a_dev_ptr)), ctypes.c_void_p(int(z_dev_ptr)), int(n_frames),
+                                               ptr(sums), ptr(mx), ptr(norms), ptr(pf)))
+        return sums, float(mx[0]), norms, pf
+
     def zroll_operator(self):
         """(U^T A U)^-1 U^T S^T V of the current bank from the subspace of ``gsub_setup`` and the operator of ``rforce_operator``;
         either call afterwards invalidates it."""

@@ -771,6 +771,23 @@ int asb_test_gsub_state(asb_ctx* ctx, int which, double* out_host, int64_t len);
 int asb_gsub_coordinates(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean, double psf,
                          const double* pos_dev, int64_t n_frames, double* out_dev);
 int asb_gsub_expand(asb_ctx* ctx, const double* z_dev, int64_t n_frames, double* out_dev);
+/* asb_force_diff(a, b, ..) for b = o + U z with b never stored: a_dev (n_frames, n, 3) and z_dev (n_frames, r, 3) are caller-owned
+ * DEVICE tensors, the four outputs mean what they mean in asb_force_diff (any may be NULL), o and U are those of the subspace the
+ * context holds.  No subspace, n_frames < 1, a NULL tensor: ASB_ERR_ARG; the frame limit of asb_gsub_expand (ASB_ERR_LIMIT).
+ * One kernel forms q~ = o + U z tile by tile with the MFMA chain of asb_gsub_expand -- its bits, whatever the tile, the width or
+ * the neighbours -- and consumes it in registers with the per-entry arithmetic of asb_force_diff (e = a - q~, fma onto the sums,
+ * fmax of |e| and of the signed a); a is read once, in runs of 96 doubles per 32 vertices and frame, through LDS.  Reductions: a
+ * lane adds its entries ascending in the vertex, the four lanes of a frame are combined in a fixed order, a block walks its
+ * vertex tiles in ascending order, the blocks' records of a frame are added in ascending vertex order, and the frames by the
+ * kernel of asb_force_diff.  No atomics: repeats give identical bits, and a frame's record depends neither on n_frames nor on
+ * the frames beside it (the split of the vertices between blocks depends on n alone).  The order over the vertices is not that
+ * of asb_force_diff: the sums agree with it to rounding, the two maxima exactly.  Vertices and frames of the padding contribute
+ * nothing and no address is formed for them; a NaN propagates through the sums of its frame and axis.
+ * Scratch, freed before the call returns: z repacked (3 rq ld doubles, ld = n_frames rounded up to 64), the blocks' records
+ * 8 G ld doubles with G = ceil(T / ceil(T / 256)) <= 256 groups of the T = ceil(n / 32) vertex tiles, and 8 (n_frames + 1)
+ * doubles of frame records -- at most 2048 ld doubles beside z, never n x n_frames.  Returns after the stream has drained. */
+int asb_gsub_expand_diff(asb_ctx* ctx, const double* a_dev, const double* z_dev, int64_t n_frames, double* sums_out, double* max_out,
+                         double* norms_out, double* per_frame_out);
 int asb_zroll_operator(asb_ctx* ctx);
 int asb_zroll_begin(asb_ctx* ctx, int which, int64_t f0, int64_t f1, int64_t fj, const double* inv_massL, int add_mean, double psf,
                     const double* diag, int mode, const double* acc3, int64_t n_touched, const int64_t* touched, const double* z_dev,
